@@ -4,6 +4,11 @@
 GPU, RCCL) or run it plainly — it then starts that launcher itself as a child process.  One "step" = preprocess + forward + 21 losses + backward + gradient all-reduce + fused AdamW on one
 synthetic base_1d batch (per-GPU batch 2 x seq_len 10, 600x960 RGB -> 320x832 crop, 64x1024 range view,
 192x192x64 voxels) that is already resident in HBM.  Prints ONE JSON line on rank 0.
+
+A plain run measures the headline only: set-up, `--warmup` untimed steps, `--steps` timed steps, the result line.  `--full`
+adds everything else the bench reports (HIP-event brackets of the dominant kernel class inside the timed region and the per-class
+table from extra untimed steps, the exact-fp32 steps, the extension workloads, the CPU baseline).  `--dump-outputs DIR` writes
+what the last timed step computed as DIR/<name>.npy (see dump_outputs).
 """
 import argparse
 import json
@@ -122,6 +127,31 @@ def run_extension(name, dev, batch, s, steps=5, warmup=2):
     gc.collect()
     torch.cuda.empty_cache()
     return res
+
+
+# the parameter store holds 176 M floats: a fixed sample of this many positions is written (48 MB)
+DUMP_SAMPLE = 12 * 2 ** 20
+
+
+def dump_outputs(path, tr, loss):
+    """What a caller of the training step holds after the last timed step, as float64 / float32 .npy files: loss.npy (the
+    returned total), loss_<term>.npy (the logged loss terms), params.npy (the updated parameters at DUMP_SAMPLE positions of the
+    flat parameter store, drawn from a generator seeded with 1234, in ascending order: the same positions in every run of the same
+    model).  The gradients are not written: with float atomics in the reductions single gradient entries differ by up to a few
+    percent of the largest from run to run, while the updated parameters agree to ~1e-5."""
+    import re
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    out = {'loss': loss.detach().double().reshape(1)}
+    for k, v in sorted(tr.last_losses.items()):
+        out['loss_' + re.sub(r'[^A-Za-z0-9_.-]', '_', k)] = v.double().reshape(-1)
+    flat = tr.store.flat_param
+    if flat.numel() > DUMP_SAMPLE:
+        g = torch.Generator().manual_seed(1234)
+        flat = flat[torch.randint(flat.numel(), (DUMP_SAMPLE,), generator=g).sort().values.to(flat.device)]
+    out['params'] = flat.float()
+    for name, t in out.items():
+        np.save(os.path.join(path, name + '.npy'), t.cpu().numpy())
 
 
 def dry_run(args):
@@ -249,7 +279,19 @@ def main():
                          'names follow the real segments (tests/test_bench_dry_run.py)')
     ap.add_argument('--no-extensions', action='store_true',
                     help='skip the extension workloads (rv2048, vox256, single-product bf16: 5 steps each after the judged region)')
+    ap.add_argument('--full', action='store_true',
+                    help='everything beyond the headline: dominant-class brackets in the timed region, per-class table, exact-fp32 '
+                         'steps, extension workloads, CPU baseline (each still switched off by its --no-* option)')
+    ap.add_argument('--dump-outputs', default='', metavar='DIR',
+                    help='after the timed steps, write what the last one computed to DIR/<name>.npy (bench.py: dump_outputs)')
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
+    if args.layer_table and not args.full:
+        ap.error('--layer-table needs --full (the table comes from the per-class instrumentation steps)')
+    if not args.full:
+        # a plain run: set-up, warm-up, the timed steps and the result line, nothing else
+        args.no_kernel_timing = args.no_exact_f32 = args.no_extensions = args.no_cpu_baseline = True
 
     if os.environ.get('MUVO_BENCH_CORES'):
         # what an 8-rank box leaves each rank: restrict this process (and the threads it starts) to that many host cores
@@ -384,6 +426,8 @@ def main():
     # hipMalloc / hipFree calls of the caching allocator inside the timed region: without the reservation above its per-stream pools
     # still grow after five warm-up steps (blocks freed on one stream while another still reads them come back late)
     alloc_delta = {k: int(ms1.get(k, 0) - ms0.get(k, 0)) for k in ('num_device_alloc', 'num_device_free', 'num_alloc_retries')}
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, tr, loss)   # before any step of --full changes the parameters
     step_ms_seq = [marks[i].elapsed_time(marks[i + 1]) for i in range(args.steps)]
     step_ms = sorted(step_ms_seq)
     median_ms = step_ms[len(step_ms) // 2] if len(step_ms) % 2 else 0.5 * (step_ms[len(step_ms) // 2 - 1] + step_ms[len(step_ms) // 2])
