@@ -50,8 +50,10 @@ CONV_CASES = [
     (3, False, 16, 16, 3, 1, 1, 0, (6, 5, 64), False, 0),
     (3, False, 8, 8, 3, 1, 1, 0, (1, 1, 64), True, 0),
     (3, False, 16, 8, 3, 1, 1, 0, (19, 12, 32), True, 2),
-    # plane-streaming weight gradient only (conv_vox.hip vox_wgrad_ps_only): z lines of 16 voxels (two rows per wave), 32 produced
-    # channels as two row blocks; forward / data gradient stay on the implicit-GEMM kernels
+    # z lines of 16 voxels / 32 produced channels (conv_vox.hip vox_wgrad_ps_only, vox_bf3_shape_ok): in bf16x3 mode the
+    # plane-streaming kernels take the weight gradient (two rows per wave at Z = 16, 32 produced channels as two row blocks) and
+    # the forward of the three Z = 16 cases, and the data gradient of 32 -> 32; the 64 -> 32 and 16 -> 8 data gradients and
+    # everything in fp32 mode at Z = 16 stay on the implicit-GEMM kernels
     (3, False, 64, 32, 3, 1, 1, 0, (5, 19, 16), True, 2),
     (3, False, 32, 32, 3, 1, 1, 0, (4, 31, 16), True, 2),      # (at (4, 33, 16) one forward value lands on the other side of the LeakyReLU kink)
     (3, False, 16, 8, 3, 1, 1, 0, (3, 16, 16), False, 0),
