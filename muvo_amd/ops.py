@@ -9,8 +9,10 @@ Parameter gradients are accumulated by the kernels straight into `param.grad` (p
 view into one flat gradient buffer, see muvo_amd/param_store.py); the autograd Functions therefore
 return None for parameters and only propagate activation gradients.
 """
+import collections
 import contextlib
 import ctypes as C
+import math
 import os
 import threading
 import weakref
@@ -626,24 +628,6 @@ MFMA_FLOPS_PER_ALGORITHMIC_FLOP = {'f32_implicit_gemm': 1.0, 'bf16x3_implicit_ge
                                    'vox_4x4x1': 1.0, 'vox_bf16x3': 3.0}
 
 
-def _conv_tag(geom, n, in_sz):
-    return (f'{"convT" if geom.transposed else "conv"}{geom.nd}d {geom.cin}->{geom.cout} k{geom.ksz} s{geom.stride} '
-            f'n{n} in{tuple(in_sz)}')
-
-
-def _conv_bytes(geom, n, in_sz, out_sz):
-    """Algorithmic HBM bytes of one conv operation (forward, data gradient or weight gradient alike): both activation
-    tensors and the weight, fp32, each touched once."""
-    import math
-    return 4.0 * (n * geom.cin * math.prod(in_sz) + n * geom.cout * math.prod(out_sz)
-                  + geom.cin * geom.cout * math.prod(geom.ksz))
-
-
-def _conv_flops(geom, n, in_sz, out_sz):
-    import math
-    taps = math.prod(geom.ksz)
-    pix = math.prod(in_sz) if geom.transposed else math.prod(out_sz)
-    return 2.0 * n * geom.cin * geom.cout * taps * pix
 
 
 # ================================================================================================ GEMM
@@ -788,7 +772,7 @@ class LinearBf16x3Fn(torch.autograd.Function):
                 pk.fwd = torch.empty(ff.value, device=x.device, dtype=torch.float32)
             _ck(L.muvo_linear_bf16x3_pack(in_f, out_f, _f(weight), _f(pk.fwd), None, _st()))
             pk.fwd_key = k
-            _PACKS.register((id(pk), _plan_epoch[0]), ('lin', (in_f, out_f), weight, weakref.ref(pk), _plan_epoch[0]))
+            _PACKS.register(_PackEntry('lin', (in_f, out_f), weight, weakref.ref(pk), _plan_epoch[0], _plan_epoch[0]))
         keep = ctx.needs_input_grad[1]      # a backward follows: wgrad reuses the planes of x
         nws = (L.muvo_linear_bf16x3_workspace_bytes(_i64(rows), in_f) + 3) // 4
         ws_x = torch.empty(nws, device=x.device, dtype=torch.float32) if keep else scratch('lin_ws_x', nws, x.device)
@@ -849,6 +833,69 @@ def linear(x, weight, bias=None, act=ACT_NONE, slope=0.0):
 
 
 # ================================================================================================ conv
+_PLAN_FIELDS = ('desc', 'out_sz', 'pack_fwd', 'pack_dgrad', 'geom', 'n', 'in_sz', 'oshape', 'pack_key',
+                'ws_fwd_x', 'ws_dgrad_dy', 'ws_wgrad_x', 'ws_wgrad_dy', 'fam_fwd', 'fam_dgrad', 'fam_wgrad',
+                'dy_planes', 'dy_planes_floats', 'timing', 'answers')
+
+
+class ConvPlan(collections.namedtuple('ConvPlan', _PLAN_FIELDS)):
+    """What the library answers about one convolution at one batch and input size in the current mode (ConvGeom.plan makes one
+    per (n, in_sz, plan epoch)): descriptor, sizes, the kernel family of each direction (include/muvo_hip.h:
+    muvo_conv_kernel_family) and what the dispatch derives from them.  Workspace sizes are bytes (muvo_conv_workspace_bytes):
+    ws_fwd_x / ws_wgrad_x the split copy of x that forward / the weight gradient read, ws_dgrad_dy / ws_wgrad_dy the split
+    copy of dy that the data / weight gradient read; pack_fwd / pack_dgrad are floats (muvo_conv_pack_sizes).  A tuple with named
+    fields, the descriptor first: plan[0] is what a caller that only wants C.byref(descriptor) takes."""
+    __slots__ = ()
+
+    def __new__(cls, geom, n, in_sz, epoch):
+        L = lib()
+        out_sz = geom.out_size(in_sz)
+        d = ConvDesc(geom.nd, geom.transposed, n, geom.cin, geom.cout, (C.c_int32 * 3)(*in_sz),
+                     (C.c_int32 * 3)(*out_sz), (C.c_int32 * 3)(*geom.ksz), (C.c_int32 * 3)(*geom.stride),
+                     (C.c_int32 * 3)(*geom.pad), (C.c_int32 * 3)(*geom.dil))
+        ff, df = C.c_int64(0), C.c_int64(0)
+        _ck(L.muvo_conv_pack_sizes(C.byref(d), C.byref(ff), C.byref(df)))
+        ws = [L.muvo_conv_workspace_bytes(C.byref(d), op) for op in (0, 1, 2, 3)]
+        if min(ws) < 0:
+            raise RuntimeError(f'muvo_hip error: {L.muvo_last_error().decode()}')
+        fam = [L.muvo_conv_kernel_family(C.byref(d), op) for op in (0, 1, 2)]
+        ws_fwd_x, ws_dgrad_dy, ws_wgrad_x, ws_wgrad_dy = ws
+        fam_fwd, fam_dgrad, fam_wgrad = fam
+        # both gradient kernels read dy through channels-last split planes (one buffer of dy_planes_floats serves both)
+        dy_planes = fam_dgrad == 1 and fam_wgrad == 1 and ws_dgrad_dy > 0 and ws_wgrad_dy > 0
+        # KernelTiming.bracket arguments per direction.  Class label: family 1 launches on the four-wave small tiles are
+        # reported as their own class (5), and so are the stem kernels (csrc/conv_stem.hip, one launch each).  Launches: a
+        # transposed convolution is one launch per stride phase in forward and weight gradient, a strided one in the data gradient
+        label = [FAMILY[5 if (f == 1 and L.muvo_conv_kernel_variant(C.byref(d), op) == 0) else f] for op, f in enumerate(fam)]
+        phases, taps, pix_in, pix_out = math.prod(geom.stride), math.prod(geom.ksz), math.prod(in_sz), math.prod(out_sz)
+        flops = 2.0 * n * geom.cin * geom.cout * taps * (pix_in if geom.transposed else pix_out)
+        # algorithmic HBM bytes of one operation (forward, data gradient or weight gradient alike): both activation tensors and
+        # the weight, fp32, each touched once
+        nbytes = 4.0 * (n * geom.cin * pix_in + n * geom.cout * pix_out + geom.cin * geom.cout * taps)
+        tag = (f'{"convT" if geom.transposed else "conv"}{geom.nd}d {geom.cin}->{geom.cout} k{geom.ksz} s{geom.stride} '
+               f'n{n} in{tuple(in_sz)}')
+        rest = (tag, nbytes)
+        timing = {'fwd': (label[0] + ':fwd', flops, phases if geom.transposed else 1) + rest,
+                  'dgrad': (label[1] + ':dgrad', flops, 1 if geom.transposed else phases) + rest,
+                  'wgrad': (label[2] + ':wgrad', flops, phases if geom.transposed else 1) + rest,
+                  'stem_fwd': ('bf16x3_small_tile:fwd', flops, 1) + rest,
+                  'stem_wgrad': ('bf16x3_small_tile:wgrad', flops, 1) + rest}
+        return super().__new__(cls, d, out_sz, ff.value, df.value, geom, n, in_sz,
+                               oshape=(n, geom.cout) + (out_sz if geom.nd == 3 else out_sz[1:]),
+                               pack_key=(in_sz, epoch),   # what a packed copy of the weight was made for (its layout is batch-independent)
+                               ws_fwd_x=ws_fwd_x, ws_dgrad_dy=ws_dgrad_dy, ws_wgrad_x=ws_wgrad_x, ws_wgrad_dy=ws_wgrad_dy,
+                               fam_fwd=fam_fwd, fam_dgrad=fam_dgrad, fam_wgrad=fam_wgrad, dy_planes=dy_planes,
+                               dy_planes_floats=(max(ws_dgrad_dy, ws_wgrad_dy) + 3) // 4, timing=timing, answers={})
+
+    def supports(self, query, *args):
+        """the library's yes / no to `query` (the name of a muvo_*_supported function of the descriptor and args), asked once"""
+        key = (query,) + args
+        ok = self.answers.get(key)
+        if ok is None:
+            ok = self.answers[key] = bool(getattr(lib(), query)(C.byref(self.desc), *args))
+        return ok
+
+
 class ConvGeom:
     """Static geometry of a conv layer (everything but the batch/input size)."""
 
@@ -866,9 +913,6 @@ class ConvGeom:
             self.dil = (1,) + self.dil[1:]
         self.pad, self.out_pad = p, op
         self._plans = {}
-        self.ws_bytes = {}
-        self.family = {}
-        self.tclass = {}
 
     def out_size(self, in_sz):
         o = []
@@ -881,27 +925,17 @@ class ConvGeom:
         return tuple(o)
 
     def plan(self, n, in_sz):
+        """the ConvPlan for batch n and input size in_sz ((D, H, W); (1, H, W) for a 2-d layer) in the current mode"""
         key = (n, in_sz, _plan_epoch[0])
         pl = self._plans.get(key)
         if pl is None:
-            out_sz = self.out_size(in_sz)
-            d = ConvDesc(self.nd, self.transposed, n, self.cin, self.cout, (C.c_int32 * 3)(*in_sz),
-                         (C.c_int32 * 3)(*out_sz), (C.c_int32 * 3)(*self.ksz), (C.c_int32 * 3)(*self.stride),
-                         (C.c_int32 * 3)(*self.pad), (C.c_int32 * 3)(*self.dil))
-            ff, df = C.c_int64(0), C.c_int64(0)
-            _ck(lib().muvo_conv_pack_sizes(C.byref(d), C.byref(ff), C.byref(df)))
-            wsf, wsd, wsx, wsy = (lib().muvo_conv_workspace_bytes(C.byref(d), op) for op in (0, 1, 2, 3))
-            if min(wsf, wsd, wsx, wsy) < 0:
-                raise RuntimeError(f'muvo_hip error: {lib().muvo_last_error().decode()}')
-            self.ws_bytes[(n, in_sz, _plan_epoch[0])] = (wsf, wsd, wsx, wsy)
-            self.family[(n, in_sz, _plan_epoch[0])] = tuple(lib().muvo_conv_kernel_family(C.byref(d), op) for op in (0, 1, 2))
-            # timing label: family 1 launches on the four-wave small tiles are reported as their own class (5)
-            self.tclass[(n, in_sz, _plan_epoch[0])] = tuple(
-                5 if (f == 1 and lib().muvo_conv_kernel_variant(C.byref(d), op) == 0) else f
-                for op, f in enumerate(self.family[(n, in_sz, _plan_epoch[0])]))
-            pl = (d, out_sz, ff.value, df.value)
-            self._plans[key] = pl
+            pl = self._plans[key] = ConvPlan(self, n, in_sz, key[2])
         return pl
+
+    def plan_for(self, x):
+        """the plan for the input tensor x, or for its shape (N, Cin, spatial...)"""
+        shape = getattr(x, 'shape', x)
+        return self.plan(shape[0], tuple(shape[2:]) if self.nd == 3 else (1,) + tuple(shape[2:]))
 
 
 class _PackedWeights:
@@ -910,35 +944,63 @@ class _PackedWeights:
     def __init__(self):
         self.fwd = self.dgr = None
         self.fwd_key = self.dgr_key = None
-        self.fwd_plan = self.dgr_plan = None     # (input size, plan epoch) the copy was packed for (layout is batch-independent)
+        self.fwd_plan = self.dgr_plan = None     # ConvPlan.pack_key the copy was packed for
 
 
 def _wkey(w):
     return (w._version, _weight_epoch[0], w.data_ptr())
 
 
-def _head_alias(geom, key, op, weight):
-    """The 1x1 head kernels (muvo_conv_kernel_family == 3, conv_pw.hip) read the weight in PyTorch's layout: their "packed copy" is
-    the parameter itself - no device-to-device copy per head, direction and optimizer step (18 launches per step at base_1d)."""
-    fam = geom.family.get(key)
-    return fam is not None and fam[op] == 3 and weight.is_contiguous()
-
-
 def _is_alias(buf, weight):
     return buf is not None and buf.data_ptr() == weight.data_ptr()
+
+
+_PACKED_ATTRS = (('fwd', 'fwd_key', 'fwd_plan'), ('dgr', 'dgr_key', 'dgr_plan'))
+
+
+def _packed_weight(plan, packed, weight, dgrad):
+    """The packed copy of `weight` that one direction of `plan` reads (dgrad 0: forward and weight gradient, 1: data gradient),
+    held by `packed` and made current here: (re)allocated, and packed again when the weight or the plan changed.  Only the
+    forward copy registers the layer for the batched repack (repack_all refreshes whichever copies a registered layer has)."""
+    a_buf, a_key, a_plan = _PACKED_ATTRS[dgrad]
+    buf, key, k = getattr(packed, a_buf), getattr(packed, a_key), _wkey(weight)
+    if (plan.fam_dgrad if dgrad else plan.fam_fwd) == 3 and weight.is_contiguous():
+        # The 1x1 head kernels (muvo_conv_kernel_family == 3, conv_pw.hip) read the weight in PyTorch's layout: their "packed
+        # copy" is the parameter itself - no device-to-device copy per head, direction and optimizer step (18 launches per
+        # step at base_1d)
+        buf = weight.detach().view(-1)
+    else:
+        size = plan.pack_dgrad if dgrad else plan.pack_fwd
+        if buf is None or buf.numel() < size or _is_alias(buf, weight):
+            buf, key = torch.empty(size, device=weight.device, dtype=torch.float32), None
+        if key == k and getattr(packed, a_plan) == plan.pack_key:
+            return buf
+        _ck(lib().muvo_conv_pack_weights(C.byref(plan.desc), _f(weight), None if dgrad else _f(buf), _f(buf) if dgrad else None,
+                                         _st()))
+        if not dgrad:
+            _PACKS.register(_PackEntry('conv', plan.desc, weight, weakref.ref(packed), plan.pack_key, plan.pack_key[1]))
+    setattr(packed, a_buf, buf)
+    setattr(packed, a_key, k)
+    setattr(packed, a_plan, plan.pack_key)
+    return buf
 
 
 # ------------------------------------------------------------------------------------------------
 # Batched weight packing (include/muvo_hip.h: muvo_pack_table_*).  Layers register themselves the first time they pack;
 # repack_all() (called once per training forward) refreshes every registered copy that already exists with ONE launch and
 # marks it current, so the per-layer staleness checks in ConvFn / LinearBf16x3Fn find nothing to do.
+# One registered layer.  kind 'conv': desc is the ConvDesc, pack_key the ConvPlan.pack_key; kind 'lin': desc is (in_features,
+# out_features), pack_key the plan epoch.  holder: weak reference to the layer's packed-copy holder; epoch: the plan epoch of the copies
+_PackEntry = collections.namedtuple('_PackEntry', 'kind desc weight holder pack_key epoch')
+
+
 class _PackRegistry:
     def __init__(self):
         self.entries, self.seen = [], set()
         self.sig, self.dev, self.n, self.nblk, self.batched = None, None, 0, 0, []
 
-    def register(self, key, entry):
-        """entry: (kind, desc, weight, weakref to the layer's packed-copy holder, plan key)"""
+    def register(self, entry):
+        key = (id(entry.holder()), entry.pack_key)
         if key not in self.seen:
             self.seen.add(key)
             self.entries.append(entry)
@@ -957,63 +1019,103 @@ def repack_all():
     ptr = lambda t: 0 if t is None else t.data_ptr()
     # drop layers that no longer exist and copies that belong to an earlier plan epoch (conv mode / policy change: their
     # buffers are re-sized lazily by the layer itself, which then registers again)
-    live = []
-    for e in R.entries:
-        pk = e[3]()
-        if pk is None or (e[0] == 'conv' and e[4][1] != _plan_epoch[0]) or (e[0] == 'lin' and e[4] != _plan_epoch[0]):
-            R.seen.discard((id(pk) if pk is not None else None, e[4]))
-            continue
-        live.append(e)
+    live = [(e, e.holder()) for e in R.entries]
+    live = [(e, pk) for e, pk in live if pk is not None and e.epoch == _plan_epoch[0]]
     if len(live) != len(R.entries):
-        R.entries = live
-        R.seen = {(id(e[3]()), e[4]) for e in live}
+        R.entries = [e for e, _ in live]
+        R.seen = {(id(pk), e.pack_key) for e, pk in live}
         R.sig = None
     if not R.entries:
         return
-    ents = [(e[0], e[1], e[2], e[3](), e[4]) for e in R.entries]
-    sig = tuple((ptr(e[3].fwd), ptr(e[3].dgr), e[2].data_ptr()) for e in ents)
+    sig = tuple((ptr(pk.fwd), ptr(pk.dgr), e.weight.data_ptr()) for e, pk in live)
     if sig != R.sig:
         item = L.muvo_pack_table_item_bytes()
-        cap = 16 * len(R.entries) + 8
+        cap = 16 * len(live) + 8
         host = torch.zeros(cap * item, dtype=torch.uint8)
         n, nblk = C.c_int(0), C.c_int64(0)
         R.batched = []
-        for e, orig in zip(ents, R.entries):
-            kind, desc, weight, pk, _ = e
+        for e, pk in live:
             if pk.fwd is None and pk.dgr is None:
                 continue
-            if _is_alias(pk.fwd, weight) or _is_alias(pk.dgr, weight):      # 1x1 heads: the kernels read the parameter itself
+            if _is_alias(pk.fwd, e.weight) or _is_alias(pk.dgr, e.weight):      # 1x1 heads: the kernels read the parameter itself
                 continue
-            if kind == 'conv':
-                rc = L.muvo_conv_pack_table_add(C.c_void_p(host.data_ptr()), cap, C.byref(n), C.byref(nblk), C.byref(desc),
-                                                _f(weight), _f(pk.fwd), _f(pk.dgr))
+            if e.kind == 'conv':
+                rc = L.muvo_conv_pack_table_add(C.c_void_p(host.data_ptr()), cap, C.byref(n), C.byref(nblk), C.byref(e.desc),
+                                                _f(e.weight), _f(pk.fwd), _f(pk.dgr))
             else:
                 rc = L.muvo_linear_bf16x3_pack_table_add(C.c_void_p(host.data_ptr()), cap, C.byref(n), C.byref(nblk),
-                                                         desc[0], desc[1], _f(weight), _f(pk.fwd), _f(pk.dgr))
+                                                         e.desc[0], e.desc[1], _f(e.weight), _f(pk.fwd), _f(pk.dgr))
             if rc == 0:
-                R.batched.append(orig)
+                R.batched.append(e)
             elif rc != 1:
                 _ck(rc)
         R.n, R.nblk = n.value, nblk.value
-        R.dev = host[:max(R.n, 1) * item].to(ents[0][2].device)
+        R.dev = host[:max(R.n, 1) * item].to(live[0][0].weight.device)
         R.sig = sig
     if R.n:
         _ck(L.muvo_pack_table_run(C.c_void_p(R.dev.data_ptr()), R.n, _i64(R.nblk), _st()))
-        for kind, _, weight, pkref, pkey in R.batched:
-            pk = pkref()
+        for e in R.batched:
+            pk = e.holder()
             if pk is None:
                 continue
-            k = _wkey(weight)
+            k = _wkey(e.weight)
             if pk.fwd is not None:
                 pk.fwd_key = k
             if pk.dgr is not None:
                 pk.dgr_key = k
-            if kind == 'conv':
-                pk.fwd_plan = pkey if pk.fwd is not None else pk.fwd_plan
-                pk.dgr_plan = pkey if pk.dgr is not None else pk.dgr_plan
+            if e.kind == 'conv':
+                pk.fwd_plan = e.pack_key if pk.fwd is not None else pk.fwd_plan
+                pk.dgr_plan = e.pack_key if pk.dgr is not None else pk.dgr_plan
 
 
 _KEEP_WS = os.environ.get('MUVO_KEEP_WS', '1') != '0'
+
+
+def _bracket(plan, direction):
+    """Opens the timing bracket around one library call of `plan` (direction: a key of ConvPlan.timing) and returns the closing
+    event.  The call sites test KERNEL_TIMING themselves, so that a site costs one global read when timing is off:
+        e1 = _bracket(plan, 'fwd') if KERNEL_TIMING is not None else None; ...; if e1 is not None: e1.record()"""
+    e0, e1 = KERNEL_TIMING.bracket(*plan.timing[direction])
+    e0.record()
+    return e1
+
+
+@contextlib.contextmanager
+def _on_wgrad_stream(wst, device, reads, dy_slot=None):
+    """Runs the body on the weight-gradient stream wst (on the current stream if wst is None or is the current one).  Everything
+    the body reads is queued on the current stream by now: wst starts behind that point, and the tensors in `reads` (None
+    entries skipped) are kept from being reused before wst is done with them.  dy_slot: the ring slot of dy planes the body
+    reads (_dy_ws_acquire), released by an event behind the body's work."""
+    cur = torch.cuda.current_stream(device)
+    if wst is None or wst == cur:
+        yield
+        return
+    wst.wait_stream(cur)
+    for t in reads:
+        if t is not None:
+            t.record_stream(wst)
+    with torch.cuda.stream(wst):
+        yield
+        if dy_slot is not None:
+            dy_slot.done = torch.cuda.Event()
+            dy_slot.done.record(wst)
+
+
+class _DyWorkspace:
+    """The dy planes both gradient kernels of one backward call read: with the weight gradient on its own stream (wst) a ring
+    buffer (one slot per backward call), otherwise the stream's scratch."""
+    __slots__ = ('wst', 'device', 'slot')
+
+    def __init__(self, wst, device):
+        self.wst, self.device, self.slot = wst, device, None
+
+    def get(self, nfloats):
+        if self.wst is None:
+            return scratch('conv_ws_dy', nfloats, self.device)
+        if self.slot is None:
+            self.slot = _dy_ws_acquire(nfloats, self.device)
+        assert self.slot.t.numel() >= nfloats
+        return self.slot.t
 
 
 class ConvFn(torch.autograd.Function):
@@ -1026,93 +1128,88 @@ class ConvFn(torch.autograd.Function):
             x = aff_src
         # split planes that came with the tensor (written by its producer: BNActFn with planes=True): (workspace, stream key)
         xp = getattr(x, '_muvo_planes', None)
-        x_is_placeholder = getattr(x, '_muvo_planes_only', False)
-        if not x_is_placeholder:
+        x_ph = getattr(x, '_muvo_planes_only', False)
+        if not x_ph:
             x = x.contiguous()
-        ctx.act_bwd_fused = act_bwd_fused
-        n = x.shape[0]
-        in_sz = tuple(x.shape[2:]) if geom.nd == 3 else (1,) + tuple(x.shape[2:])
-        d, out_sz, ff, df = geom.plan(n, in_sz)
-        L = lib()
+        plan = geom.plan_for(x)
+        hf = getattr(ctx, '_head_fwd', None)      # ConvHeadFn: (head weight, head bias, logits) of a head fused into the epilogue
+        ctx.geom, ctx.packed, ctx.act, ctx.slope, ctx.act_bwd_fused = geom, packed, act, slope, act_bwd_fused
+        ctx.weight, ctx.bias = weight, bias
         # the 7x7 stride-2 stems of the ResNet-18 trunks: direct convolution on bf16x3 products from the fp32 parameter itself
         # (csrc/conv_stem.hip); only where the arithmetic mode is bf16x3 and the input needs no gradient
-        skey = ('stem', n, in_sz, _plan_epoch[0])
-        stem = geom.family.get(skey)
-        if stem is None:
-            stem = geom.family[skey] = bool(L.muvo_stem_conv_supported(C.byref(d)))
-        ctx.stem = bool(stem and get_conv_mode() != CONV_F32 and bias is None and act == ACT_NONE and moments is None and aff is None
-                        and not x_is_placeholder and not ctx.needs_input_grad[0] and getattr(ctx, '_head_fwd', None) is None
-                        and weight.is_contiguous())
+        ctx.stem = bool(plan.supports('muvo_stem_conv_supported') and get_conv_mode() != CONV_F32 and bias is None
+                        and act == ACT_NONE and moments is None and aff is None and not x_ph and not ctx.needs_input_grad[0]
+                        and hf is None and weight.is_contiguous())
         if ctx.stem:
-            y = torch.empty((n, geom.cout) + out_sz[1:], device=x.device, dtype=torch.float32)
-            kt = KERNEL_TIMING
-            if kt is not None:
-                e0, e1 = kt.bracket('bf16x3_small_tile:fwd', _conv_flops(geom, n, in_sz, out_sz), 1, _conv_tag(geom, n, in_sz),
-                                    _conv_bytes(geom, n, in_sz, out_sz))
-                e0.record()
-            _ck(L.muvo_stem_conv_forward(C.byref(d), _f(x), _f(weight), None, _f(y), 0, _st()))
-            if kt is not None:
-                e1.record()
-            ctx.geom, ctx.packed, ctx.act, ctx.slope = geom, packed, act, slope
-            ctx.weight, ctx.bias, ctx.in_sz, ctx.ws_x, ctx.x_is_placeholder = weight, bias, in_sz, None, False
-            ctx.save_for_backward(x, None)
-            return y
-        k = _wkey(weight)
-        pkey = (in_sz, _plan_epoch[0])
-        if _head_alias(geom, (n, in_sz, _plan_epoch[0]), 0, weight):
-            packed.fwd, packed.fwd_key, packed.fwd_plan = weight.detach().view(-1), k, pkey       # 1x1 heads read the PyTorch layout
-        else:
-            if packed.fwd is None or packed.fwd.numel() < ff or _is_alias(packed.fwd, weight):
-                packed.fwd = torch.empty(ff, device=x.device, dtype=torch.float32)
-                packed.fwd_key = None
-            if packed.fwd_key != k or packed.fwd_plan != pkey:
-                _ck(L.muvo_conv_pack_weights(C.byref(d), _f(weight), _f(packed.fwd), None, _st()))
-                packed.fwd_key, packed.fwd_plan = k, pkey
-                _PACKS.register((id(packed), pkey), ('conv', d, weight, weakref.ref(packed), pkey))
-        oshape = (n, geom.cout) + (out_sz if geom.nd == 3 else out_sz[1:])
-        y = torch.empty(oshape, device=x.device, dtype=torch.float32)
-        kt = KERNEL_TIMING
-        if kt is not None:
-            import math
-            e0, e1 = kt.bracket(FAMILY[geom.tclass[(n, in_sz, _plan_epoch[0])][0]] + ':fwd', _conv_flops(geom, n, in_sz, out_sz),
-                                math.prod(geom.stride) if geom.transposed else 1, _conv_tag(geom, n, in_sz),
-                                _conv_bytes(geom, n, in_sz, out_sz))
-            e0.record()
-        wsb = geom.ws_bytes[(n, in_sz, _plan_epoch[0])]
-        hf = getattr(ctx, '_head_fwd', None)
-        use_xp = (xp is not None and wsb[0] > 0 and geom.family[(n, in_sz, _plan_epoch[0])][0] == 1 and hf is None and aff is None
-                  and moments is None and xp[1] == _stream_key(x.device) and xp[0].numel() * 4 >= wsb[0])
-        if x_is_placeholder and not (use_xp and (wsb[2] > 0 or not ctx.needs_input_grad[1])):
-            raise RuntimeError('muvo_hip: a planes-only tensor (BNActFn keep_f32=False) reached a convolution that needs its fp32 values')
-        # wgrad reuses the split copy of x (grad mode is off inside forward: needs_input_grad says whether a backward follows)
-        keep_ws = wsb[0] > 0 and wsb[2] > 0 and ctx.needs_input_grad[1] and _KEEP_WS
-        if use_xp:
-            ws = xp[0]
-            keep_ws = wsb[2] > 0 and ctx.needs_input_grad[1] and (_KEEP_WS or x_is_placeholder)
-        elif keep_ws:
-            ws = torch.empty((wsb[0] + 3) // 4, device=x.device, dtype=torch.float32)
-        else:
-            ws = scratch('conv_ws', (wsb[0] + 3) // 4, x.device) if wsb[0] else None
-        ctx.ws_x = ws if keep_ws else None
-        ctx.x_is_placeholder = x_is_placeholder
+            return ConvFn._stem_forward(ctx, plan, x, weight)
+        wp = _packed_weight(plan, packed, weight, 0)
+        y = torch.empty(plan.oshape, device=x.device, dtype=torch.float32)
+        e1 = _bracket(plan, 'fwd') if KERNEL_TIMING is not None else None
+        use_xp = (xp is not None and plan.ws_fwd_x > 0 and plan.fam_fwd == 1 and hf is None and aff is None
+                  and moments is None and xp[1] == _stream_key(x.device) and xp[0].numel() * 4 >= plan.ws_fwd_x)
+        ws = ConvFn._forward_workspace(ctx, plan, x, xp[0] if use_xp else None, x_ph)
+        L, d = lib(), C.byref(plan.desc)
         if hf is not None:
-            _ck(L.muvo_conv_forward_head(C.byref(d), _f(x), _f(packed.fwd), _f(bias), _f(y), act, _fl(slope), _p(ws),
+            _ck(L.muvo_conv_forward_head(d, _f(x), _f(wp), _f(bias), _f(y), act, _fl(slope), _p(ws),
                                          _f(hf[0]), _f(hf[1]), hf[0].shape[0], _f(hf[2]), _st()))
         elif aff is not None:
-            _ck(L.muvo_conv_forward_affine(C.byref(d), _f(x), _f(aff), _f(packed.fwd), _f(bias), _f(y), act, _fl(slope), _p(moments), _st()))
+            _ck(L.muvo_conv_forward_affine(d, _f(x), _f(aff), _f(wp), _f(bias), _f(y), act, _fl(slope), _p(moments), _st()))
         elif moments is not None:     # instance-norm statistics of y from the epilogue registers (voxel bf16x3 kernels)
-            _ck(L.muvo_conv_forward_moments(C.byref(d), _f(x), _f(packed.fwd), _f(bias), _f(y), act, _fl(slope), _p(moments), _st()))
+            _ck(L.muvo_conv_forward_moments(d, _f(x), _f(wp), _f(bias), _f(y), act, _fl(slope), _p(moments), _st()))
         elif use_xp:
-            _ck(L.muvo_conv_forward_planes(C.byref(d), None if x_is_placeholder else _f(x), _f(packed.fwd), _f(bias), _f(y), act,
-                                           _fl(slope), _p(ws), 1, _st()))
+            _ck(L.muvo_conv_forward_planes(d, None if x_ph else _f(x), _f(wp), _f(bias), _f(y), act, _fl(slope), _p(ws), 1, _st()))
         else:
-            _ck(L.muvo_conv_forward(C.byref(d), _f(x), _f(packed.fwd), _f(bias), _f(y), act, _fl(slope), _p(ws), _st()))
-        if kt is not None:
+            _ck(L.muvo_conv_forward(d, _f(x), _f(wp), _f(bias), _f(y), act, _fl(slope), _p(ws), _st()))
+        if e1 is not None:
             e1.record()
-        ctx.geom, ctx.packed, ctx.act, ctx.slope = geom, packed, act, slope
-        ctx.weight, ctx.bias, ctx.in_sz = weight, bias, in_sz
         ctx.save_for_backward(x, y if (act != ACT_NONE and not act_bwd_fused) else None)
         return y
+
+    @staticmethod
+    def _forward_workspace(ctx, plan, x, planes, x_ph):
+        """The split copy of x the forward kernel reads (None: this family reads x itself).  planes: the copy that came with x
+        where the kernel can read it as it is; x_ph: x has no fp32 values, only those planes.  Leaves in ctx.ws_x the copy
+        that the weight gradient reuses."""
+        wgrad_follows = ctx.needs_input_grad[1]   # grad mode is off inside forward: needs_input_grad says whether a backward follows
+        if x_ph and not (planes is not None and (plan.ws_wgrad_x > 0 or not wgrad_follows)):
+            raise RuntimeError('muvo_hip: a planes-only tensor (BNActFn keep_f32=False) reached a convolution that needs its fp32 values')
+        if planes is not None:
+            ws = planes
+            keep_ws = plan.ws_wgrad_x > 0 and wgrad_follows and (_KEEP_WS or x_ph)
+        else:
+            keep_ws = plan.ws_fwd_x > 0 and plan.ws_wgrad_x > 0 and wgrad_follows and _KEEP_WS
+            if keep_ws:
+                ws = torch.empty((plan.ws_fwd_x + 3) // 4, device=x.device, dtype=torch.float32)
+            else:
+                ws = scratch('conv_ws', (plan.ws_fwd_x + 3) // 4, x.device) if plan.ws_fwd_x else None
+        ctx.ws_x = ws if keep_ws else None
+        ctx.x_is_placeholder = x_ph
+        return ws
+
+    @staticmethod
+    def _stem_forward(ctx, plan, x, weight):
+        y = torch.empty(plan.oshape, device=x.device, dtype=torch.float32)
+        e1 = _bracket(plan, 'stem_fwd') if KERNEL_TIMING is not None else None
+        _ck(lib().muvo_stem_conv_forward(C.byref(plan.desc), _f(x), _f(weight), None, _f(y), 0, _st()))
+        if e1 is not None:
+            e1.record()
+        ctx.ws_x, ctx.x_is_placeholder = None, False
+        ctx.save_for_backward(x, None)
+        return y
+
+    @staticmethod
+    def _stem_backward(ctx, plan, x, dy):
+        # stem: only the weight gradient exists (the input image needs none); on the weight-gradient stream like the others
+        weight = ctx.weight
+        if not (weight.requires_grad and dy is not None):
+            return
+        dy = dy.contiguous()
+        gw = grad_of(weight)
+        with _on_wgrad_stream(wgrad_stream(x.device), x.device, (x, dy)):
+            e1 = _bracket(plan, 'stem_wgrad') if KERNEL_TIMING is not None else None
+            _ck(lib().muvo_stem_conv_wgrad(C.byref(plan.desc), _f(x), _f(dy), _f(gw), _st()))
+            if e1 is not None:
+                e1.record()
 
     @staticmethod
     def backward(ctx, dy):
@@ -1120,172 +1217,121 @@ class ConvFn(torch.autograd.Function):
 
     @staticmethod
     def _backward(ctx, dy, head):
-        """head: None, or (dlogits, head_weight (CO, Cout)) of a 1x1 output head that reads this layer's output: its data
-        gradient W_head^T dlogits is added to dy inside the split pass (muvo_conv_prepare_dy_head) — dy may then be None (the
-        head is the only consumer)."""
+        """head: None, or (dlogits, head_weight (CO, Cout), head_bias, head_wgrad) of a 1x1 output head that reads this layer's
+        output: its data gradient W_head^T dlogits is added to dy inside the split pass (muvo_conv_prepare_dy_head) — dy may
+        then be None (the head is the only consumer); head_wgrad() runs the head's own weight-gradient pass."""
         x, y = ctx.saved_tensors
-        geom, packed, weight, bias = ctx.geom, ctx.packed, ctx.weight, ctx.bias
-        d, out_sz, ff, df = geom.plan(x.shape[0], ctx.in_sz)
-        L = lib()
+        # the plan of the current epoch, not forward's: the library picks its kernels from its mode at the time of the call
+        plan = ctx.geom.plan_for(x)
         if getattr(ctx, 'stem', False):
-            # stem: only the weight gradient exists (the input image needs none); on the weight-gradient stream like the others
-            if weight.requires_grad and dy is not None:
-                dy = dy.contiguous()
-                gw = grad_of(weight)
-                cur, wst = torch.cuda.current_stream(x.device), wgrad_stream(x.device)
-                kt = KERNEL_TIMING
-                side = wst is not None and wst != cur
-                if side:
-                    wst.wait_stream(cur)
-                    x.record_stream(wst)
-                    dy.record_stream(wst)
-                with (torch.cuda.stream(wst) if side else contextlib.nullcontext()):
-                    if kt is not None:
-                        e0, e1 = kt.bracket('bf16x3_small_tile:wgrad', _conv_flops(geom, x.shape[0], ctx.in_sz, out_sz), 1,
-                                            _conv_tag(geom, x.shape[0], ctx.in_sz), _conv_bytes(geom, x.shape[0], ctx.in_sz, out_sz))
-                        e0.record()
-                    _ck(L.muvo_stem_conv_wgrad(C.byref(d), _f(x), _f(dy), _f(gw), _st()))
-                    if kt is not None:
-                        e1.record()
-            return None, None, None, None, None, None, None, None, None, None, None
+            ConvFn._stem_backward(ctx, plan, x, dy)
+            return (None,) * 11
+        need_dx, need_dw = ctx.needs_input_grad[0], ctx.weight.requires_grad
+        # both gradient kernels read dy through the channels-last split planes: one fused pass makes them from (y, dy)
+        # together with the activation derivative and the bias gradient
+        fused_dy = plan.dy_planes and need_dx and need_dw
+        dy_ws = _DyWorkspace(wgrad_stream(x.device) if need_dw else None, x.device)
+        dz, planes = ConvFn._resolve_dy(ctx, plan, x, y, dy, head, fused_dy, dy_ws)
+        dx = None
+        if need_dx:
+            dx, planes = ConvFn._data_grad(ctx, plan, x, dz, planes, fused_dy, dy_ws)
+        if need_dw:
+            # the planes hold dy only if the data gradient (or the fused pass before it) split dy into them
+            ConvFn._weight_grad(ctx, plan, x, y, dz, planes, need_dx and plan.ws_dgrad_dy > 0, fused_dy, dy_ws)
+        return (dx,) + (None,) * 10
+
+    @staticmethod
+    def _resolve_dy(ctx, plan, x, y, dy, head, fused_dy, dy_ws):
+        """-> (dz, planes): the gradient at the convolution's result (before its activation) as the gradient kernels take it.
+        planes: its split planes where they exist already, else None.  Where they exist the bf16x3 kernels (fused_dy says both
+        directions run on them) read nothing else, and dz is only some valid pointer."""
         dyp = getattr(dy, '_muvo_planes', None) if dy is not None else None     # dy arrives as split planes (BNActFn.backward)
         if dy is not None and dyp is None:
             dy = dy.contiguous()
-        key = (x.shape[0], ctx.in_sz, _plan_epoch[0])
-        fam, wsb = geom.family[key], geom.ws_bytes[key]
-        x_ph = getattr(ctx, 'x_is_placeholder', False)
-        xptr = ctx.ws_x if x_ph else x            # a planes-only input has no fp32 storage: the kernels read ctx.ws_x (flags bit 0)
-        # both gradient kernels read dy through the channels-last split planes: one fused pass makes them from (y, dy)
-        # together with the activation derivative and the bias gradient
-        fused_dy = (fam[1] == 1 and fam[2] == 1 and ctx.needs_input_grad[0] and weight.requires_grad and wsb[1] > 0
-                    and wsb[3] > 0)
-        if head is not None:
-            gl, head_w, head_b, head_wgrad = head
-            co = head_w.shape[0]
-            if not (fused_dy and L.muvo_conv_prepare_dy_head_supported(C.byref(d), co)):
-                # no fused preamble for this shape: materialise the head's data gradient (dy + W_head^T dlogits)
-                hd = torch.einsum('nk...,kc->nc...', gl, head_w.view(co, -1))
-                dy = hd.contiguous() if dy is None else dy + hd
-                head_wgrad()
-                head = None
-        ws_dy_fused = None
-        wst = wgrad_stream(x.device) if weight.requires_grad else None
-        dy_slot = None
-
-        def dy_workspace(nfloats):
-            # the dy planes both gradient kernels read: with the weight gradient on its own stream a ring buffer (one per
-            # backward call), otherwise the stream's scratch
-            nonlocal dy_slot
-            if wst is None:
-                return scratch('conv_ws_dy', nfloats, x.device)
-            if dy_slot is None:
-                dy_slot = _dy_ws_acquire(nfloats, x.device)
-            assert dy_slot.t.numel() >= nfloats
-            return dy_slot.t
+        use_act = ctx.act != ACT_NONE and not ctx.act_bwd_fused
+        if head is not None and not (fused_dy and plan.supports('muvo_conv_prepare_dy_head_supported', head[1].shape[0])):
+            # no fused preamble for this shape: materialise the head's data gradient (dy + W_head^T dlogits)
+            gl, head_w, _, head_wgrad = head
+            hd = torch.einsum('nk...,kc->nc...', gl, head_w.view(head_w.shape[0], -1))
+            dy = hd.contiguous() if dy is None else dy + hd
+            head_wgrad()
+            head = None
         if dyp is not None:
-            if not (fused_dy and head is None and bias is None and (ctx.act == ACT_NONE or ctx.act_bwd_fused)
-                    and dyp[0].numel() * 4 >= max(wsb[1], wsb[3]) and dyp[1] == _stream_key(x.device)):
+            if not (fused_dy and head is None and ctx.bias is None and not use_act
+                    and dyp[0].numel() >= plan.dy_planes_floats and dyp[1] == _stream_key(x.device)):
                 raise RuntimeError('muvo_hip: a gradient that exists only as split planes reached a convolution backward that cannot read them')
-            ws_dy_fused = dyp[0]
-            dz = dy = dyp[0]          # (pointer stand-in: the bf16x3 kernels read the planes only)
-        elif fused_dy:
-            ws_dy_fused = dy_workspace((max(wsb[1], wsb[3]) + 3) // 4)
-            use_act = ctx.act != ACT_NONE and not ctx.act_bwd_fused
-            if head is not None:
-                # with an activation the pass reads y anyway: the head's weight / bias gradient rides along
-                ride = use_act and head_w.requires_grad
-                if not ride:
-                    head_wgrad()
-                _ck(L.muvo_conv_prepare_dy_head(C.byref(d), _f(y) if use_act else None, _f(dy) if dy is not None else None,
-                                                _f(gl.contiguous()), _f(head_w.contiguous().view(co, -1)), co,
-                                                ctx.act if use_act else ACT_NONE, _fl(ctx.slope), _p(ws_dy_fused),
-                                                _f(grad_of(bias)) if bias is not None else None,
-                                                _f(grad_of(head_w)) if ride else None,
-                                                _f(grad_of(head_b)) if (ride and head_b is not None) else None, _st()))
-                if dy is None:
-                    dy = y if y is not None else x     # placeholder pointer: the bf16x3 kernels read the planes only
-            else:
-                _ck(L.muvo_conv_prepare_dy(C.byref(d), _f(y) if use_act else None, _f(dy), ctx.act if use_act else ACT_NONE,
-                                           _fl(ctx.slope), _p(ws_dy_fused), _f(grad_of(bias)) if bias is not None else None,
-                                           _st()))
-            dz = dy   # not read by the bf16x3 kernels
-        elif ctx.act != ACT_NONE and not ctx.act_bwd_fused:
+            return dyp[0], dyp[0]          # (dz: pointer stand-in)
+        if fused_dy:
+            return ConvFn._split_dy(ctx, plan, x, y, dy, head, use_act, dy_ws.get(plan.dy_planes_floats))
+        if use_act:
             dz = torch.empty_like(dy)
-            _ck(L.muvo_act_bwd(_f(y), _f(dy), _f(dz), _i64(dy.numel()), ctx.act, _fl(ctx.slope), _st()))
-        else:
-            dz = dy   # no activation, or its derivative was already chained by the consumer's backward
-        dx = None
-        ws_dy, dy_split = None, False
-        if ctx.needs_input_grad[0]:
-            k = _wkey(weight)
-            if _head_alias(geom, key, 1, weight):
-                packed.dgr, packed.dgr_key, packed.dgr_plan = weight.detach().view(-1), k, key[1:]
+            _ck(lib().muvo_act_bwd(_f(y), _f(dy), _f(dz), _i64(dy.numel()), ctx.act, _fl(ctx.slope), _st()))
+            return dz, None
+        return dy, None   # no activation, or its derivative was already chained by the consumer's backward
+
+    @staticmethod
+    def _split_dy(ctx, plan, x, y, dy, head, use_act, planes):
+        """The fused split pass: planes <- split(act'(y) * (dy + the head's data gradient)), bias gradient accumulated.
+        -> (pointer stand-in for dz, planes)"""
+        L, d, bias = lib(), C.byref(plan.desc), ctx.bias
+        act = ctx.act if use_act else ACT_NONE
+        if head is None:
+            _ck(L.muvo_conv_prepare_dy(d, _f(y) if use_act else None, _f(dy), act, _fl(ctx.slope), _p(planes),
+                                       _f(grad_of(bias)) if bias is not None else None, _st()))
+            return dy, planes
+        gl, head_w, head_b, head_wgrad = head
+        co = head_w.shape[0]
+        # with an activation the pass reads y anyway: the head's weight / bias gradient rides along
+        ride = use_act and head_w.requires_grad
+        if not ride:
+            head_wgrad()
+        _ck(L.muvo_conv_prepare_dy_head(d, _f(y) if use_act else None, _f(dy) if dy is not None else None,
+                                        _f(gl.contiguous()), _f(head_w.contiguous().view(co, -1)), co, act, _fl(ctx.slope),
+                                        _p(planes), _f(grad_of(bias)) if bias is not None else None,
+                                        _f(grad_of(head_w)) if ride else None,
+                                        _f(grad_of(head_b)) if (ride and head_b is not None) else None, _st()))
+        if dy is None:
+            dy = y if y is not None else x     # placeholder pointer: the bf16x3 kernels read the planes only
+        return dy, planes
+
+    @staticmethod
+    def _data_grad(ctx, plan, x, dz, planes, fused_dy, dy_ws):
+        """-> (dx, the dy workspace the kernel used: the given planes, or where it split dz itself; None if it needs none)"""
+        wp = _packed_weight(plan, ctx.packed, ctx.weight, 1)
+        dx = torch.empty(x.shape, device=dz.device, dtype=torch.float32)
+        e1 = _bracket(plan, 'dgrad') if KERNEL_TIMING is not None else None
+        if planes is None and (plan.ws_dgrad_dy > 0 or plan.ws_wgrad_dy > 0):
+            planes = dy_ws.get(plan.dy_planes_floats)
+        _ck(lib().muvo_conv_dgrad(C.byref(plan.desc), _f(dz), _f(wp), _f(dx), _p(planes), 1 if fused_dy else 0, _st()))
+        if e1 is not None:
+            e1.record()
+        return dx, planes
+
+    @staticmethod
+    def _weight_grad(ctx, plan, x, y, dz, ws_dy, dy_is_split, fused_dy, dy_ws):
+        """dy_is_split: ws_dy already holds the split planes of dz"""
+        bias = ctx.bias
+        gw = grad_of(ctx.weight)
+        db = grad_of(bias) if (bias is not None and not fused_dy) else None   # fused_dy: already accumulated
+        ws_x = ctx.ws_x
+        x_ph = getattr(ctx, 'x_is_placeholder', False)
+        xptr = ws_x if x_ph else x            # a planes-only input has no fp32 storage: the kernels read ctx.ws_x (flags bit 0)
+        flags = (1 if ws_x is not None else 0) | (2 if (dy_is_split and plan.ws_wgrad_dy > 0) else 0)
+        with _on_wgrad_stream(dy_ws.wst, x.device, (xptr, y, dz, ws_x, ctx.aff), dy_ws.slot):
+            ws = scratch_zeroed('wgrad', plan.pack_fwd, x.device)         # (per stream)
+            e1 = _bracket(plan, 'wgrad') if KERNEL_TIMING is not None else None
+            if ws_x is None and plan.ws_wgrad_x:
+                ws_x = scratch('conv_ws', (plan.ws_wgrad_x + 3) // 4, x.device)
+            if plan.ws_wgrad_dy and ws_dy is None:
+                ws_dy = scratch('conv_ws_dy', (plan.ws_wgrad_dy + 3) // 4, x.device)
+            if ctx.aff is not None:
+                _ck(lib().muvo_conv_wgrad_affine(C.byref(plan.desc), _f(x), _f(ctx.aff), _f(dz), _f(gw), _f(db), _st()))
             else:
-                if packed.dgr is None or packed.dgr.numel() < df or _is_alias(packed.dgr, weight):
-                    packed.dgr = torch.empty(df, device=x.device, dtype=torch.float32)
-                    packed.dgr_key = None
-                if packed.dgr_key != k or packed.dgr_plan != key[1:]:
-                    _ck(L.muvo_conv_pack_weights(C.byref(d), _f(weight), None, _f(packed.dgr), _st()))
-                    packed.dgr_key, packed.dgr_plan = k, key[1:]
-            dx = torch.empty(x.shape, device=dz.device, dtype=torch.float32)
-            kt = KERNEL_TIMING
-            if kt is not None:
-                import math
-                e0, e1 = kt.bracket(FAMILY[geom.tclass[(x.shape[0], ctx.in_sz, _plan_epoch[0])][1]] + ':dgrad',
-                                    _conv_flops(geom, x.shape[0], ctx.in_sz, out_sz),
-                                    1 if geom.transposed else math.prod(geom.stride), _conv_tag(geom, x.shape[0], ctx.in_sz),
-                                    _conv_bytes(geom, x.shape[0], ctx.in_sz, out_sz))
-                e0.record()
-            nb = max(wsb[1], wsb[3])
-            ws_dy = (ws_dy_fused if dyp is not None else dy_workspace((nb + 3) // 4)) if nb else None
-            dy_split = wsb[1] > 0
-            _ck(L.muvo_conv_dgrad(C.byref(d), _f(dz), _f(packed.dgr), _f(dx), _p(ws_dy), 1 if fused_dy else 0, _st()))
-            if kt is not None:
+                assert not x_ph or (flags & 1)
+                _ck(lib().muvo_conv_wgrad(C.byref(plan.desc), _f(xptr), _f(dz), _f(ws), _f(gw), _f(db), _p(ws_x), _p(ws_dy),
+                                          flags, _st()))
+            if e1 is not None:
                 e1.record()
-        if weight.requires_grad:
-            gw = grad_of(weight)
-            db = grad_of(bias) if (bias is not None and not fused_dy) else None   # fused_dy: already accumulated
-            ws_x = ctx.ws_x
-            flags = (1 if ws_x is not None else 0) | (2 if (dy_split and wsb[3] > 0) else 0)
-            cur = torch.cuda.current_stream(x.device)
-            if wst is not None and wst != cur:
-                # everything the weight gradient reads is queued on the current stream by now; it starts behind that point
-                wst.wait_stream(cur)
-                for t in (xptr, y, dz, ctx.ws_x, ctx.aff):
-                    if t is not None:
-                        t.record_stream(wst)
-                wctx = torch.cuda.stream(wst)
-                wctx.__enter__()
-            else:
-                wctx = None
-            try:
-                ws = scratch_zeroed('wgrad', ff, x.device)         # (per stream)
-                kt = KERNEL_TIMING
-                if kt is not None:
-                    import math
-                    e0, e1 = kt.bracket(FAMILY[geom.tclass[(x.shape[0], ctx.in_sz, _plan_epoch[0])][2]] + ':wgrad',
-                                        _conv_flops(geom, x.shape[0], ctx.in_sz, out_sz),
-                                        math.prod(geom.stride) if geom.transposed else 1, _conv_tag(geom, x.shape[0], ctx.in_sz),
-                                        _conv_bytes(geom, x.shape[0], ctx.in_sz, out_sz))
-                    e0.record()
-                if ws_x is None and wsb[2]:
-                    ws_x = scratch('conv_ws', (wsb[2] + 3) // 4, x.device)
-                if wsb[3] and ws_dy is None:
-                    ws_dy = scratch('conv_ws_dy', (wsb[3] + 3) // 4, x.device)
-                if ctx.aff is not None:
-                    _ck(L.muvo_conv_wgrad_affine(C.byref(d), _f(x), _f(ctx.aff), _f(dz), _f(gw), _f(db), _st()))
-                else:
-                    assert not x_ph or (flags & 1)
-                    _ck(L.muvo_conv_wgrad(C.byref(d), _f(xptr), _f(dz), _f(ws), _f(gw), _f(db), _p(ws_x), _p(ws_dy), flags, _st()))
-                if kt is not None:
-                    e1.record()
-                if wctx is not None and dy_slot is not None:
-                    dy_slot.done = torch.cuda.Event()
-                    dy_slot.done.record(wst)
-            finally:
-                if wctx is not None:
-                    wctx.__exit__(None, None, None)
-        return dx, None, None, None, None, None, None, None, None, None, None
 
 
 def conv(x, weight, bias, geom, packed, act=ACT_NONE, slope=0.0, act_bwd_fused=False, moments=None, lazy=None):
@@ -1294,15 +1340,10 @@ def conv(x, weight, bias, geom, packed, act=ACT_NONE, slope=0.0, act_bwd_fused=F
         return ConvFn.apply(x, weight, bias, geom, packed, act, slope, act_bwd_fused, moments, lazy[0], lazy[1])
     y = ConvFn.apply(x, weight, bias, geom, packed, act, slope, act_bwd_fused, moments)
     if (BN_PLANES and bias is None and act == ACT_NONE and moments is None and x.requires_grad and weight.requires_grad
-            and torch.is_grad_enabled()):
+            and torch.is_grad_enabled() and geom.plan_for(x).dy_planes):
         # the backward of this convolution reads dy as split planes (ConvFn._backward: fused_dy): a BatchNorm behind it may hand
         # its dx over in that form (bn_act(from_conv=True))
-        n = x.shape[0]
-        in_sz = tuple(x.shape[2:]) if geom.nd == 3 else (1,) + tuple(x.shape[2:])
-        key = (n, in_sz, _plan_epoch[0])
-        fam, wsb = geom.family.get(key), geom.ws_bytes.get(key)
-        if fam is not None and fam[1] == 1 and fam[2] == 1 and wsb[1] > 0 and wsb[3] > 0:
-            y._muvo_dy_planes_ok = True
+        y._muvo_dy_planes_ok = True
     return y
 
 
@@ -1314,14 +1355,7 @@ def conv_affine_supported(x, geom, moments):
     AdaIN as a per-(n, channel) scale / shift (muvo_conv_forward_affine)?  Needs the statistics from the producer's epilogue."""
     if not CONV_AFFINE or moments is None or x.dim() != 5 or not (x.requires_grad and torch.is_grad_enabled()):
         return False
-    n = x.shape[0]
-    in_sz = tuple(x.shape[2:])
-    d = geom.plan(n, in_sz)[0]
-    key = ('affine', n, in_sz, _plan_epoch[0])
-    ok = geom.family.get(key)
-    if ok is None:
-        ok = geom.family[key] = bool(lib().muvo_conv_affine_supported(C.byref(d)))
-    return ok
+    return geom.plan_for(x).supports('muvo_conv_affine_supported')
 
 
 CONV_MOMENTS = os.environ.get('MUVO_CONV_MOMENTS', '1') != '0'
@@ -1331,17 +1365,9 @@ def conv_moments_buffer(x, geom):
     """A zeroed (N, Cout, 2) float64 buffer if the convolution `geom` on input x can deliver the instance-norm statistics of
     its output from its epilogue (muvo_conv_forward_moments), else None.  The buffer is per layer and stays all-zero between
     uses (muvo_adain_fwd_moments clears it)."""
-    if not CONV_MOMENTS:
+    if not CONV_MOMENTS or not geom.plan_for(x).supports('muvo_conv_forward_moments_supported'):
         return None
     n = x.shape[0]
-    in_sz = tuple(x.shape[2:]) if geom.nd == 3 else (1,) + tuple(x.shape[2:])
-    d = geom.plan(n, in_sz)[0]
-    key = ('moments', n, in_sz, _plan_epoch[0])
-    ok = geom.family.get(key)
-    if ok is None:
-        ok = geom.family[key] = bool(lib().muvo_conv_forward_moments_supported(C.byref(d)))
-    if not ok:
-        return None
     cache = geom.__dict__.setdefault('_moments', {})       # one zeroed buffer per batch size (training / validation / imagination)
     buf = cache.get((n, x.device))
     if buf is None:
@@ -1373,37 +1399,28 @@ class HeadBranchFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, gx, gy):
         x, _ = ctx.saved_tensors
-        geom, packed, weight, bias = ctx.geom, ctx.packed, ctx.weight, ctx.bias
+        weight, bias = ctx.weight, ctx.bias
         if gy is None:
-            return gx, None, None, None, None
-        d, out_sz, ff, df = geom.plan(x.shape[0], ctx.in_sz)
-        L = lib()
+            return (gx,) + (None,) * 4
+        plan = ctx.geom.plan_for(x)
+        L, d = lib(), C.byref(plan.desc)
         gy = gy.contiguous()
         dx = None
         if ctx.needs_input_grad[0]:
-            k, pkey = _wkey(weight), (ctx.in_sz, _plan_epoch[0])
-            if _head_alias(geom, (x.shape[0], ctx.in_sz, _plan_epoch[0]), 1, weight):
-                packed.dgr, packed.dgr_key, packed.dgr_plan = weight.detach().view(-1), k, pkey
-            else:
-                if packed.dgr is None or packed.dgr.numel() < df or _is_alias(packed.dgr, weight):
-                    packed.dgr = torch.empty(df, device=x.device, dtype=torch.float32)
-                    packed.dgr_key = None
-                if packed.dgr_key != k or packed.dgr_plan != pkey:
-                    _ck(L.muvo_conv_pack_weights(C.byref(d), _f(weight), None, _f(packed.dgr), _st()))
-                    packed.dgr_key, packed.dgr_plan = k, pkey
+            wp = _packed_weight(plan, ctx.packed, weight, 1)
             if gx is not None and gx.is_contiguous() and _grad_is_private(gx):
                 dx = gx            # a fresh tensor made by the trunk's backward for this one consumer: accumulated in place
-                _ck(L.muvo_conv_dgrad_accumulate(C.byref(d), _f(gy), _f(packed.dgr), _f(dx), _st()))
+                _ck(L.muvo_conv_dgrad_accumulate(d, _f(gy), _f(wp), _f(dx), _st()))
             else:
                 dx = torch.empty_like(x)
-                _ck(L.muvo_conv_dgrad(C.byref(d), _f(gy), _f(packed.dgr), _f(dx), None, 0, _st()))
+                _ck(L.muvo_conv_dgrad(d, _f(gy), _f(wp), _f(dx), None, 0, _st()))
                 if gx is not None:
                     dx = dx + gx
         if weight.requires_grad:
-            ws = scratch_zeroed('wgrad', ff, x.device)
-            _ck(L.muvo_conv_wgrad(C.byref(d), _f(x), _f(gy), _f(ws), _f(grad_of(weight)), _f(grad_of(bias)) if bias is not None else None,
+            ws = scratch_zeroed('wgrad', plan.pack_fwd, x.device)
+            _ck(L.muvo_conv_wgrad(d, _f(x), _f(gy), _f(ws), _f(grad_of(weight)), _f(grad_of(bias)) if bias is not None else None,
                                   None, None, 0, _st()))
-        return dx, None, None, None, None
+        return (dx,) + (None,) * 4
 
 
 class ConvHeadFn(torch.autograd.Function):
@@ -1415,47 +1432,26 @@ class ConvHeadFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, weight, bias, geom, packed, act, slope, head_w, head_b, head_geom, head_packed):
-        n0 = x.shape[0]
-        in_sz0 = tuple(x.shape[2:]) if geom.nd == 3 else (1,) + tuple(x.shape[2:])
-        d0, out_sz0 = geom.plan(n0, in_sz0)[:2]
+        plan = geom.plan_for(x)
         co = head_geom.cout
-        fkey = ('head_fwd', n0, in_sz0, co, _plan_epoch[0])
-        fused = geom.family.get(fkey)
-        if fused is None:
-            fused = geom.family[fkey] = bool(lib().muvo_conv_forward_head_supported(C.byref(d0), co))
+        fused = plan.supports('muvo_conv_forward_head_supported', co)
         logits = None
         if fused:
             # the head's forward rides on the stage's epilogue (muvo_conv_forward_head): no pass over y
-            logits = torch.empty((n0, co) + (out_sz0 if geom.nd == 3 else out_sz0[1:]), device=x.device, dtype=torch.float32)
+            logits = torch.empty((plan.n, co) + plan.oshape[2:], device=x.device, dtype=torch.float32)
             ctx._head_fwd = (head_w.contiguous().view(co, -1), head_b, logits)
         y = ConvFn.forward(ctx, x, weight, bias, geom, packed, act, slope)
         ctx._head_fwd = None
         ctx.save_for_backward(x, y)            # y is needed for the head's weight gradient even when act needs no derivative
-        if fused:
-            ctx.head = (head_w, head_b, head_geom, tuple(y.shape[2:]) if head_geom.nd == 3 else (1,) + tuple(y.shape[2:]))
-            ctx.set_materialize_grads(False)
-            return y, logits
+        ctx.head = (head_w, head_b, head_geom)
         # an output nobody differentiates through (the last stage's feature map has the head as its only consumer) arrives
         # as None in backward instead of a zero tensor of its size (1.36 GB filled, then read by the split pass)
         ctx.set_materialize_grads(False)
-        n = y.shape[0]
-        hin = tuple(y.shape[2:]) if head_geom.nd == 3 else (1,) + tuple(y.shape[2:])
-        hd, hout, hff, _ = head_geom.plan(n, hin)
-        L = lib()
-        k, pkey = _wkey(head_w), (hin, _plan_epoch[0])
-        if _head_alias(head_geom, (n, hin, _plan_epoch[0]), 0, head_w):
-            head_packed.fwd, head_packed.fwd_key, head_packed.fwd_plan = head_w.detach().view(-1), k, pkey
-        else:
-            if head_packed.fwd is None or head_packed.fwd.numel() < hff or _is_alias(head_packed.fwd, head_w):
-                head_packed.fwd = torch.empty(hff, device=x.device, dtype=torch.float32)
-                head_packed.fwd_key = None
-            if head_packed.fwd_key != k or head_packed.fwd_plan != pkey:
-                _ck(L.muvo_conv_pack_weights(C.byref(hd), _f(head_w), _f(head_packed.fwd), None, _st()))
-                head_packed.fwd_key, head_packed.fwd_plan = k, pkey
-                _PACKS.register((id(head_packed), pkey), ('conv', hd, head_w, weakref.ref(head_packed), pkey))
-        logits = torch.empty((n, head_geom.cout) + (hout if head_geom.nd == 3 else hout[1:]), device=x.device, dtype=torch.float32)
-        _ck(L.muvo_conv_forward(C.byref(hd), _f(y), _f(head_packed.fwd), _f(head_b), _f(logits), ACT_NONE, _fl(0.0), None, _st()))
-        ctx.head = (head_w, head_b, head_geom, hin)
+        if not fused:
+            hplan = head_geom.plan_for(y)
+            hwp = _packed_weight(hplan, head_packed, head_w, 0)
+            logits = torch.empty(hplan.oshape, device=x.device, dtype=torch.float32)
+            _ck(lib().muvo_conv_forward(C.byref(hplan.desc), _f(y), _f(hwp), _f(head_b), _f(logits), ACT_NONE, _fl(0.0), None, _st()))
         return y, logits
 
     @staticmethod
@@ -1465,14 +1461,14 @@ class ConvHeadFn(torch.autograd.Function):
                 return (None,) * 11
             return ConvFn._backward(ctx, gy, None)[:7] + (None,) * 4
         x, y = ctx.saved_tensors
-        head_w, head_b, head_geom, hin = ctx.head
-        hd, _, hff, _ = head_geom.plan(y.shape[0], hin)
+        head_w, head_b, head_geom = ctx.head
+        hplan = head_geom.plan_for(y)
         gl = gl.contiguous()
 
         def head_wgrad():        # the head's own weight-gradient pass (when it cannot ride on the split pass)
             if head_w.requires_grad:
-                ws = scratch_zeroed('wgrad', hff, x.device)
-                _ck(lib().muvo_conv_wgrad(C.byref(hd), _f(y), _f(gl), _f(ws), _f(grad_of(head_w)),
+                ws = scratch_zeroed('wgrad', hplan.pack_fwd, x.device)
+                _ck(lib().muvo_conv_wgrad(C.byref(hplan.desc), _f(y), _f(gl), _f(ws), _f(grad_of(head_w)),
                                           _f(grad_of(head_b)) if head_b is not None else None, None, None, 0, _st()))
         return ConvFn._backward(ctx, gy, (gl, head_w, head_b, head_wgrad))[:7] + (None,) * 4
 
@@ -1482,15 +1478,12 @@ def conv_head_supported(x, geom, head_geom, act_bwd_fused=False):
     kernels in both gradient directions (its backward preamble is the split pass that absorbs the head's data gradient)."""
     if not CONV_HEAD or not (x.requires_grad and torch.is_grad_enabled()) or act_bwd_fused:
         return False
-    n = x.shape[0]
-    in_sz = tuple(x.shape[2:]) if geom.nd == 3 else (1,) + tuple(x.shape[2:])
-    d, out_sz, _, _ = geom.plan(n, in_sz)
-    fam = geom.family[(n, in_sz, _plan_epoch[0])]
-    if not (fam[1] == 1 and fam[2] == 1):
+    plan = geom.plan_for(x)
+    if not (plan.fam_dgrad == 1 and plan.fam_wgrad == 1):
         return False
-    head_geom.plan(n, out_sz)
-    hf = head_geom.family[(n, out_sz, _plan_epoch[0])]
-    return hf[0] == 3 and hf[2] == 3 and bool(lib().muvo_conv_prepare_dy_head_supported(C.byref(d), head_geom.cout))
+    hplan = head_geom.plan(plan.n, plan.out_sz)
+    return (hplan.fam_fwd == 3 and hplan.fam_wgrad == 3
+            and plan.supports('muvo_conv_prepare_dy_head_supported', head_geom.cout))
 
 
 CONV_HEAD = os.environ.get('MUVO_CONV_HEAD', '1') != '0'
@@ -1502,11 +1495,8 @@ def conv_head(x, weight, bias, geom, packed, act, slope, head_w, head_b, head_ge
 
 def head_branch(x, weight, bias, geom, packed):
     """(x, head(x)); fused backward when the head runs on the 1x1 head kernels, plain conv otherwise."""
-    n = x.shape[0]
-    in_sz = tuple(x.shape[2:]) if geom.nd == 3 else (1,) + tuple(x.shape[2:])
-    geom.plan(n, in_sz)
-    fam = geom.family[(n, in_sz, _plan_epoch[0])]
-    if fam[0] == 3 and fam[1] == 3 and fam[2] == 3 and x.requires_grad and torch.is_grad_enabled():
+    plan = geom.plan_for(x)
+    if plan.fam_fwd == 3 and plan.fam_dgrad == 3 and plan.fam_wgrad == 3 and x.requires_grad and torch.is_grad_enabled():
         return HeadBranchFn.apply(x, weight, bias, geom, packed)
     return x, conv(x, weight, bias, geom, packed)
 
@@ -1624,14 +1614,9 @@ def flush_bn_counters():
 def conv_reads_planes(conv, x_shape, need_wgrad):
     """will the convolution module `conv` read split planes of an input of shape x_shape in forward (and, if a backward follows,
     in its weight gradient)?  -> (forward reads planes, and the fp32 values are needed by nobody inside the convolution)"""
-    geom = conv.geom
-    n = x_shape[0]
-    in_sz = tuple(x_shape[2:]) if geom.nd == 3 else (1,) + tuple(x_shape[2:])
-    geom.plan(n, in_sz)
-    key = (n, in_sz, _plan_epoch[0])
-    fam, wsb = geom.family[key], geom.ws_bytes[key]
-    fwd = fam[0] == 1 and wsb[0] > 0
-    return fwd, fwd and (not need_wgrad or (fam[2] == 1 and wsb[2] > 0 and _KEEP_WS))
+    plan = conv.geom.plan_for(x_shape)
+    fwd = plan.fam_fwd == 1 and plan.ws_fwd_x > 0
+    return fwd, fwd and (not need_wgrad or (plan.fam_wgrad == 1 and plan.ws_wgrad_x > 0 and _KEEP_WS))
 
 
 def bn_act(x, bn, residual=None, res_mode=1, relu=True, consumers=(), sole_consumer=False, from_conv=False):

@@ -1247,7 +1247,7 @@ def test_stem_convolution_kernel(dev, cin, shape):
         y = m(x.to(dev))
         d = m.geom.plan(n, (1, h, w))[0]
         assert ops.lib().muvo_stem_conv_supported(C.byref(d)) == 1
-        assert m.geom.family[('stem', n, (1, h, w), ops._plan_epoch[0])] is True
+        assert m.geom.plan(n, (1, h, w)).supports('muvo_stem_conv_supported') is True and y.grad_fn.stem is True
         wc = m.weight.detach().cpu().clone().requires_grad_(True)
         yr = F.conv2d(x, wc, None, 2, 3)
         assert y.shape == yr.shape

@@ -41,8 +41,9 @@ def main():
             g = torch.randn_like(y)
             m.weight.grad, m.bias.grad = torch.zeros_like(m.weight), torch.zeros_like(m.bias)
             y.backward(g)
-            key = (nb, (1,) * (3 - nd) + tuple(isz), ops._plan_epoch[0])
-            out[mode] = (y.detach(), x.grad, m.weight.grad.clone(), m.bias.grad.clone(), m.geom.family.get(key))
+            plan = m.geom.plan_for(x)
+            out[mode] = (y.detach(), x.grad, m.weight.grad.clone(), m.bias.grad.clone(),
+                         (plan.fam_fwd, plan.fam_dgrad, plan.fam_wgrad))
             del m, x, y, g
         a, b = out[ops.CONV_F32], out[ops.CONV_BF16X3]
         errs = [rel(b[i], a[i]) for i in range(4)]

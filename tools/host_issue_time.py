@@ -1,7 +1,7 @@
 """Host issue time of one training step: time until the Python side has queued everything vs. time until the GPU is done.
     python tools/host_issue_time.py [batch] [seq]   (batch 1, seq 1 makes the GPU work tiny: the total is then the host cost)"""
 import os, sys, time, torch
-sys.path.insert(0, '/root/repo')
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from muvo_amd import ops
 from muvo_amd.config import base_1d_cfg
 from muvo_amd.data.synthetic import make_batch

@@ -74,9 +74,10 @@ def main():
         L = ops.lib()
         geom, packed = m.geom, m._packed
         in_sz = tuple(sz) if len(sz) == 3 else (1,) + tuple(sz)
-        d, out_sz, ff, df = geom.plan(args.n, in_sz)
+        plan = geom.plan(args.n, in_sz)
+        d = plan.desc
         y.backward(g)  # packs dgrad weights, warms everything
-        ws = ops.scratch_zeroed('wgrad', ff, dev)
+        ws = ops.scratch_zeroed('wgrad', plan.pack_fwd, dev)
         import ctypes as C
 
         def run(fn):
@@ -90,11 +91,8 @@ def main():
             torch.cuda.synchronize()
             return e0.elapsed_time(e1) / args.iters
         xd, gd = x.detach(), g
-        wb = geom.ws_bytes[(args.n, in_sz, ops._plan_epoch[0])]
-        wsf = torch.empty(wb[0] // 4 + 1, device=dev) if wb[0] else None
-        wsd = torch.empty(wb[1] // 4 + 1, device=dev) if wb[1] else None
-        wsx = torch.empty(wb[2] // 4 + 1, device=dev) if wb[2] else None
-        wsy = torch.empty(wb[3] // 4 + 1, device=dev) if wb[3] else None
+        wsf, wsd, wsx, wsy = (torch.empty(nb // 4 + 1, device=dev) if nb else None
+                              for nb in (plan.ws_fwd_x, plan.ws_dgrad_dy, plan.ws_wgrad_x, plan.ws_wgrad_dy))
         dx = torch.empty_like(xd)
         fns = {
             'fwd': lambda: ops._ck(L.muvo_conv_forward(C.byref(d), ops._f(xd), ops._f(packed.fwd), ops._f(m.bias), ops._f(y.detach()), 0, ops._fl(0.0), ops._p(wsf), ops._st())),
