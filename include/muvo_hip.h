@@ -464,6 +464,36 @@ int muvo_range_projection(const float* points_xyz, const uint8_t* obj_tag, const
                           float* xyzd, uint8_t* seg, void* stream);
 int muvo_voxel_grid(const int64_t* rows, int64_t Q, const uint8_t* remap, int X, int Y, int Z, uint32_t* scratch, uint8_t* voxels,
                     void* stream);
+/* ---- voxel labels from raw sensor data: the reference's offline step data/generate_voxels.py::voxelize_one ->
+ * data/data_preprocessing.py::merge_pcd + voxel_filter, for F frames per call ----
+ * depth_semantic (F,H,W,4) uint8: R, G, B = 24-bit depth code, A = CARLA tag; points_xyz (F,Pmax,3) float32 in the lidar sensor
+ * frame, obj_tag (F,Pmax) uint8, num_points (F) int32 or NULL (= Pmax everywhere; rows beyond num_points[f] are never read).
+ * Camera pixels are unprojected (depth < 1000, camera-frame range < max_range) and moved to the ego frame, lidar points by
+ * convert_coor_lidar; points inside the ego-vehicle box are dropped (mask_ego); b = p + off must lie in [0, hi) on every axis;
+ * np.divmod(b, res) gives voxel and remainder; every occupied voxel takes the raw tag of the point with the smallest squared
+ * remainder (exact ties: the lowest global index, camera pixels row-major first, lidar points after them), or 6 if any of its
+ * points has tag 6 (road line).  All geometry in float64, operation by operation as the reference; integer atomics only, so the
+ * result is independent of the execution order.
+ * Outputs (either may be NULL, not both):
+ *   rows (F,cap,4) int64 x, y, z, tag ascending in x + y*Dx + z*Dx*Dy, counts (F) int32 = rows written per frame
+ *     (cap >= min(H*W + Pmax, Dx*Dy*Dz) holds every possible result);
+ *   dense (F,Dx,Dy,Dz) uint8 = remap[tag == 255 ? 0 : tag], 0 where empty: what muvo_voxel_grid makes of the rows.
+ * scratch: muvo_voxelize_scratch_bytes(F, Dx, Dy, Dz) bytes (15 per voxel and frame; -1 for sizes the entry refuses). */
+typedef struct muvo_voxelize_geom {
+  double cam[3];      /* float32(forward), float32(-right), float32(up) of the camera position, widened (convert_coor_img) */
+  double lidar[3];    /* lidar position forward, right, up */
+  double f, cx, cy;   /* W / (2 tan(fov pi / 360)), W / 2, H / 2 */
+  double max_range;
+  double ego_lo[3], ego_hi[3];
+  double off[3];      /* offset + res * size / 2 */
+  double hi[3];       /* size * res */
+  double res;
+  int32_t mask_ego, H, W, Dx, Dy, Dz;
+} muvo_voxelize_geom;
+int64_t muvo_voxelize_scratch_bytes(int F, int Dx, int Dy, int Dz);
+int muvo_voxelize_frames(const uint8_t* depth_semantic, const float* points_xyz, const uint8_t* obj_tag, const int32_t* num_points, int F,
+                         int64_t Pmax, const muvo_voxelize_geom* geom, const uint8_t* remap, void* scratch, int64_t* rows, int64_t cap,
+                         int32_t* counts, uint8_t* dense, void* stream);
 /* convert_instance_mask_to_center_and_offset_label (muvo/utils/instance_utils.py:4-35, called from
  * PreProcess.prepare_bev_labels, preprocess.py:68-100): instance ids (F,H,W) uint8 (0 = background) -> centre heat map
  * center (F,H,W) = max over the instances of the frame of exp(-d^2 / sigma^2) around the rounded centroid, and offset (F,2,H,W)

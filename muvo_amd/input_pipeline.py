@@ -46,3 +46,76 @@ def voxel_grid(voxel_data, size=(192, 192, 64)):
     ops._ck(ops.lib().muvo_voxel_grid(ops._p(rows), ops._i64(rows.shape[0]), ops._p(label_remap(dev)), size[0], size[1], size[2],
                                      ops._p(scratch), ops._p(vox), ops._st()))
     return vox
+
+
+class VoxelizeGeom(C.Structure):
+    """muvo_voxelize_geom of include/muvo_hip.h."""
+    _fields_ = [('cam', C.c_double * 3), ('lidar', C.c_double * 3), ('f', C.c_double), ('cx', C.c_double), ('cy', C.c_double),
+                ('max_range', C.c_double), ('ego_lo', C.c_double * 3), ('ego_hi', C.c_double * 3), ('off', C.c_double * 3),
+                ('hi', C.c_double * 3), ('res', C.c_double), ('mask_ego', C.c_int32), ('H', C.c_int32), ('W', C.c_int32),
+                ('Dx', C.c_int32), ('Dy', C.c_int32), ('Dz', C.c_int32)]
+
+
+def voxelize_geometry(H, W, *, camera_position, lidar_position, fov, voxel_resolution, voxel_size, offset, mask_ego=True,
+                      max_range=100.0):
+    """The host-side constants of depth_lidar_voxels, each computed in numpy float64 in the order the reference computes it
+    (data_preprocessing.py:86-89 focal length, :108-113 float32 camera matrix, :134-135 ego box, :173-178 grid offset and
+    extent): the kernels compare against them exactly."""
+    size, res = np.asarray(voxel_size), np.asarray(voxel_resolution)
+    off = np.asarray(offset, dtype=np.float64) + res * size / 2
+    hi = size * res
+    forward, right, up = camera_position
+    cam = np.float32([forward, -right, up]).astype(np.float64)
+    x, y, z = EGO_VEHICLE_DIMENSION
+    g = VoxelizeGeom()
+    g.cam[:], g.lidar[:] = cam.tolist(), [float(v) for v in lidar_position]
+    g.f, g.cx, g.cy = float(W / (2.0 * np.tan(fov * np.pi / 360.0))), W / 2.0, H / 2.0
+    g.max_range = float(max_range)
+    g.ego_lo[:], g.ego_hi[:] = [-x / 2, -y / 2, 0.0], [x / 2, y / 2, z]
+    g.off[:], g.hi[:], g.res = off.tolist(), hi.tolist(), float(res)
+    g.mask_ego, g.H, g.W = int(bool(mask_ego)), int(H), int(W)
+    g.Dx, g.Dy, g.Dz = (int(v) for v in size)
+    return g
+
+
+def depth_lidar_voxels(depth_semantic, points_xyz, obj_tag, num_points=None, *, camera_position, lidar_position, fov,
+                       voxel_resolution, voxel_size, offset, mask_ego=True, max_range=100.0, dense=False, frames_per_call=4):
+    """Voxel labels from raw sensor data (the reference's data/generate_voxels.py::voxelize_one, data_preprocessing.py:125-228).
+    depth_semantic (H, W, 4) or (F, H, W, 4) uint8 device tensor as PIL loads the recorder's PNG (R, G, B depth code, A = CARLA
+    tag); points_xyz (P, 3) / (F, Pmax, 3) float32 in the lidar sensor frame, obj_tag (P,) / (F, Pmax) uint8, num_points (F,)
+    valid points per frame (None: all).  dense=False: list of F int64 (Q_f, 4) tensors x, y, z, raw tag ascending in
+    x + y*Dx + z*Dx*Dy (voxel_grid takes them as they are; .to(uint16) is the reference's file content); one host read of the
+    counts per `frames_per_call` frames.  dense=True: uint8 (F, Dx, Dy, Dz), equal to voxel_grid of the rows, no host sync.
+    Exact ties of the distance are broken by the lowest index (camera pixels row-major, then lidar points)."""
+    img = depth_semantic.to(torch.uint8)
+    img = (img[None] if img.dim() == 3 else img).contiguous()
+    F, H, W = img.shape[:3]
+    assert img.dim() == 4 and img.shape[3] == 4, 'depth_semantic must be (H, W, 4) or (F, H, W, 4)'
+    dev = img.device
+    pts, tag = points_xyz.float(), obj_tag.to(torch.uint8)
+    pts, tag = (pts[None] if pts.dim() == 2 else pts).contiguous(), (tag[None] if tag.dim() == 1 else tag).contiguous()
+    Pmax = pts.shape[1]
+    assert pts.shape == (F, Pmax, 3) and tag.shape == (F, Pmax), 'points_xyz (F, Pmax, 3) and obj_tag (F, Pmax) must match the frames'
+    npt = None if num_points is None else torch.as_tensor(num_points, device=dev).to(torch.int32).reshape(F).contiguous()
+    g = voxelize_geometry(H, W, camera_position=camera_position, lidar_position=lidar_position, fov=fov,
+                          voxel_resolution=voxel_resolution, voxel_size=voxel_size, offset=offset, mask_ego=mask_ego,
+                          max_range=max_range)
+    n = g.Dx * g.Dy * g.Dz
+    cap = max(1, min(H * W + Pmax, n))
+    step = max(1, min(int(frames_per_call), F))          # bounds the scratch: 15 bytes per voxel and frame in flight
+    L = ops.lib()
+    nbytes = L.muvo_voxelize_scratch_bytes(step, g.Dx, g.Dy, g.Dz)
+    scratch = ops.scratch('voxelize', nbytes, dev, torch.uint8) if nbytes > 0 else torch.empty(16, device=dev, dtype=torch.uint8)
+    remap = label_remap(dev)
+    out = torch.empty((F, g.Dx, g.Dy, g.Dz), device=dev, dtype=torch.uint8) if dense else []
+    for f0 in range(0, F, step):
+        f1 = min(F, f0 + step)
+        rows = None if dense else torch.empty((f1 - f0, cap, 4), device=dev, dtype=torch.int64)
+        counts = None if dense else torch.empty(f1 - f0, device=dev, dtype=torch.int32)
+        ops._ck(L.muvo_voxelize_frames(ops._p(img[f0:f1]), ops._f(pts[f0:f1]) if Pmax else None, ops._p(tag[f0:f1]) if Pmax else None,
+                                       ops._p(None if npt is None else npt[f0:f1]), f1 - f0, ops._i64(Pmax), C.byref(g), ops._p(remap),
+                                       ops._p(scratch), ops._p(rows), ops._i64(cap), ops._p(counts),
+                                       ops._p(out[f0:f1]) if dense else None, ops._st()))
+        if not dense:
+            out += [rows[i, :q].clone() for i, q in enumerate(counts.tolist())]
+    return out

@@ -77,6 +77,7 @@ EXPORTS = [
     'muvo_fake_allreduce', 'muvo_resize_bilinear_aa', 'muvo_bn_train_fwd_planes', 'muvo_bn_train_bwd_planes', 'muvo_conv_forward_planes',
     'muvo_stem_conv_supported', 'muvo_stem_conv_forward', 'muvo_stem_conv_wgrad',
     'muvo_rssm_supported', 'muvo_rssm_transposed_floats', 'muvo_rssm_scratch_floats', 'muvo_rssm_forward', 'muvo_rssm_backward',
+    'muvo_voxelize_scratch_bytes', 'muvo_voxelize_frames',
 ]
 
 
@@ -97,6 +98,7 @@ def lib():
                 L.muvo_split_planes_bytes.restype = C.c_int64
                 L.muvo_rssm_transposed_floats.restype = C.c_int64
                 L.muvo_rssm_scratch_floats.restype = C.c_int64
+                L.muvo_voxelize_scratch_bytes.restype = C.c_int64
                 for name in EXPORTS:
                     getattr(L, name)  # AttributeError if a declared symbol is missing
                 _lib = L
