@@ -24,14 +24,13 @@ __global__ void __launch_bounds__(256) spatial_loss_fwd_kernel(const float* __re
                                                                const float* __restrict__ target, long F, int Ct, long HW,
                                                                int c0, int c1, int norm, float ignore,
                                                                double* __restrict__ stats, unsigned* ticket,
-                                                               const uint8_t* __restrict__ imask) {
-  // grid = (pixel blocks, frames): no 64-bit division per pixel, four consecutive pixels per trip (16-byte loads when
-  // HW % 4 == 0), ONE workgroup reduction for both sums (few hundred workgroups: the two atomics are not contended)
+                                                               const uint8_t* __restrict__ imask, bool vec) {
+  // grid = (pixel blocks, frames): no 64-bit division per pixel, four consecutive pixels per trip (16-byte loads when `vec`:
+  // HW % 4 == 0 and 16-byte aligned pointers, decided by the launcher), ONE workgroup reduction for both sums (few hundred workgroups: the two atomics are not contended)
   __shared__ double red[2][4];
   const long f = blockIdx.y;
   const float* pf = pred + f * Ct * HW;
   const float* tf = target + f * Ct * HW;
-  const bool vec = (HW & 3) == 0;
   const long nq = (HW + 3) >> 2;
   float s = 0.f, cnt = 0.f;
   double ds = 0.0;
@@ -118,7 +117,7 @@ template <int CT>
 __global__ void __launch_bounds__(256) voxel_loss_fwd_kernel(const float* __restrict__ logits,
                                                              const uint8_t* __restrict__ target, long F, int C, long V,
                                                              const float* __restrict__ class_w, double* __restrict__ stats,
-                                                             unsigned* ticket) {
+                                                             unsigned* ticket, bool vec) {
   constexpr int NCU = CT ? CT : MAXC;     // unrolled class loops
   const int Cc = CT ? CT : C;
   __shared__ double red[4];
@@ -128,12 +127,12 @@ __global__ void __launch_bounds__(256) voxel_loss_fwd_kernel(const float* __rest
 #pragma unroll
   for (int c = 0; c < NCU; ++c) { P[c] = 0.f; Nn[c] = 0.f; T[c] = 0.f; Q[c] = 0.f; R[c] = 0.f; }
   // grid = (voxel blocks, frames): no 64-bit division per voxel; a thread takes FOUR consecutive voxels per trip (one 16-byte
-  // load per class plane + one 4-byte label load when V % 4 == 0).  fp32 thread-local accumulation over <= ~2k voxels per
+  // load per class plane + one 4-byte label load when `vec`: V % 4 == 0, logits 16-byte and labels 4-byte aligned, decided by the
+  // launcher; else scalar loads with a guarded tail).  fp32 thread-local accumulation over <= ~2k voxels per
   // thread (values in [0,1]), then fp64 combine.
   const long f = blockIdx.y;
   const float* lf = logits + f * C * V;
   const uint8_t* tf = target + f * V;
-  const bool vec = (V & 3) == 0;
   const long nq = (V + 3) >> 2;
   for (long q = (long)blockIdx.x * 256 + threadIdx.x; q < nq; q += (long)gridDim.x * 256) {
     const long v0 = q << 2;
@@ -224,6 +223,8 @@ __global__ void __launch_bounds__(256) voxel_loss_fwd_kernel(const float* __rest
 
 // BCE(x, 1) = -max(log x, -100) (torch clamps the log)
 __device__ __forceinline__ double bce1(double x) { double l = log(x); return -(l < -100.0 ? -100.0 : l); }
+// its derivative -1/x reaches x only where the clamp is not active (a NaN passes, as through torch's clamp)
+__device__ __forceinline__ bool bce1_live(double x) { return !(log(x) < -100.0); }
 
 // loss[0]=CE mean *w, loss[1]=sem_scal*w, loss[2]=geo_scal*w.  coef (floats), used by backward:
 //   coef[0] = 1/Ncount; per class i at 1+3i: a_i (coefficient of ct_i), b_i (constant), s_i (coefficient of (1-ct_i))
@@ -241,15 +242,16 @@ __global__ void voxel_loss_finalize_kernel(const double* __restrict__ stats, int
       count += 1.0;
       if (P > 0) {
         const double prec = N / P;
-        if (prec >= 0 && prec <= 1) { sem += bce1(prec); if (N > 0) a -= 1.0 / N; b += 1.0 / P; }
+        // (N == 0, reachable only with an underflowing softmax: the clamped log has no gradient, neither -1/N nor +1/P)
+        if (prec >= 0 && prec <= 1) { sem += bce1(prec); if (bce1_live(prec)) { a -= 1.0 / N; b += 1.0 / P; } }
       }
       {
         const double rec = N / T;
-        if (rec >= 0 && rec <= 1) { sem += bce1(rec); if (N > 0) a -= 1.0 / N; }
+        if (rec >= 0 && rec <= 1) { sem += bce1(rec); if (bce1_live(rec)) a -= 1.0 / N; }
       }
       if (R > 0) {
         const double spec = Q / R;
-        if (spec >= 0 && spec <= 1) { sem += bce1(spec); if (Q > 0) s += 1.0 / Q; }
+        if (spec >= 0 && spec <= 1) { sem += bce1(spec); if (bce1_live(spec)) s += 1.0 / Q; }
       }
     }
     coef[1 + 3 * i] = (float)a; coef[2 + 3 * i] = (float)b; coef[3 + 3 * i] = (float)s;
@@ -261,10 +263,12 @@ __global__ void voxel_loss_finalize_kernel(const double* __restrict__ stats, int
   const double* g = stats + 2 + 5 * C;
   const double I = g[0], A = g[1], B = g[2], S = g[3], R = g[4];
   loss[2] = (float)(weight * (bce1(I / A) + bce1(I / B) + bce1(S / R)));
-  // d geo / d p0(v) = m * ( net*(2/I) - 1/A - (1-net)/S )
-  coef[1 + 3 * C + 0] = (float)(2.0 / I);
-  coef[1 + 3 * C + 1] = (float)(-1.0 / A);
-  coef[1 + 3 * C + 2] = (float)(-1.0 / S);
+  // d geo / d p0(v) = m * ( net*(2/I) - 1/A - (1-net)/S ): 1/I from precision I/A and from recall I/B, -1/A from precision,
+  // -1/S from specificity S/R; a term whose log is clamped contributes nothing
+  const bool lp = bce1_live(I / A), lr = bce1_live(I / B), ls = bce1_live(S / R);
+  coef[1 + 3 * C + 0] = (float)((lp ? 1.0 / I : 0.0) + (lr ? 1.0 / I : 0.0));
+  coef[1 + 3 * C + 1] = (float)(lp ? -1.0 / A : 0.0);
+  coef[1 + 3 * C + 2] = (float)(ls ? -1.0 / S : 0.0);
 }
 
 // dlogits = w*( g_ce * (p - onehot)/N * cw + softmaxJ^T (g_sem * dsem/dp + g_geo * dgeo/dp) )
@@ -274,7 +278,7 @@ __global__ void __launch_bounds__(256) voxel_loss_bwd_kernel(const float* __rest
                                                              const uint8_t* __restrict__ target, float* __restrict__ dlogits,
                                                              long F, int C, long V, const float* __restrict__ class_w,
                                                              const float* __restrict__ coef, const float* __restrict__ gout,
-                                                             float weight) {
+                                                             float weight, bool vec) {
   constexpr int NCU = CT ? CT : MAXC;     // unrolled class loops
   const int Cc = CT ? CT : C;
   const float gce = gout[0] * weight, gsem = gout[1] * weight, ggeo = gout[2] * weight;
@@ -288,7 +292,6 @@ __global__ void __launch_bounds__(256) voxel_loss_bwd_kernel(const float* __rest
   const float* lf = logits + f * C * V;
   float* df = dlogits + f * C * V;
   const uint8_t* tf = target + f * V;
-  const bool vec = (V & 3) == 0;
   const long nq = (V + 3) >> 2;
   for (long q = (long)blockIdx.x * 256 + threadIdx.x; q < nq; q += (long)gridDim.x * 256) {
     const long v0 = q << 2;
@@ -552,8 +555,10 @@ int muvo_spatial_loss_masked_fwd(const float* pred, const float* target, const u
   long nbx = (HW / 4 + 1023) / 1024;             // ~4 trips of 4 pixels per thread
   if (nbx * F > 1024) nbx = 1024 / F > 0 ? 1024 / F : 1;
   if (nbx < 1) nbx = 1;
+  // 16-byte loads need HW % 4 == 0 AND 16-byte aligned tensors (a contiguous view can start at any element)
+  const bool vec = HW % 4 == 0 && (((uintptr_t)pred | (uintptr_t)target) & 15) == 0;
   hipLaunchKernelGGL(spatial_loss_fwd_kernel, dim3((unsigned)nbx, (unsigned)F), dim3(256), 0, ST, pred, target, (long)F, Ct, (long)HW,
-                     c0, c1, norm, ignore, stats2, muvo_det_ticket(ST), mask);
+                     c0, c1, norm, ignore, stats2, muvo_det_ticket(ST), mask, vec);
   hipLaunchKernelGGL(spatial_loss_finalize_kernel, dim3(1), dim3(64), 0, ST, stats2, loss, weight);
   MUVO_CHECK_LAUNCH("spatial_loss_fwd");
   return MUVO_OK;
@@ -588,8 +593,10 @@ int muvo_voxel_loss_fwd(const float* logits, const uint8_t* target, int64_t F, i
   if (nbx * F > nb_cap) nbx = nb_cap / F > 0 ? nb_cap / F : 1;
   const dim3 grid((unsigned)nbx, (unsigned)F);
   unsigned* ticket = muvo_det_ticket(ST);
-  if (C == 2) hipLaunchKernelGGL(voxel_loss_fwd_kernel<2>, grid, dim3(256), 0, ST, logits, target, (long)F, C, (long)V, class_w, stats, ticket);
-  else hipLaunchKernelGGL(voxel_loss_fwd_kernel<0>, grid, dim3(256), 0, ST, logits, target, (long)F, C, (long)V, class_w, stats, ticket);
+  // 16-byte logit / 4-byte label loads need V % 4 == 0 AND aligned tensors (a contiguous view can start at any element)
+  const bool vec = V % 4 == 0 && ((uintptr_t)logits & 15) == 0 && ((uintptr_t)target & 3) == 0;
+  if (C == 2) hipLaunchKernelGGL(voxel_loss_fwd_kernel<2>, grid, dim3(256), 0, ST, logits, target, (long)F, C, (long)V, class_w, stats, ticket, vec);
+  else hipLaunchKernelGGL(voxel_loss_fwd_kernel<0>, grid, dim3(256), 0, ST, logits, target, (long)F, C, (long)V, class_w, stats, ticket, vec);
   hipLaunchKernelGGL(voxel_loss_finalize_kernel, dim3(1), dim3(64), 0, ST, stats, C, (double)F * (double)V, weight, loss3, coef);
   MUVO_CHECK_LAUNCH("voxel_loss_fwd");
   return MUVO_OK;
@@ -602,12 +609,13 @@ int muvo_voxel_loss_bwd(const float* logits, const uint8_t* target, float* dlogi
   long nbx = (V + 4095) / 4096;
   if (nbx * F > 8192) nbx = 8192 / F > 0 ? 8192 / F : 1;
   const dim3 grid((unsigned)nbx, (unsigned)F);
+  const bool vec = V % 4 == 0 && (((uintptr_t)logits | (uintptr_t)dlogits) & 15) == 0 && ((uintptr_t)target & 3) == 0;
   if (C == 2)
     hipLaunchKernelGGL(voxel_loss_bwd_kernel<2>, grid, dim3(256), 0, ST, logits, target, dlogits, (long)F, C, (long)V, class_w,
-                       coef, gout3, weight);
+                       coef, gout3, weight, vec);
   else
     hipLaunchKernelGGL(voxel_loss_bwd_kernel<0>, grid, dim3(256), 0, ST, logits, target, dlogits, (long)F, C, (long)V, class_w,
-                       coef, gout3, weight);
+                       coef, gout3, weight, vec);
   MUVO_CHECK_LAUNCH("voxel_loss_bwd");
   return MUVO_OK;
 }
