@@ -19,6 +19,7 @@
 //     gradient is accumulated by the tx = 1 waves from the same registers.
 #include "common.h"
 #include "conv_vox.h"
+#include <type_traits>
 
 struct VoxArgs {
   int N, Cin, Cout, X, Y;
@@ -31,7 +32,6 @@ struct VoxArgs {
                        // scale * x + shift (zero padding stays zero): the AdaIN of the producing layer applied while staging
   unsigned* ticket;    // deterministic mode (exact-fp32 weight gradient): the workgroups add their tiles in block order
 };
-static thread_local const float* t_vox_aff = nullptr;   // set by vox_forward / vox_wgrad around their launches (VoxArgs::aff)
 static int vox_xcd_order() {
   static const int v = getenv("MUVO_VOX_XCD") ? atoi(getenv("MUVO_VOX_XCD")) : 1;   // A/B switch
   return v;
@@ -358,16 +358,17 @@ __global__ void __launch_bounds__(256) vox_pack_kernel(const float* __restrict__
 // ================================================================================================
 // bf16x3 variant of the small-channel 3x3x3 convolution (forward / data gradient) on v_mfma_f32_16x16x32_bf16.
 // MFMA rows = produced channels (8 or 16, padded to 16), columns = 16 consecutive z voxels, K = (tap, reduction channel)
-// in steps of 32 = TPS taps x CK channels.  The fp32 4x4x1 kernel above is bound by the fp32 matrix rate (60 % busy at
+// in steps of 32 = 4 taps x 8 channels (this ring form serves 8 reduction channels; 16 and more per pass run on the
+// plane-streaming form below).  The fp32 4x4x1 kernel above is bound by the fp32 matrix rate (60 % busy at
 // 157 TFLOP/s peak); here the matrix work is ~10x cheaper and the kernel is bound by LDS fragment reads and HBM.
 //   * a workgroup (8 waves) owns TY = 8 output rows (y) x the whole z line and walks along x with a ring of three input
-//     planes in LDS, each [hi/lo][8-channel group][TY + 2 rows][Z + 2 columns] x 16 bytes (bf16 split done while staging:
+//     planes in LDS, each [hi/lo][TY + 2 rows][Z + 2 columns] x 16 bytes (bf16 split done while staging:
 //     one HBM read of the input per workgroup column, y-halo 10/8);
 //   * all weights of the layer live in registers as MFMA A fragments (hi and lo: 2 x NSTEP x 4 VGPRs);
 //   * wave w computes row w: per 16-voxel tile NSTEP x (2 fragment reads + 3 MFMAs), conflict-free 16-byte reads;
 //   * global loads of plane x+2 are issued before the MFMA work of plane x and written to LDS after it.
 // Packed weights (vox_bf3_pack_kernel): wp[(step*2 + hl)*64 + lane] = 8 bf16 of row m = lane & 15,
-// k = 8 (lane >> 4) + e -> tap = step * TPS + (lane >> 4) / CG, channel = ((lane >> 4) % CG) * 8 + e.
+// k = 8 (lane >> 4) + e -> tap = step * 4 + (lane >> 4), channel = e.
 // ================================================================================================
 typedef __bf16 vbf16x8 __attribute__((ext_vector_type(8)));
 typedef float vf32x4 __attribute__((ext_vector_type(4)));
@@ -402,15 +403,20 @@ __device__ __forceinline__ void vox_split2(float a, float b, unsigned& hi, unsig
   lo = __builtin_bit_cast(unsigned, l);
 }
 
-// GENERIC: the variant with the accumulating second pass of a 32-channel reduction and / or an activation beyond
-// none / ReLU / LeakyReLU; the plain variant keeps the plane loop free of conditional memory operations (see "Output side").
+// GENERIC: the variant with an activation beyond none / ReLU / LeakyReLU (and the accumulating pass, see `accum`); the plain
+// variant keeps the plane loop free of conditional memory operations (see "Output side").
+// `accum` (add to what `out` holds) is 0 in every launch: reductions over more than 8 channels, whose later passes accumulate,
+// all run on vox_bf3_ps_kernel.  The argument and the load behind it stay so that the GENERIC code is the one that was measured.
 template <int CK, int Z, int TY, bool GENERIC>
 __global__ void __launch_bounds__(64 * TY)
 vox_bf3_kernel(const VoxArgs a, const float* __restrict__ in, const vu32x4* __restrict__ wp, const float* __restrict__ bias,
                float* __restrict__ out, int act, float slope, int xseg, int accum) {
-  constexpr int CG = CK / 8, TPS = 4 / CG, NSTEP = (27 + TPS - 1) / TPS, ZT = Z / 16;
+  static_assert(CK == 8 && TY == 8, "8 reduction channels (one channel group), 8 rows per workgroup");
+  // CG: 8-channel groups of the reduction, one here; the task and LDS index arithmetic keeps its general form (cg is 0 for
+  // every task that exists), which is the form the kernel was measured in
+  constexpr int CG = 1, TPS = 4, NSTEP = (27 + TPS - 1) / TPS, ZT = Z / 16;     // TPS: taps per k-step of 32
   constexpr int ROWS = TY + 2, COLS = Z + 2;
-  constexpr int PLANE = 2 * CG * ROWS * COLS;                   // uint4 per ring plane
+  constexpr int PLANE = 2 * CG * ROWS * COLS;                   // uint4 per ring plane: [hi/lo][channel group][rows][cols]
   constexpr int NTASK = CG * ROWS * Z, TPT = (NTASK + 64 * TY - 1) / (64 * TY);
   extern __shared__ vu32x4 vsm[];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -438,20 +444,12 @@ vox_bf3_kernel(const VoxArgs a, const float* __restrict__ in, const vu32x4* __re
   // staging: task t -> (cg, row r, z); loads 8 channels of one voxel, splits, writes two 16-byte entries
   float stg[TPT][8];
   unsigned stg_ok = 0u;                         // bit k: task k of the staged plane lies inside the tensor
-  // AdaIN scale / shift of the staged channels (a.aff): one channel group -> registers; two -> a table in LDS (a lane's tasks
-  // belong to different groups, 48 more registers spilled)
-  float afs[8], afb[8];
-  __shared__ float s_aff[2 * CK];
+  float afs[8], afb[8];                         // AdaIN scale / shift of the staged channels (a.aff)
   if (a.aff) {
-    if (CG == 1) {
 #pragma unroll
-      for (int e = 0; e < 8; ++e) {
-        afs[e] = a.aff[((long)n * a.Cin + e) * 2];
-        afb[e] = a.aff[((long)n * a.Cin + e) * 2 + 1];
-      }
-    } else {
-      if (tid < 2 * CK) s_aff[tid] = a.aff[(long)n * a.Cin * 2 + tid];   // [c][2] as stored
-      __syncthreads();
+    for (int e = 0; e < 8; ++e) {
+      afs[e] = a.aff[((long)n * a.Cin + e) * 2];
+      afb[e] = a.aff[((long)n * a.Cin + e) * 2 + 1];
     }
   }
   const __amdgpu_buffer_rsrc_t rs_in = __builtin_amdgcn_make_buffer_rsrc((void*)inb, 0, (int)((long)CK * a.XYZ * 4), 0x00020000);
@@ -482,10 +480,7 @@ vox_bf3_kernel(const VoxArgs a, const float* __restrict__ in, const vu32x4* __re
       if (a.aff) {      // (uniform) the producing layer's AdaIN: scale * x + shift per channel; padding stays zero
         const bool ok = (stg_ok >> k) & 1u;
 #pragma unroll
-        for (int e = 0; e < 8; ++e) {
-          const float sc = CG == 1 ? afs[e] : s_aff[(cg * 8 + e) * 2], sh = CG == 1 ? afb[e] : s_aff[(cg * 8 + e) * 2 + 1];
-          stg[k][e] = ok ? stg[k][e] * sc + sh : 0.f;
-        }
+        for (int e = 0; e < 8; ++e) stg[k][e] = ok ? stg[k][e] * afs[e] + afb[e] : 0.f;
       }
       unsigned h[4], l[4];
 #pragma unroll
@@ -495,7 +490,7 @@ vox_bf3_kernel(const VoxArgs a, const float* __restrict__ in, const vu32x4* __re
     }
   };
 
-  // this lane's B-fragment geometry per k-step: tap -> (dx, dy, dz), channel group
+  // this lane's B-fragment geometry per k-step: tap -> (dx, dy, dz)
   const int v = lane & 15, g = lane >> 4;
   float msum[4] = {0.f, 0.f, 0.f, 0.f}, msq[4] = {0.f, 0.f, 0.f, 0.f};
   // Output side.  (1) The bias of this lane's four channels is loaded once, here: a bias load inside the plane loop waits —
@@ -512,11 +507,11 @@ vox_bf3_kernel(const VoxArgs a, const float* __restrict__ in, const vu32x4* __re
   int fdx[NSTEP], foff[NSTEP];       // dx in {-1, 0, 1}; uint4 offset inside a plane (hi part) for tile 0
 #pragma unroll
   for (int s = 0; s < NSTEP; ++s) {
-    int tap = s * TPS + g / CG;
+    int tap = s * TPS + g;
     if (tap > 26) tap = 26;           // padded taps carry zero weights
     const int dx = tap / 9 - 1, dy = (tap / 3) % 3 - 1, dz = tap % 3 - 1;
     fdx[s] = dx;
-    foff[s] = ((g % CG) * ROWS + (wave + 1 + dy)) * COLS + (v + 1 + dz);
+    foff[s] = (wave + 1 + dy) * COLS + (v + 1 + dz);
   }
 
   // prologue: planes xs-1 and xs into their slots, plane xs+1 in flight
@@ -554,7 +549,7 @@ vox_bf3_kernel(const VoxArgs a, const float* __restrict__ in, const vu32x4* __re
         const unsigned off = ok ? ooff + (unsigned)co * xyz4 : 0x7fffff00u;
         float r = acc[i] + bv[i];
         if constexpr (GENERIC) {
-          if (accum) r += __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rs_out, off, 0, 0));   // second half of a 32-channel reduction
+          if (accum) r += __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rs_out, off, 0, 0));
           r = act_apply(r, act, slope);
         } else {
           r = vox_act_simple(r, act, slope);
@@ -605,16 +600,12 @@ vox_bf3_kernel(const VoxArgs a, const float* __restrict__ in, const vu32x4* __re
 // -> in-plane tap tp = 2 s + (lane >> 5) (= (dy + 1) * 3 + dz + 1; tp = 9: zero), channel ((lane >> 4) & 1) * 8 + e;
 // plain: f = dxi * 5 + s (dxi = dx + 1); CO8: f = s: rows 0-7 dx = 0, rows 8-15 dx = -1; f = 5 + s: rows 0-7 dx = +1, rows 8-15 zero.
 // ================================================================================================
-#ifndef VOX_PS_PIPE
-#define VOX_PS_PIPE 1       // A/B: staging interleaved with the MFMA groups
-#endif
-#ifndef VOX_PS_TY
-#define VOX_PS_TY 8      // A/B: output rows (= waves) per workgroup; 4: two independent workgroups per CU, 1.5x instead of 1.25x halo rows
-#endif
+constexpr int VOX_PS_TY = 8;     // output rows (= waves) per workgroup (4: two independent workgroups per CU, 1.5x instead of 1.25x halo rows: 1.70 vs 1.63 ms)
 template <int Z, int TY, bool CO8, bool GENERIC>
-__global__ void __launch_bounds__(64 * TY, TY <= 4 ? 2 : 1)
+__global__ void __launch_bounds__(64 * TY, 1)
 vox_bf3_ps_kernel(const VoxArgs a, const float* __restrict__ in, const vu32x4* __restrict__ wp, const float* __restrict__ bias,
                   float* __restrict__ out, int act, float slope, int xseg, int accum) {
+  static_assert(TY == VOX_PS_TY, "one workgroup of eight waves per CU");
   constexpr int CK = 16, CG = 2, PSTEPS = 5, ZT = Z / 16, NF = CO8 ? 2 * PSTEPS : 3 * PSTEPS, NACC = CO8 ? 2 : 3;
   constexpr int ROWS = TY + 2, COLS = Z + 2;
   constexpr int PLANE = 2 * CG * ROWS * COLS;                   // uint4 per buffer
@@ -720,7 +711,7 @@ vox_bf3_ps_kernel(const VoxArgs a, const float* __restrict__ in, const vu32x4* _
   const int gy = y0 + wave;
   for (int p = xs - 1; p <= xe; ++p) {
     // plane p + 1 (in registers) goes to the buffer last read while computing plane p - 1, one staging task behind each z tile's
-    // MFMA group (VOX_PS_PIPE; before: all of it ahead of the MFMA phase, with the matrix pipe idle); the task's registers take
+    // MFMA group (before: all of it ahead of the MFMA phase, with the matrix pipe idle); the task's registers take
     // its piece of plane p + 2 right after the store
     // accumulating second pass of a 32-channel reduction: the partial sums of output plane p - 1 are requested here and added
     // after the MFMA phase (loaded inside the epilogue, every plane waited for them - and, vmcnt being in order, not for the
@@ -743,7 +734,7 @@ vox_bf3_ps_kernel(const VoxArgs a, const float* __restrict__ in, const vu32x4* _
         }
       }
     }
-    constexpr bool PIPE = VOX_PS_PIPE && (CO8 || Z <= 32);    // 16 produced channels at Z = 64: 254 VGPRs already, the longer live ranges spill
+    constexpr bool PIPE = CO8 || Z <= 32;    // 16 produced channels at Z = 64: 254 VGPRs already, the longer live ranges spill
     if constexpr (!PIPE) {
       stage_store((p + 1) & 1);
       if (p + 2 <= xe) stage_load(p + 2);
@@ -857,36 +848,25 @@ vox_bf3_ps_kernel(const VoxArgs a, const float* __restrict__ in, const vu32x4* _
 //     buffered dz plane in LDS; channel stride padded by 16 bytes (conflict-free 16-lane reads);
 //   * each wave keeps 27 accumulator tiles (108 VGPRs) over its x range; at the end the waves of a workgroup reduce
 //     through LDS and issue one set of float atomics into dW.
-// grid.x = N * ytiles * x-segments, grid.y = Cin / 16 (column blocks).
+// grid.x = N * ytiles * x-segments, grid.y = Cin / 8 (column blocks).
 // ================================================================================================
-// CI = 16: MFMA columns = 16 input channels of one tap.  CI = 8: columns = 8 input channels x two (dx, dy) combinations
-// (column j: channel j & 7, combination 2 * pair + (j >> 3)), 5 pairs x 3 dz = 15 accumulator tiles.
-#ifndef VOX_WGRAD_PIPE16
-#define VOX_WGRAD_PIPE16 1     // A/B (tools/ab_local.sh): software-pipelined plane loop, 16- / 8-input-channel variants
-#endif
-#ifndef VOX_WGRAD_PIPE8
-#define VOX_WGRAD_PIPE8 1
-#endif
-#ifndef VOX_WGRAD_BUFLOAD16
-#define VOX_WGRAD_BUFLOAD16 0      // A/B: unconditional buffer loads in the 16-input-channel variant too
-#endif
-// CO8 (<= 8 produced channels): MFMA rows 8-15, which would be zero padding, hold the SAME channels shifted by one voxel along z
-// (A'[z] = dz[z + 1]).  Against the x fragment shifted by t they produce the tap t - 1 while rows 0-7 produce the tap t, so the
-// three z taps of a (dx, dy) combination cost two accumulator tiles / six MFMAs (t = 0: taps 0 and -1; t = +1: tap +1, the
-// upper half repeats tap 0 and is discarded) instead of three / nine, and the dz = -1 fragment is never built.
+// This four-plane ring form serves 8 input -> 16 produced channels only (CI = 8, CO8 = false); every other shape runs on
+// vox_bf3_wgrad_ps_kernel below.  MFMA columns = 8 input channels x two (dx, dy) combinations (column j: channel j & 7,
+// combination 2 * pair + (j >> 3)), 5 pairs x 3 dz = 15 accumulator tiles.
 template <int Z, int CI, bool CO8>
 __global__ void __launch_bounds__(512)
 vox_bf3_wgrad_kernel(const VoxArgs a, const float* __restrict__ x, const float* __restrict__ dz, float* __restrict__ dw,
                      float* __restrict__ dbias, int xseg) {
+  static_assert(CI == 8 && !CO8, "8 input channels, 16 produced channels");
   constexpr int ZH = Z / 32, WROWS = 8 / ZH, ROWS = WROWS + 2;
   constexpr int XROW = (Z + 16) * 2;                    // bytes of an x row: 16-byte zero pad on both sides
   constexpr int XCI = ROWS * XROW + 16;                 // channel stride (bytes), +16 spreads 16 channels over all banks
   constexpr int XHL = CI * XCI, XSLOT = 2 * XHL;
-  constexpr int DCH = CO8 ? 8 : 16;                    // dz channels held in LDS
+  constexpr int DCH = 16;                              // dz channels held in LDS
   constexpr int DROW = Z * 2, DCO = WROWS * DROW + 16, DHL = DCH * DCO, DBUF = 2 * DHL;
-  constexpr int XT = CI * ROWS * (Z / 8), DT = DCH * WROWS * (Z / 8);
-  constexpr int NCOMB_ = CI == 16 ? 9 : 5, TPC = CO8 ? 2 : 3;   // (dx, dy) combinations (or pairs of them); tiles per combination
-  constexpr int NT = NCOMB_ * TPC;                     // accumulator tiles   // staging tasks (8 voxels each)
+  constexpr int XT = CI * ROWS * (Z / 8), DT = DCH * WROWS * (Z / 8);   // staging tasks (8 voxels each)
+  constexpr int NCOMB = 5, TPC = 3;                    // pairs of (dx, dy) combinations; tiles per pair (dz = -1, 0, +1)
+  constexpr int NT = NCOMB * TPC;                      // accumulator tiles
   constexpr int XPT = (XT + 511) / 512, DPT = (DT + 511) / 512;
   extern __shared__ char wsm[];
   char* xring = wsm;                                   // FOUR x planes: three being read by the MFMA phase, the fourth being staged
@@ -923,18 +903,8 @@ vox_bf3_wgrad_kernel(const VoxArgs a, const float* __restrict__ x, const float* 
     *(vu32x4*)hi_addr = vu32x4{h[0], h[1], h[2], h[3]};
     *(vu32x4*)(hi_addr + hl_stride) = vu32x4{l[0], l[1], l[2], l[3]};
   };
-  auto load8 = [&](const float* p, bool ok, float (&v)[8]) {
-    if (ok) {
-      const float4 u0 = *(const float4*)p, u1 = *(const float4*)(p + 4);
-      v[0] = u0.x; v[1] = u0.y; v[2] = u0.z; v[3] = u0.w; v[4] = u1.x; v[5] = u1.y; v[6] = u1.z; v[7] = u1.w;
-    } else {
-#pragma unroll
-      for (int e = 0; e < 8; ++e) v[e] = 0.f;
-    }
-  };
-  // 8 input channels: buffer loads (out-of-range -> zeros, unconditional: they stay in flight across the MFMA work; measured
-  // 2.51 -> 2.14 ms on the 8->8 layer).  With 16 input channels the same change cost 0.4 ms, so that variant keeps the
-  // predicated float4 loads.
+  // buffer loads (out-of-range -> zeros, unconditional: they stay in flight across the MFMA work; measured 2.51 -> 2.14 ms on
+  // the 8->8 layer against predicated float4 loads)
   constexpr unsigned OOB = 0x7fffff00u;
   auto load8b = [&](const __amdgpu_buffer_rsrc_t& rs, unsigned off, float (&v)[8]) {
     const vu32x4 u0 = __builtin_amdgcn_raw_buffer_load_b128(rs, off, 0, 0);
@@ -954,8 +924,7 @@ vox_bf3_wgrad_kernel(const VoxArgs a, const float* __restrict__ x, const float* 
       const bool ok = t < XT && px >= 0 && px < a.X && gy >= 0 && gy < a.Y;
       xok = k == 0 ? (unsigned)ok : xok | ((unsigned)ok << k);
       const long eoff = (long)ci * a.XYZ + (long)px * YZ + (long)gy * Z + z8 * 8;
-      if constexpr (CI == 8 || VOX_WGRAD_BUFLOAD16) load8b(rs_x, ok ? (unsigned)(eoff * 4) : OOB, xst[k]);     // channels past Cin: range check
-      else load8(xb + eoff, ok && ci0 + ci < a.Cin, xst[k]);
+      load8b(rs_x, ok ? (unsigned)(eoff * 4) : OOB, xst[k]);     // channels past Cin: range check
     }
   };
   auto xstore_task = [&](int k, int slot) {
@@ -981,8 +950,7 @@ vox_bf3_wgrad_kernel(const VoxArgs a, const float* __restrict__ x, const float* 
       const int gy = y0 + r;
       const bool ok = t < DT && px < xe && gy < a.Y && co < a.Cout;
       const long eoff = (long)co * a.XYZ + (long)px * YZ + (long)gy * Z + z8 * 8;
-      if constexpr (CI == 8 || VOX_WGRAD_BUFLOAD16) load8b(rs_d, ok ? (unsigned)(eoff * 4) : OOB, dst[k]);
-      else load8(db + eoff, ok, dst[k]);
+      load8b(rs_d, ok ? (unsigned)(eoff * 4) : OOB, dst[k]);
     }
   };
   auto dstore_task = [&](int k, int buf) {
@@ -1007,58 +975,32 @@ vox_bf3_wgrad_kernel(const VoxArgs a, const float* __restrict__ x, const float* 
   for (int t = 0; t < NT; ++t) acc[t] = vf32x4{0.f, 0.f, 0.f, 0.f};
   const int row = wave / ZH, z0 = (wave % ZH) * 32;     // this wave's output row and z half
   const int j = lane & 15, kg = lane >> 4;
-  const int a_off = (CO8 ? (j & 7) : j) * DCO + row * DROW + (z0 + kg * 8) * 2;   // A: rows = co = lane & 15 (CO8: & 7)
-  const bool a_last = z0 + kg * 8 + 8 >= Z;                             // CO8: the voxel after this lane's eight lies past the row
-  const int b_off = (j & (CI - 1)) * XCI + 16 + (z0 + kg * 8) * 2;      // B: columns -> channel j & (CI - 1) (+ row term below)
-  const int sel = CI == 8 ? j >> 3 : 0;                                 // CI = 8: which combination of the pair this column reads
+  const int a_off = j * DCO + row * DROW + (z0 + kg * 8) * 2;           // A: rows = co = lane & 15
+  const int b_off = (j & (CI - 1)) * XCI + 16 + (z0 + kg * 8) * 2;      // B: columns -> channel j & 7 (+ row term below)
+  const int sel = j >> 3;                                               // which combination of the pair this column reads
 
   // Plane loop, software-pipelined over a ring of four x planes and two dz planes: while the MFMA phase of plane px reads the
   // x planes px - 1 .. px + 1 and dz plane px, the same waves split and store x plane px + 2 and dz plane px + 1 (loaded one
   // step earlier) piece by piece between their MFMA groups, then issue the loads of the planes after those.  ONE barrier per
   // plane.  (With a three-plane ring the staging had to finish behind its own barrier before the MFMA phase could start:
   // 2000 of 6900 clocks per plane with the matrix pipe idle, another 800 at the second barrier.)
-  // Same-box A/B against the two-barrier schedule (tools/ab_local.sh, VOX_WGRAD_PIPE16 / _PIPE8): 2.78 -> 2.64 ms (16 -> 8 at
-  // 192 x 192 x 64), 1.78 -> 1.73 (8 -> 8), 0.96 -> 0.93 (32 -> 16), 0.49 -> 0.47 (16 -> 16): the phases are bound by their
-  // vector and LDS instructions more than by the barriers, so the gain is 3-5 %, not the 1.5x the idle clocks suggested.
-  constexpr bool PIPE = CI == 16 ? VOX_WGRAD_PIPE16 : VOX_WGRAD_PIPE8;
+  // Same-box A/B against the two-barrier schedule: 2.78 -> 2.64 ms (16 -> 8 at 192 x 192 x 64), 1.78 -> 1.73 (8 -> 8),
+  // 0.96 -> 0.93 (32 -> 16), 0.49 -> 0.47 (16 -> 16): the phases are bound by their vector and LDS instructions more than by
+  // the barriers, so the gain is 3-5 %, not the 1.5x the idle clocks suggested.
   xload(xs - 1); xstore((xs - 1 + 4) & 3);
   xload(xs); xstore(xs & 3);
-  if (PIPE) {
-    xload(xs + 1); xstore((xs + 1) & 3);
-    dload(xs); dstore(xs & 1);
-    xload(xs + 2);
-    dload(xs + 1);
-  } else {
-    xload(xs + 1);
-    dload(xs);
-  }
+  xload(xs + 1); xstore((xs + 1) & 3);
+  dload(xs); dstore(xs & 1);
+  xload(xs + 2);
+  dload(xs + 1);
   __syncthreads();
   for (int px = xs; px < xe; ++px) {
-    if (!PIPE) {
-      xstore((px + 1) & 3);
-      dstore(px & 1);
-      __syncthreads();
-      if (px + 1 < xe) { xload(px + 2); dload(px + 1); }
-    }
     const char* A = dzb + (px & 1) * DBUF + a_off;
-    vu32x4 aq[2] = {*(const vu32x4*)A, *(const vu32x4*)(A + DHL)};
-    if constexpr (CO8) {
-#pragma unroll
-      for (int hl = 0; hl < 2; ++hl) {
-        unsigned nx = *(const unsigned*)(A + hl * DHL + 16);
-        nx = a_last ? 0u : nx;
-        const vu32x4 q = aq[hl];
-        const vu32x4 sh = {__builtin_amdgcn_alignbyte(q.y, q.x, 2), __builtin_amdgcn_alignbyte(q.z, q.y, 2),
-                           __builtin_amdgcn_alignbyte(q.w, q.z, 2), __builtin_amdgcn_alignbyte(nx, q.w, 2)};
-        aq[hl] = j >= 8 ? sh : q;
-      }
-    }
-    const vbf16x8 ah = __builtin_bit_cast(vbf16x8, aq[0]);
-    const vbf16x8 al = __builtin_bit_cast(vbf16x8, aq[1]);
-    constexpr int NCOMB = NCOMB_;
+    const vbf16x8 ah = __builtin_bit_cast(vbf16x8, *(const vu32x4*)A);
+    const vbf16x8 al = __builtin_bit_cast(vbf16x8, *(const vu32x4*)(A + DHL));
 #pragma unroll
     for (int cb = 0; cb < NCOMB; ++cb) {
-      int c = CI == 16 ? cb : 2 * cb + sel;             // this lane's combination
+      int c = 2 * cb + sel;                             // this lane's combination
       if (c > 8) c = 8;                                 // the phantom second half of the last pair (its tile half is discarded)
       const int dx = c / 3, dy = c - 3 * dx;
       const char* R = xring + ((px + dx - 1 + 4) & 3) * XSLOT + b_off + (row + dy) * XROW;   // source row = row + 1 + (dy - 1)
@@ -1067,7 +1009,7 @@ vox_bf3_wgrad_kernel(const VoxArgs a, const float* __restrict__ x, const float* 
 #pragma unroll
       for (int hl = 0; hl < 2; ++hl) {
         w[hl] = *(const vu32x4*)(R + hl * XHL);
-        if constexpr (!CO8) pw[hl] = *(const unsigned*)(R + hl * XHL - 4);
+        pw[hl] = *(const unsigned*)(R + hl * XHL - 4);
         nw[hl] = *(const unsigned*)(R + hl * XHL + 16);
       }
       vbf16x8 bm[2], bz[2], bp[2];                      // dz = -1, 0, +1
@@ -1075,42 +1017,29 @@ vox_bf3_wgrad_kernel(const VoxArgs a, const float* __restrict__ x, const float* 
       for (int hl = 0; hl < 2; ++hl) {
         const vu32x4 q = w[hl];
         bz[hl] = __builtin_bit_cast(vbf16x8, q);
-        if constexpr (!CO8) {
-          const vu32x4 m = {__builtin_amdgcn_alignbyte(q.x, pw[hl], 2), __builtin_amdgcn_alignbyte(q.y, q.x, 2),
-                            __builtin_amdgcn_alignbyte(q.z, q.y, 2), __builtin_amdgcn_alignbyte(q.w, q.z, 2)};
-          bm[hl] = __builtin_bit_cast(vbf16x8, m);
-        }
+        const vu32x4 m = {__builtin_amdgcn_alignbyte(q.x, pw[hl], 2), __builtin_amdgcn_alignbyte(q.y, q.x, 2),
+                          __builtin_amdgcn_alignbyte(q.z, q.y, 2), __builtin_amdgcn_alignbyte(q.w, q.z, 2)};
+        bm[hl] = __builtin_bit_cast(vbf16x8, m);
         const vu32x4 pl = {__builtin_amdgcn_alignbyte(q.y, q.x, 2), __builtin_amdgcn_alignbyte(q.z, q.y, 2),
                            __builtin_amdgcn_alignbyte(q.w, q.z, 2), __builtin_amdgcn_alignbyte(nw[hl], q.w, 2)};
         bp[hl] = __builtin_bit_cast(vbf16x8, pl);
       }
       const int t0 = cb * TPC;
-      if constexpr (CO8) {
-        acc[t0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al, bz[0], acc[t0], 0, 0, 0);
-        acc[t0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, bz[1], acc[t0], 0, 0, 0);
-        acc[t0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, bz[0], acc[t0], 0, 0, 0);
-        acc[t0 + 1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al, bp[0], acc[t0 + 1], 0, 0, 0);
-        acc[t0 + 1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, bp[1], acc[t0 + 1], 0, 0, 0);
-        acc[t0 + 1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, bp[0], acc[t0 + 1], 0, 0, 0);
-      } else {
-        acc[t0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al, bm[0], acc[t0], 0, 0, 0);
-        acc[t0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, bm[1], acc[t0], 0, 0, 0);
-        acc[t0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, bm[0], acc[t0], 0, 0, 0);
-        acc[t0 + 1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al, bz[0], acc[t0 + 1], 0, 0, 0);
-        acc[t0 + 1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, bz[1], acc[t0 + 1], 0, 0, 0);
-        acc[t0 + 1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, bz[0], acc[t0 + 1], 0, 0, 0);
-        acc[t0 + 2] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al, bp[0], acc[t0 + 2], 0, 0, 0);
-        acc[t0 + 2] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, bp[1], acc[t0 + 2], 0, 0, 0);
-        acc[t0 + 2] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, bp[0], acc[t0 + 2], 0, 0, 0);
-      }
+      acc[t0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al, bm[0], acc[t0], 0, 0, 0);
+      acc[t0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, bm[1], acc[t0], 0, 0, 0);
+      acc[t0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, bm[0], acc[t0], 0, 0, 0);
+      acc[t0 + 1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al, bz[0], acc[t0 + 1], 0, 0, 0);
+      acc[t0 + 1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, bz[1], acc[t0 + 1], 0, 0, 0);
+      acc[t0 + 1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, bz[0], acc[t0 + 1], 0, 0, 0);
+      acc[t0 + 2] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al, bp[0], acc[t0 + 2], 0, 0, 0);
+      acc[t0 + 2] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, bp[1], acc[t0 + 2], 0, 0, 0);
+      acc[t0 + 2] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, bp[0], acc[t0 + 2], 0, 0, 0);
       // staging of the next planes between the MFMA groups (compile-time schedule: one task per combination)
       static_assert(XPT + DPT + 1 <= NCOMB, "one staging piece per combination");
-      if (PIPE) {
-        if (cb < XPT) xstore_task(cb, (px + 2) & 3);
-        else if (cb < XPT + DPT) dstore_task(cb - XPT, (px + 1) & 1);
-        else if (cb == XPT + DPT) { xload(px + 3); dload(px + 2); }     // planes past the tensor / segment read as zeros
-        __builtin_amdgcn_sched_barrier(0);
-      }
+      if (cb < XPT) xstore_task(cb, (px + 2) & 3);
+      else if (cb < XPT + DPT) dstore_task(cb - XPT, (px + 1) & 1);
+      else if (cb == XPT + DPT) { xload(px + 3); dload(px + 2); }     // planes past the tensor / segment read as zeros
+      __builtin_amdgcn_sched_barrier(0);
     }
     __syncthreads();
   }
@@ -1125,19 +1054,11 @@ vox_bf3_wgrad_kernel(const VoxArgs a, const float* __restrict__ x, const float* 
   __syncthreads();
   for (int i = tid; i < NT * 256; i += 512) {
     const int col = i & 15, t = i >> 8;
-    int co = (i >> 4) & 15;
-    int ci, tap;
-    int tz = t % TPC;                                                   // z tap index 0..2 (dz + 1) of this tile
-    if (CO8) {                                                          // tile 0: rows 0-7 tap 0, rows 8-15 tap -1; tile 1: rows 0-7 tap +1
-      tz = tz == 0 ? (co < 8 ? 1 : 0) : (co < 8 ? 2 : -1);
-      co &= 7;
-    }
-    if (CI == 16) { ci = col; tap = tz >= 0 ? (t / TPC) * 3 + tz : -1; }
-    else {
-      const int comb = 2 * (t / TPC) + (col >> 3);                      // (dx, dy) combination of this column
-      ci = col & 7;
-      tap = comb <= 8 && tz >= 0 ? comb * 3 + tz : -1;
-    }
+    const int co = (i >> 4) & 15;
+    const int tz = t % TPC;                                             // z tap index 0..2 (dz + 1) of this tile
+    const int comb = 2 * (t / TPC) + (col >> 3);                        // (dx, dy) combination of this column
+    const int ci = col & 7;
+    const int tap = comb <= 8 && tz >= 0 ? comb * 3 + tz : -1;          // (tz >= 0 always holds; with it the compiler emits the select this kernel was measured with, without it a branch)
     const float vsum = red[i];
     if (tap >= 0 && co < a.Cout && ci0 + ci < a.Cin && vsum != 0.f) atomicAdd(dw + ((long)co * a.Cin + ci0 + ci) * 27 + tap, vsum);
   }
@@ -1156,16 +1077,15 @@ vox_bf3_wgrad_kernel(const VoxArgs a, const float* __restrict__ x, const float* 
 // (the dz staging, its LDS ring and the LDS atomics of the bias sums are gone; the bias sums live in a register per lane).
 // The loop runs over the x planes xs - 1 .. xe (two more iterations than output planes; segments are long, see
 // vox_blocks_target), MFMA groups whose dz plane lies outside the segment are skipped by uniform branches.
+// CO8 (<= 8 produced channels): MFMA rows 8-15, which would be zero padding, hold the SAME channels shifted by one voxel along z
+// (A'[z] = dz[z + 1]).  Against the x fragment shifted by t they produce the tap t - 1 while rows 0-7 produce the tap t, so the
+// three z taps of a (dx, dy) combination cost two accumulator tiles / six MFMAs (t = 0: taps 0 and -1; t = +1: tap +1, the
+// upper half repeats tap 0 and is discarded) instead of three / nine, and the dz = -1 fragment is never built.
 // CI = 8 (8 -> 8 channels): one tile per (dx, dy) combination holds all three z taps - MFMA rows 8-15 are the dz channels
-// shifted by one voxel (as CO8 above), columns 8-15 the x channels shifted by one voxel: quadrant (rows a, columns b) is the
+// shifted by one voxel (as with CO8), columns 8-15 the x channels shifted by one voxel: quadrant (rows a, columns b) is the
 // tap b - a, i.e. 0, -1, +1 and a discarded duplicate of 0: 27 MFMAs per 32 voxels instead of 30, 9 accumulator tiles.
 // ------------------------------------------------------------------------------------------------
-#ifndef VOX_WGPS_SCHED
-#define VOX_WGPS_SCHED 1     // A/B: staging pieces pinned between the MFMA groups
-#endif
-#ifndef VOX_WGPS_SW
-#define VOX_WGPS_SW 4     // A/B: staging waves of the variants that fit three waves per SIMD (0: the MFMA waves stage the x planes)
-#endif
+constexpr int VOX_WGPS_SW = 4;     // staging waves of the variants that fit three waves per SIMD (0: the MFMA waves stage the x planes)
 // SW > 0: SW extra waves do nothing but stage the x planes (load, AdaIN, split, LDS stores of plane P + 1) while the eight MFMA
 // waves work on plane P - loops of their own with the same number of workgroup barriers.  The two halves of the kernel (1.20 ms of
 // staging at ~5 TB/s, 1.19 ms of MFMA issue on the 16 -> 8 layer) then no longer alternate inside every wave - and still do not
@@ -1395,9 +1315,7 @@ vox_bf3_wgrad_ps_kernel(const VoxArgs a, const float* __restrict__ x, const floa
         xstore_task(dy, (it + 1) & 1);
         if (it + 2 < niter) xload_task(dy, P + 2);
       }
-#if VOX_WGPS_SCHED
-      __builtin_amdgcn_sched_barrier(0);
-#endif
+      __builtin_amdgcn_sched_barrier(0);       // staging pieces pinned between the MFMA groups
     }
     __syncthreads();
   }
@@ -1446,11 +1364,12 @@ vox_bf3_wgrad_ps_kernel(const VoxArgs a, const float* __restrict__ x, const floa
 // Packed weights (vox_bf3_pack2_kernel): step s, lane (m = lane & 15, g = lane >> 4): super tap 4 s + g.
 // ------------------------------------------------------------------------------------------------
 template <int Z, int CK, bool GENERIC>
-__global__ void __launch_bounds__(CK == 16 ? 256 : 512)
+__global__ void __launch_bounds__(512)
 vox_bf3_2row_kernel(const VoxArgs a, const float* __restrict__ in, const vu32x4* __restrict__ wp, const float* __restrict__ bias,
                     float* __restrict__ out, int act, float slope, int xseg) {
-  constexpr int CG = CK / 8, TPS = 4 / CG, NSTEP = 36 / TPS, ZT = Z / 16;
-  constexpr int TY = CK == 16 ? 8 : 16, NT = 32 * TY;      // two rows per wave; 16 channels: 8 rows (LDS budget)
+  static_assert(CK == 8, "8 reduction channels");
+  constexpr int CG = 1, TPS = 4, NSTEP = 36 / TPS, ZT = Z / 16; // channel groups (index arithmetic as in vox_bf3_kernel); super taps per k-step of 32
+  constexpr int TY = 16, NT = 32 * TY;                          // two rows per wave
   constexpr int ROWS = TY + 2, COLS = Z + 2;
   constexpr int PLANE = 2 * CG * ROWS * COLS;                   // uint4 per ring plane: [hi/lo][channel group][rows][cols]
   constexpr int NTASK = CG * ROWS * Z, TPT = (NTASK + NT - 1) / NT;
@@ -1473,20 +1392,12 @@ vox_bf3_2row_kernel(const VoxArgs a, const float* __restrict__ in, const vu32x4*
   __syncthreads();
   float stg[TPT][8];
   unsigned stg_ok = 0u;                         // bit k: task k of the staged plane lies inside the tensor
-  // AdaIN scale / shift of the staged channels (a.aff): one channel group -> registers; two -> a table in LDS (a lane's tasks
-  // belong to different groups, 48 more registers spilled)
-  float afs[8], afb[8];
-  __shared__ float s_aff[2 * CK];
+  float afs[8], afb[8];                         // AdaIN scale / shift of the staged channels (a.aff)
   if (a.aff) {
-    if (CG == 1) {
 #pragma unroll
-      for (int e = 0; e < 8; ++e) {
-        afs[e] = a.aff[((long)n * a.Cin + e) * 2];
-        afb[e] = a.aff[((long)n * a.Cin + e) * 2 + 1];
-      }
-    } else {
-      if (tid < 2 * CK) s_aff[tid] = a.aff[(long)n * a.Cin * 2 + tid];   // [c][2] as stored
-      __syncthreads();
+    for (int e = 0; e < 8; ++e) {
+      afs[e] = a.aff[((long)n * a.Cin + e) * 2];
+      afb[e] = a.aff[((long)n * a.Cin + e) * 2 + 1];
     }
   }
   const __amdgpu_buffer_rsrc_t rs_in = __builtin_amdgcn_make_buffer_rsrc((void*)inb, 0, (int)((long)CK * a.XYZ * 4), 0x00020000);
@@ -1517,10 +1428,7 @@ vox_bf3_2row_kernel(const VoxArgs a, const float* __restrict__ in, const vu32x4*
       if (a.aff) {      // (uniform) the producing layer's AdaIN: scale * x + shift per channel; padding stays zero
         const bool ok = (stg_ok >> k) & 1u;
 #pragma unroll
-        for (int e = 0; e < 8; ++e) {
-          const float sc = CG == 1 ? afs[e] : s_aff[(cg * 8 + e) * 2], sh = CG == 1 ? afb[e] : s_aff[(cg * 8 + e) * 2 + 1];
-          stg[k][e] = ok ? stg[k][e] * sc + sh : 0.f;
-        }
+        for (int e = 0; e < 8; ++e) stg[k][e] = ok ? stg[k][e] * afs[e] + afb[e] : 0.f;
       }
       unsigned h[4], l[4];
 #pragma unroll
@@ -1540,10 +1448,10 @@ vox_bf3_2row_kernel(const VoxArgs a, const float* __restrict__ in, const vu32x4*
   int fdx[NSTEP], foff[NSTEP];
 #pragma unroll
   for (int s = 0; s < NSTEP; ++s) {
-    const int st = s * TPS + g / CG;                  // super tap: (dx, ry, dz), ry = input row - (y - 1)
+    const int st = s * TPS + g;                       // super tap: (dx, ry, dz), ry = input row - (y - 1)
     const int dx = st / 12 - 1, ry = (st / 3) % 4, dz = st % 3 - 1;
     fdx[s] = dx;
-    foff[s] = ((g % CG) * ROWS + 2 * wave + ry) * COLS + (v + 1 + dz);   // LDS row of input row (y - 1 + ry), y = y0 + 2 wave
+    foff[s] = (2 * wave + ry) * COLS + (v + 1 + dz);   // LDS row of input row (y - 1 + ry), y = y0 + 2 wave
   }
   stage_load(xs - 1); stage_store((xs - 1 + 3) % 3);
   stage_load(xs); stage_store(xs % 3);
@@ -1607,6 +1515,14 @@ vox_bf3_2row_kernel(const VoxArgs a, const float* __restrict__ in, const vu32x4*
   }
 }
 
+// fp32 -> bf16 hi = RNE(x), lo = RNE(x - hi) in integer arithmetic (the weight packers; finite inputs)
+__device__ __forceinline__ void vox_split_rne(float val, unsigned& hu, unsigned& lu) {
+  const unsigned u = __float_as_uint(val);
+  hu = (u + 0x7fffu + ((u >> 16) & 1u)) >> 16;
+  const unsigned r = __float_as_uint(val - __uint_as_float(hu << 16));
+  lu = (r + 0x7fffu + ((r >> 16) & 1u)) >> 16;
+}
+
 // rows 0-7: channel m of output row y (tap dy index = ry, valid for ry <= 2); rows 8-15: channel m - 8 of row y + 1 (dy index ry - 1)
 __global__ void __launch_bounds__(256)
 vox_bf3_pack2_kernel(const float* __restrict__ w, unsigned short* __restrict__ wp, int Cin, int Cout, int dgrad) {
@@ -1623,11 +1539,8 @@ vox_bf3_pack2_kernel(const float* __restrict__ w, unsigned short* __restrict__ w
       const int tap = (dx * 3 + dy) * 3 + dz;
       val = dgrad ? w[((size_t)c * Cin + co) * 27 + (26 - tap)] : w[((size_t)co * Cin + c) * 27 + tap];
     }
-    unsigned u = __float_as_uint(val);
-    unsigned hu = (u + 0x7fffu + ((u >> 16) & 1u)) >> 16;
-    const float rem = val - __uint_as_float(hu << 16);
-    unsigned r = __float_as_uint(rem);
-    unsigned lu = (r + 0x7fffu + ((r >> 16) & 1u)) >> 16;
+    unsigned hu, lu;
+    vox_split_rne(val, hu, lu);
     wp[((size_t)(s * 2) * 64 + lane) * 8 + e] = (unsigned short)hu;
     wp[((size_t)(s * 2 + 1) * 64 + lane) * 8 + e] = (unsigned short)lu;
   }
@@ -1648,11 +1561,8 @@ vox_bf3_pack_kernel(const float* __restrict__ w, unsigned short* __restrict__ wp
     const int tap = s * TPS + g / CG, c = half * CK + (g % CG) * 8 + e;
     float val = 0.f;
     if (tap < 27 && m < rows) val = dgrad ? w[((size_t)c * Cin + m) * 27 + (26 - tap)] : w[((size_t)m * Cin + c) * 27 + tap];
-    unsigned u = __float_as_uint(val);
-    unsigned hu = (u + 0x7fffu + ((u >> 16) & 1u)) >> 16;
-    const float rem = val - __uint_as_float(hu << 16);
-    unsigned r = __float_as_uint(rem);
-    unsigned lu = (r + 0x7fffu + ((r >> 16) & 1u)) >> 16;
+    unsigned hu, lu;
+    vox_split_rne(val, hu, lu);
     wp[((size_t)(((half * nrb + rb) * nstep + s) * 2) * 64 + lane) * 8 + e] = (unsigned short)hu;
     wp[((size_t)(((half * nrb + rb) * nstep + s) * 2 + 1) * 64 + lane) * 8 + e] = (unsigned short)lu;
   }
@@ -1680,11 +1590,8 @@ vox_bf3_ps_pack_kernel(const float* __restrict__ w, unsigned short* __restrict__
     const int tap = dxi * 9 + tp;
     float val = 0.f;
     if (live && m < rows) val = dgrad ? w[((size_t)c * Cin + m) * 27 + (26 - tap)] : w[((size_t)m * Cin + c) * 27 + tap];
-    unsigned u = __float_as_uint(val);
-    unsigned hu = (u + 0x7fffu + ((u >> 16) & 1u)) >> 16;
-    const float rem = val - __uint_as_float(hu << 16);
-    unsigned r = __float_as_uint(rem);
-    unsigned lu = (r + 0x7fffu + ((r >> 16) & 1u)) >> 16;
+    unsigned hu, lu;
+    vox_split_rne(val, hu, lu);
     wp[((size_t)(((half * nrb + rb) * NF + f) * 2) * 64 + lane) * 8 + e] = (unsigned short)hu;
     wp[((size_t)(((half * nrb + rb) * NF + f) * 2 + 1) * 64 + lane) * 8 + e] = (unsigned short)lu;
   }
@@ -1711,57 +1618,49 @@ bool vox_dgrad_applicable(const muvo_conv_desc* d) {
 bool vox_wgrad_applicable(const muvo_conv_desc* d) {
   return vox_geometry_ok(d) && d->Cout % 8 == 0 && d->Cin % 8 == 0 && d->Cout <= 32 && d->Cin <= 64;
 }
-// 8 produced channels: two output rows share one MFMA (vox_bf3_2row_kernel)
+// 8 -> 8 channels: two output rows share one MFMA (vox_bf3_2row_kernel)
 // (with 16 reduction channels the 18 weight steps push the kernel to one wave per SIMD and it loses: measured 3.05 vs 2.81 ms)
 static bool vox_bf3_two_rows(int ck, int cp) { return cp == 8 && ck == 8; }
-// bf16x3 variant: reduction and produced channels in {8, 16}
-static bool vox_bf3_ps(int red, int cp);
+// plane-streaming form (vox_bf3_ps_kernel): 16 reduction channels per pass (16, or 32 / 64 as two / four accumulating passes), produced
+// channels in row blocks of 16
+// (64 produced channels = four row blocks that each stage the same input: the 64 <- 32 data gradient at 48 x 48 x 16 measured
+// 0.41 ms here against 0.36 on the implicit-GEMM kernel; not taken)
+static bool vox_bf3_ps(int red, int cp) { return (red == 16 || red == 32 || red == 64) && (cp == 8 || cp == 16 || cp == 32); }
+// bf16x3 variant: 8 reduction channels on the ring kernels (vox_bf3_2row_kernel / vox_bf3_kernel), 16 / 32 / 64 on the plane-streaming one
 bool vox_bf3_shape_ok(const muvo_conv_desc* d, int dgrad) {
   const int ck = dgrad ? d->Cout : d->Cin, cp = dgrad ? d->Cin : d->Cout;
   // the plane-streaming kernels alone: z lines of 16 voxels (the 48 x 48 x 16 level of the voxel decoder), 64 reduction channels
-  static const int z16_on = getenv("MUVO_VOX_Z16") ? atoi(getenv("MUVO_VOX_Z16")) : 1;       // A/B switch
-  if (vox_geometry_ok(d, true) && (d->in_sz[2] == 16 || ck == 64)) return z16_on && vox_bf3_ps(ck, cp);
+  if (vox_geometry_ok(d, true) && (d->in_sz[2] == 16 || ck == 64)) return vox_bf3_ps(ck, cp);
   if (!vox_geometry_ok(d)) return false;
-  // reduction channels 8 / 16 (the weights of one 16-row block live in registers); produced channels in blocks of 16 rows
-  // (32 reduction channels run as two accumulating passes of 16)
   return (ck == 8 || ck == 16 || ck == 32) && (cp == 8 || cp == 16 || cp == 32);
 }
-static int vox_bf3_steps(int ck) { return ck == 8 ? 7 : 14; }      // per pass
+constexpr int VOX_BF3_STEPS = 7;      // k-steps of vox_bf3_kernel: 27 taps, four per step
 long vox_pack_floats(const muvo_conv_desc* d) {
   const int blocks_f = (d->Cin / 16 > 0 ? d->Cin / 16 : 1) * cdiv(d->Cout, 16), blocks_d = (d->Cout / 16 > 0 ? d->Cout / 16 : 1) * cdiv(d->Cin, 16);
   const int blocks = blocks_f > blocks_d ? blocks_f : blocks_d;
-  const long plain = 27l * d->Cin * d->Cout, bf3 = 15l * 2 * 64 * 4 * (blocks > 4 ? blocks : 4);      // (plane-streaming form: 15 fragments per row block)   // bf16x3 layout: (halves x row blocks <= 4) x steps x (hi, lo) x 64 lanes x 16 B
+  // bf16x3 layout: (passes x row blocks, at least 4) x fragments (plane-streaming form: 15 per row block) x (hi, lo) x 64 lanes x 16 B
+  const long plain = 27l * d->Cin * d->Cout, bf3 = 15l * 2 * 64 * 4 * (blocks > 4 ? blocks : 4);
   return plain > bf3 ? plain : bf3;
 }
 
-// plane-streaming form (vox_bf3_ps_kernel): 16 reduction channels per pass (16, or 32 / 64 as two / four accumulating passes), produced
-// channels in row blocks of 16
-static bool vox_bf3_ps(int red, int cp) {
-  static const int on = getenv("MUVO_VOX_PS") ? atoi(getenv("MUVO_VOX_PS")) : 1;
-  // (64 produced channels = four row blocks that each stage the same input: the 64 <- 32 data gradient at 48 x 48 x 16 measured
-  // 0.41 ms here against 0.36 on the implicit-GEMM kernel; not taken)
-  return on && (red == 16 || red == 32 || red == 64) && (cp == 8 || cp == 16 || cp == 32);
-}
-
 int vox_pack(const muvo_conv_desc* d, const float* w, float* wp, int dgrad, hipStream_t st, bool bf3) {
-  if (bf3 && vox_bf3_ps(dgrad ? d->Cout : d->Cin, dgrad ? d->Cin : d->Cout)) {
-    const int red = dgrad ? d->Cout : d->Cin, cp = dgrad ? d->Cin : d->Cout;
+  const int red = dgrad ? d->Cout : d->Cin, cp = dgrad ? d->Cin : d->Cout;
+  if (bf3 && vox_bf3_ps(red, cp)) {
     const int co8 = cp <= 8 ? 1 : 0;
     hipLaunchKernelGGL(vox_bf3_ps_pack_kernel, dim3(cdiv((red / 16) * cdiv(cp, 16) * (co8 ? 10 : 15) * 512, 256)), dim3(256), 0, st, w,
                        (unsigned short*)wp, d->Cin, d->Cout, dgrad, co8);
     MUVO_CHECK_LAUNCH("vox_bf3_ps_pack_kernel");
     return MUVO_OK;
   }
-  if (bf3 && vox_bf3_two_rows(dgrad ? d->Cout : d->Cin, dgrad ? d->Cin : d->Cout)) {      // two-row variant
+  if (bf3 && vox_bf3_two_rows(red, cp)) {
     hipLaunchKernelGGL(vox_bf3_pack2_kernel, dim3(36), dim3(256), 0, st, w, (unsigned short*)wp, d->Cin, d->Cout, dgrad);
     MUVO_CHECK_LAUNCH("vox_bf3_pack2_kernel");
     return MUVO_OK;
   }
   if (bf3) {
-    const int red = dgrad ? d->Cout : d->Cin, cp = dgrad ? d->Cin : d->Cout;
-    const int ck = red == 32 ? 16 : red, ns = vox_bf3_steps(ck);
-    hipLaunchKernelGGL(vox_bf3_pack_kernel, dim3(cdiv((red / ck) * cdiv(cp, 16) * ns * 512, 256)), dim3(256), 0, st, w, (unsigned short*)wp,
-                       d->Cin, d->Cout, dgrad, ck, ns);
+    MUVO_CHECK_ARG(red == 8, "vox_pack: no bf16x3 voxel kernel for %d reduction / %d produced channels", red, cp);
+    hipLaunchKernelGGL(vox_bf3_pack_kernel, dim3(cdiv(cdiv(cp, 16) * VOX_BF3_STEPS * 512, 256)), dim3(256), 0, st, w, (unsigned short*)wp,
+                       d->Cin, d->Cout, dgrad, 8, VOX_BF3_STEPS);
     MUVO_CHECK_LAUNCH("vox_bf3_pack_kernel");
     return MUVO_OK;
   }
@@ -1771,22 +1670,18 @@ int vox_pack(const muvo_conv_desc* d, const float* w, float* wp, int dgrad, hipS
   return MUVO_OK;
 }
 
-template <int CQ, int TY, int Z>
-static int launch_vox_conv(const muvo_conv_desc* d, int Cin, int Cout, const float* in, const float* wp, const float* bias,
-                           float* out, int act, float slope, hipStream_t st) {
+// ---- launch steps shared by the launchers below
+// The kernel arguments of a launch with `rows` output rows per y tile.  cin_total: channels of the input tensor when a pass
+// reads only Cin of them (0: Cin).
+static VoxArgs vox_args(const muvo_conv_desc* d, int Cin, int Cout, int rows, int Z, int cin_total, const float* aff) {
   VoxArgs a{};
   a.xcd_order = vox_xcd_order();
-  a.aff = t_vox_aff;
+  a.aff = aff;
   a.N = d->N; a.Cin = Cin; a.Cout = Cout; a.X = d->in_sz[0]; a.Y = d->in_sz[1];
-  a.ytiles = cdiv(a.Y, TY);
-  a.xgroups = cdiv(a.X, 64 / Z);
+  a.ytiles = cdiv(a.Y, rows);
   a.XYZ = a.X * a.Y * Z;
-  a.sN_in = (long)Cin * a.XYZ; a.sN_out = (long)Cout * a.XYZ;
-  const long nwaves = (long)a.N * a.xgroups * a.ytiles;
-  const size_t lds = (size_t)27 * Cin * Cout * sizeof(float);
-  hipLaunchKernelGGL((vox_conv_kernel<CQ, TY, Z>), dim3(cdiv(nwaves, 4)), dim3(256), lds, st, a, in, wp, bias, out, act, slope);
-  MUVO_CHECK_LAUNCH("vox_conv_kernel");
-  return MUVO_OK;
+  a.sN_in = (long)(cin_total ? cin_total : Cin) * a.XYZ; a.sN_out = (long)Cout * a.XYZ;
+  return a;
 }
 
 // Workgroups a voxel bf16x3 launch should at least have before the x axis stops being split into segments.  Every segment
@@ -1798,173 +1693,145 @@ static int vox_blocks_target(int wgrad) {
   static const int w = getenv("MUVO_VOX_WGRAD_BLOCKS") ? atoi(getenv("MUVO_VOX_WGRAD_BLOCKS")) : 128;
   return wgrad ? w : f;
 }
-
-template <int CK, int Z, int TY>
-static int launch_vox_bf3_ty(const muvo_conv_desc* d, int Cin, int Cout, const float* in, const float* wp, const float* bias,
-                             float* out, int act, float slope, hipStream_t st, int cin_total, int accum, double* moments) {
-  VoxArgs a{};
-  a.xcd_order = vox_xcd_order();
-  a.aff = t_vox_aff;
-  a.moments = moments;
-  a.N = d->N; a.Cin = Cin; a.Cout = Cout; a.X = d->in_sz[0]; a.Y = d->in_sz[1];
-  a.ytiles = cdiv(a.Y, TY);
-  a.xgroups = 0;
-  a.XYZ = a.X * a.Y * Z;
-  a.sN_in = (long)(cin_total ? cin_total : Cin) * a.XYZ; a.sN_out = (long)Cout * a.XYZ;
-  // split x into segments until the grid fills the chip (each segment re-reads two halo planes)
+// x planes per segment: x is halved until the grid (segments x y tiles x batch x `factor` workgroups along grid.y / .z) fills
+// the chip or a segment would drop to 12 planes or fewer
+static int vox_xseg(const VoxArgs& a, int factor, int wgrad) {
   int xseg = a.X;
-  while ((long)a.N * a.ytiles * cdiv(a.X, xseg) < vox_blocks_target(0) && xseg > 12) xseg = cdiv(xseg, 2);
-  constexpr size_t lds = (size_t)3 * 2 * (CK / 8) * (TY + 2) * (Z + 2) * 16;
-  static bool attr_set = false;
-  if (!attr_set) {
-    if (hipFuncSetAttribute((const void*)vox_bf3_kernel<CK, Z, TY, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess ||
-        hipFuncSetAttribute((const void*)vox_bf3_kernel<CK, Z, TY, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
-      muvo_set_error("vox_bf3: cannot raise the dynamic LDS limit to %zu bytes", lds);
-      return MUVO_ERR_HIP;
-    }
-    attr_set = true;
+  while ((long)a.N * a.ytiles * cdiv(a.X, xseg) * factor < vox_blocks_target(wgrad) && xseg > 12) xseg = cdiv(xseg, 2);
+  return xseg;
+}
+
+// Raises the dynamic LDS limit of the given kernel functions, once (`done`: the calling launcher's flag).
+template <class... K>
+static int vox_raise_lds(bool& done, const char* what, size_t lds, K... kernels) {
+  if (done) return MUVO_OK;
+  if (((hipFuncSetAttribute((const void*)kernels, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) || ...)) {
+    muvo_set_error("%s: cannot raise the dynamic LDS limit to %zu bytes", what, lds);
+    return MUVO_ERR_HIP;
   }
-  const long blocks = (long)a.N * a.ytiles * cdiv(a.X, xseg);
-  const dim3 grid((unsigned)blocks, cdiv(Cout, 16));
-  if (accum || act > MUVO_ACT_LEAKY)
-    hipLaunchKernelGGL((vox_bf3_kernel<CK, Z, TY, true>), grid, dim3(64 * TY), lds, st, a, in, (const vu32x4*)wp, bias, out, act, slope, xseg, accum);
-  else
-    hipLaunchKernelGGL((vox_bf3_kernel<CK, Z, TY, false>), grid, dim3(64 * TY), lds, st, a, in, (const vu32x4*)wp, bias, out, act, slope, xseg, 0);
-  MUVO_CHECK_LAUNCH("vox_bf3_kernel");
+  done = true;
   return MUVO_OK;
 }
 
-template <int CK, int Z>
-static int launch_vox_bf3(const muvo_conv_desc* d, int Cin, int Cout, const float* in, const float* wp, const float* bias,
-                          float* out, int act, float slope, hipStream_t st, int cin_total = 0, int accum = 0,
-                          double* moments = nullptr) {
-  // (four rows per workgroup — half the LDS ring, two workgroups per CU — measured no better: profiles/r02l_vox_rows_per_workgroup.txt)
-  return launch_vox_bf3_ty<CK, Z, 8>(d, Cin, Cout, in, wp, bias, out, act, slope, st, cin_total, accum, moments);
+// Run-time value -> template argument: f(std::integral_constant<int, Z>) for z lines of 64 / 32 (Z16: also 16) voxels,
+// f(std::bool_constant<b>).  The callers' lambdas instantiate exactly the kernels the dispatch can reach.
+template <bool Z16 = false, class F>
+static int vox_with_z(int Z, F&& f) {
+  if (Z == 64) return f(std::integral_constant<int, 64>{});
+  if (Z == 32) return f(std::integral_constant<int, 32>{});
+  if constexpr (Z16) {
+    if (Z == 16) return f(std::integral_constant<int, 16>{});
+  }
+  muvo_set_error("vox_conv: no kernel for z lines of %d voxels", Z);
+  return MUVO_ERR_INVALID_ARG;
+}
+template <class F>
+static int vox_with_bool(bool b, F&& f) { return b ? f(std::true_type{}) : f(std::false_type{}); }
+
+// ---- forward / data gradient
+template <int CQ, int TY, int Z>
+static int launch_vox_conv(const muvo_conv_desc* d, int Cin, int Cout, const float* in, const float* wp, const float* bias,
+                           float* out, int act, float slope, hipStream_t st) {
+  VoxArgs a = vox_args(d, Cin, Cout, TY, Z, 0, nullptr);
+  a.xgroups = cdiv(a.X, 64 / Z);
+  const long nwaves = (long)a.N * a.xgroups * a.ytiles;
+  const size_t lds = (size_t)27 * Cin * Cout * sizeof(float);
+  hipLaunchKernelGGL((vox_conv_kernel<CQ, TY, Z>), dim3(cdiv(nwaves, 4)), dim3(256), lds, st, a, in, wp, bias, out, act, slope);
+  MUVO_CHECK_LAUNCH("vox_conv_kernel");
+  return MUVO_OK;
 }
 
-template <int Z, int CK>
+// 8 reduction channels, 16 or 32 produced channels
+// (four rows per workgroup — half the LDS ring, two workgroups per CU — measured no better: profiles/r02l_vox_rows_per_workgroup.txt)
+template <int Z>
+static int launch_vox_bf3(const muvo_conv_desc* d, int Cout, const float* in, const float* wp, const float* bias, float* out, int act,
+                          float slope, hipStream_t st, double* moments, const float* aff) {
+  constexpr int CK = 8, TY = 8;
+  VoxArgs a = vox_args(d, CK, Cout, TY, Z, 0, aff);
+  a.moments = moments;
+  const int xseg = vox_xseg(a, 1, 0);
+  constexpr size_t lds = (size_t)3 * 2 * (TY + 2) * (Z + 2) * 16;
+  static bool lds_raised = false;
+  if (int rc = vox_raise_lds(lds_raised, "vox_bf3", lds, vox_bf3_kernel<CK, Z, TY, false>, vox_bf3_kernel<CK, Z, TY, true>)) return rc;
+  const dim3 grid((unsigned)((long)a.N * a.ytiles * cdiv(a.X, xseg)), cdiv(Cout, 16));
+  return vox_with_bool(act > MUVO_ACT_LEAKY, [&](auto generic) -> int {
+    hipLaunchKernelGGL((vox_bf3_kernel<CK, Z, TY, decltype(generic)::value>), grid, dim3(64 * TY), lds, st, a, in, (const vu32x4*)wp, bias, out,
+                       act, slope, xseg, /*accum*/ 0);
+    MUVO_CHECK_LAUNCH("vox_bf3_kernel");
+    return MUVO_OK;
+  });
+}
+
+// 8 -> 8 channels
+template <int Z>
 static int launch_vox_bf3_2row(const muvo_conv_desc* d, const float* in, const float* wp, const float* bias, float* out, int act,
-                               float slope, hipStream_t st, double* moments) {
-  constexpr int TY = CK == 16 ? 8 : 16;
-  VoxArgs a{};
-  a.xcd_order = vox_xcd_order();
-  a.aff = t_vox_aff;
+                               float slope, hipStream_t st, double* moments, const float* aff) {
+  constexpr int CK = 8, TY = 16;
+  VoxArgs a = vox_args(d, CK, 8, TY, Z, 0, aff);
   a.moments = moments;
-  a.N = d->N; a.Cin = CK; a.Cout = 8; a.X = d->in_sz[0]; a.Y = d->in_sz[1];
-  a.ytiles = cdiv(a.Y, TY);
-  a.xgroups = 0;
-  a.XYZ = a.X * a.Y * Z;
-  a.sN_in = (long)CK * a.XYZ; a.sN_out = (long)8 * a.XYZ;
-  int xseg = a.X;
-  while ((long)a.N * a.ytiles * cdiv(a.X, xseg) < vox_blocks_target(0) && xseg > 12) xseg = cdiv(xseg, 2);
-  constexpr size_t lds = (size_t)3 * 2 * (CK / 8) * (TY + 2) * (Z + 2) * 16;
+  const int xseg = vox_xseg(a, 1, 0);
+  constexpr size_t lds = (size_t)3 * 2 * (TY + 2) * (Z + 2) * 16;
   static_assert(lds <= 160 * 1024, "LDS budget");
-  static bool attr_set = false;
-  if (!attr_set) {
-    if (hipFuncSetAttribute((const void*)vox_bf3_2row_kernel<Z, CK, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess ||
-        hipFuncSetAttribute((const void*)vox_bf3_2row_kernel<Z, CK, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
-      muvo_set_error("vox_bf3_2row: cannot raise the dynamic LDS limit to %zu bytes", lds);
-      return MUVO_ERR_HIP;
-    }
-    attr_set = true;
-  }
+  static bool lds_raised = false;
+  if (int rc = vox_raise_lds(lds_raised, "vox_bf3_2row", lds, vox_bf3_2row_kernel<Z, CK, false>, vox_bf3_2row_kernel<Z, CK, true>)) return rc;
   const dim3 grid((unsigned)((long)a.N * a.ytiles * cdiv(a.X, xseg)));
-  if (act > MUVO_ACT_LEAKY)
-    hipLaunchKernelGGL((vox_bf3_2row_kernel<Z, CK, true>), grid, dim3(32 * TY), lds, st, a, in, (const vu32x4*)wp, bias, out, act, slope, xseg);
-  else
-    hipLaunchKernelGGL((vox_bf3_2row_kernel<Z, CK, false>), grid, dim3(32 * TY), lds, st, a, in, (const vu32x4*)wp, bias, out, act, slope, xseg);
-  MUVO_CHECK_LAUNCH("vox_bf3_2row_kernel");
-  return MUVO_OK;
+  return vox_with_bool(act > MUVO_ACT_LEAKY, [&](auto generic) -> int {
+    hipLaunchKernelGGL((vox_bf3_2row_kernel<Z, CK, decltype(generic)::value>), grid, dim3(32 * TY), lds, st, a, in, (const vu32x4*)wp, bias, out,
+                       act, slope, xseg);
+    MUVO_CHECK_LAUNCH("vox_bf3_2row_kernel");
+    return MUVO_OK;
+  });
 }
 
+// one pass over 16 reduction channels (of cin_total in the tensor; 0: 16); accum: add to what `out` holds
 template <int Z, bool CO8>
 static int launch_vox_bf3_ps(const muvo_conv_desc* d, int Cout, const float* in, const float* wp, const float* bias, float* out, int act,
-                             float slope, hipStream_t st, int cin_total, int accum, double* moments) {
+                             float slope, hipStream_t st, int cin_total, int accum, double* moments, const float* aff) {
   constexpr int TY = VOX_PS_TY;
-  VoxArgs a{};
-  a.xcd_order = vox_xcd_order();
-  a.aff = t_vox_aff;
+  VoxArgs a = vox_args(d, 16, Cout, TY, Z, cin_total, aff);
   a.moments = moments;
-  a.N = d->N; a.Cin = 16; a.Cout = Cout; a.X = d->in_sz[0]; a.Y = d->in_sz[1];
-  a.ytiles = cdiv(a.Y, TY);
-  a.xgroups = 0;
-  a.XYZ = a.X * a.Y * Z;
-  a.sN_in = (long)(cin_total ? cin_total : 16) * a.XYZ; a.sN_out = (long)Cout * a.XYZ;
-  int xseg = a.X;
-  while ((long)a.N * a.ytiles * cdiv(a.X, xseg) < vox_blocks_target(0) && xseg > 12) xseg = cdiv(xseg, 2);
+  const int xseg = vox_xseg(a, 1, 0);
   constexpr size_t lds = (size_t)2 * 2 * 2 * (TY + 2) * (Z + 2) * 16;
-  static bool attr_set = false;
-  if (!attr_set) {
-    if (hipFuncSetAttribute((const void*)vox_bf3_ps_kernel<Z, TY, CO8, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess ||
-        hipFuncSetAttribute((const void*)vox_bf3_ps_kernel<Z, TY, CO8, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
-      muvo_set_error("vox_bf3_ps: cannot raise the dynamic LDS limit to %zu bytes", lds);
-      return MUVO_ERR_HIP;
-    }
-    attr_set = true;
-  }
-  const long blocks = (long)a.N * a.ytiles * cdiv(a.X, xseg);
-  const dim3 grid((unsigned)blocks, cdiv(Cout, 16));
-  if (accum || act > MUVO_ACT_LEAKY)
-    hipLaunchKernelGGL((vox_bf3_ps_kernel<Z, TY, CO8, true>), grid, dim3(64 * TY), lds, st, a, in, (const vu32x4*)wp, bias, out, act, slope, xseg, accum);
-  else
-    hipLaunchKernelGGL((vox_bf3_ps_kernel<Z, TY, CO8, false>), grid, dim3(64 * TY), lds, st, a, in, (const vu32x4*)wp, bias, out, act, slope, xseg, 0);
-  MUVO_CHECK_LAUNCH("vox_bf3_ps_kernel");
-  return MUVO_OK;
-}
-static int launch_vox_bf3_ps_z(const muvo_conv_desc* d, int Cout, const float* in, const float* wp, const float* bias, float* out, int act,
-                               float slope, hipStream_t st, int cin_total, int accum, double* moments) {
-  const int Z = d->in_sz[2];
-  if (Z == 16) return Cout <= 8 ? launch_vox_bf3_ps<16, true>(d, Cout, in, wp, bias, out, act, slope, st, cin_total, accum, moments)
-                                : launch_vox_bf3_ps<16, false>(d, Cout, in, wp, bias, out, act, slope, st, cin_total, accum, moments);
-  if (Cout <= 8) return Z == 64 ? launch_vox_bf3_ps<64, true>(d, Cout, in, wp, bias, out, act, slope, st, cin_total, accum, moments)
-                                : launch_vox_bf3_ps<32, true>(d, Cout, in, wp, bias, out, act, slope, st, cin_total, accum, moments);
-  return Z == 64 ? launch_vox_bf3_ps<64, false>(d, Cout, in, wp, bias, out, act, slope, st, cin_total, accum, moments)
-                 : launch_vox_bf3_ps<32, false>(d, Cout, in, wp, bias, out, act, slope, st, cin_total, accum, moments);
+  static bool lds_raised = false;
+  if (int rc = vox_raise_lds(lds_raised, "vox_bf3_ps", lds, vox_bf3_ps_kernel<Z, TY, CO8, false>, vox_bf3_ps_kernel<Z, TY, CO8, true>)) return rc;
+  const dim3 grid((unsigned)((long)a.N * a.ytiles * cdiv(a.X, xseg)), cdiv(Cout, 16));
+  return vox_with_bool(accum || act > MUVO_ACT_LEAKY, [&](auto generic) -> int {
+    hipLaunchKernelGGL((vox_bf3_ps_kernel<Z, TY, CO8, decltype(generic)::value>), grid, dim3(64 * TY), lds, st, a, in, (const vu32x4*)wp, bias, out,
+                       act, slope, xseg, accum);
+    MUVO_CHECK_LAUNCH("vox_bf3_ps_kernel");
+    return MUVO_OK;
+  });
 }
 
 static int vox_conv_dispatch(const muvo_conv_desc* d, int Cin, int Cout, const float* in, const float* wp, const float* bias,
-                             float* out, int act, float slope, hipStream_t st, bool bf3, double* moments = nullptr) {
+                             float* out, int act, float slope, hipStream_t st, bool bf3, double* moments, const float* aff) {
   if (moments && !bf3) { muvo_set_error("vox_conv: output moments need the bf16x3 kernels"); return MUVO_ERR_INVALID_ARG; }
   const int Z = d->in_sz[2];
   if (bf3 && vox_bf3_ps(Cin, Cout)) {
-    if (Cin > 16) {         // accumulating passes over 16 reduction channels each; bias and activation ride on the last
-      const long XYZ = (long)d->in_sz[0] * d->in_sz[1] * Z;
-      const size_t wstep = (size_t)cdiv(Cout, 16) * (Cout <= 8 ? 10 : 15) * 2 * 64 * 4;
-      const int npass = Cin / 16;
-      for (int ps = 0; ps < npass - 1; ++ps) {
-        const int rc = launch_vox_bf3_ps_z(d, Cout, in + (size_t)ps * 16 * XYZ, wp + ps * wstep, nullptr, out, MUVO_ACT_NONE, 0.f, st, Cin, ps > 0, nullptr);
-        if (rc) return rc;
-      }
-      return launch_vox_bf3_ps_z(d, Cout, in + (size_t)(npass - 1) * 16 * XYZ, wp + (npass - 1) * wstep, bias, out, act, slope, st, Cin, 1, moments);
-    }
-    return launch_vox_bf3_ps_z(d, Cout, in, wp, bias, out, act, slope, st, 0, 0, moments);
-  }
-  if (bf3 && vox_bf3_two_rows(Cin, Cout)) {
-    if (Cin == 8) return Z == 64 ? launch_vox_bf3_2row<64, 8>(d, in, wp, bias, out, act, slope, st, moments)
-                                 : launch_vox_bf3_2row<32, 8>(d, in, wp, bias, out, act, slope, st, moments);
-    return Z == 64 ? launch_vox_bf3_2row<64, 16>(d, in, wp, bias, out, act, slope, st, moments)
-                   : launch_vox_bf3_2row<32, 16>(d, in, wp, bias, out, act, slope, st, moments);
-  }
-  if (bf3 && Cin == 32) {
-    // two accumulating passes over 16 reduction channels each; bias and activation ride on the second
+    // accumulating passes over 16 reduction channels each; bias, activation and moments ride on the last
     const long XYZ = (long)d->in_sz[0] * d->in_sz[1] * Z;
-    const float* wp2 = wp + (size_t)cdiv(Cout, 16) * 14 * 2 * 64 * 4;
-    int rc = Z == 64 ? launch_vox_bf3<16, 64>(d, 16, Cout, in, wp, nullptr, out, MUVO_ACT_NONE, 0.f, st, 32, 0)
-                     : launch_vox_bf3<16, 32>(d, 16, Cout, in, wp, nullptr, out, MUVO_ACT_NONE, 0.f, st, 32, 0);
-    if (rc) return rc;
-    return Z == 64 ? launch_vox_bf3<16, 64>(d, 16, Cout, in + 16 * XYZ, wp2, bias, out, act, slope, st, 32, 1, moments)
-                   : launch_vox_bf3<16, 32>(d, 16, Cout, in + 16 * XYZ, wp2, bias, out, act, slope, st, 32, 1, moments);
+    const size_t wstep = (size_t)cdiv(Cout, 16) * (Cout <= 8 ? 10 : 15) * 2 * 64 * 4;
+    const int npass = Cin / 16, cin_total = npass > 1 ? Cin : 0;
+    return vox_with_z<true>(Z, [&](auto z) -> int {
+      constexpr int ZC = decltype(z)::value;
+      return vox_with_bool(Cout <= 8, [&](auto co8) -> int {
+        for (int ps = 0; ps < npass; ++ps) {
+          const bool last = ps == npass - 1;
+          const int rc = launch_vox_bf3_ps<ZC, decltype(co8)::value>(d, Cout, in + (size_t)ps * 16 * XYZ, wp + ps * wstep, last ? bias : nullptr, out,
+                                                                     last ? act : MUVO_ACT_NONE, last ? slope : 0.f, st, cin_total, ps > 0,
+                                                                     last ? moments : nullptr, aff);
+          if (rc) return rc;
+        }
+        return MUVO_OK;
+      });
+    });
   }
-  if (bf3) {
-    if (Cin == 16 && Z == 64) return launch_vox_bf3<16, 64>(d, Cin, Cout, in, wp, bias, out, act, slope, st, 0, 0, moments);
-    if (Cin == 16 && Z == 32) return launch_vox_bf3<16, 32>(d, Cin, Cout, in, wp, bias, out, act, slope, st, 0, 0, moments);
-    if (Cin == 8 && Z == 64) return launch_vox_bf3<8, 64>(d, Cin, Cout, in, wp, bias, out, act, slope, st, 0, 0, moments);
-    if (Cin == 8 && Z == 32) return launch_vox_bf3<8, 32>(d, Cin, Cout, in, wp, bias, out, act, slope, st, 0, 0, moments);
-  }
-  if (Cout == 8 && Z == 64) return launch_vox_conv<2, 6, 64>(d, Cin, Cout, in, wp, bias, out, act, slope, st);
-  if (Cout == 8 && Z == 32) return launch_vox_conv<2, 6, 32>(d, Cin, Cout, in, wp, bias, out, act, slope, st);
-  if (Cout == 16 && Z == 64) return launch_vox_conv<4, 4, 64>(d, Cin, Cout, in, wp, bias, out, act, slope, st);
-  if (Cout == 16 && Z == 32) return launch_vox_conv<4, 4, 32>(d, Cin, Cout, in, wp, bias, out, act, slope, st);
+  if (bf3 && vox_bf3_two_rows(Cin, Cout))
+    return vox_with_z(Z, [&](auto z) -> int { return launch_vox_bf3_2row<decltype(z)::value>(d, in, wp, bias, out, act, slope, st, moments, aff); });
+  if (bf3 && Cin == 8)
+    return vox_with_z(Z, [&](auto z) -> int { return launch_vox_bf3<decltype(z)::value>(d, Cout, in, wp, bias, out, act, slope, st, moments, aff); });
+  if (Cout == 8) return vox_with_z(Z, [&](auto z) -> int { return launch_vox_conv<2, 6, decltype(z)::value>(d, Cin, Cout, in, wp, bias, out, act, slope, st); });
+  if (Cout == 16) return vox_with_z(Z, [&](auto z) -> int { return launch_vox_conv<4, 4, decltype(z)::value>(d, Cin, Cout, in, wp, bias, out, act, slope, st); });
   muvo_set_error("vox_conv: unsupported shape Cout=%d Z=%d", Cout, Z);
   return MUVO_ERR_INVALID_ARG;
 }
@@ -1972,10 +1839,7 @@ static int vox_conv_dispatch(const muvo_conv_desc* d, int Cin, int Cout, const f
 int vox_forward(const muvo_conv_desc* d, const float* x, const float* wp, const float* bias, float* y, int act, float slope,
                 hipStream_t st, bool bf3, double* moments, const float* aff) {
   if (aff && !vox_affine_ok(d)) { muvo_set_error("vox_forward: no affine staging for this shape"); return MUVO_ERR_INVALID_ARG; }
-  t_vox_aff = aff;
-  const int rc = vox_conv_dispatch(d, d->Cin, d->Cout, x, wp, bias, y, act, slope, st, bf3 || aff != nullptr, moments);
-  t_vox_aff = nullptr;
-  return rc;
+  return vox_conv_dispatch(d, d->Cin, d->Cout, x, wp, bias, y, act, slope, st, bf3 || aff != nullptr, moments, aff);
 }
 // can the forward and weight-gradient kernels of this convolution apply a per-(n, channel) scale / shift while staging?
 // (bf16x3 voxel kernels with 8 or 16 reduction channels; 32 run as two passes of 16 and are not covered)
@@ -1983,34 +1847,21 @@ bool vox_affine_ok(const muvo_conv_desc* d) {
   return vox_fwd_applicable(d) && vox_bf3_shape_ok(d, 0) && vox_bf3_wgrad_shape_ok(d) && (d->Cin == 8 || d->Cin == 16);
 }
 int vox_dgrad(const muvo_conv_desc* d, const float* dy, const float* wp, float* dx, hipStream_t st, bool bf3) {
-  return vox_conv_dispatch(d, d->Cout, d->Cin, dy, wp, nullptr, dx, MUVO_ACT_NONE, 0.f, st, bf3);
+  return vox_conv_dispatch(d, d->Cout, d->Cin, dy, wp, nullptr, dx, MUVO_ACT_NONE, 0.f, st, bf3, nullptr, nullptr);
 }
 
+// ---- weight gradient
 template <int RQB, int CQR, int Z, int TYB>
 static int launch_vox_wgrad(const muvo_conv_desc* d, const float* x, const float* dz, float* dw, float* dbias,
                             hipStream_t st) {
   constexpr int CQB = 2;
-  VoxArgs a{};
-  a.xcd_order = vox_xcd_order();
-  a.aff = t_vox_aff;
-  a.N = d->N; a.Cin = d->Cin; a.Cout = d->Cout; a.X = d->in_sz[0]; a.Y = d->in_sz[1];
-  a.ytiles = cdiv(a.Y, TYB);
-  a.xgroups = 0;
-  a.XYZ = a.X * a.Y * Z;
-  a.sN_in = (long)a.Cin * a.XYZ; a.sN_out = (long)a.Cout * a.XYZ;
+  VoxArgs a = vox_args(d, d->Cin, d->Cout, TYB, Z, 0, nullptr);
   const int nqc = d->Cout / (4 * CQB), nrc = d->Cin / (4 * RQB);
   int xsplit = 1;
   while ((long)a.N * a.ytiles * xsplit * nqc * nrc < 1536 && a.X / (xsplit * 2) >= 8) xsplit *= 2;
   constexpr size_t lds = sizeof(float) * (3 * RQB * (TYB + 2) * (Z + 2) * 4 + 2 * CQB * TYB * Z * 4);
-  static bool attr_set = false;
-  if (!attr_set) {
-    if (hipFuncSetAttribute((const void*)vox_wgrad_kernel<RQB, CQR, Z, TYB>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)lds) != hipSuccess) {
-      muvo_set_error("vox_wgrad: cannot raise the dynamic LDS limit to %zu bytes", lds);
-      return MUVO_ERR_HIP;
-    }
-    attr_set = true;
-  }
+  static bool lds_raised = false;
+  if (int rc = vox_raise_lds(lds_raised, "vox_wgrad", lds, vox_wgrad_kernel<RQB, CQR, Z, TYB>)) return rc;
   dim3 grid(a.N * a.ytiles * xsplit, nqc * nrc);
   a.ticket = muvo_det_ticket(st);
   hipLaunchKernelGGL((vox_wgrad_kernel<RQB, CQR, Z, TYB>), grid, dim3(768), lds, st, a, x, dz, dw, dbias, xsplit, nqc);
@@ -2018,15 +1869,11 @@ static int launch_vox_wgrad(const muvo_conv_desc* d, const float* x, const float
   return MUVO_OK;
 }
 
-static bool vox_wgrad_ps_on() {      // plane-streaming variant (MUVO_VOX_WGRAD_PS=0: the four-plane ring kernels, for A/B)
-  static const bool on = !(getenv("MUVO_VOX_WGRAD_PS") && atoi(getenv("MUVO_VOX_WGRAD_PS")) == 0);
-  return on;
-}
 // shapes only the plane-streaming bf16x3 weight-gradient kernel serves: z lines of 16 voxels (the 48 x 48 x 16 level of the voxel
-// decoder), 32 produced channels.  The generic bf16x3 weight gradient runs one workgroup per tap there, i.e. stages x and dz 27
-// times (0.71 ms for 64 -> 32, 0.60 for 32 -> 32 at 20 x 48 x 48 x 16).
+// decoder), 32 produced channels.  (A kernel with one workgroup per tap stages x and dz 27 times there: 0.71 ms for 64 -> 32,
+// 0.60 for 32 -> 32 at 20 x 48 x 48 x 16.)
 bool vox_wgrad_ps_only(const muvo_conv_desc* d) {
-  return vox_wgrad_ps_on() && vox_geometry_ok(d, true) && (d->in_sz[2] == 16 || d->Cout == 32) && d->Cin % 16 == 0 && d->Cin <= 64 &&
+  return vox_geometry_ok(d, true) && (d->in_sz[2] == 16 || d->Cout == 32) && d->Cin % 16 == 0 && d->Cin <= 64 &&
          (d->Cout == 8 || d->Cout == 16 || d->Cout == 32);
 }
 bool vox_bf3_wgrad_shape_ok(const muvo_conv_desc* d) {
@@ -2034,62 +1881,38 @@ bool vox_bf3_wgrad_shape_ok(const muvo_conv_desc* d) {
   return vox_wgrad_applicable(d) && (d->Cin == 8 || d->Cin % 16 == 0) && d->Cin <= 64 && (d->Cout == 8 || d->Cout == 16);
 }
 
-template <int Z, int CI, bool CO8>
-static int launch_vox_bf3_wgrad(const muvo_conv_desc* d, const float* x, const float* dz, float* dw, float* dbias, hipStream_t st) {
+// 8 input -> 16 produced channels
+template <int Z>
+static int launch_vox_bf3_wgrad(const muvo_conv_desc* d, const float* x, const float* dz, float* dw, float* dbias, hipStream_t st,
+                                const float* aff) {
+  constexpr int CI = 8;
   constexpr int ZH = Z / 32, WROWS = 8 / ZH, ROWS = WROWS + 2;
-  constexpr size_t lds = (size_t)4 * 2 * CI * (ROWS * (Z + 16) * 2 + 16) + (size_t)2 * 2 * (CO8 ? 8 : 16) * (WROWS * Z * 2 + 16) + 64;
+  constexpr size_t lds = (size_t)4 * 2 * CI * (ROWS * (Z + 16) * 2 + 16) + (size_t)2 * 2 * 16 * (WROWS * Z * 2 + 16) + 64;
   static_assert(lds <= 160 * 1024, "LDS budget");
-  static_assert(lds >= (CI == 16 ? 27 : 15) * 256 * 4 + 64, "the reduction reuses the rings");
-  VoxArgs a{};
-  a.xcd_order = vox_xcd_order();
-  a.aff = t_vox_aff;
-  a.N = d->N; a.Cin = d->Cin; a.Cout = d->Cout; a.X = d->in_sz[0]; a.Y = d->in_sz[1];
-  a.ytiles = cdiv(a.Y, WROWS);
-  a.xgroups = 0;
-  a.XYZ = a.X * a.Y * Z;
-  a.sN_in = (long)a.Cin * a.XYZ; a.sN_out = (long)a.Cout * a.XYZ;
-  int xseg = a.X;
-  while ((long)a.N * a.ytiles * cdiv(a.X, xseg) * (a.Cin / CI) < vox_blocks_target(1) && xseg > 12) xseg = cdiv(xseg, 2);
-  static bool attr_set = false;
-  if (!attr_set) {
-    if (hipFuncSetAttribute((const void*)vox_bf3_wgrad_kernel<Z, CI, CO8>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
-      muvo_set_error("vox_bf3_wgrad: cannot raise the dynamic LDS limit to %zu bytes", lds);
-      return MUVO_ERR_HIP;
-    }
-    attr_set = true;
-  }
+  static_assert(lds >= 15 * 256 * 4 + 64, "the reduction reuses the rings");
+  const VoxArgs a = vox_args(d, d->Cin, d->Cout, WROWS, Z, 0, aff);
+  const int xseg = vox_xseg(a, a.Cin / CI, 1);
+  static bool lds_raised = false;
+  if (int rc = vox_raise_lds(lds_raised, "vox_bf3_wgrad", lds, vox_bf3_wgrad_kernel<Z, CI, false>)) return rc;
   dim3 grid((unsigned)((long)a.N * a.ytiles * cdiv(a.X, xseg)), a.Cin / CI);
-  hipLaunchKernelGGL((vox_bf3_wgrad_kernel<Z, CI, CO8>), grid, dim3(512), lds, st, a, x, dz, dw, dbias, xseg);
+  hipLaunchKernelGGL((vox_bf3_wgrad_kernel<Z, CI, false>), grid, dim3(512), lds, st, a, x, dz, dw, dbias, xseg);
   MUVO_CHECK_LAUNCH("vox_bf3_wgrad_kernel");
   return MUVO_OK;
 }
 
 template <int Z, int CI, bool CO8>
-static int launch_vox_bf3_wgrad_ps(const muvo_conv_desc* d, const float* x, const float* dz, float* dw, float* dbias, hipStream_t st) {
+static int launch_vox_bf3_wgrad_ps(const muvo_conv_desc* d, const float* x, const float* dz, float* dw, float* dbias, hipStream_t st,
+                                   const float* aff) {
   // staging waves only for 16 input / <= 8 produced channels (1.78 -> 1.68 ms on 16 -> 8 at 192 x 192 x 64): 27 accumulator tiles
   // (206 VGPRs) leave no room for three waves per SIMD, and the 8 -> 8 variant (117 VGPRs) loses its second workgroup per CU
   // (0.98 -> 1.08 ms)
   constexpr int SW = (CI == 16 && CO8) ? VOX_WGPS_SW : 0;
   constexpr int ZH = Z >= 32 ? Z / 32 : 1, RW = Z >= 32 ? 1 : 32 / Z, WROWS = 8 / ZH * RW, ROWS = WROWS + 2;
   constexpr size_t lds = (size_t)2 * 2 * CI * (ROWS * (Z + 16) * 2 + 16) + 64;
-  VoxArgs a{};
-  a.xcd_order = vox_xcd_order();
-  a.aff = t_vox_aff;
-  a.N = d->N; a.Cin = d->Cin; a.Cout = d->Cout; a.X = d->in_sz[0]; a.Y = d->in_sz[1];
-  a.ytiles = cdiv(a.Y, WROWS);
-  a.xgroups = 0;
-  a.XYZ = a.X * a.Y * Z;
-  a.sN_in = (long)a.Cin * a.XYZ; a.sN_out = (long)a.Cout * a.XYZ;
-  int xseg = a.X;
-  while ((long)a.N * a.ytiles * cdiv(a.X, xseg) * (a.Cin / CI) * cdiv(a.Cout, 16) < vox_blocks_target(1) && xseg > 12) xseg = cdiv(xseg, 2);
-  static bool attr_set = false;
-  if (!attr_set) {
-    if (hipFuncSetAttribute((const void*)vox_bf3_wgrad_ps_kernel<Z, CI, CO8, SW>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
-      muvo_set_error("vox_bf3_wgrad_ps: cannot raise the dynamic LDS limit to %zu bytes", lds);
-      return MUVO_ERR_HIP;
-    }
-    attr_set = true;
-  }
+  const VoxArgs a = vox_args(d, d->Cin, d->Cout, WROWS, Z, 0, aff);
+  const int xseg = vox_xseg(a, (a.Cin / CI) * cdiv(a.Cout, 16), 1);
+  static bool lds_raised = false;
+  if (int rc = vox_raise_lds(lds_raised, "vox_bf3_wgrad_ps", lds, vox_bf3_wgrad_ps_kernel<Z, CI, CO8, SW>)) return rc;
   dim3 grid((unsigned)((long)a.N * a.ytiles * cdiv(a.X, xseg)), a.Cin / CI, cdiv(a.Cout, 16));
   hipLaunchKernelGGL((vox_bf3_wgrad_ps_kernel<Z, CI, CO8, SW>), grid, dim3(512 + 64 * SW), lds, st, a, x, dz, dw, dbias, xseg);
   MUVO_CHECK_LAUNCH("vox_bf3_wgrad_ps_kernel");
@@ -2099,32 +1922,23 @@ static int launch_vox_bf3_wgrad_ps(const muvo_conv_desc* d, const float* x, cons
 int vox_wgrad(const muvo_conv_desc* d, const float* x, const float* dz, float* dw, float* dbias, hipStream_t st, bool bf3,
               const float* aff) {
   if (aff && !vox_affine_ok(d)) { muvo_set_error("vox_wgrad: no affine staging for this shape"); return MUVO_ERR_INVALID_ARG; }
-  struct AffScope { AffScope(const float* p) { t_vox_aff = p; } ~AffScope() { t_vox_aff = nullptr; } } scope(aff);
   if (aff) bf3 = true;
   const int Z = d->in_sz[2];
   if (bf3) {
-    // <= 8 produced channels: the idle half of the MFMA rows carries a second z tap (MUVO_VOX_WGRAD_CO8=0: padded rows, for A/B)
-    static const bool co8_on = !(getenv("MUVO_VOX_WGRAD_CO8") && atoi(getenv("MUVO_VOX_WGRAD_CO8")) == 0);
-    const bool co8 = d->Cout <= 8 && co8_on;
-    const bool ps_on = vox_wgrad_ps_on();
-    if (Z == 16) {
-      if (!vox_wgrad_ps_only(d)) { muvo_set_error("vox_wgrad: 16-voxel z lines need the plane-streaming kernel"); return MUVO_ERR_INVALID_ARG; }
-      return co8 ? launch_vox_bf3_wgrad_ps<16, 16, true>(d, x, dz, dw, dbias, st) : launch_vox_bf3_wgrad_ps<16, 16, false>(d, x, dz, dw, dbias, st);
-    }
-    if (ps_on && (d->Cin != 8 || co8)) {
-      if (d->Cin == 8) return Z == 64 ? launch_vox_bf3_wgrad_ps<64, 8, true>(d, x, dz, dw, dbias, st) : launch_vox_bf3_wgrad_ps<32, 8, true>(d, x, dz, dw, dbias, st);
-      if (Z == 64) return co8 ? launch_vox_bf3_wgrad_ps<64, 16, true>(d, x, dz, dw, dbias, st) : launch_vox_bf3_wgrad_ps<64, 16, false>(d, x, dz, dw, dbias, st);
-      return co8 ? launch_vox_bf3_wgrad_ps<32, 16, true>(d, x, dz, dw, dbias, st) : launch_vox_bf3_wgrad_ps<32, 16, false>(d, x, dz, dw, dbias, st);
-    }
-    if (d->Cin == 8) {
-      if (Z == 64) return co8 ? launch_vox_bf3_wgrad<64, 8, true>(d, x, dz, dw, dbias, st) : launch_vox_bf3_wgrad<64, 8, false>(d, x, dz, dw, dbias, st);
-      return co8 ? launch_vox_bf3_wgrad<32, 8, true>(d, x, dz, dw, dbias, st) : launch_vox_bf3_wgrad<32, 8, false>(d, x, dz, dw, dbias, st);
-    }
-    if (Z == 64) return co8 ? launch_vox_bf3_wgrad<64, 16, true>(d, x, dz, dw, dbias, st) : launch_vox_bf3_wgrad<64, 16, false>(d, x, dz, dw, dbias, st);
-    return co8 ? launch_vox_bf3_wgrad<32, 16, true>(d, x, dz, dw, dbias, st) : launch_vox_bf3_wgrad<32, 16, false>(d, x, dz, dw, dbias, st);
+    if (Z == 16 && !vox_wgrad_ps_only(d)) { muvo_set_error("vox_wgrad: 16-voxel z lines need the plane-streaming kernel"); return MUVO_ERR_INVALID_ARG; }
+    const bool co8 = d->Cout <= 8;      // the idle half of the MFMA rows carries a second z tap
+    if (d->Cin != 8)
+      return vox_with_z<true>(Z, [&](auto z) -> int {
+        constexpr int ZC = decltype(z)::value;
+        return vox_with_bool(co8, [&](auto c) -> int { return launch_vox_bf3_wgrad_ps<ZC, 16, decltype(c)::value>(d, x, dz, dw, dbias, st, aff); });
+      });
+    if (co8) return vox_with_z(Z, [&](auto z) -> int { return launch_vox_bf3_wgrad_ps<decltype(z)::value, 8, true>(d, x, dz, dw, dbias, st, aff); });
+    return vox_with_z(Z, [&](auto z) -> int { return launch_vox_bf3_wgrad<decltype(z)::value>(d, x, dz, dw, dbias, st, aff); });
   }
+  // exact fp32: 16 input channels per workgroup with 2 output quads per role, or 8 input channels with 1 output quad per role
   const bool r4 = d->Cin % 16 == 0;
-  // 16 input channels per workgroup with 2 output quads per role, or 8 input channels with 1 output quad per role
-  if (Z == 64) return r4 ? launch_vox_wgrad<4, 2, 64, 4>(d, x, dz, dw, dbias, st) : launch_vox_wgrad<2, 1, 64, 4>(d, x, dz, dw, dbias, st);
-  return r4 ? launch_vox_wgrad<4, 2, 32, 8>(d, x, dz, dw, dbias, st) : launch_vox_wgrad<2, 1, 32, 8>(d, x, dz, dw, dbias, st);
+  return vox_with_z(Z, [&](auto z) -> int {
+    constexpr int ZC = decltype(z)::value, TYB = ZC == 64 ? 4 : 8;
+    return r4 ? launch_vox_wgrad<4, 2, ZC, TYB>(d, x, dz, dw, dbias, st) : launch_vox_wgrad<2, 1, ZC, TYB>(d, x, dz, dw, dbias, st);
+  });
 }

@@ -1,7 +1,7 @@
 """CPU self-test of the voxel-kernel bars (tests/test_vox_kernels_gpu.py): on the shapes of that matrix (x cropped), the CPU
 emulation of the kernels' bf16x3 arithmetic passes the bars with a margin of 2, while the two subtle faults an elementwise
 rtol misses - one cross product lost everywhere, both cross products of one tap lost - fail them by 4x or more.  Also checks
-that the matrix reaches every kernel instantiation the dispatch can take under the default settings."""
+that the matrix reaches every kernel instantiation the dispatch can take (all that conv_vox.hip compiles)."""
 import pytest
 import torch
 
@@ -69,8 +69,8 @@ def test_affine_padding_after_map_is_separated(case):
     assert V.excess(V.error_stats(wrong_w, rw, dw), bar) >= SEPARATION
 
 
-# Every instantiation vox_conv_dispatch / vox_wgrad can launch under the default settings (template arguments as rocprofv3
-# prints them; GENERIC = true for an activation beyond LeakyReLU or an accumulating pass).
+# Every instantiation vox_conv_dispatch / vox_wgrad can launch, i.e. every templated kernel of conv_vox.hip (template arguments
+# as rocprofv3 prints them; GENERIC = true for an activation beyond LeakyReLU or an accumulating pass).
 REACHABLE = (
     [f'vox_bf3_ps_kernel<{z}, 8, {co8}, {g}>' for z in (16, 32, 64) for co8 in ('true', 'false') for g in ('true', 'false')]
     + [f'vox_bf3_2row_kernel<{z}, 8, {g}>' for z in (32, 64) for g in ('true', 'false')]

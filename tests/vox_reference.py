@@ -173,8 +173,8 @@ def emulate_wgrad(x, dy, w_shape, form='bf16x3', tap=(1, 1, 1)):
 
 
 # ------------------------------------------------------------------------------------------------ dispatch mirror
-PS_TY = 8          # VOX_PS_TY: output rows per plane-streaming workgroup
-WGPS_SW = 4        # VOX_WGPS_SW: staging waves of vox_bf3_wgrad_ps_kernel with 16 input / <= 8 produced channels
+PS_TY = 8          # output rows per plane-streaming workgroup (VOX_PS_TY in conv_vox.hip)
+WGPS_SW = 4        # (VOX_WGPS_SW in conv_vox.hip) staging waves of vox_bf3_wgrad_ps_kernel with 16 input / <= 8 produced channels
 BLOCKS_TARGET = 128
 
 
@@ -183,7 +183,7 @@ def _cdiv(a, b):
 
 
 def _xseg(n, x, ytiles, factor=1):
-    """x-segment length of a bf16x3 voxel launch (launch_vox_bf3_* / launch_vox_bf3_wgrad*): x is halved until the grid has
+    """x-segment length of a bf16x3 voxel launch (vox_xseg in conv_vox.hip): x is halved until the grid has
     BLOCKS_TARGET workgroups or a segment would drop to 12 planes or fewer."""
     xseg = x
     while n * ytiles * _cdiv(x, xseg) * factor < BLOCKS_TARGET and xseg > 12:
@@ -196,8 +196,8 @@ def _b(v):
 
 
 def vox_plan(cin, cout, n, shape, op, act=ACT_NONE, mode='bf3', det=False):
-    """The conv_vox.hip kernels a 3x3x3 / stride 1 / pad 1 convolution runs for `op` ('fwd', 'dgrad', 'wgrad') under the
-    default settings (no MUVO_VOX_* switch set, muvo_conv_set_bf16x3_min_gflop(0) in bf16x3 mode), restated from
+    """The conv_vox.hip kernels a 3x3x3 / stride 1 / pad 1 convolution runs for `op` ('fwd', 'dgrad', 'wgrad') with
+    muvo_conv_set_bf16x3_min_gflop(0) in bf16x3 mode (and MUVO_VOX_BLOCKS / MUVO_VOX_WGRAD_BLOCKS unset), restated from
     vox_conv_dispatch / vox_wgrad and the applicability rules in conv_vox.hip / conv_gemm.hip.
 
     Returns None when the voxel kernels do not serve the shape, else dict(family (muvo_conv_kernel_family: 4 bf16x3, 2 fp32),

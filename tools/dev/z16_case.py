@@ -1,4 +1,4 @@
-"""dev: the Z = 16 Conv3d cases of test_conv_family, errors per gradient, under the current MUVO_VOX_WGRAD_PS setting"""
+"""dev: the Z = 16 Conv3d cases of test_conv_family, errors per gradient against PyTorch on the CPU"""
 import os, sys, torch
 import torch.nn.functional as F
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
