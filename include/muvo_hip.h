@@ -464,6 +464,35 @@ int muvo_range_projection(const float* points_xyz, const uint8_t* obj_tag, const
                           float* xyzd, uint8_t* seg, void* stream);
 int muvo_voxel_grid(const int64_t* rows, int64_t Q, const uint8_t* remap, int X, int Y, int Z, uint32_t* scratch, uint8_t* voxels,
                     void* stream);
+/* ---- dataset frame preparation, batched over the F = b*s frames of a batch (csrc/dataset.hip; muvo/data/dataset.py:231-369) ----
+ * The host reads and decodes the files of a recording; these entry points turn the raw frames into the batch dict.  Frames are
+ * a grid dimension: one call per batch, no host loop over frames, no host sync.  Every output is bit-exact (integer work, or
+ * float64 in the reference's order of operations).
+ * muvo_birdview_decode_frames: integer bird's-eye view (F,H,W) int32 -> bit planes birdview (F,n_classes,H,W) float32
+ *   (integer_to_binary), label (F,H,W) int64 = highest set bit, n_classes-1 where none is set (calculate_birdview_labels), and
+ *   instance_mask (F,H,W) uint8 = bit 3 | bit 4 (dataset.py:266).
+ * muvo_label_components_frames: scipy.ndimage.label of each (1,H,W) mask with the default structure (4-connectivity in the
+ *   plane): labels (F,H,W) int32, components numbered 1, 2, ... by their first pixel in row-major order, background 0.  Union-find
+ *   by smallest linear index in 32x32 LDS tiles, borders merged with atomicMin, flattened, roots numbered by a scan; every loop
+ *   is bounded by the pixel count (csrc/dataset.hip).  Any H, W with H*W < 2^30.  scratch: 2*F*H*W int32.
+ * muvo_depth_semantic_decode_frames: RGBA (F,H,W,4) uint8 -> semantic_image (F,H,W) int64 = remap[A], image_instance_mask (F,H,W)
+ *   uint8 = A == vehicle_tag | A == pedestrian_tag, depth_color (F,3,H,W) float64 = RGB / 255.0, depth (F,H,W) float64 =
+ *   (65536 R + 256 G + B) / (256^3 - 1), values > 0.999 -> -1 (dataset.py:330-352).  Each output may be NULL (not all).
+ * muvo_range_projection_frames / muvo_voxel_grid_frames: muvo_range_projection / muvo_voxel_grid over padded arrays
+ *   points_xyz (F,Pmax,3), obj_tag (F,Pmax), rows (F,Qmax,4) with per-frame counts num_points / num_rows (F) int32 on the device
+ *   (clamped to the padding); xyzd (F,4,H,W), seg (F,H,W) int64 or NULL, voxels (F,X,Y,Z).  scratch: 12*F*H*W bytes /
+ *   4*F*X*Y*Z bytes.  Same device functions, same results frame by frame. */
+int muvo_birdview_decode_frames(const int32_t* birdview_int, int F, int H, int W, int n_classes, float* birdview, int64_t* label,
+                                uint8_t* instance_mask, void* stream);
+int muvo_label_components_frames(const uint8_t* mask, int F, int H, int W, int32_t* scratch, int32_t* labels, void* stream);
+int muvo_depth_semantic_decode_frames(const uint8_t* depth_semantic, int F, int H, int W, const uint8_t* remap, int vehicle_tag,
+                                      int pedestrian_tag, int64_t* semantic_image, uint8_t* image_instance_mask, double* depth_color,
+                                      double* depth, void* stream);
+int muvo_range_projection_frames(const float* points_xyz, const uint8_t* obj_tag, const int32_t* num_points, const uint8_t* remap, int F,
+                                 int64_t Pmax, const double* lidar_pos, const double* ego_dim, double fov_down_deg, double fov_up_deg,
+                                 int H, int W, void* scratch, float* xyzd, int64_t* seg, void* stream);
+int muvo_voxel_grid_frames(const int64_t* rows, const int32_t* num_rows, const uint8_t* remap, int F, int64_t Qmax, int X, int Y, int Z,
+                           uint32_t* scratch, uint8_t* voxels, void* stream);
 /* ---- voxel labels from raw sensor data: the reference's offline step data/generate_voxels.py::voxelize_one ->
  * data/data_preprocessing.py::merge_pcd + voxel_filter, for F frames per call ----
  * depth_semantic (F,H,W,4) uint8: R, G, B = 24-bit depth code, A = CARLA tag; points_xyz (F,Pmax,3) float32 in the lidar sensor

@@ -3,35 +3,7 @@
 // PointCloud.do_range_projection (muvo/utils/geometry_utils.py:176-213).  HBM-bound scatter kernels; the reference's
 // "sort by depth, scatter, last write wins" becomes a 64-bit atomicMin on (depth, point index) per pixel.
 #include "common.h"
-
-struct RangeArgs {
-  double lidar[3];        // POINTS.LIDAR_POSITION
-  double ego_lo[3], ego_hi[3];
-  double fov_down_abs, fov;   // |fov_down|, fov_up - fov_down  (radians)
-  int H, W;
-};
-
-// Geometry of one point exactly as the reference does it: float32 conversion to the ego frame, float64 projection.
-__device__ __forceinline__ bool range_point(const float* __restrict__ raw, long i, const RangeArgs& a, float (&p)[3], double& depth,
-                                            int& ph, int& pw) {
-  // convert_coor_lidar (data_preprocessing.py:119-122): float32 += position, y mirrored
-  p[0] = (float)((double)raw[i * 3] + a.lidar[0]);
-  p[1] = -(float)((double)raw[i * 3 + 1] + a.lidar[1]);
-  p[2] = (float)((double)raw[i * 3 + 2] + a.lidar[2]);
-  // ego-vehicle box (dataset.py:286-290), strict inequalities in float64
-  const bool ego = a.ego_lo[0] < (double)p[0] && (double)p[0] < a.ego_hi[0] && a.ego_lo[1] < (double)p[1] &&
-                   (double)p[1] < a.ego_hi[1] && a.ego_lo[2] < (double)p[2] && (double)p[2] < a.ego_hi[2];
-  if (ego) return false;
-  // do_range_projection (geometry_utils.py:176-198)
-  const double cx = (double)p[0] - a.lidar[0], cy = -(double)p[1] - a.lidar[1], cz = (double)p[2] - a.lidar[2];
-  depth = sqrt(cx * cx + cy * cy + cz * cz);
-  const double yaw = atan2(-cy, cx), pitch = asin(cz / depth);
-  double fw = floor(0.5 * (1.0 - yaw / M_PI) * (double)a.W), fh = floor((1.0 - (pitch + a.fov_down_abs) / a.fov) * (double)a.H);
-  fw = fmin((double)(a.W - 1), fw); fw = fmax(0.0, fw);
-  fh = fmin((double)(a.H - 1), fh); fh = fmax(0.0, fh);
-  pw = (int)fw; ph = (int)fh;
-  return true;
-}
+#include "input_dev.h"
 
 // pass 1: best[pixel] = min over its points of the depth bit pattern (non-negative doubles order like their bits)
 __global__ void __launch_bounds__(256)
@@ -59,16 +31,9 @@ range_write_kernel(const float* __restrict__ raw, const unsigned char* __restric
                    RangeArgs a, const unsigned int* __restrict__ winner, float* __restrict__ xyzd, unsigned char* __restrict__ seg) {
   const long HW = (long)a.H * a.W;
   for (long px = blockIdx.x * 256L + threadIdx.x; px < HW; px += (long)gridDim.x * 256) {
-    const unsigned int w = winner[px];
-    float p[3] = {0.f, 0.f, 0.f};
-    float d = -1.f;
-    unsigned char s = 0;
-    if (w != 0xffffffffu) {
-      double depth; int ph, pw;
-      range_point(raw, (long)w, a, p, depth, ph, pw);
-      d = (float)depth;
-      s = remap[tag[w]];
-    }
+    float p[3], d;
+    unsigned char s;
+    range_pixel(raw, tag, remap, a, winner[px], p, d, s);
     xyzd[px] = p[0]; xyzd[HW + px] = p[1]; xyzd[2 * HW + px] = p[2]; xyzd[3 * HW + px] = d;
     if (seg) seg[px] = s;
   }
@@ -79,11 +44,7 @@ __global__ void __launch_bounds__(256)
 voxel_scatter_kernel(const long long* __restrict__ rows, long Q, const unsigned char* __restrict__ remap, int X, int Y, int Z,
                      unsigned int* __restrict__ key) {
   for (long i = blockIdx.x * 256L + threadIdx.x; i < Q; i += (long)gridDim.x * 256) {
-    const long long x = rows[i * 4], y = rows[i * 4 + 1], z = rows[i * 4 + 2];
-    long long t = rows[i * 4 + 3];
-    if (x < 0 || x >= X || y < 0 || y >= Y || z < 0 || z >= Z) continue;
-    if (t == 255) t = 0;
-    atomicMax(key + ((x * Y + y) * Z + z), ((unsigned int)(i + 1) << 8) | (unsigned int)remap[t]);
+    voxel_scatter_row(rows, i, remap, X, Y, Z, key);
   }
 }
 __global__ void __launch_bounds__(256)
@@ -151,12 +112,7 @@ int muvo_range_projection(const float* points_xyz, const uint8_t* obj_tag, const
                           float* xyzd, uint8_t* seg, void* stream) {
   MUVO_CHECK_ARG(points_xyz && obj_tag && remap && lidar_pos && ego_dim && scratch && xyzd, "range_projection: null pointer");
   MUVO_CHECK_ARG(P >= 0 && P < 0xffffffffll && H > 0 && W > 0, "range_projection: bad sizes");
-  RangeArgs a;
-  for (int k = 0; k < 3; ++k) a.lidar[k] = lidar_pos[k];
-  a.ego_lo[0] = -ego_dim[0] / 2; a.ego_lo[1] = -ego_dim[1] / 2; a.ego_lo[2] = 0.0;
-  a.ego_hi[0] = ego_dim[0] / 2; a.ego_hi[1] = ego_dim[1] / 2; a.ego_hi[2] = ego_dim[2];
-  const double fd = fov_down_deg / 180.0 * M_PI, fu = fov_up_deg / 180.0 * M_PI;
-  a.fov_down_abs = fabs(fd); a.fov = fu - fd; a.H = H; a.W = W;
+  const RangeArgs a = range_args(lidar_pos, ego_dim, fov_down_deg, fov_up_deg, H, W);
   const long HW = (long)H * W;
   unsigned long long* best = (unsigned long long*)scratch;
   unsigned int* winner = (unsigned int*)(best + HW);

@@ -119,3 +119,135 @@ def depth_lidar_voxels(depth_semantic, points_xyz, obj_tag, num_points=None, *, 
         if not dense:
             out += [rows[i, :q].clone() for i, q in enumerate(counts.tolist())]
     return out
+
+
+# ---- frame preparation of the dataset, batched over the F = b*s frames of a batch (csrc/dataset.hip) --------------------------
+VEHICLE_TAG, PEDESTRIAN_TAG = 10, 4                # VOXEL_LABEL_CARLA, constants.py:41-65
+_REMAP = {}
+
+
+def _remap(dev):
+    """label_remap, uploaded once per device and complete before it is handed out: the cached table is used from whichever
+    stream calls (the loader's, the main one), so its upload must not be ordered on one of them only."""
+    if dev not in _REMAP:
+        table = label_remap(dev)
+        torch.cuda.current_stream(dev).synchronize()
+        _REMAP[dev] = table
+    return _REMAP[dev]
+
+
+def birdview_decode_frames(birdview_int, n_classes):
+    """birdview_int (F, H, W) int32 device tensor (the bird's-eye-view PNG) -> (birdview (F, n_classes, H, W) float32 bit
+    planes, birdview_label (F, H, W) int64 = highest set bit, instance mask (F, H, W) uint8 = bit 3 | bit 4)."""
+    bev = birdview_int.to(torch.int32).contiguous()
+    F, H, W = bev.shape
+    dev = bev.device
+    planes = torch.empty(F, n_classes, H, W, device=dev, dtype=torch.float32)
+    label = torch.empty(F, H, W, device=dev, dtype=torch.int64)
+    mask = torch.empty(F, H, W, device=dev, dtype=torch.uint8)
+    ops._ck(ops.lib().muvo_birdview_decode_frames(ops._p(bev), F, H, W, int(n_classes), ops._f(planes), ops._p(label), ops._p(mask),
+                                                 ops._st()))
+    return planes, label, mask
+
+
+def label_components_frames(mask):
+    """mask (F, H, W) uint8 device tensor -> (F, H, W) int32: scipy.ndimage.label of every frame (4-connectivity, components
+    numbered from 1 in the order of their first pixel in a row-major scan)."""
+    m = mask.to(torch.uint8).contiguous()
+    F, H, W = m.shape
+    scratch = torch.empty(2 * F * H * W, device=m.device, dtype=torch.int32)
+    out = torch.empty(F, H, W, device=m.device, dtype=torch.int32)
+    ops._ck(ops.lib().muvo_label_components_frames(ops._p(m), F, H, W, ops._p(scratch), ops._p(out), ops._st()))
+    return out
+
+
+def depth_semantic_decode_frames(depth_semantic, semantic=True, instance_mask=True, depth=True):
+    """depth_semantic (F, H, W, 4) uint8 device tensor as PIL loads the PNG -> dict with, as asked for, `semantic_image`
+    (F, H, W) int64, `image_instance_mask` (F, H, W) bool, `depth_color` (F, 3, H, W) and `depth` (F, H, W) float64
+    (dataset.py:330-352)."""
+    img = depth_semantic.to(torch.uint8).contiguous()
+    F, H, W = img.shape[:3]
+    assert img.dim() == 4 and img.shape[3] == 4, 'depth_semantic must be (F, H, W, 4)'
+    dev = img.device
+    sem = torch.empty(F, H, W, device=dev, dtype=torch.int64) if semantic else None
+    inst = torch.empty(F, H, W, device=dev, dtype=torch.bool) if instance_mask else None
+    col = torch.empty(F, 3, H, W, device=dev, dtype=torch.float64) if depth else None
+    dep = torch.empty(F, H, W, device=dev, dtype=torch.float64) if depth else None
+    ops._ck(ops.lib().muvo_depth_semantic_decode_frames(ops._p(img), F, H, W, ops._p(_remap(dev)), VEHICLE_TAG, PEDESTRIAN_TAG,
+                                                       ops._p(sem), ops._p(inst), ops._p(col), ops._p(dep), ops._st()))
+    out = {'semantic_image': sem, 'image_instance_mask': inst, 'depth_color': col, 'depth': dep}
+    return {k: v for k, v in out.items() if v is not None}
+
+
+def range_projection_frames(points_xyz, obj_tag, num_points, lidar_position=(1.0, 0.0, 2.0), fov=(-30, 10), H=64, W=1024, with_seg=True):
+    """range_projection of F frames in one call: points_xyz (F, Pmax, 3) float32, obj_tag (F, Pmax) uint8, num_points (F,)
+    int32 device tensors -> (range_view_pcd_xyzd (F, 4, H, W) float32, range_view_pcd_seg (F, H, W) int64 or None)."""
+    pts, tag = points_xyz.float().contiguous(), obj_tag.to(torch.uint8).contiguous()
+    F, Pmax = tag.shape
+    dev = pts.device
+    npt = num_points.to(torch.int32).contiguous()
+    assert pts.shape == (F, Pmax, 3) and npt.shape == (F,)
+    xyzd = torch.empty(F, 4, H, W, device=dev, dtype=torch.float32)
+    seg = torch.empty(F, H, W, device=dev, dtype=torch.int64) if with_seg else None
+    scratch = torch.empty(F * H * W * 3, device=dev, dtype=torch.int32)
+    lp = (C.c_double * 3)(*lidar_position)
+    ego = (C.c_double * 3)(*EGO_VEHICLE_DIMENSION)
+    ops._ck(ops.lib().muvo_range_projection_frames(ops._f(pts) if Pmax else None, ops._p(tag) if Pmax else None, ops._p(npt),
+                                                  ops._p(_remap(dev)), F, ops._i64(Pmax), lp, ego, C.c_double(fov[0]),
+                                                  C.c_double(fov[1]), H, W, ops._p(scratch), ops._f(xyzd), ops._p(seg), ops._st()))
+    return xyzd, seg
+
+
+def voxel_grid_frames(voxel_rows, num_rows, size=(192, 192, 64)):
+    """voxel_grid of F frames in one call: voxel_rows (F, Qmax, 4) int64, num_rows (F,) int32 device tensors -> (F, *size) uint8."""
+    rows = voxel_rows.to(torch.int64).contiguous()
+    F, Qmax = rows.shape[:2]
+    dev = rows.device
+    nq = num_rows.to(torch.int32).contiguous()
+    assert rows.shape == (F, Qmax, 4) and nq.shape == (F,)
+    scratch = torch.empty(F * size[0] * size[1] * size[2], device=dev, dtype=torch.int32)
+    vox = torch.empty((F, *size), device=dev, dtype=torch.uint8)
+    ops._ck(ops.lib().muvo_voxel_grid_frames(ops._p(rows) if Qmax else None, ops._p(nq), ops._p(_remap(dev)), F, ops._i64(Qmax),
+                                            size[0], size[1], size[2], ops._p(scratch), ops._p(vox), ops._st()))
+    return vox
+
+
+# what the host hands over per frame (muvo_amd.data.dataset.CarlaDataset.read_raw); arrays of (b, s, ...) on the device
+RAW_PASS_THROUGH = ('image', 'route_map', 'steering', 'throttle_brake', 'speed', 'reward', 'value_function', 'intrinsics', 'extrinsics')
+
+
+def prepare_frames(raw, cfg):
+    """The reference's batch dict (muvo/data/dataset.py:231-369 after the DataLoader's collation) from a batch of raw frames
+    on the device.  raw: dict of (b, s, ...) device tensors - the RAW_PASS_THROUGH keys as the batch carries them, plus
+    `birdview_int` (b, s, H, W) int32 with `n_classes` (int), `points_xyz` (b, s, Pmax, 3) float32, `obj_tag` (b, s, Pmax) uint8,
+    `num_points` (b, s) int32, `voxel_rows` (b, s, Qmax, 4) int64 and `num_voxels` (b, s) int32 (VOXEL_SEG.ENABLED),
+    `depth_semantic` (b, s, H, W, 4) uint8 (only when a head needs it).  One launch group per kind of data, none per frame."""
+    b, s = raw['image'].shape[:2]
+    out = {k: raw[k] for k in RAW_PASS_THROUGH}
+
+    def frames(t):
+        return t.reshape(b * s, *t.shape[2:])
+
+    def batch(t, channel=True):
+        return t.reshape(b, s, 1, *t.shape[1:]) if channel else t.reshape(b, s, *t.shape[1:])
+
+    planes, label, mask = birdview_decode_frames(frames(raw['birdview_int']), int(raw['n_classes']))
+    out['birdview'], out['birdview_label'] = batch(planes, False), batch(label)
+    out['instance_label'] = batch(label_components_frames(mask))
+    want_seg = bool(cfg.LIDAR_SEG.ENABLED)
+    if cfg.MODEL.LIDAR.ENABLED or want_seg:
+        xyzd, seg = range_projection_frames(frames(raw['points_xyz']), frames(raw['obj_tag']), frames(raw['num_points']),
+                                            lidar_position=cfg.POINTS.LIDAR_POSITION, fov=cfg.POINTS.FOV, H=cfg.POINTS.CHANNELS,
+                                            W=cfg.POINTS.HORIZON_RESOLUTION, with_seg=want_seg)
+        if cfg.MODEL.LIDAR.ENABLED:
+            out['range_view_pcd_xyzd'] = batch(xyzd, False)
+        if want_seg:
+            out['range_view_pcd_seg'] = batch(seg)
+    if cfg.VOXEL_SEG.ENABLED:
+        out['voxel'] = batch(voxel_grid_frames(frames(raw['voxel_rows']), frames(raw['num_voxels']), size=tuple(cfg.VOXEL.SIZE)))
+    sem, inst, dep = bool(cfg.SEMANTIC_IMAGE.ENABLED), bool(cfg.LOSSES.RGB_INSTANCE), bool(cfg.DEPTH.ENABLED)
+    if sem or inst or dep:
+        d = depth_semantic_decode_frames(frames(raw['depth_semantic']), semantic=sem, instance_mask=inst, depth=dep)
+        for k, v in d.items():
+            out[k] = batch(v, k != 'depth_color')
+    return out

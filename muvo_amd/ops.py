@@ -78,6 +78,8 @@ EXPORTS = [
     'muvo_stem_conv_supported', 'muvo_stem_conv_forward', 'muvo_stem_conv_wgrad',
     'muvo_rssm_supported', 'muvo_rssm_transposed_floats', 'muvo_rssm_scratch_floats', 'muvo_rssm_forward', 'muvo_rssm_backward',
     'muvo_voxelize_scratch_bytes', 'muvo_voxelize_frames',
+    'muvo_birdview_decode_frames', 'muvo_label_components_frames', 'muvo_depth_semantic_decode_frames',
+    'muvo_range_projection_frames', 'muvo_voxel_grid_frames',
 ]
 
 

@@ -5,11 +5,14 @@ LightningModule — training_step -> zero_grad -> backward -> (gradient exchange
 callback: every `VAL_CHECK_INTERVAL` steps a Lightning-format checkpoint is written INTO THE CURRENT WORKING DIRECTORY under
 Lightning's file name (`MyModelCheckpoint`, train.py:31-48: `filename = filepath.split('/')[-1]`).
 
-The dataset (CARLA recordings, muvo/data) is out of scope: batches are synthetic with the reference's batch schema
-(`muvo_amd/data/synthetic.py`).  One process per GPU; under `torch.distributed.run` the ranks form an RCCL group and
+With a data root (`DATASET.DATAROOT` or `--dataset-root`) the batches come from recorded CARLA runs through
+`muvo_amd.data.dataset.DataModule` (host threads read and decode the files ahead of the step, the GPU prepares the frames of a batch in a
+handful of launches); without one they are synthetic with the reference's batch schema (`muvo_amd/data/synthetic.py`).
+One process per GPU; under `torch.distributed.run` the ranks form an RCCL group and
 `WorldModelTrainer` exchanges gradients itself (muvo_amd/parallel.py) — no DistributedDataParallel wrapper.
 
     python -m muvo_amd.train --config-file muvo_amd/configs/test_base_1d.yml STEPS 100 BATCHSIZE 2 [--resume epoch=0-step=50.ckpt]
+    python -m muvo_amd.train --config-file muvo_amd/configs/test_base_1d.yml --dataset-root /data/carla STEPS 100 BATCHSIZE 2
 """
 import json
 import os
@@ -49,9 +52,10 @@ def load_checkpoint(module, optimizer, scheduler, path):
     return int(ck['global_step'])
 
 
-def fit(cfg, device, steps=None, resume=None, log=None, seed=1234, batch_fn=None, setup=None):
+def fit(cfg, device, steps=None, resume=None, log=None, seed=1234, batch_fn=None, setup=None, dataset_root=None, input_stream=False):
     """The training loop; returns (module, list of per-step loss dicts as floats).  batch_fn(micro_index) / setup(module):
-    hooks for tests (own batches, e.g. switching dropout off)."""
+    hooks for tests (own batches, e.g. switching dropout off).  dataset_root (default: cfg.DATASET.DATAROOT): batches from the
+    recordings below it instead of synthetic ones; input_stream=True prepares them on a side stream instead of the main one."""
     import torch.distributed as dist
     rank = dist.get_rank() if dist.is_initialized() else 0
     torch.manual_seed(seed)
@@ -69,6 +73,13 @@ def fit(cfg, device, steps=None, resume=None, log=None, seed=1234, batch_fn=None
     s = cfg.RECEPTIVE_FIELD + cfg.FUTURE_HORIZON
     world = dist.get_world_size() if dist.is_initialized() else 1
     history, micro = [], global_step * accum
+    dataset_root = dataset_root or cfg.DATASET.DATAROOT
+    if dataset_root and batch_fn is None:
+        from muvo_amd.data.dataset import DataModule
+        data = DataModule(cfg, dataset_root, device=device, rank=rank, world_size=world, seed=seed, input_stream=input_stream)
+        data.setup()
+        recorded = data.train_batches(start=micro)        # a resumed run continues the order of the interrupted one
+        batch_fn = lambda _micro: next(recorded)          # noqa: E731
     t0 = time.time()
     while global_step < steps:
         # every optimizer step starts from its own seed: a resumed run draws the same RSSM noise / augmentation as the
@@ -103,6 +114,7 @@ def fit(cfg, device, steps=None, resume=None, log=None, seed=1234, batch_fn=None
 def main(argv=None):
     parser = get_parser()
     parser.add_argument('--resume', default='', help='Lightning-format checkpoint to continue from')
+    parser.add_argument('--dataset-root', default='', help='directory of recorded runs (overrides DATASET.DATAROOT)')
     args = parser.parse_args(argv)
     cfg = get_cfg(args)
     import torch.distributed as dist
@@ -112,7 +124,7 @@ def main(argv=None):
     device = torch.device('cuda', local_rank)
     if world > 1:
         dist.init_process_group('nccl', device_id=device)
-    fit(cfg, device, resume=args.resume or None)
+    fit(cfg, device, resume=args.resume or None, dataset_root=args.dataset_root or None)
     if world > 1:
         dist.destroy_process_group()
 
