@@ -423,12 +423,13 @@ extern "C" int muvo_bn_train_fwd(const float* x, const float* gamma, const float
   hipLaunchKernelGGL(moments_kernel, dim3(C, chunks), dim3(256), 0, st, x, sums, (long)S, (long)C * S, cnt,
                      (int)(S % 4 == 0 && ((uintptr_t)x & 15) == 0));
   const long total = cnt * C;
-  if (S % 4 == 0 && S >= 1024 && (long)N * C <= 65535 && (((uintptr_t)x | (uintptr_t)y | (uintptr_t)(residual ? residual : x)) & 15) == 0) {
+  const bool aligned = (((uintptr_t)x | (uintptr_t)y | (uintptr_t)(residual ? residual : x)) & 15) == 0;
+  if (S % 4 == 0 && S >= 1024 && (long)N * C <= 65535 && aligned) {
     int gx = cdiv(S / 4, 256 * 4);
     if (gx > 64) gx = 64;
     hipLaunchKernelGGL(bn_apply_vec_kernel, dim3(gx, N * C), dim3(256), 0, st, x, residual, y, save_mean, save_rstd, gamma, beta,
                        C, (long)S, res_mode, relu, (const double*)sums, (double)cnt, eps, running_mean, running_var, momentum);
-  } else if (S % 4 == 0)
+  } else if (S % 4 == 0 && aligned)      // float4 loads and stores here too: a view at an odd element offset takes the scalar kernel
     hipLaunchKernelGGL(bn_apply_kernel, dim3(ew_grid(total / 4)), dim3(256), 0, st, x, residual, y, save_mean,
                        save_rstd, gamma, beta, C, (long)S, total / 4, res_mode, relu, (const double*)sums, (double)cnt, eps,
                        running_mean, running_var, momentum);
