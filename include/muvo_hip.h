@@ -301,6 +301,20 @@ int muvo_attention_fwd(const float* qkv, float* out, float* lse, int L, int N, i
                        void* stream);
 int muvo_attention_bwd(const float* qkv, const float* out, const float* dout, const float* lse, float* dqkv, int L, int N, int H,
                        int DH, float p, uint64_t seed, void* stream);
+/* The same attention core for any L >= 1 (csrc/attention.hip, streamed kernels): keys (forward, dQ) or queries (dK, dV) pass
+ * through LDS in blocks of bk rows, the forward carries a running maximum and running sum per query (online softmax), a
+ * workgroup owns bq rows; nothing of size L x L is written anywhere.  Same layouts, same exact-fp32 MFMA arithmetic, same
+ * dropout mask index as above, so one seed gives one mask on every path.  muvo_attention_stream_supported: DH in {16,32,48,64}
+ * and L >= 1.  muvo_attention_stream_blocks reports the compiled (bq, bk).  muvo_attention_stream_bwd takes a caller-allocated
+ * workspace dws of N*H*L floats: the dQ kernel stores D = dout . out per query there and the dK/dV kernel, queued after it on
+ * the same stream, reads it; the contents afterwards are D (nothing to keep).  All of dqkv is written; no atomics, no
+ * communication between workgroups: bit-reproducible. */
+int muvo_attention_stream_supported(int L, int DH);
+int muvo_attention_stream_blocks(int* bq, int* bk);
+int muvo_attention_stream_fwd(const float* qkv, float* out, float* lse, int L, int N, int H, int DH, float p, uint64_t seed,
+                              void* stream);
+int muvo_attention_stream_bwd(const float* qkv, const float* out, const float* dout, const float* lse, float* dqkv, float* dws,
+                              int L, int N, int H, int DH, float p, uint64_t seed, void* stream);
 /* The whole recurrent state-space model (muvo/models/transition.py:76-173) as two persistent kernels (csrc/rssm.hip): one
  * workgroup per CU walks the T time steps, 4 grid barriers per step; T <= 64, H/S/E/A multiples of 4; B <= 64 sequences, run as
  * consecutive launches over slabs of 4 (sequences are independent).  The grid is clamped to what the occupancy calculator says
@@ -351,7 +365,7 @@ int muvo_resize_bilinear(const float* x, float* y, int64_t NC, int H, int W, int
 int muvo_resize_nearest_f32(const float* x, float* y, int64_t NC, int D, int H, int W, int OD, int OH, int OW, void* stream);
 int muvo_resize_nearest_u8(const uint8_t* x, uint8_t* y, int64_t NC, int D, int H, int W, int OD, int OH, int OW,
                            void* stream);
-/* attention probabilities: P = softmax(S), Pd = dropout(P) (functional MHA dropout) */
+/* attention probabilities: P = softmax(S), Pd = dropout(P) (functional MHA dropout); cols <= 1088 */
 int muvo_softmax_dropout_fwd(const float* S, float* P, float* Pd, int64_t rows, int cols, float p, uint64_t seed, void* stream);
 int muvo_softmax_dropout_bwd(const float* P, const float* dPd, float* dS, int64_t rows, int cols, float p, uint64_t seed,
                              void* stream);

@@ -683,7 +683,10 @@ __global__ void resize_nearest_kernel(const T* __restrict__ x, T* __restrict__ y
 }
 
 // ----------------------------------------------------------------------------------- attention
-// P = softmax(S) over cols (S already scaled); Pd = dropout(P).  One wave per row, cols <= 64*MAXV.
+// P = softmax(S) over cols (S already scaled); Pd = dropout(P).  One wave per row, cols <= 64*MAXV.  Rows of up to 512 columns
+// use MAXV = 8; longer ones, up to 64 * SOFTMAX_MAXV = 1088 (the unfused path as a comparison for the streamed attention kernels
+// at 517 and 1037 tokens), the wider instance.
+#define SOFTMAX_MAXV 17
 template <int MAXV>
 __global__ void __launch_bounds__(256) softmax_dropout_fwd_kernel(const float* __restrict__ S, float* __restrict__ P,
                                                                   float* __restrict__ Pd, long rows, int cols, float p,
@@ -1082,15 +1085,21 @@ int muvo_resize_nearest_u8(const uint8_t* x, uint8_t* y, int64_t NC, int D, int 
 }
 int muvo_softmax_dropout_fwd(const float* S, float* P, float* Pd, int64_t rows, int cols, float p, uint64_t seed,
                              void* stream) {
-  MUVO_CHECK_ARG(S && P && rows > 0 && cols > 0 && cols <= 512, "softmax_fwd: bad args (cols=%d, max 512)", cols);
-  hipLaunchKernelGGL((softmax_dropout_fwd_kernel<8>), dim3(cdiv(rows, 4)), dim3(256), 0, ST, S, P, Pd, (long)rows, cols, p, seed);
+  MUVO_CHECK_ARG(S && P && rows > 0 && cols > 0 && cols <= 64 * SOFTMAX_MAXV, "softmax_fwd: bad args (cols=%d, max %d)", cols, 64 * SOFTMAX_MAXV);
+  if (cols <= 512)
+    hipLaunchKernelGGL((softmax_dropout_fwd_kernel<8>), dim3(cdiv(rows, 4)), dim3(256), 0, ST, S, P, Pd, (long)rows, cols, p, seed);
+  else
+    hipLaunchKernelGGL((softmax_dropout_fwd_kernel<SOFTMAX_MAXV>), dim3(cdiv(rows, 4)), dim3(256), 0, ST, S, P, Pd, (long)rows, cols, p, seed);
   MUVO_CHECK_LAUNCH("softmax_fwd");
   return MUVO_OK;
 }
 int muvo_softmax_dropout_bwd(const float* P, const float* dPd, float* dS, int64_t rows, int cols, float p, uint64_t seed,
                              void* stream) {
-  MUVO_CHECK_ARG(P && dPd && dS && rows > 0 && cols > 0 && cols <= 512, "softmax_bwd: bad args");
-  hipLaunchKernelGGL((softmax_dropout_bwd_kernel<8>), dim3(cdiv(rows, 4)), dim3(256), 0, ST, P, dPd, dS, (long)rows, cols, p, seed);
+  MUVO_CHECK_ARG(P && dPd && dS && rows > 0 && cols > 0 && cols <= 64 * SOFTMAX_MAXV, "softmax_bwd: bad args");
+  if (cols <= 512)
+    hipLaunchKernelGGL((softmax_dropout_bwd_kernel<8>), dim3(cdiv(rows, 4)), dim3(256), 0, ST, P, dPd, dS, (long)rows, cols, p, seed);
+  else
+    hipLaunchKernelGGL((softmax_dropout_bwd_kernel<SOFTMAX_MAXV>), dim3(cdiv(rows, 4)), dim3(256), 0, ST, P, dPd, dS, (long)rows, cols, p, seed);
   MUVO_CHECK_LAUNCH("softmax_bwd");
   return MUVO_OK;
 }

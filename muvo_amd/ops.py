@@ -80,6 +80,7 @@ EXPORTS = [
     'muvo_voxelize_scratch_bytes', 'muvo_voxelize_frames',
     'muvo_birdview_decode_frames', 'muvo_label_components_frames', 'muvo_depth_semantic_decode_frames',
     'muvo_range_projection_frames', 'muvo_voxel_grid_frames',
+    'muvo_attention_stream_supported', 'muvo_attention_stream_blocks', 'muvo_attention_stream_fwd', 'muvo_attention_stream_bwd',
 ]
 
 
@@ -2147,14 +2148,56 @@ class FlashAttentionFn(torch.autograd.Function):
         return dqkv, None, None, None
 
 
+class StreamAttentionFn(torch.autograd.Function):
+    """The attention core for any sequence length (csrc/attention.hip, streamed kernels): K / V pass through LDS block by block
+    under an online softmax, backward recomputes the probabilities from the row log-sum-exp.  Saves qkv, o and lse only; the one
+    extra buffer of backward is D = do . o, (N * heads, L) floats."""
+
+    @staticmethod
+    def forward(ctx, qkv, nheads, p, seed):
+        qkv = qkv.contiguous()
+        l, n, e3 = qkv.shape
+        e = e3 // 3
+        o = torch.empty(l, n, e, device=qkv.device, dtype=torch.float32)
+        lse = torch.empty(n * nheads, l, device=qkv.device, dtype=torch.float32)
+        _ck(lib().muvo_attention_stream_fwd(_f(qkv), _f(o), _f(lse), l, n, nheads, e // nheads, _fl(p), C.c_uint64(seed), _st()))
+        ctx.dims = (l, n, nheads, e // nheads, p, seed)
+        ctx.save_for_backward(qkv, o, lse)
+        return o
+
+    @staticmethod
+    def backward(ctx, do):
+        qkv, o, lse = ctx.saved_tensors
+        l, n, nheads, dh, p, seed = ctx.dims
+        dqkv = torch.empty_like(qkv)
+        dws = torch.empty_like(lse)
+        _ck(lib().muvo_attention_stream_bwd(_f(qkv), _f(o), _f(do.contiguous()), _f(lse), _f(dqkv), _f(dws), l, n, nheads, dh,
+                                            _fl(p), C.c_uint64(seed), _st()))
+        return dqkv, None, None, None
+
+
 FLASH_ATTENTION = os.environ.get('MUVO_FLASH_ATTN', '1') != '0'
+# Shortest sequence the streamed kernels take from the unfused path.  Everything the fused kernels support (L <= 384) goes to
+# them first, so this only matters above 384.  Set from the measurement in DESIGN.md section 7 (tools/attention_bench.py).
+STREAM_MIN_L = 385
+
+
+def attention_path(l, dh):
+    """'fused' | 'stream' | 'unfused': which implementation attention() uses for sequence length l and head dimension dh"""
+    if FLASH_ATTENTION:
+        if lib().muvo_attention_supported(l, dh):
+            return 'fused'
+        if l >= STREAM_MIN_L and lib().muvo_attention_stream_supported(l, dh):
+            return 'stream'
+    return 'unfused'
+
+
+_ATTENTION_FNS = {'fused': FlashAttentionFn, 'stream': StreamAttentionFn, 'unfused': AttentionFn}
 
 
 def attention(qkv, nheads, p, seed):
     l, _, e3 = qkv.shape
-    if FLASH_ATTENTION and lib().muvo_attention_supported(l, e3 // 3 // nheads):
-        return FlashAttentionFn.apply(qkv, nheads, p, seed)
-    return AttentionFn.apply(qkv, nheads, p, seed)
+    return _ATTENTION_FNS[attention_path(l, e3 // 3 // nheads)].apply(qkv, nheads, p, seed)
 
 
 # ================================================================================================ RSSM
