@@ -586,6 +586,29 @@ int muvo_stem_conv_supported(const muvo_conv_desc* d);
 int muvo_stem_conv_forward(const muvo_conv_desc* d, const float* x, const float* w, const float* bias, float* y, int relu, void* stream);
 int muvo_stem_conv_wgrad(const muvo_conv_desc* d, const float* x, const float* dy, float* dw, void* stream);
 
+/* ---- prediction export (csrc/export.hip; the reference's sim_run.py:75-92 does this on the host after copying whole tensors) ----
+ * Occupied-voxel rows: for F frames of a grid (X, Y, Z), z fastest, the voxels whose class is not 0 as rows x, y, z, class of four
+ * uint16 - the recorder's (Q, 4) uint16 voxel files - in ascending h = (x*Y + y)*Z + z (the order of torch.where), the frames
+ * concatenated: frame f owns rows [counts[0] + ... + counts[f-1], ... + counts[f]).
+ *   muvo_voxel_rows_logits: class = first maximum over the C planes of logits (F, C, X, Y, Z) float32 with a strict > comparison
+ *     (torch.argmax on finite input; non-finite logits are outside the contract), 2 <= C <= 16.  The logits are read once.
+ *   muvo_voxel_rows_grid: class = grid (F, X, Y, Z) uint8 itself.
+ * counts (F) int64 always receives the true number of rows per frame; rows beyond `cap` are not written (rows may be NULL with
+ * cap 0: counts only).  muvo_voxel_rows_write writes the rows of the preceding counting call on the same scratch and counts (grid:
+ * the same grid again, NULL after muvo_voxel_rows_logits), so a caller can size `rows` from the counts and the input is still read
+ * only once.  rows must be 8-byte aligned.  scratch: muvo_voxel_rows_scratch_bytes(F, X, Y, Z) bytes (1 per voxel and frame plus
+ * the chunk counters; -1 for sizes the entries refuse: an axis beyond 65536, 2^31 voxels or more, F beyond 65535).
+ * muvo_image_u8: y[i] = trunc(x[i] * 255.0f) saturated to [0, 255], NaN -> 0, for n contiguous float32 elements (any n; 16-byte
+ * loads where x is 16-byte and y 4-byte aligned).  For 0 <= x*255 < 256 this is numpy's (x * 255).astype(np.uint8). */
+int64_t muvo_voxel_rows_scratch_bytes(int F, int X, int Y, int Z);
+int muvo_voxel_rows_logits(const float* logits, int F, int C, int X, int Y, int Z, void* scratch, uint16_t* rows, int64_t cap,
+                           int64_t* counts, void* stream);
+int muvo_voxel_rows_grid(const uint8_t* grid, int F, int X, int Y, int Z, void* scratch, uint16_t* rows, int64_t cap, int64_t* counts,
+                         void* stream);
+int muvo_voxel_rows_write(const uint8_t* grid, int F, int X, int Y, int Z, const void* scratch, const int64_t* counts, uint16_t* rows,
+                          int64_t cap, void* stream);
+int muvo_image_u8(const float* x, uint8_t* y, int64_t n, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

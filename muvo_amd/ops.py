@@ -81,6 +81,7 @@ EXPORTS = [
     'muvo_birdview_decode_frames', 'muvo_label_components_frames', 'muvo_depth_semantic_decode_frames',
     'muvo_range_projection_frames', 'muvo_voxel_grid_frames',
     'muvo_attention_stream_supported', 'muvo_attention_stream_blocks', 'muvo_attention_stream_fwd', 'muvo_attention_stream_bwd',
+    'muvo_voxel_rows_scratch_bytes', 'muvo_voxel_rows_logits', 'muvo_voxel_rows_grid', 'muvo_voxel_rows_write', 'muvo_image_u8',
 ]
 
 
@@ -102,6 +103,7 @@ def lib():
                 L.muvo_rssm_transposed_floats.restype = C.c_int64
                 L.muvo_rssm_scratch_floats.restype = C.c_int64
                 L.muvo_voxelize_scratch_bytes.restype = C.c_int64
+                L.muvo_voxel_rows_scratch_bytes.restype = C.c_int64
                 for name in EXPORTS:
                     getattr(L, name)  # AttributeError if a declared symbol is missing
                 _lib = L
@@ -2886,3 +2888,72 @@ def fake_allreduce(buf, peers=8, workgroups=None, ms_per_100mb=None):
 
 def fake_allreduce_calibration():
     return [v for k, v in _FAKE_AR.items() if k and k[0] == 'calibration']
+
+
+# ---- prediction export (csrc/export.hip) -----------------------------------------------------------------------------------------
+VOXEL_ROWS_CHUNK = 2048        # EXP_CHUNK of csrc/export.hip: voxels per workgroup of the counting and the compaction pass
+
+
+def _voxel_rows_args(src):
+    """(contiguous source, is_logits, F, C, X, Y, Z, scratch) of a voxel_rows call."""
+    if src.dtype == torch.float32 and src.dim() == 5:
+        F, Cn, X, Y, Z = src.shape
+        logits = True
+    elif src.dtype == torch.uint8 and src.dim() == 4:
+        (F, X, Y, Z), Cn, logits = src.shape, 0, False
+    else:
+        raise ValueError(f'voxel_rows: class logits (F, C, X, Y, Z) float32 or a class grid (F, X, Y, Z) uint8, got '
+                         f'{tuple(src.shape)} {src.dtype}')
+    nbytes = lib().muvo_voxel_rows_scratch_bytes(int(F), int(X), int(Y), int(Z))
+    if nbytes < 0:
+        raise RuntimeError(f'voxel_rows: sizes F {F}, grid {X} {Y} {Z} are not supported (include/muvo_hip.h)')
+    return src.contiguous(), logits, int(F), int(Cn), int(X), int(Y), int(Z), scratch('voxel_rows', nbytes, src.device, torch.uint8)
+
+
+def _voxel_rows_call(src, logits, F, Cn, X, Y, Z, ws, rows, cap, counts):
+    L = lib()
+    if logits:
+        _ck(L.muvo_voxel_rows_logits(_f(src), F, Cn, X, Y, Z, _p(ws), _p(rows), _i64(cap), _p(counts), _st()))
+    else:
+        _ck(L.muvo_voxel_rows_grid(_p(src), F, X, Y, Z, _p(ws), _p(rows), _i64(cap), _p(counts), _st()))
+
+
+def voxel_rows_into(src, rows, cap=None):
+    """One call of the entry point with a caller-owned buffer: `rows` (>= cap, 4) uint16 receives the first `cap` (default: all of
+    the buffer) rows, the returned counts (F,) int64 are the true totals whatever the capacity.  No host synchronisation."""
+    assert rows.dtype == torch.uint16 and rows.dim() == 2 and rows.shape[1] == 4 and rows.is_contiguous()
+    cap = rows.shape[0] if cap is None else int(cap)
+    assert 0 <= cap <= rows.shape[0]
+    src, logits, F, Cn, X, Y, Z, ws = _voxel_rows_args(src)
+    counts = torch.empty(F, dtype=torch.int64, device=src.device)
+    _voxel_rows_call(src, logits, F, Cn, X, Y, Z, ws, rows if cap else None, cap, counts)
+    return counts
+
+
+def voxel_rows(src):
+    """Occupied-voxel rows of F frames: src = class logits (F, C, X, Y, Z) float32 (class = torch.argmax over C) or a class grid
+    (F, X, Y, Z) uint8.  Returns (rows (Q, 4) uint16 device tensor: x, y, z, class of every voxel whose class is not 0, in the
+    order of torch.where, frames concatenated; counts: F Python ints).  The counting pass runs first, the host reads the F
+    counts (the one synchronisation of the call), the rows are then written into a tensor of exactly their size - the logits are
+    read once, the byte grid between the passes stays on the device."""
+    src, logits, F, Cn, X, Y, Z, ws = _voxel_rows_args(src)
+    counts = torch.empty(F, dtype=torch.int64, device=src.device)
+    _voxel_rows_call(src, logits, F, Cn, X, Y, Z, ws, None, 0, counts)
+    per_frame = counts.tolist()
+    total = sum(per_frame)
+    rows = torch.empty((total, 4), dtype=torch.uint16, device=src.device)
+    if total:
+        _ck(lib().muvo_voxel_rows_write(_p(None if logits else src), F, X, Y, Z, _p(ws), _p(counts), _p(rows), _i64(total), _st()))
+    return rows, per_frame
+
+
+def image_u8(x):
+    """float32 tensor (any shape; made contiguous) -> uint8 of the same shape: trunc(x * 255) SATURATED to [0, 255], NaN -> 0.
+    Equal to numpy's `(x * 255).astype(np.uint8)` wherever that is defined (0 <= x * 255 < 256); outside it - the decoder heads
+    have no squashing activation - the cast of the reference is implementation-defined and this is the product's definition."""
+    assert x.dtype == torch.float32
+    x = x.contiguous()
+    y = torch.empty(x.shape, dtype=torch.uint8, device=x.device)
+    if x.numel():
+        _ck(lib().muvo_image_u8(_f(x), _p(y), _i64(x.numel()), _st()))
+    return y

@@ -1,0 +1,312 @@
+"""Predict over recorded runs with a trained checkpoint: the counterpart of the reference's two inference entry points,
+`prediction.py` (`trainer.test` over the test loaders) and `sim_run.py` (`sim_forward` over test loader 2, dumping label,
+reconstruction and imagination per batch).  One process, one GPU.
+
+    python -m muvo_amd.predict --config-file muvo_amd/configs/test_base_1d.yml --dataset-root /data/carla \\
+        --checkpoint epoch=0-step=50000.ckpt --out runs/eval --mode test
+    python -m muvo_amd.predict --config-file muvo_amd/configs/test_base_1d.yml --dataset-root /data/carla \\
+        --checkpoint epoch=0-step=50000.ckpt --out runs/sim --mode sim [--loader 2] [--limit-batches 100] [--shard-size 500]
+
+`--mode test` runs `WorldModelTrainer.test_step` over the chosen test loaders (default: all three), then `on_test_epoch_end`,
+prints every logged metric as a JSON line and writes `metrics.json`: the logged names mapped to floats, plus `batches`, the
+number of batches each loader delivered.  The bird's-eye-view, lidar and camera IoU of the reference (torchmetrics.JaccardIndex)
+are not built; the tool says once which enabled heads therefore have no metric.
+
+`--mode sim` follows the loop of sim_run.py:49-116 (module in train() mode, the transformer's dropout modules off, no_grad;
+per batch `preprocess`, then `model.sim_forward(batch, is_dreaming=False)`) over one loader (default 2, sim_run.py:44) and
+records, for batch element 0, the reference's eleven entries.  Every `--shard-size` batches, and at the end, a shard
+`data_{i}.npz` is written, i = index of the last batch in it.
+
+Shard layout (B batches in the shard, K = the steps of (0, 3, 9) the imagination has; arrays of a shard are stacked over B):
+
+    rgb_label, rgb_re       (B, 3, h, w) uint8      frame 0 of the label / the rendered current state, muvo_image_u8
+    rgb_im                  (B, K, 3, h, w) uint8   imagined steps
+    throttle_brake, steering (B, 1) float32         recorded action of frame 0
+    pcd_label, pcd_re       (B, 4, H, W) float32    range views, copied as they are
+    pcd_im                  (B, K, 4, H, W) float32
+    voxel_label_rows, voxel_re_rows, voxel_im_rows   (sum Q, 4) uint16   x, y, z, class of every voxel whose class is not 0
+        (label: the uint8 grid itself; re / im: argmax of the logits), ascending in (x * Y + y) * Z + z - the order of
+        torch.where, the layout of the recorder's voxel files
+    voxel_label_offsets, voxel_re_offsets (B + 1,) int64, voxel_im_offsets (B * K + 1,) int64: entry j of the row list
+        ((batch, step) in row-major order for `im`) owns rows [offsets[j], offsets[j + 1])
+    imagine_steps (K,) int64, batch_index (B,) int64
+
+Bytes are `trunc(x * 255)` saturated to [0, 255] with NaN -> 0: numpy's `(x * 255).astype(np.uint8)` of the reference
+wherever that is defined.  Neither a logits tensor nor a float image crosses to the host: the voxel entries are compacted by
+csrc/export.hip (class argmax + ordered stream compaction) and leave as rows, the images leave as bytes.  `read_shard` gives
+the per-batch lists back."""
+import json
+import os
+import sys
+
+import numpy as np
+import torch
+
+from muvo_amd.config import get_cfg, get_parser
+
+ENTRIES = ('rgb_label', 'throttle_brake', 'steering', 'pcd_label', 'voxel_label', 'rgb_re', 'pcd_re', 'voxel_re', 'rgb_im',
+           'pcd_im', 'voxel_im')                       # sim_run.py:55-67
+VOXEL_ENTRIES = ('voxel_label', 'voxel_re', 'voxel_im')
+IMAGINE_STEPS = (0, 3, 9)                              # sim_run.py:81,92-93
+
+
+def refuse_multi_process(environ=None):
+    environ = os.environ if environ is None else environ
+    world = int(environ.get('WORLD_SIZE', '1') or 1)
+    if world > 1:
+        raise RuntimeError(f'muvo_amd.predict runs in one process on one GPU (WORLD_SIZE={world}): start it without a launcher; '
+                           'multi-process evaluation is not built')
+
+
+def build_parser():
+    parser = get_parser()
+    parser.description = 'World model prediction over recorded runs'
+    parser.add_argument('--dataset-root', default='', help='directory of recorded runs (overrides DATASET.DATAROOT)')
+    parser.add_argument('--checkpoint', default='', help='Lightning-format checkpoint (goes to PRETRAINED.PATH)')
+    parser.add_argument('--out', required=True, metavar='DIR', help='directory for metrics.json / data_{i}.npz')
+    parser.add_argument('--mode', choices=('test', 'sim'), required=True)
+    parser.add_argument('--loader', type=int, choices=(0, 1, 2), default=None,
+                        help='test loader (default: 2 for sim, all three for test)')
+    parser.add_argument('--limit-batches', type=int, default=None, metavar='N', help='at most N batches per loader')
+    parser.add_argument('--shard-size', type=int, default=500, metavar='N', help='batches per data_{i}.npz (sim)')
+    parser.add_argument('--seed', type=int, default=1234)
+    return parser
+
+
+def parse_args(argv=None):
+    args = build_parser().parse_args(argv)
+    if args.limit_batches is not None and args.limit_batches < 1:
+        raise SystemExit('--limit-batches must be positive')
+    if args.shard_size < 1:
+        raise SystemExit('--shard-size must be positive')
+    return args
+
+
+def chosen_loaders(mode, loader=None):
+    return [int(loader)] if loader is not None else ([2] if mode == 'sim' else [0, 1, 2])
+
+
+def expected_metric_names(cfg, counts):
+    """The names `on_test_epoch_end` logs when loader idx delivered counts[idx] batches (an empty loader logs nothing)."""
+    from muvo_amd.trainer import metric_log_names
+    names = []
+    for kind, has in (('test', True), ('test_imagine', cfg.PREDICTION.N_SAMPLES > 0)):
+        for idx in sorted(counts):
+            if counts[idx] and has:
+                names += metric_log_names(cfg, f'{kind}{idx}')
+    return names
+
+
+# ---- shards -----------------------------------------------------------------------------------------------------------------------
+def write_shard(path, records, batch_index, imagine_steps):
+    """records: one dict per batch with the ENTRIES; fixed-shape entries are numpy arrays, `voxel_label` / `voxel_re` a (Q, 4)
+    uint16 array, `voxel_im` a list of K such arrays."""
+    out = {'imagine_steps': np.asarray(imagine_steps, dtype=np.int64), 'batch_index': np.asarray(batch_index, dtype=np.int64)}
+    for name in ENTRIES:
+        if name in VOXEL_ENTRIES:
+            lists = [r[name] if name == 'voxel_im' else [r[name]] for r in records]
+            flat = [np.asarray(a, dtype=np.uint16).reshape(-1, 4) for per_batch in lists for a in per_batch]
+            out[f'{name}_rows'] = np.concatenate(flat) if flat else np.zeros((0, 4), np.uint16)
+            out[f'{name}_offsets'] = np.concatenate([[0], np.cumsum([len(a) for a in flat])]).astype(np.int64)
+        else:
+            out[name] = np.stack([np.asarray(r[name]) for r in records])
+    with open(path, 'wb') as fh:
+        np.savez(fh, **out)
+    return path
+
+
+def read_shard(path):
+    """The per-batch lists of a shard: {entry: list over the batches}; a voxel entry is a (Q, 4) uint16 array per batch
+    (`voxel_im`: a list of K arrays per batch).  Plus `imagine_steps` and `batch_index`."""
+    with np.load(path) as z:
+        data = {k: z[k] for k in z.files}
+    n, k = len(data['batch_index']), len(data['imagine_steps'])
+    out = {'imagine_steps': data['imagine_steps'], 'batch_index': data['batch_index']}
+    for name in ENTRIES:
+        if name in VOXEL_ENTRIES:
+            rows, off = data[f'{name}_rows'], data[f'{name}_offsets']
+            parts = [rows[off[j]:off[j + 1]] for j in range(len(off) - 1)]
+            out[name] = [parts[i * k:(i + 1) * k] for i in range(n)] if name == 'voxel_im' else parts
+            assert len(out[name]) == n, (name, len(parts), n, k)
+        else:
+            out[name] = list(data[name])
+    return out
+
+
+def _split_rows(rows, counts):
+    host = rows.cpu().numpy()
+    edges = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
+    return [host[edges[j]:edges[j + 1]] for j in range(len(counts))]
+
+
+def sim_record(batch, output, output_imagine):
+    """The eleven entries of sim_run.py:75-94 for batch element 0 from device tensors; returns (record, imagined steps)."""
+    from muvo_amd import ops
+    n_im = output_imagine['voxel_1'].shape[1] if output_imagine else 0
+    steps = [k for k in IMAGINE_STEPS if k < n_im]
+    idx = torch.as_tensor(steps, dtype=torch.long, device=output['voxel_1'].device)
+    rec = {'throttle_brake': batch['throttle_brake'][0][0].float().cpu().numpy(),
+           'steering': batch['steering'][0][0].float().cpu().numpy(),
+           'rgb_label': ops.image_u8(batch['rgb_label_1'][0][0].float()).cpu().numpy(),
+           'rgb_re': ops.image_u8(output['rgb_1'][0][0].detach().float()).cpu().numpy(),
+           'pcd_label': batch['range_view_label_1'][0][0].float().cpu().numpy(),
+           'pcd_re': output['lidar_reconstruction_1'][0][0].detach().float().cpu().numpy()}
+    label = batch['voxel_label_1'][0][0]
+    label = label.reshape(1, *label.shape[-3:]).to(torch.uint8)
+    rec['voxel_label'] = _split_rows(*ops.voxel_rows(label))[0]
+    rec['voxel_re'] = _split_rows(*ops.voxel_rows(output['voxel_1'][0][0:1].detach().float()))[0]
+    if steps:
+        rec['rgb_im'] = ops.image_u8(output_imagine['rgb_1'][0].detach().float().index_select(0, idx)).cpu().numpy()
+        rec['pcd_im'] = output_imagine['lidar_reconstruction_1'][0].detach().float().index_select(0, idx).cpu().numpy()
+        rec['voxel_im'] = _split_rows(*ops.voxel_rows(output_imagine['voxel_1'][0].detach().float().index_select(0, idx)))
+    else:
+        rec['rgb_im'] = np.zeros((0, *rec['rgb_re'].shape), np.uint8)
+        rec['pcd_im'] = np.zeros((0, *rec['pcd_re'].shape), np.float32)
+        rec['voxel_im'] = []
+    return rec, steps
+
+
+# ---- the two modes ----------------------------------------------------------------------------------------------------------------
+def _check_heads(cfg, mode):
+    on = {'EVAL.RGB_SUPERVISION': cfg.EVAL.RGB_SUPERVISION, 'LIDAR_RE.ENABLED': cfg.LIDAR_RE.ENABLED,
+          'VOXEL_SEG.ENABLED': cfg.VOXEL_SEG.ENABLED}
+    off = [k for k, v in on.items() if not v]
+    if mode == 'sim' and off:
+        raise RuntimeError(f'--mode sim records the RGB, lidar and voxel outputs (sim_run.py:84-94): {off} must be on')
+
+
+def seed_batch(module, seed, loader_idx, i):
+    """Every batch starts from seeds of its own - torch (RSSM noise), numpy (the Chamfer subset, trainer.py:453) and the model's
+    dropout counters - so a run does not depend on what the module did before, and a second run repeats the first."""
+    s = seed + 104729 * (i + 1) + 7919 * loader_idx
+    torch.manual_seed(s)
+    np.random.seed(s % (2 ** 32))
+    module.model.seed_epoch = 0
+    module.model._step_seed = ((loader_idx << 20) + i) << 8
+
+
+def run(cfg, device, out_dir, mode, loaders=None, limit_batches=None, shard_size=500, seed=1234, hook=None, dataset_root=None,
+        data=None, module=None, log=print):
+    """Runs one mode and returns what it wrote: {'files': [...], 'batches': {loader: n}, 'metrics': {...} (test)}.
+    hook(i, batch, output, output_imagine): called per batch with the device tensors (test mode: output_imagine is the list
+    of imagined samples).  data: a set-up DataModule to take the test loaders from (default: one over dataset_root /
+    cfg.DATASET.DATAROOT); module: a WorldModelTrainer to use instead of building one from cfg."""
+    refuse_multi_process()
+    if mode not in ('test', 'sim'):
+        raise ValueError(f'mode {mode!r}: test or sim')
+    _check_heads(cfg, mode)
+    device = torch.device(device)
+    os.makedirs(out_dir, exist_ok=True)
+    torch.manual_seed(seed)
+    if module is None:
+        from muvo_amd.trainer import WorldModelTrainer
+        module = WorldModelTrainer(cfg.convert_to_dict(), device=device)
+    if data is None:
+        from muvo_amd.data.dataset import DataModule
+        data = DataModule(cfg, dataset_root or cfg.DATASET.DATAROOT, device=device, seed=seed)
+        data.setup()
+    test_loaders = data.test_dataloader()
+    which = chosen_loaders(mode, None) if loaders is None else [int(v) for v in loaders]
+    if mode == 'sim' and len(which) != 1:
+        raise ValueError('mode sim runs over one loader')
+    fn = _run_test if mode == 'test' else _run_sim
+    return fn(cfg, module, {idx: test_loaders[idx] for idx in which}, out_dir, limit_batches, shard_size, seed, hook, log)
+
+
+def _batches(loader, limit):
+    for i, batch in enumerate(loader):
+        if limit is not None and i >= limit:
+            return
+        yield i, batch
+
+
+def _run_test(cfg, module, loaders, out_dir, limit_batches, shard_size, seed, hook, log):
+    from muvo_amd.trainer import metric_heads_left_out
+    left_out = metric_heads_left_out(cfg)
+    if left_out:
+        log(json.dumps({'no_metric_for': left_out, 'reason': 'torchmetrics.JaccardIndex is not built'}))
+    counts = {}
+    for idx, loader in loaders.items():
+        counts[idx] = 0
+        for i, batch in _batches(loader, limit_batches):
+            seed_batch(module, seed, idx, i)
+            output, output_imagines = module.test_step(batch, i, idx)
+            if hook is not None:
+                hook(i, batch, output, output_imagines)
+            counts[idx] += 1
+    logged = {}
+    was_fn, module.log_fn = module.log_fn, lambda name, value: logged.__setitem__(name, float(value))
+    try:
+        module.on_test_epoch_end()
+    finally:
+        module.log_fn = was_fn
+    result = dict(logged)
+    result['batches'] = {str(idx): n for idx, n in counts.items()}
+    for name, value in logged.items():
+        log(json.dumps({name: value}))
+    log(json.dumps({'batches': result['batches']}))
+    path = os.path.join(out_dir, 'metrics.json')
+    with open(path, 'w') as fh:
+        json.dump(result, fh, indent=1, sort_keys=True)
+        fh.write('\n')
+    return {'files': [path], 'batches': counts, 'metrics': logged}
+
+
+def _run_sim(cfg, module, loaders, out_dir, limit_batches, shard_size, seed, hook, log):
+    (idx, loader), = loaders.items()
+    module.train()
+    m = module.model
+    m.last_h = m.last_sample = m.last_action = None       # the latent memory of sim_forward starts empty, like a fresh process
+    m.count = 0
+    layers = list(module.model.transformer_encoder.layers)
+    saved = [getattr(layer, 'module_dropout_off', False) for layer in layers]
+    for layer in layers:
+        layer.module_dropout_off = True
+    files, records, index, steps_of_shard, n = [], [], [], None, 0
+
+    def flush():
+        nonlocal records, index, steps_of_shard
+        if records:
+            files.append(write_shard(os.path.join(out_dir, f'data_{index[-1]}.npz'), records, index, steps_of_shard))
+            log(json.dumps({'shard': files[-1], 'batches': len(records)}))
+        records, index, steps_of_shard = [], [], None
+    try:
+        with torch.no_grad():
+            for i, batch in _batches(loader, limit_batches):
+                seed_batch(module, seed, idx, i)
+                batch = module.preprocess(batch)
+                output, output_imagine = module.model.sim_forward(batch, is_dreaming=False)
+                if hook is not None:
+                    hook(i, batch, output, output_imagine)
+                rec, steps = sim_record(batch, output, output_imagine)
+                if steps_of_shard is not None and steps != steps_of_shard:
+                    flush()                                   # arrays of a shard are stacked: one set of steps per shard
+                steps_of_shard = steps
+                records.append(rec)
+                index.append(i)
+                n += 1
+                if len(records) >= shard_size:
+                    flush()
+        flush()
+    finally:
+        for layer, v in zip(layers, saved):
+            layer.module_dropout_off = v
+    return {'files': files, 'batches': {idx: n}}
+
+
+def main(argv=None):
+    args = parse_args(argv)
+    refuse_multi_process()
+    cfg = get_cfg(args)
+    if args.checkpoint:
+        cfg.defrost()
+        cfg.PRETRAINED.PATH = args.checkpoint
+        cfg.freeze()
+    torch.cuda.set_device(0)
+    device = torch.device('cuda', 0)
+    run(cfg, device, args.out, args.mode, loaders=chosen_loaders(args.mode, args.loader), limit_batches=args.limit_batches,
+        shard_size=args.shard_size, seed=args.seed, dataset_root=args.dataset_root or None)
+
+
+if __name__ == '__main__':
+    sys.exit(main())

@@ -4,8 +4,9 @@ Same constructor `(hparams, path_to_conf_file=None, pretrained_path=None)`, attr
 `preprocess`, `model`) and methods (`forward`, `compute_loss`, `shared_step(mode='train')`, `training_step`,
 `configure_optimizers`, `load_pretrained_weights`) as trainer.py:26-231,251-402,511-513,1022-1073.  If
 `lightning` is importable the class derives from `pl.LightningModule`, otherwise from `torch.nn.Module` with
-the same hooks so the build's own loop (bench.py / train.py) can drive it.  Validation/visualisation
-(trainer.py:404-1020) are outside the training hot path."""
+the same hooks so the build's own loop (bench.py / train.py / predict.py) can drive it.  The evaluation half (`validation_step`,
+`test_step`, `log_metrics`, `on_validation_epoch_end`, `on_test_epoch_end`; trainer.py:404-567,1075-1095) is here without the
+visualisation (trainer.py:569-1020) and without the three torchmetrics IoU metrics."""
 import os
 
 import numpy as np
@@ -36,6 +37,28 @@ def _refuse_ddp(module, args):
     strategy = getattr(tr, 'strategy', None)
     if strategy is not None and isinstance(getattr(strategy, 'model', None), torch.nn.parallel.DistributedDataParallel):
         raise RuntimeError(_DDP_MSG)
+
+
+VOXEL_LABEL = ('Background', 'Occupancy')          # the names of the reference's voxel class table (constants.py VOXEL_LABEL)
+
+
+def metric_log_names(cfg, prefix):
+    """The names log_metrics sends for one non-empty metric set, in order (trainer.py:532-567)."""
+    names = []
+    if cfg.EVAL.RGB_SUPERVISION:
+        names += [f'{prefix}_ssim', f'{prefix}_psnr']
+    if cfg.LIDAR_RE.ENABLED:
+        names.append(f'{prefix}_chamfer_distance')
+    if cfg.VOXEL_SEG.ENABLED:
+        names += [f'{prefix}_Voxel_{name}_SemIoU' for name in VOXEL_LABEL[:cfg.VOXEL_SEG.N_CLASSES]]
+        names += [f'{prefix}_Voxel_mIoU', f'{prefix}_Voxel_IoU', f'{prefix}_Voxel_Precision', f'{prefix}_Voxel_Recall']
+    return names
+
+
+def metric_heads_left_out(cfg):
+    """Enabled heads whose metric of the reference (torchmetrics.JaccardIndex, trainer.py:525-554) is not built here."""
+    heads = (('SEMANTIC_SEG', 'bev_iou'), ('LIDAR_SEG', 'lidar_iou'), ('SEMANTIC_IMAGE', 'camera_iou'))
+    return [name for key, name in heads if cfg[key].ENABLED]
 
 
 class WorldModelTrainer(_Base):
@@ -169,10 +192,10 @@ class WorldModelTrainer(_Base):
         b, s, c, x, y, z = y_pred.shape
         metric.add_batch(y_pred.reshape(b * s, c, x, y, z), y_true.reshape(b * s, x, y, z))
 
-    def validation_step(self, batch, batch_idx=0, dataloader_idx=0, noise=None, use_prior=None, cd_index=None):
-        """trainer.py:404-424 (visualisation/logging hooks excepted): train-mode BatchNorm, transformer nn.Dropout modules
-        off (the functional attention dropout of nn.MultiheadAttention stays on), no_grad; then the
-        reconstruction metrics on the observed frames and the imagination metrics on the future frames."""
+    def _eval_step(self, batch, mode, metrics, metrics_imagine, noise, use_prior, cd_index):
+        """The body validation_step and test_step share (trainer.py:404-417,1079-1092): train-mode BatchNorm, transformer
+        nn.Dropout modules off (the functional attention dropout of nn.MultiheadAttention stays on, SURVEY App. B 11), no_grad;
+        then the reconstruction metrics on the observed frames and the imagination metrics on the future frames."""
         self.train()
         layers = list(self.model.transformer_encoder.layers)
         saved = [getattr(layer, 'module_dropout_off', False) for layer in layers]
@@ -180,19 +203,68 @@ class WorldModelTrainer(_Base):
             layer.module_dropout_off = True
         try:
             with torch.no_grad():
-                loss, output, loss_imagines, output_imagines = self.shared_step(batch, mode='val', predict_action=False,
+                loss, output, loss_imagines, output_imagines = self.shared_step(batch, mode=mode, predict_action=False,
                                                                                 noise=noise, use_prior=use_prior)
         finally:
             for layer, v in zip(layers, saved):
                 layer.module_dropout_off = v
         batch_rf = {key: value[:, :self.rf] for key, value in batch.items() if torch.is_tensor(value)}
         batch_fh = {key: value[:, self.rf:] for key, value in batch.items() if torch.is_tensor(value)}
-        self.add_metrics(self.metrics_vals[dataloader_idx], batch_rf, output, cd_index)
+        self.add_metrics(metrics, batch_rf, output, cd_index)
         for output_imagine in output_imagines:
-            self.add_metrics(self.metrics_vals_imagine[dataloader_idx], batch_fh, output_imagine, cd_index)
+            self.add_metrics(metrics_imagine, batch_fh, output_imagine, cd_index)
+        return loss, output, loss_imagines, output_imagines
+
+    def validation_step(self, batch, batch_idx=0, dataloader_idx=0, noise=None, use_prior=None, cd_index=None):
+        """trainer.py:404-424 (visualisation/logging hooks excepted)."""
+        loss, output, loss_imagines, output_imagines = self._eval_step(
+            batch, 'val', self.metrics_vals[dataloader_idx], self.metrics_vals_imagine[dataloader_idx], noise, use_prior, cd_index)
         out = {f'val{dataloader_idx}_loss': self.loss_reducing(loss),
                f'val{dataloader_idx}_loss_imagine': sum(self.loss_reducing(li) for li in loss_imagines) / len(loss_imagines)}
         return out, loss, output, loss_imagines, output_imagines
+
+    def test_step(self, batch, batch_idx=0, dataloader_idx=0, noise=None, use_prior=None, cd_index=None):
+        """trainer.py:1079-1095 (the visualisation excepted): the evaluation step feeding `metrics_tests` /
+        `metrics_tests_imagine`; returns (output, output_imagines)."""
+        _, output, _, output_imagines = self._eval_step(
+            batch, 'test', self.metrics_tests[dataloader_idx], self.metrics_tests_imagine[dataloader_idx], noise, use_prior, cd_index)
+        return output, output_imagines
+
+    def log_metrics(self, metrics_list, metrics_type):
+        """trainer.py:519-567 for the metrics built here: every non-empty metric set of `metrics_list` goes out through
+        `self.log` under `{metrics_type}{idx}_...` (metric_log_names) and is reset.  The bird's-eye-view, lidar and camera IoU
+        of the reference are torchmetrics.JaccardIndex objects, which this project does not build: skipped (metric_heads_left_out)."""
+        for idx, metrics in enumerate(metrics_list):
+            if not metrics:
+                continue
+            prefix = f'{metrics_type}{idx}'
+            if 'ssim' in metrics:
+                self.log(f'{prefix}_ssim', metrics['ssim'].get_stat())
+                metrics['ssim'].reset()
+                self.log(f'{prefix}_psnr', metrics['psnr'].get_stat())
+                metrics['psnr'].reset()
+            if 'cd' in metrics:
+                self.log(f'{prefix}_chamfer_distance', metrics['cd'].get_stat())
+                metrics['cd'].reset()
+            if 'ssc' in metrics:
+                stats = metrics['ssc'].get_stats()
+                for class_name, value in zip(VOXEL_LABEL, stats['iou_ssc']):        # stops at the shorter list, like the reference
+                    self.log(f'{prefix}_Voxel_{class_name}_SemIoU', value)
+                self.log(f'{prefix}_Voxel_mIoU', stats['iou_ssc_mean'])
+                self.log(f'{prefix}_Voxel_IoU', stats['iou'])
+                self.log(f'{prefix}_Voxel_Precision', stats['precision'])
+                self.log(f'{prefix}_Voxel_Recall', stats['recall'])
+                metrics['ssc'].reset()
+
+    def on_validation_epoch_end(self):
+        """trainer.py:515-517"""
+        self.log_metrics(self.metrics_vals, 'val')
+        self.log_metrics(self.metrics_vals_imagine, 'val_imagine')
+
+    def on_test_epoch_end(self):
+        """trainer.py:1075-1077"""
+        self.log_metrics(self.metrics_tests, 'test')
+        self.log_metrics(self.metrics_tests_imagine, 'test_imagine')
 
     def compute_loss(self, batch, output):
         """The reference's 21 weighted loss terms (trainer.py:251-390), computed by fused kernels."""
