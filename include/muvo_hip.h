@@ -425,7 +425,13 @@ int muvo_adamw_step(float* p, const float* g, float* m, float* v, int64_t n, flo
  * muvo_chamfer_sums: sums[2n] += sum_i min_j |a_i - b_j|, sums[2n+1] += sum_j min_i |a_i - b_j| for point sets a (N,P,3),
  *   b (N,Q,3) (CDMetric.add_batch, metrics.py:243-249).
  * muvo_ssc_counts: prediction = argmax over the C logits (N,C,V); counts[0..2] += completion tp/fp/fn, counts[3+3j..] +=
- *   tp/fp/fn of class j over voxels with label != 255 (trainer.py:482-490, SSCMetrics.add_batch, metrics.py:77-100). */
+ *   tp/fp/fn of class j over voxels with label != 255 (trainer.py:482-490, SSCMetrics.add_batch, metrics.py:77-100).
+ * muvo_seg_confusion: the confusion matrix behind the bird's-eye-view, lidar and camera IoU (torchmetrics.JaccardIndex as fed
+ *   by trainer.py:427-478).  logits (F,C,P) float32, label (F,P) bytes, 2 <= C <= 16; counts is uint64[C*C + 1]:
+ *   counts[t*C + p] += pixels with label t and prediction p = first maximum over the C planes (strict >, torch.argmax on
+ *   finite input; NaN logits are outside the contract), counts[C*C] += pixels with label >= C, which reach no other bin.
+ *   One launch, no host read: the matrix stays on the device until the caller reads it.
+ * muvo_seg_confusion_index: the same from n already arg-maxed byte predictions; a prediction >= C also goes to counts[C*C]. */
 int muvo_ssim_frames(const float* pred, const float* target, const float* window, double* sums, int N, int C, int H, int W,
                      float c1, float c2, void* stream);
 /* SSIM as a training loss (LOSSES.SSIM: trainer.py:312-318, SSIMLoss losses.py:292-348): muvo_ssim_maps = muvo_ssim_frames plus
@@ -438,6 +444,8 @@ int muvo_ssim_bwd(const float* pred, const float* target, const float* window, c
 int muvo_sqdiff_frames(const float* pred, const float* target, double* sums, int N, int64_t L, void* stream);
 int muvo_chamfer_sums(const float* a, const float* b, double* sums, int N, int P, int Q, void* stream);
 int muvo_ssc_counts(const float* logits, const uint8_t* label, uint64_t* counts, int64_t F, int C, int64_t V, void* stream);
+int muvo_seg_confusion(const float* logits, const uint8_t* label, uint64_t* counts, int64_t F, int C, int64_t P, void* stream);
+int muvo_seg_confusion_index(const uint8_t* pred, const uint8_t* label, uint64_t* counts, int64_t n, int C, void* stream);
 
 /* ---- BEV lifting: FrustumPooling (muvo/models/frustum_pooling.py:67-217) as called from Mile.encode (mile.py:506-522) ----
  * muvo_frustum_cells: cells[b][d][h][w] = (iz*ny + iy)*nx + ix of the frustum point, -1 outside the grid (get_geometry

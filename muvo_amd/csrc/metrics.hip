@@ -3,6 +3,8 @@
 //   PSNR  — muvo/metrics.py:305-309 (per-frame mean squared error; the log is taken by the caller)
 //   Chamfer distance — muvo/metrics.py:243-249 (torch.cdist + two min reductions), brute force in LDS tiles
 //   SSC counts — muvo/metrics.py:77-100,143-214 with argmax of trainer.py:482-490 fused in
+//   Segmentation confusion matrix — what torchmetrics.JaccardIndex(task='multiclass', average='none') keeps, as fed by
+//     trainer.py:427-478 (argmax over the class logits, then prediction and label to the host): argmax and counting fused
 // Every kernel adds per-frame partial sums into caller-zeroed fp64 / int64 accumulators.
 #include "common.h"
 
@@ -216,6 +218,139 @@ ssc_counts_kernel(const float* __restrict__ logits, const unsigned char* __restr
     if (lc[i]) atomicAdd(counts + i, (unsigned long long)lc[i]);
 }
 
+// ---- confusion matrix of a segmentation head ------------------------------------------------------------------------------
+// counts[t * C + p] += pixels with label t and prediction p; counts[C * C] += pixels whose label (or, on the index path, whose
+// prediction) is >= C - those reach no other bin.  Prediction = first maximum over the C planes with strict > (ssc_counts_kernel,
+// export.hip): torch.argmax on finite input.  NaN logits are outside the contract (a NaN never wins here, torch.argmax picks it).
+//
+// Shape: a grid-stride loop over items of PPL pixels per lane (PPL = 4: one 16-byte load per class plane and one 4-byte load of
+// the labels, chosen by the host only where a frame's base is 16-byte aligned, i.e. P % 4 == 0; PPL = 1 otherwise).  The
+// histogram lives in LDS as 32-bit counters, one copy per wave (a block sees < 2^32 pixels, checked by the host).  Segmentation
+// maps are spatially coherent - 64 lanes on one bin is the normal case - so the lanes of a wave that hold the same bin are merged
+// before the LDS atomic: ballot on bin == bin of the first remaining lane, one add of the popcount by that lane, repeat for the
+// lanes left (1 round for a constant map, at most 64).  At block end one 64-bit global atomic per non-zero bin.
+#define SEG_MAXC 16
+#define SEG_THREADS 256
+#define SEG_WAVES (SEG_THREADS / 64)
+// Two blocks per CU, the stride loop takes the rest: every block ends with one global atomic per non-zero bin on the same
+// C * C addresses, so fewer, longer blocks win - measured at 20 frames, 256 / 512 / 1024 / 2048 blocks: lidar head 24 / 22 / 29 /
+// 35 us, camera head 77 / 47 / 48 / 62 us (profiles/predict_confusion_grid_cap.txt).
+#ifndef SEG_MAX_BLOCKS
+#define SEG_MAX_BLOCKS 512
+#endif
+
+__device__ __forceinline__ void seg_wave_add(unsigned int* hist, int bin, bool live) {
+  unsigned long long todo = __ballot(live);
+  const int lane = threadIdx.x & 63;
+  while (todo) {                                                 // wave-uniform: todo is the same in every lane
+    const int lead = __builtin_amdgcn_readfirstlane(__ffsll((long long)todo) - 1);
+    const int b = __builtin_amdgcn_readlane(bin, lead);
+    const unsigned long long same = __ballot(live && bin == b);  // holds lane `lead`: the loop ends
+    if (lane == lead) atomicAdd(hist + b, (unsigned int)__popcll(same));
+    todo &= ~same;
+  }
+}
+
+// first maximum over C planes for PPL neighbouring pixels; lg points at plane 0 of the item
+template <int C, int PPL>
+__device__ __forceinline__ void seg_argmax(const float* __restrict__ lg, long P, int* pr) {
+  float best[PPL];
+  if constexpr (PPL == 4) {
+    float4 x[C];
+#pragma unroll
+    for (int c = 0; c < C; ++c) x[c] = *reinterpret_cast<const float4*>(lg + (size_t)c * P);
+    best[0] = x[0].x; best[1] = x[0].y; best[2] = x[0].z; best[3] = x[0].w;
+    pr[0] = pr[1] = pr[2] = pr[3] = 0;
+#pragma unroll
+    for (int c = 1; c < C; ++c) {
+      if (x[c].x > best[0]) { best[0] = x[c].x; pr[0] = c; }
+      if (x[c].y > best[1]) { best[1] = x[c].y; pr[1] = c; }
+      if (x[c].z > best[2]) { best[2] = x[c].z; pr[2] = c; }
+      if (x[c].w > best[3]) { best[3] = x[c].w; pr[3] = c; }
+    }
+  } else {
+    float x[C];
+#pragma unroll
+    for (int c = 0; c < C; ++c) x[c] = lg[(size_t)c * P];
+    best[0] = x[0];
+    pr[0] = 0;
+#pragma unroll
+    for (int c = 1; c < C; ++c)
+      if (x[c] > best[0]) { best[0] = x[c]; pr[0] = c; }
+  }
+}
+
+// LOGITS: pred = float logits (F, C, P); otherwise pred = uint8 class indices (F * P), C a run-time value in `Crt`.
+// n_items = F * P / PPL; with PPL == 4 the host guarantees P % 4 == 0 (logits) or F * P % 4 == 0 (indices) and aligned bases.
+template <int C, int PPL, bool LOGITS>
+__global__ void __launch_bounds__(SEG_THREADS)
+seg_confusion_kernel(const void* __restrict__ pred, const unsigned char* __restrict__ label, unsigned long long* __restrict__ counts,
+                     long n_items, long P, int Crt) {
+  __shared__ unsigned int hist[SEG_WAVES][SEG_MAXC * SEG_MAXC + 1];
+  const int nc = LOGITS ? C : Crt, nbins = nc * nc + 1;
+  for (int i = threadIdx.x; i < SEG_WAVES * (SEG_MAXC * SEG_MAXC + 1); i += SEG_THREADS) (&hist[0][0])[i] = 0u;
+  __syncthreads();
+  unsigned int* mine = hist[threadIdx.x >> 6];
+  const bool narrow = n_items * PPL < (1L << 32);               // 32-bit division for every size a head really has
+  // every lane of the block runs the same number of rounds, so the ballots in seg_wave_add always see whole waves
+  for (long base = blockIdx.x * (long)SEG_THREADS; base < n_items; base += (long)gridDim.x * SEG_THREADS) {
+    const long it = base + threadIdx.x;
+    const bool live = it < n_items;
+    int tl[PPL], pr[PPL];
+#pragma unroll
+    for (int j = 0; j < PPL; ++j) tl[j] = pr[j] = 0;
+    if (live) {
+      const long i = it * PPL;                                   // first pixel of the item
+      if constexpr (PPL == 4) {
+        const unsigned int w = *reinterpret_cast<const unsigned int*>(label + i);
+        tl[0] = w & 255u; tl[1] = (w >> 8) & 255u; tl[2] = (w >> 16) & 255u; tl[3] = w >> 24;
+      } else {
+        tl[0] = label[i];
+      }
+      if constexpr (LOGITS) {
+        long f, v;
+        if (narrow) { const unsigned int fi = (unsigned int)i / (unsigned int)P; f = fi; v = (unsigned int)i - fi * (unsigned int)P; }
+        else { f = i / P; v = i - f * P; }
+        seg_argmax<C, PPL>(static_cast<const float*>(pred) + ((size_t)f * C) * P + v, P, pr);
+      } else {
+        const unsigned char* pi = static_cast<const unsigned char*>(pred);
+        if constexpr (PPL == 4) {
+          const unsigned int w = *reinterpret_cast<const unsigned int*>(pi + i);
+          pr[0] = w & 255u; pr[1] = (w >> 8) & 255u; pr[2] = (w >> 16) & 255u; pr[3] = w >> 24;
+        } else {
+          pr[0] = pi[i];
+        }
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < PPL; ++j) {
+      const bool inside = tl[j] < nc && pr[j] < nc;
+      seg_wave_add(mine, inside ? tl[j] * nc + pr[j] : nc * nc, live);
+    }
+  }
+  __syncthreads();
+  for (int i = threadIdx.x; i < nbins; i += SEG_THREADS) {
+    unsigned int s = 0u;
+#pragma unroll
+    for (int w = 0; w < SEG_WAVES; ++w) s += hist[w][i];
+    if (s) atomicAdd(counts + i, (unsigned long long)s);
+  }
+}
+
+// shared launch step of the two entry points below
+template <int C, bool LOGITS>
+static void seg_confusion_launch(const void* pred, const uint8_t* label, uint64_t* counts, long F, long P, int Crt, bool vec, hipStream_t s) {
+  const long n_items = vec ? F * P / 4 : F * P;
+  long nb = (n_items + SEG_THREADS - 1) / SEG_THREADS;
+  if (nb > SEG_MAX_BLOCKS) nb = SEG_MAX_BLOCKS;
+  if (vec)
+    hipLaunchKernelGGL((seg_confusion_kernel<C, 4, LOGITS>), dim3((int)nb), dim3(SEG_THREADS), 0, s, pred, label,
+                       (unsigned long long*)counts, n_items, P, Crt);
+  else
+    hipLaunchKernelGGL((seg_confusion_kernel<C, 1, LOGITS>), dim3((int)nb), dim3(SEG_THREADS), 0, s, pred, label,
+                       (unsigned long long*)counts, n_items, P, Crt);
+}
+
 #define ST ((hipStream_t)stream)
 extern "C" {
 
@@ -274,6 +409,34 @@ int muvo_ssc_counts(const float* logits, const uint8_t* label, uint64_t* counts,
   if (nb > 4096) nb = 4096;
   hipLaunchKernelGGL(ssc_counts_kernel, dim3((int)nb), dim3(256), 0, ST, logits, label, (unsigned long long*)counts, (long)F, C, (long)V);
   MUVO_CHECK_LAUNCH("ssc_counts_kernel");
+  return MUVO_OK;
+}
+
+int muvo_seg_confusion(const float* logits, const uint8_t* label, uint64_t* counts, int64_t F, int C, int64_t P, void* stream) {
+  MUVO_CHECK_ARG(logits && label && counts, "seg_confusion: null pointer");
+  MUVO_CHECK_ARG(F > 0 && P > 0, "seg_confusion: need F, P > 0 (got %ld, %ld)", (long)F, (long)P);
+  MUVO_CHECK_ARG(C >= 2 && C <= SEG_MAXC, "seg_confusion: C=%d unsupported (2..%d)", C, SEG_MAXC);
+  // 2^40 pixels over SEG_MAX_BLOCKS (512) blocks: 2^31 per block, inside the range of the LDS counters
+  MUVO_CHECK_ARG(F <= (1L << 40) / P, "seg_confusion: F*P = %ld x %ld exceeds 2^40 pixels", (long)F, (long)P);
+  // 16-byte loads need every frame and plane base aligned: P % 4 == 0 and an aligned allocation; 4-byte label loads likewise
+  const bool vec = P % 4 == 0 && ((uintptr_t)logits & 15) == 0 && ((uintptr_t)label & 3) == 0;
+  switch (C) {
+#define SEG_CASE(c) case c: seg_confusion_launch<c, true>(logits, label, counts, (long)F, (long)P, c, vec, ST); break;
+    SEG_CASE(2) SEG_CASE(3) SEG_CASE(4) SEG_CASE(5) SEG_CASE(6) SEG_CASE(7) SEG_CASE(8) SEG_CASE(9) SEG_CASE(10)
+    SEG_CASE(11) SEG_CASE(12) SEG_CASE(13) SEG_CASE(14) SEG_CASE(15) SEG_CASE(16)
+#undef SEG_CASE
+  }
+  MUVO_CHECK_LAUNCH("seg_confusion_kernel");
+  return MUVO_OK;
+}
+
+int muvo_seg_confusion_index(const uint8_t* pred, const uint8_t* label, uint64_t* counts, int64_t n, int C, void* stream) {
+  MUVO_CHECK_ARG(pred && label && counts, "seg_confusion_index: null pointer");
+  MUVO_CHECK_ARG(n > 0 && n <= (1L << 40), "seg_confusion_index: need 0 < n <= 2^40 (got %ld)", (long)n);
+  MUVO_CHECK_ARG(C >= 2 && C <= SEG_MAXC, "seg_confusion_index: C=%d unsupported (2..%d)", C, SEG_MAXC);
+  const bool vec = n % 4 == 0 && ((uintptr_t)pred & 3) == 0 && ((uintptr_t)label & 3) == 0;
+  seg_confusion_launch<SEG_MAXC, false>(pred, label, counts, 1L, (long)n, C, vec, ST);
+  MUVO_CHECK_LAUNCH("seg_confusion_kernel (index)");
   return MUVO_OK;
 }
 

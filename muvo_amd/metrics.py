@@ -1,7 +1,11 @@
 """Evaluation metrics of the validation path on the GPU: the reference's SSIMMetric, PSNRMetric,
 CDMetric and SSCMetrics (muvo/metrics.py:47-317) as driven by WorldModelTrainer.add_metrics / compute_ssc_metrics
 (muvo/trainer.py:426-490), computed by the HIP kernels of csrc/metrics.hip through the C ABI.  Same class names, methods
-and running-average semantics (including the reference's `count = 1e-8` start value); no CPU fallback."""
+and running-average semantics (including the reference's `count = 1e-8` start value); no CPU fallback.
+
+JaccardIndex is the multiclass, per-class form of torchmetrics.JaccardIndex the reference's trainer keeps per segmentation
+head (trainer.py:74-178): a confusion matrix counted on the device by one kernel per update (argmax fused in), read once per
+epoch in compute()."""
 import ctypes as C
 
 import numpy as np
@@ -64,6 +68,103 @@ def ssc_counts(logits, label, n_classes):
     ops._ck(ops.lib().muvo_ssc_counts(ops._f(lg), ops._p(lb), ops._p(counts), ops._i64(n), c, ops._i64(V), ops._st()))
     per = counts[3:].view(c, 3)
     return counts[:3], per[:, 0], per[:, 1], per[:, 2]
+
+
+SEG_MAX_CLASSES = 16        # SEG_MAXC of csrc/metrics.hip
+
+
+def _class_bytes(x, n_classes):
+    """Integer class map -> contiguous uint8 with every value outside [0, n_classes) turned into 255, which the kernel counts
+    as out of range (a plain .to(torch.uint8) would wrap -1 or 256 into a valid class).  uint8 input passes as it is."""
+    if x.dtype == torch.uint8:
+        return x.contiguous()
+    if x.is_floating_point() or x.dtype == torch.bool or x.is_complex():
+        raise TypeError(f'seg_confusion: class indices must be an integer tensor, got {x.dtype}')
+    if x.dtype == torch.int8:                        # 255 does not fit
+        x = x.to(torch.int16)
+    return x.masked_fill((x < 0) | (x >= n_classes), 255).to(torch.uint8).contiguous()
+
+
+def seg_confusion(preds, target, n_classes, out=None):
+    """Confusion counts of a segmentation head, argmax fused in.  preds: float logits (N, C, ...) or integer class indices
+    shaped like target; target: integer class map (N, ...) or (N, 1, ...).  -> int64 (C*C + 1,) device tensor: entry t*C + p
+    counts the pixels with label t and prediction p, the last entry those whose label (index path: or prediction) is outside
+    [0, C).  `out`: such a tensor to ADD into instead of a fresh one.  One kernel launch, no host read."""
+    c = int(n_classes)
+    if not 2 <= c <= SEG_MAX_CLASSES:
+        raise ValueError(f'seg_confusion: n_classes={c} unsupported (2..{SEG_MAX_CLASSES})')
+    if out is None:
+        out = torch.zeros(c * c + 1, dtype=torch.int64, device=preds.device)
+    assert out.dtype == torch.int64 and out.shape == (c * c + 1,)
+    if preds.is_floating_point():
+        if preds.dim() < 2 or preds.shape[1] != c:
+            raise ValueError(f'seg_confusion: logits {tuple(preds.shape)} need {c} classes in dimension 1')
+        n = preds.shape[0]
+        P = preds[0, 0].numel()
+        if target.numel() != n * P:
+            raise ValueError(f'seg_confusion: target {tuple(target.shape)} does not match logits {tuple(preds.shape)}')
+        if n * P == 0:
+            return out
+        lg, lb = preds.detach().float().contiguous(), _class_bytes(target, c)
+        ops._ck(ops.lib().muvo_seg_confusion(ops._f(lg), ops._p(lb), ops._p(out), ops._i64(n), c, ops._i64(P), ops._st()))
+    else:
+        if target.numel() != preds.numel():
+            raise ValueError(f'seg_confusion: target {tuple(target.shape)} does not match predictions {tuple(preds.shape)}')
+        if preds.numel() == 0:
+            return out
+        pr, lb = _class_bytes(preds, c), _class_bytes(target, c)
+        ops._ck(ops.lib().muvo_seg_confusion_index(ops._p(pr), ops._p(lb), ops._p(out), ops._i64(pr.numel()), c, ops._st()))
+    return out
+
+
+def jaccard_from_confmat(confmat):
+    """torchmetrics' _jaccard_index_reduce with average='none': (C, C) integer matrix [label, prediction] -> float32 (C,)
+    intersection / union per class; a class absent from both prediction and label (union 0) scores 0.  Any device."""
+    num = confmat.diag()
+    den = confmat.sum(0) + confmat.sum(1) - num
+    num, den = num.float(), den.float()
+    return torch.where(den != 0, num / den, torch.zeros_like(num))
+
+
+class JaccardIndex:
+    """torchmetrics.JaccardIndex(task='multiclass', num_classes=C, average='none') as the reference's trainer uses it
+    (trainer.py:74-178,427-478,525-554).  update() takes the head's LOGITS (N, C, ...) - the argmax of trainer.py:429 happens in
+    the counting kernel - or integer predictions, launches that kernel and nothing else; the (C, C) int64 matrix `confmat`
+    [label, prediction] and the count `out_of_range` stay on the device until compute() reads them once.  The reference's metric
+    raises on the first batch holding a label outside [0, C); here compute() raises with their count (validate_args=True) or
+    leaves such pixels out (False)."""
+
+    def __init__(self, task='multiclass', num_classes=None, average='none', validate_args=True, device=None):
+        if task != 'multiclass':
+            raise NotImplementedError(f"JaccardIndex: task={task!r} is not built (only 'multiclass')")
+        if average != 'none':
+            raise NotImplementedError(f"JaccardIndex: average={average!r} is not built (only 'none')")
+        if num_classes is None or not 2 <= int(num_classes) <= SEG_MAX_CLASSES:
+            raise ValueError(f'JaccardIndex: num_classes={num_classes} unsupported (2..{SEG_MAX_CLASSES})')
+        self.num_classes, self.validate_args = int(num_classes), validate_args
+        self.device = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
+        c = self.num_classes
+        self._counts = torch.zeros(c * c + 1, dtype=torch.int64, device=self.device)
+        self.confmat, self.out_of_range = self._counts[:c * c].view(c, c), self._counts[c * c]
+
+    def update(self, preds, target):
+        seg_confusion(preds, target, self.num_classes, out=self._counts)
+
+    __call__ = update
+
+    def compute(self, with_confmat=False):
+        """float32 (C,) scores on the host; with_confmat=True: (scores, the host copy of confmat they were computed from)."""
+        c = self.num_classes
+        counts = self._counts.cpu()                      # the one host read of an epoch
+        bad = int(counts[c * c])
+        if bad and self.validate_args:
+            raise RuntimeError(f'JaccardIndex: {bad} pixels carry a label outside [0, {c}) (validate_args=False leaves them out)')
+        confmat = counts[:c * c].view(c, c)
+        scores = jaccard_from_confmat(confmat)
+        return (scores, confmat) if with_confmat else scores
+
+    def reset(self):
+        self._counts.zero_()
 
 
 class SSIMMetric:

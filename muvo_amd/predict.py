@@ -9,8 +9,12 @@ reconstruction and imagination per batch).  One process, one GPU.
 
 `--mode test` runs `WorldModelTrainer.test_step` over the chosen test loaders (default: all three), then `on_test_epoch_end`,
 prints every logged metric as a JSON line and writes `metrics.json`: the logged names mapped to floats, plus `batches`, the
-number of batches each loader delivered.  The bird's-eye-view, lidar and camera IoU of the reference (torchmetrics.JaccardIndex)
-are not built; the tool says once which enabled heads therefore have no metric.
+number of batches each loader delivered.  With the bird's-eye-view, lidar or camera segmentation head enabled the file also
+holds that head's per-class and mean IoU (`{set}_{bev,lidar,camera}_iou_{class}`, `..._mean_iou`; the reference sends these to
+the TensorBoard writer, here they arrive with the rest) and `{set}_{bev,lidar,camera}_confusion`: the C x C count matrix
+[label][prediction] as nested integer lists.  The reference's class-name table has two entries, so only two of the lidar and
+camera head's nine per-class scores carry a name; the matrix holds what the other seven are computed from.  The counts are
+taken on the device (csrc/metrics.hip: argmax + confusion matrix in one kernel per head and batch) and read once at the end.
 
 `--mode sim` follows the loop of sim_run.py:49-116 (module in train() mode, the transformer's dropout modules off, no_grad;
 per batch `preprocess`, then `model.sim_forward(batch, is_dreaming=False)`) over one loader (default 2, sim_run.py:44) and
@@ -88,12 +92,12 @@ def chosen_loaders(mode, loader=None):
 
 def expected_metric_names(cfg, counts):
     """The names `on_test_epoch_end` logs when loader idx delivered counts[idx] batches (an empty loader logs nothing)."""
-    from muvo_amd.trainer import metric_log_names
+    from muvo_amd.trainer import metric_names
     names = []
     for kind, has in (('test', True), ('test_imagine', cfg.PREDICTION.N_SAMPLES > 0)):
         for idx in sorted(counts):
             if counts[idx] and has:
-                names += metric_log_names(cfg, f'{kind}{idx}')
+                names += metric_names(cfg, f'{kind}{idx}')
     return names
 
 
@@ -187,7 +191,7 @@ def seed_batch(module, seed, loader_idx, i):
 
 def run(cfg, device, out_dir, mode, loaders=None, limit_batches=None, shard_size=500, seed=1234, hook=None, dataset_root=None,
         data=None, module=None, log=print):
-    """Runs one mode and returns what it wrote: {'files': [...], 'batches': {loader: n}, 'metrics': {...} (test)}.
+    """Runs one mode and returns what it wrote: {'files': [...], 'batches': {loader: n}, 'metrics': {...}, 'confusion': {...} (test)}.
     hook(i, batch, output, output_imagine): called per batch with the device tensors (test mode: output_imagine is the list
     of imagined samples).  data: a set-up DataModule to take the test loaders from (default: one over dataset_root /
     cfg.DATASET.DATAROOT); module: a WorldModelTrainer to use instead of building one from cfg."""
@@ -221,10 +225,6 @@ def _batches(loader, limit):
 
 
 def _run_test(cfg, module, loaders, out_dir, limit_batches, shard_size, seed, hook, log):
-    from muvo_amd.trainer import metric_heads_left_out
-    left_out = metric_heads_left_out(cfg)
-    if left_out:
-        log(json.dumps({'no_metric_for': left_out, 'reason': 'torchmetrics.JaccardIndex is not built'}))
     counts = {}
     for idx, loader in loaders.items():
         counts[idx] = 0
@@ -234,22 +234,24 @@ def _run_test(cfg, module, loaders, out_dir, limit_batches, shard_size, seed, ho
             if hook is not None:
                 hook(i, batch, output, output_imagines)
             counts[idx] += 1
-    logged = {}
+    logged, confusion = {}, {}
     was_fn, module.log_fn = module.log_fn, lambda name, value: logged.__setitem__(name, float(value))
+    was_cm, module.on_confusion = module.on_confusion, lambda name, matrix: confusion.__setitem__(name, matrix.tolist())
     try:
         module.on_test_epoch_end()
     finally:
-        module.log_fn = was_fn
-    result = dict(logged)
+        module.log_fn, module.on_confusion = was_fn, was_cm
+    result = {**logged, **confusion}
     result['batches'] = {str(idx): n for idx, n in counts.items()}
-    for name, value in logged.items():
-        log(json.dumps({name: value}))
+    for name, value in result.items():
+        if name != 'batches':
+            log(json.dumps({name: value}))
     log(json.dumps({'batches': result['batches']}))
     path = os.path.join(out_dir, 'metrics.json')
     with open(path, 'w') as fh:
         json.dump(result, fh, indent=1, sort_keys=True)
         fh.write('\n')
-    return {'files': [path], 'batches': counts, 'metrics': logged}
+    return {'files': [path], 'batches': counts, 'metrics': logged, 'confusion': confusion}
 
 
 def _run_sim(cfg, module, loaders, out_dir, limit_batches, shard_size, seed, hook, log):

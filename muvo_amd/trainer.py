@@ -6,7 +6,7 @@ Same constructor `(hparams, path_to_conf_file=None, pretrained_path=None)`, attr
 `lightning` is importable the class derives from `pl.LightningModule`, otherwise from `torch.nn.Module` with
 the same hooks so the build's own loop (bench.py / train.py / predict.py) can drive it.  The evaluation half (`validation_step`,
 `test_step`, `log_metrics`, `on_validation_epoch_end`, `on_test_epoch_end`; trainer.py:404-567,1075-1095) is here without the
-visualisation (trainer.py:569-1020) and without the three torchmetrics IoU metrics."""
+visualisation (trainer.py:569-1020); the three torchmetrics IoU metrics are muvo_amd.metrics.JaccardIndex."""
 import os
 
 import numpy as np
@@ -40,10 +40,39 @@ def _refuse_ddp(module, args):
 
 
 VOXEL_LABEL = ('Background', 'Occupancy')          # the names of the reference's voxel class table (constants.py VOXEL_LABEL)
+BEV_CLASS_NAMES = ('Background', 'Road', 'Lane marking', 'Vehicle', 'Pedestrian', 'Green light', 'Yellow light',
+                   'Red light and stop sign')       # trainer.py:520-521
+# (metric key, config node, its class-count field, tag in the logged names, class names the per-class scores are zipped with)
+IOU_HEADS = (('iou', 'SEMANTIC_SEG', 'N_CHANNELS', 'bev', BEV_CLASS_NAMES),
+             ('pcd_iou', 'LIDAR_SEG', 'N_CLASSES', 'lidar', VOXEL_LABEL),
+             ('image_iou', 'SEMANTIC_IMAGE', 'N_CLASSES', 'camera', VOXEL_LABEL))
+
+
+def _iou_names(cfg, prefix, head):
+    key, node, field, tag, class_names = head
+    if not cfg[node].ENABLED:
+        return []
+    return [f'{prefix}_{tag}_iou_{name}' for name in class_names[:cfg[node][field]]] + [f'{prefix}_{tag}_mean_iou']
+
+
+def metric_names(cfg, prefix):
+    """Every name log_metrics sends for one non-empty metric set, in the reference's order (trainer.py:525-567): the IoU
+    names of the segmentation heads, which travel on the logger channel (log_scalar), interleaved with those of
+    metric_log_names.  The zip with the class-name table stops at the shorter side, like the reference's."""
+    names = _iou_names(cfg, prefix, IOU_HEADS[0])
+    if cfg.EVAL.RGB_SUPERVISION:
+        names += [f'{prefix}_ssim', f'{prefix}_psnr']
+    if cfg.LIDAR_RE.ENABLED:
+        names.append(f'{prefix}_chamfer_distance')
+    names += _iou_names(cfg, prefix, IOU_HEADS[1]) + _iou_names(cfg, prefix, IOU_HEADS[2])
+    if cfg.VOXEL_SEG.ENABLED:
+        names += [f'{prefix}_Voxel_{name}_SemIoU' for name in VOXEL_LABEL[:cfg.VOXEL_SEG.N_CLASSES]]
+        names += [f'{prefix}_Voxel_mIoU', f'{prefix}_Voxel_IoU', f'{prefix}_Voxel_Precision', f'{prefix}_Voxel_Recall']
+    return names
 
 
 def metric_log_names(cfg, prefix):
-    """The names log_metrics sends for one non-empty metric set, in order (trainer.py:532-567)."""
+    """The names log_metrics sends through `self.log` for one non-empty metric set, in order (trainer.py:532-567)."""
     names = []
     if cfg.EVAL.RGB_SUPERVISION:
         names += [f'{prefix}_ssim', f'{prefix}_psnr']
@@ -56,7 +85,9 @@ def metric_log_names(cfg, prefix):
 
 
 def metric_heads_left_out(cfg):
-    """Enabled heads whose metric of the reference (torchmetrics.JaccardIndex, trainer.py:525-554) is not built here."""
+    """Enabled heads whose metric is an IoU (torchmetrics.JaccardIndex in the reference, muvo_amd.metrics.JaccardIndex here,
+    trainer.py:525-554): their scores travel on the logger channel (`log_scalar`), not through `self.log`, so their names are
+    in metric_names and not in metric_log_names."""
     heads = (('SEMANTIC_SEG', 'bev_iou'), ('LIDAR_SEG', 'lidar_iou'), ('SEMANTIC_IMAGE', 'camera_iou'))
     return [name for key, name in heads if cfg[key].ENABLED]
 
@@ -89,6 +120,7 @@ class WorldModelTrainer(_Base):
         self._global_step = 0          # plain-loop counterpart of LightningModule.global_step
         self.log_fn = None             # plain loop: callable(name, value) receiving what Lightning's self.log would
         self.logged = {}
+        self.on_confusion = None       # callable(name, (C, C) host int64 matrix): the IoU heads' counts, handed over by log_metrics
         self.accumulate_now = False    # plain loop: True while a non-final micro-batch of gradient accumulation runs
         # evaluation metrics per validation / test dataloader (trainer.py:51-55,100-129,191-197); created on first use
         # because they hold device accumulators
@@ -155,9 +187,13 @@ class WorldModelTrainer(_Base):
         return losses, output, losses_imagines, output_imagines
 
     def _metric_set(self, metrics):
-        """trainer.py:100-129,191-197: the metrics base_1d enables (ssim, psnr, cd, ssc)."""
+        """trainer.py:73-197: the metrics of the enabled heads (base_1d: ssim, psnr, cd, ssc; iou, pcd_iou, image_iou with the
+        bird's-eye-view, lidar and camera segmentation heads)."""
         if not metrics:
-            from .metrics import CDMetric, PSNRMetric, SSCMetrics, SSIMMetric
+            from .metrics import CDMetric, JaccardIndex, PSNRMetric, SSCMetrics, SSIMMetric
+            for key, node, field, _, _ in IOU_HEADS:
+                if self.cfg[node].ENABLED:
+                    metrics[key] = JaccardIndex(task='multiclass', num_classes=self.cfg[node][field], average='none')
             if self.cfg.EVAL.RGB_SUPERVISION:
                 metrics['ssim'], metrics['psnr'] = SSIMMetric(channel=3), PSNRMetric(max_pixel_val=1.0)
             if self.cfg.LIDAR_RE.ENABLED:
@@ -167,9 +203,12 @@ class WorldModelTrainer(_Base):
         return metrics
 
     def add_metrics(self, metrics, batch, output, cd_index=None):
-        """trainer.py:426-480 for the heads of base_1d.  cd_index: the 10000-point subset of the Chamfer metric; the
-        reference draws it with np.random.randint (trainer.py:455), pass it explicitly for reproducible numbers."""
+        """trainer.py:426-480.  cd_index: the 10000-point subset of the Chamfer metric; the reference draws it with
+        np.random.randint (trainer.py:455), pass it explicitly for reproducible numbers.  The IoU metrics get the heads' logits:
+        the argmax of trainer.py:429,466,474 is part of the counting kernel, and neither side goes to the host."""
         metrics = self._metric_set(metrics)
+        if self.cfg.SEMANTIC_SEG.ENABLED:
+            metrics['iou'](output['bev_segmentation_1'].detach().flatten(0, 1), batch['birdview_label'])
         if self.cfg.EVAL.RGB_SUPERVISION:
             metrics['ssim'].add_batch(prediction=output['rgb_1'].detach(), target=batch['rgb_label_1'])
             metrics['psnr'].add_batch(prediction=output['rgb_1'].detach(), target=batch['rgb_label_1'])
@@ -182,6 +221,10 @@ class WorldModelTrainer(_Base):
                 cd_index = np.random.randint(0, pcd_target.size(-2), 10000)
             index = torch.as_tensor(cd_index, device=pcd_pred.device).long()
             metrics['cd'].add_batch(pcd_pred[:, index, :-1], pcd_target[:, index, :-1])
+        if self.cfg.LIDAR_SEG.ENABLED:
+            metrics['pcd_iou'](output['lidar_segmentation_1'].detach().flatten(0, 1), batch['range_view_seg_label_1'])
+        if self.cfg.SEMANTIC_IMAGE.ENABLED:
+            metrics['image_iou'](output['semantic_image_1'].detach().flatten(0, 1), batch['semantic_image_label_1'])
         if self.cfg.VOXEL_SEG.ENABLED:
             self.compute_ssc_metrics(batch, output, metrics['ssc'])
 
@@ -231,13 +274,16 @@ class WorldModelTrainer(_Base):
         return output, output_imagines
 
     def log_metrics(self, metrics_list, metrics_type):
-        """trainer.py:519-567 for the metrics built here: every non-empty metric set of `metrics_list` goes out through
-        `self.log` under `{metrics_type}{idx}_...` (metric_log_names) and is reset.  The bird's-eye-view, lidar and camera IoU
-        of the reference are torchmetrics.JaccardIndex objects, which this project does not build: skipped (metric_heads_left_out)."""
+        """trainer.py:519-567: every non-empty metric set of `metrics_list` goes out under `{metrics_type}{idx}_...`
+        (metric_names) and is reset.  The per-class and mean IoU of the bird's-eye-view, lidar and camera heads go through
+        `log_scalar` (the reference's `self.logger.experiment.add_scalar`), everything else through `self.log`
+        (metric_log_names).  `on_confusion(name, matrix)`, if set, gets each head's (C, C) count matrix - host int64, already
+        read for the scores - before the reset."""
         for idx, metrics in enumerate(metrics_list):
             if not metrics:
                 continue
             prefix = f'{metrics_type}{idx}'
+            self._log_iou(metrics, prefix, IOU_HEADS[0])
             if 'ssim' in metrics:
                 self.log(f'{prefix}_ssim', metrics['ssim'].get_stat())
                 metrics['ssim'].reset()
@@ -246,6 +292,8 @@ class WorldModelTrainer(_Base):
             if 'cd' in metrics:
                 self.log(f'{prefix}_chamfer_distance', metrics['cd'].get_stat())
                 metrics['cd'].reset()
+            self._log_iou(metrics, prefix, IOU_HEADS[1])
+            self._log_iou(metrics, prefix, IOU_HEADS[2])
             if 'ssc' in metrics:
                 stats = metrics['ssc'].get_stats()
                 for class_name, value in zip(VOXEL_LABEL, stats['iou_ssc']):        # stops at the shorter list, like the reference
@@ -255,6 +303,35 @@ class WorldModelTrainer(_Base):
                 self.log(f'{prefix}_Voxel_Precision', stats['precision'])
                 self.log(f'{prefix}_Voxel_Recall', stats['recall'])
                 metrics['ssc'].reset()
+
+    def _log_iou(self, metrics, prefix, head):
+        """trainer.py:525-530,542-554 for one head: per-class scores zipped with the class names, the mean over ALL classes."""
+        key, _, _, tag, class_names = head
+        if key not in metrics:
+            return
+        scores, confmat = metrics[key].compute(with_confmat=True)
+        for name, value in zip(class_names, scores):
+            self.log_scalar(f'{prefix}_{tag}_iou_{name}', value)
+        self.log_scalar(f'{prefix}_{tag}_mean_iou', torch.mean(scores))
+        if self.on_confusion is not None:
+            self.on_confusion(f'{prefix}_{tag}_confusion', confmat)
+        metrics[key].reset()
+
+    def log_scalar(self, name, value):
+        """The reference's `self.logger.experiment.add_scalar(name, value, global_step=self.global_step)`: under Lightning
+        with a logger whose `experiment` has `add_scalar` (TensorBoard) exactly that; otherwise the value goes to
+        `self.log_fn(name, value)` if one is set, else into `self.logged`."""
+        if pl is not None and getattr(self, '_trainer', None) is not None:
+            experiment = getattr(getattr(self, 'logger', None), 'experiment', None)
+            if hasattr(experiment, 'add_scalar'):
+                experiment.add_scalar(name, value, global_step=self.global_step)
+                return
+        if torch.is_tensor(value):
+            value = value.detach()
+        if self.log_fn is not None:
+            self.log_fn(name, value)
+        else:
+            self.logged[name] = value
 
     def on_validation_epoch_end(self):
         """trainer.py:515-517"""

@@ -1,7 +1,9 @@
-"""Time of the two voxel-export routes of a prediction run (muvo_amd/predict.py) on the GPU.
+"""Time of the two voxel-export routes of a prediction run (muvo_amd/predict.py) on the GPU, and of the
+confusion counts behind the segmentation heads' IoU.
 
     python tools/predict_bench.py [--rounds 5] [--iters 50] [--host-iters 1] [--out profiles/predict_export.txt]
     (--host-iters 0: the kernel route only, e.g. under a kernel trace)
+    python tools/predict_bench.py --what confusion [--rounds 5] [--iters 50] [--host-iters 3] [--out profiles/predict_confusion.txt]
 
 Routes, on the same logits (F frames of C x 192 x 192 x 64 float32 on the device, about 10 % of the voxels occupied):
   kernels    ops.voxel_rows (csrc/export.hip: classify + count, scan, ordered compaction), the rows copied to the host.
@@ -12,7 +14,17 @@ Routes, on the same logits (F frames of C x 192 x 192 x 64 float32 on the device
              clock; `copy` is the .cpu() alone.  torch's CPU thread count is printed: it bounds argmax and where.
 Warm-up first, then `--rounds` windows per route, the routes alternating; median (min .. max) over the windows of the
 per-call mean.  The traffic floor of the kernel route is C * 4 B read + 1 B written and 1 B read per voxel + 8 B per row; its
-share of the HBM peak is quoted for the `device` time only.  Before timing, the rows of both routes are compared once."""
+share of the HBM peak is quoted for the `device` time only.  Before timing, the rows of both routes are compared once.
+
+--what confusion: the three segmentation heads at their real sizes, 20 frames each (bird's-eye view 8 x 192 x 192, lidar
+9 x 64 x 1024, camera 9 x 320 x 832 = the cropped image of base_1d), labels and predictions constant over 16 x 16 tiles, the
+prediction equal to the label in about nine tiles of ten:
+  kernel     muvo_seg_confusion alone between HIP events, adding into one buffer; traffic floor C * 4 + 1 bytes per pixel.
+  update     JaccardIndex.update by the host clock: `queued` = calls back to back with one synchronise per window (how the
+             evaluation loop runs it), `synced` = a synchronise after every call.
+  reference  the reference's route restated (trainer.py:428-433 + the metric's update): torch.argmax on the device, prediction
+             and label to the host, bincount of label * C + prediction there - by the host clock.
+The counts of both routes are compared once before timing."""
 import argparse
 import os
 import statistics
@@ -79,8 +91,93 @@ def fmt(t):
     return f'{statistics.median(t):10.3f} ({min(t):9.3f} .. {max(t):9.3f})'
 
 
+CONFUSION_CASES = [('bev', 8, 192, 192), ('lidar', 9, 64, 1024), ('camera', 9, 320, 832)]
+CONFUSION_FRAMES = 20
+
+
+def make_head(F, C, H, W, dev, tile=16, agree=0.9):
+    g = torch.Generator(device=dev).manual_seed(C * 1000 + H)
+    th, tw = (H + tile - 1) // tile, (W + tile - 1) // tile
+    label_t = torch.randint(0, C, (F, th, tw), generator=g, device=dev)
+    other_t = torch.randint(0, C, (F, th, tw), generator=g, device=dev)
+    pred_t = torch.where(torch.rand((F, th, tw), generator=g, device=dev) < agree, label_t, other_t)
+
+    def up(t):
+        return t.repeat_interleave(tile, 1).repeat_interleave(tile, 2)[:, :H, :W].contiguous()
+    lg = torch.randn((F, C, H, W), generator=g, device=dev)
+    lg.scatter_add_(1, up(pred_t).unsqueeze(1), torch.full((F, 1, H, W), 8.0, device=dev))
+    return lg, up(label_t).to(torch.uint8).unsqueeze(1).contiguous()
+
+
+def reference_confusion(lg, lb, C):
+    pred = torch.argmax(lg, dim=1).view(-1).cpu()
+    target = lb.view(-1).cpu()
+    return torch.bincount(target.long() * C + pred, minlength=C * C)
+
+
+def confusion_main(a):
+    from muvo_amd.metrics import JaccardIndex, seg_confusion
+    dev = torch.device('cuda')
+    F = CONFUSION_FRAMES
+    lines = [f'# confusion counts of the segmentation heads, {F} frames; {a.rounds} alternating windows; kernel / update: {a.iters} calls '
+             f'per window, reference: {a.host_iters}; median ms per call (min .. max); torch CPU threads: {torch.get_num_threads()}']
+    for name, C, H, W in CONFUSION_CASES:
+        lg, lb = make_head(F, C, H, W, dev)
+        counts = torch.zeros(C * C + 1, dtype=torch.int64, device=dev)
+        seg_confusion(lg, lb, C, out=counts)
+        want = reference_confusion(lg, lb, C)
+        assert torch.equal(counts[:-1].cpu(), want) and int(counts[-1]) == 0, 'the two routes disagree'
+        m = JaccardIndex(task='multiclass', num_classes=C, average='none')
+
+        def kernel_ms(iters):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(iters):
+                seg_confusion(lg, lb, C, out=counts)
+            e1.record()
+            torch.cuda.synchronize()
+            return e0.elapsed_time(e1) / iters
+
+        def synced():
+            m.update(lg, lb)
+            torch.cuda.synchronize()
+        kernel_ms(3)
+        wall(lambda: m.update(lg, lb), 3)
+        wall(lambda: reference_confusion(lg, lb, C), 1)
+        k_t, q_t, s_t, r_t = [], [], [], []
+        for _ in range(a.rounds):
+            k_t.append(kernel_ms(a.iters))
+            q_t.append(wall(lambda: m.update(lg, lb), a.iters))
+            s_t.append(wall(synced, a.iters))
+            if a.host_iters:
+                r_t.append(wall(lambda: reference_confusion(lg, lb, C), a.host_iters))
+        floor = F * H * W * (4 * C + 1)
+        med = statistics.median(k_t)
+        first = len(lines)
+        lines += [f'{name}  F {F}  C {C}  {H} x {W}  logits {4 * F * C * H * W / 1e6:.1f} MB  diagonal share {float(want.view(C, C).diag().sum()) / (F * H * W):.3f}',
+                  f'  kernel              {fmt(k_t)}   traffic floor {floor / 1e6:.1f} MB -> {floor / med / 1e6:.0f} GB/s, '
+                  f'{100 * floor / med / 1e6 / HBM_PEAK_GBS:.1f} % of the {HBM_PEAK_GBS / 1e3:.0f} TB/s HBM peak',
+                  f'  update   queued     {fmt(q_t)}',
+                  f'  update   synced     {fmt(s_t)}']
+        if r_t:
+            lines += [f'  reference           {fmt(r_t)}',
+                      f'  reference / update synced = {statistics.median(r_t) / statistics.median(s_t):.0f}']
+        for line in lines[first:]:
+            print(line, flush=True)
+        del lg, lb
+    return lines
+
+
+def write_out(path, lines):
+    if path:
+        os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+        with open(path, 'w') as f:
+            f.write('\n'.join(lines) + '\n')
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument('--what', choices=('export', 'confusion'), default='export')
     ap.add_argument('--rounds', type=int, default=5)
     ap.add_argument('--iters', type=int, default=50)
     ap.add_argument('--host-iters', type=int, default=1)
@@ -88,6 +185,9 @@ def main():
     a = ap.parse_args()
     assert torch.cuda.is_available(), 'this benchmark needs a GPU'
     dev = torch.device('cuda')
+    if a.what == 'confusion':
+        write_out(a.out, confusion_main(a))
+        return
     lines = [f'# voxel export routes, {GRID[0]} x {GRID[1]} x {GRID[2]} voxels per frame; {a.rounds} alternating windows; kernels: '
              f'{a.iters} calls per window, host: {a.host_iters}; median ms per call (min .. max); torch CPU threads: {torch.get_num_threads()}']
     for F, C in CASES:
@@ -120,11 +220,7 @@ def main():
         for line in lines[(-6 if h_t else -3):]:
             print(line, flush=True)
         del lg, buf
-    text = '\n'.join(lines) + '\n'
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, 'w') as f:
-            f.write(text)
+    write_out(a.out, lines)
 
 
 if __name__ == '__main__':
