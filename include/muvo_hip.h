@@ -617,6 +617,53 @@ int muvo_voxel_rows_write(const uint8_t* grid, int F, int X, int Y, int Z, const
                           int64_t cap, void* stream);
 int muvo_image_u8(const float* x, uint8_t* y, int64_t n, void* stream);
 
+/* ---- prediction panels (csrc/visualise.hip) ------------------------------------------------------------------------------------
+ * Tiles of the reference's picture grids (trainer.py:569-1007), written from device tensors straight into a caller-allocated
+ * uint8 panel.  A call places F = b * T tiles: frame f belongs to sample f / T and time step t = t0 + f % T, and its padded
+ * tile starts at row y0 + t * ystep, column x0 + t * xstep (+ sepw when t >= tsep) of the sample's PH x PW planes.  Channel c
+ * of sample n starts at byte n * sample_stride + c * chan_stride.  Every entry checks, before it launches anything, that every
+ * tile lies inside its planes and the planes inside `panel_bytes`.
+ * Common arguments: pad / padbyte - a border of `pad` pixels of value `padbyte` on every channel is part of the tile
+ * ((h + 2 pad) x (w + 2 pad)); rotate (class tiles) - the padded tile goes in as torch.rot90(k = 1): out[i][j] = in[j][Wp - 1 - i],
+ * (w + 2 pad) rows x (h + 2 pad) columns.  palette: 256 x 3 bytes R, G, B on the device.
+ *   muvo_panel_image: channels c0 .. c0 + nch - 1 (nch = 1 or 3) of (F, C, h, w) float32; bytes by the rule of muvo_image_u8.
+ *   muvo_panel_logits: (F, C, h, w) float32, 2 <= C <= 16; class = first maximum over C (strict >), then the palette.
+ *   muvo_panel_labels: (F, h, w) uint8 or int64 (is_int64); palette entry of the value's low byte.
+ *   muvo_panel_fill: h x w of `value` inside the border, on nch channels.
+ *   muvo_panel_bars: one action value per frame -> the (int(h/4), w + 10) bar of trainer.py:679-706 without the text: all 255,
+ *     rows [5, int(h/4) - 5), columns [mid, mid + k) for v >= 0 else [mid + k, mid), mid = int(w/2) + 5,
+ *     k = (int)((float)(w / 2.0) * v), clipped to the tile (NaN: no bar); kind 0: (0, 200, 0) / (200, 0, 0) for v >= 0 / v < 0,
+ *     kind 1: (0, 0, 200).
+ *   muvo_panel_scatter: range view (F, C, H, W) float32 with x, y in channels 0, 1 and the range in channel C - 1 ->
+ *     pcd_xy_image (trainer.py:980-1007) on a 256 x 256 tile: zeros, then 255 at ((int)r, (int)c) for every point with
+ *     d * scale > 0, 0 < r < 256, 0 < c < 256, r = (-(x * scale)) * 2.56f + 128f, c likewise from y; fp32, uncontracted.
+ *   muvo_panel_voxel_top_*: logits (F, C, X, Y, Z) float32 (first maximum) or a grid (F, X, Y, Z) uint8 -> an X x Y tile, pixel
+ *     [i][j] = column x = X - 1 - i, y = j: z* = the highest z whose class is not 0; none: palette[0]; otherwise per channel
+ *     (p * (96 + (159 * z*) / max(Z - 1, 1))) / 255 in integers, p = palette[class at z*]. */
+typedef struct MuvoTilePlace {
+  int64_t sample_stride, chan_stride;
+  int32_t PH, PW;
+  int32_t T, t0;
+  int32_t x0, y0, xstep, ystep;
+  int32_t tsep, sepw;
+} MuvoTilePlace;
+int muvo_panel_image(const float* src, int F, int C, int c0, int h, int w, int pad, int padbyte, int nch, uint8_t* panel, int64_t panel_bytes,
+                     const MuvoTilePlace* place, void* stream);
+int muvo_panel_logits(const float* src, int F, int C, int h, int w, const uint8_t* palette, int pad, int padbyte, int rotate, uint8_t* panel,
+                      int64_t panel_bytes, const MuvoTilePlace* place, void* stream);
+int muvo_panel_labels(const void* src, int is_int64, int F, int h, int w, const uint8_t* palette, int pad, int padbyte, int rotate,
+                      uint8_t* panel, int64_t panel_bytes, const MuvoTilePlace* place, void* stream);
+int muvo_panel_fill(int F, int h, int w, int value, int pad, int padbyte, int nch, uint8_t* panel, int64_t panel_bytes,
+                    const MuvoTilePlace* place, void* stream);
+int muvo_panel_bars(const float* values, int kind, int F, int h, int w, uint8_t* panel, int64_t panel_bytes, const MuvoTilePlace* place,
+                    void* stream);
+int muvo_panel_scatter(const float* range_view, int F, int C, int H, int W, float scale, int pad, int padbyte, uint8_t* panel,
+                       int64_t panel_bytes, const MuvoTilePlace* place, void* stream);
+int muvo_panel_voxel_top_logits(const float* logits, int F, int C, int X, int Y, int Z, const uint8_t* palette, int pad, int padbyte,
+                                uint8_t* panel, int64_t panel_bytes, const MuvoTilePlace* place, void* stream);
+int muvo_panel_voxel_top_grid(const uint8_t* grid, int F, int X, int Y, int Z, const uint8_t* palette, int pad, int padbyte, uint8_t* panel,
+                              int64_t panel_bytes, const MuvoTilePlace* place, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

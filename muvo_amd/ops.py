@@ -82,6 +82,8 @@ EXPORTS = [
     'muvo_range_projection_frames', 'muvo_voxel_grid_frames',
     'muvo_attention_stream_supported', 'muvo_attention_stream_blocks', 'muvo_attention_stream_fwd', 'muvo_attention_stream_bwd',
     'muvo_voxel_rows_scratch_bytes', 'muvo_voxel_rows_logits', 'muvo_voxel_rows_grid', 'muvo_voxel_rows_write', 'muvo_image_u8',
+    'muvo_panel_image', 'muvo_panel_logits', 'muvo_panel_labels', 'muvo_panel_fill', 'muvo_panel_bars', 'muvo_panel_scatter',
+    'muvo_panel_voxel_top_logits', 'muvo_panel_voxel_top_grid',
 ]
 
 
@@ -2957,3 +2959,109 @@ def image_u8(x):
     if x.numel():
         _ck(lib().muvo_image_u8(_f(x), _p(y), _i64(x.numel()), _st()))
     return y
+
+
+# ---- prediction panels (csrc/visualise.hip) --------------------------------------------------------------------------------------
+class TilePlace(C.Structure):
+    """MuvoTilePlace of include/muvo_hip.h: where the tiles of one call go inside the panel."""
+    _fields_ = [('sample_stride', C.c_int64), ('chan_stride', C.c_int64), ('PH', C.c_int32), ('PW', C.c_int32),
+                ('T', C.c_int32), ('t0', C.c_int32), ('x0', C.c_int32), ('y0', C.c_int32), ('xstep', C.c_int32), ('ystep', C.c_int32),
+                ('tsep', C.c_int32), ('sepw', C.c_int32)]
+
+
+PANEL_NO_SEP = 1 << 30          # tsep of a layout without a separator
+
+
+def tile_place(panel, T, t0=0, x0=0, y0=0, xstep=0, ystep=0, tsep=PANEL_NO_SEP, sepw=0):
+    """The placement of T tiles per sample in `panel`: (b, C, PH, PW) uint8, or a video (b, Tv, 1, H2, W), whose frames are
+    addressed as one (Tv * H2) x W plane per sample.  Step t = t0 + frame % T starts at row y0 + t * ystep, column
+    x0 + t * xstep (+ sepw when t >= tsep)."""
+    assert panel.dtype == torch.uint8 and panel.is_cuda and panel.is_contiguous() and panel.dim() in (4, 5)
+    if panel.dim() == 5:
+        b, Tv, ch, H2, W = panel.shape
+        assert ch == 1
+        PH, PW, cs = Tv * H2, W, Tv * H2 * W
+        ss = cs
+    else:
+        b, ch, PH, PW = panel.shape
+        cs, ss = PH * PW, ch * PH * PW
+    return TilePlace(ss, cs, PH, PW, int(T), int(t0), int(x0), int(y0), int(xstep), int(ystep), int(tsep), int(sepw))
+
+
+def _panel_args(panel, place):
+    assert panel.dtype == torch.uint8 and panel.is_contiguous()
+    return _p(panel), _i64(panel.numel()), C.byref(place), _st()
+
+
+def _panel_nch(panel):
+    return 1 if panel.dim() == 5 else int(panel.shape[1])
+
+
+def _palette(palette, device):
+    assert palette.dtype == torch.uint8 and tuple(palette.shape) == (256, 3) and palette.device == device
+    return _p(palette)
+
+
+def panel_image(src, panel, place, pad=0, padbyte=0, channel=0):
+    """Float image tiles: the panel's 1 or 3 channels are channels `channel` ... of src (F, C, h, w) float32 (a negative
+    `channel` counts from the end); bytes by the rule of image_u8."""
+    assert src.dtype == torch.float32 and src.dim() == 4
+    src = src.contiguous()
+    F, Cn, h, w = src.shape
+    c0 = channel + Cn if channel < 0 else channel
+    _ck(lib().muvo_panel_image(_f(src), int(F), int(Cn), int(c0), int(h), int(w), int(pad), int(padbyte), _panel_nch(panel),
+                               *_panel_args(panel, place)))
+
+
+def panel_classes(src, palette, panel, place, pad=0, padbyte=0, rotate=False):
+    """Class tiles: src = logits (F, C, h, w) float32 (first maximum over C, strict >) or labels (F, h, w) uint8 / int64;
+    palette (256, 3) uint8 on the device.  rotate: the padded tile goes in as torch.rot90(k=1)."""
+    src = src.contiguous()
+    pal = _palette(palette, src.device)
+    if src.dtype == torch.float32 and src.dim() == 4:
+        F, Cn, h, w = src.shape
+        _ck(lib().muvo_panel_logits(_f(src), int(F), int(Cn), int(h), int(w), pal, int(pad), int(padbyte), int(bool(rotate)),
+                                    *_panel_args(panel, place)))
+    elif src.dtype in (torch.uint8, torch.int64) and src.dim() == 3:
+        F, h, w = src.shape
+        _ck(lib().muvo_panel_labels(_p(src), int(src.dtype == torch.int64), int(F), int(h), int(w), pal, int(pad), int(padbyte),
+                                    int(bool(rotate)), *_panel_args(panel, place)))
+    else:
+        raise ValueError(f'panel_classes: logits (F, C, h, w) float32 or labels (F, h, w) uint8 / int64, got {tuple(src.shape)} {src.dtype}')
+
+
+def panel_fill(F, h, w, value, panel, place, pad=0, padbyte=0):
+    """Constant tiles: h x w of `value` inside a border of `padbyte`, F of them."""
+    _ck(lib().muvo_panel_fill(int(F), int(h), int(w), int(value), int(pad), int(padbyte), _panel_nch(panel), *_panel_args(panel, place)))
+
+
+def panel_bars(values, kind, h, w, panel, place):
+    """Action bars of an h x w camera image: values (F,) float32 on the device (never read by the host); kind 0
+    throttle_brake, 1 steering.  A tile is (int(h / 4), w + 10)."""
+    assert values.dtype == torch.float32
+    values = values.contiguous().view(-1)
+    _ck(lib().muvo_panel_bars(_f(values), int(kind), int(values.numel()), int(h), int(w), *_panel_args(panel, place)))
+
+
+def panel_scatter(range_view, scale, panel, place, pad=0, padbyte=0):
+    """Bird's-eye scatter of range views (F, C, H, W) float32 (x, y, ..., range) on 256 x 256 tiles (pcd_xy_image)."""
+    assert range_view.dtype == torch.float32 and range_view.dim() == 4
+    range_view = range_view.contiguous()
+    F, Cn, H, W = range_view.shape
+    _ck(lib().muvo_panel_scatter(_f(range_view), int(F), int(Cn), int(H), int(W), _fl(scale), int(pad), int(padbyte),
+                                 *_panel_args(panel, place)))
+
+
+def panel_voxel_top(src, palette, panel, place, pad=0, padbyte=0):
+    """Top view of voxel grids: src = logits (F, C, X, Y, Z) float32 or a class grid (F, X, Y, Z) uint8; an X x Y tile each."""
+    src = src.contiguous()
+    pal = _palette(palette, src.device)
+    if src.dtype == torch.float32 and src.dim() == 5:
+        F, Cn, X, Y, Z = src.shape
+        _ck(lib().muvo_panel_voxel_top_logits(_f(src), int(F), int(Cn), int(X), int(Y), int(Z), pal, int(pad), int(padbyte),
+                                              *_panel_args(panel, place)))
+    elif src.dtype == torch.uint8 and src.dim() == 4:
+        F, X, Y, Z = src.shape
+        _ck(lib().muvo_panel_voxel_top_grid(_p(src), int(F), int(X), int(Y), int(Z), pal, int(pad), int(padbyte), *_panel_args(panel, place)))
+    else:
+        raise ValueError(f'panel_voxel_top: logits (F, C, X, Y, Z) float32 or a grid (F, X, Y, Z) uint8, got {tuple(src.shape)} {src.dtype}')

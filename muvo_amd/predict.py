@@ -8,7 +8,8 @@ reconstruction and imagination per batch).  One process, one GPU.
         --checkpoint epoch=0-step=50000.ckpt --out runs/sim --mode sim [--loader 2] [--limit-batches 100] [--shard-size 500]
 
 `--mode test` runs `WorldModelTrainer.test_step` over the chosen test loaders (default: all three), then `on_test_epoch_end`,
-prints every logged metric as a JSON line and writes `metrics.json`: the logged names mapped to floats, plus `batches`, the
+prints every logged metric as a JSON line and writes `metrics.json` (with `--panels N` also the picture grids of the first N
+batches of every loader, as PNG files below `OUT/panels`; muvo_amd/visualise.py): the logged names mapped to floats, plus `batches`, the
 number of batches each loader delivered.  With the bird's-eye-view, lidar or camera segmentation head enabled the file also
 holds that head's per-class and mean IoU (`{set}_{bev,lidar,camera}_iou_{class}`, `..._mean_iou`; the reference sends these to
 the TensorBoard writer, here they arrive with the rest) and `{set}_{bev,lidar,camera}_confusion`: the C x C count matrix
@@ -74,6 +75,8 @@ def build_parser():
     parser.add_argument('--limit-batches', type=int, default=None, metavar='N', help='at most N batches per loader')
     parser.add_argument('--shard-size', type=int, default=500, metavar='N', help='batches per data_{i}.npz (sim)')
     parser.add_argument('--seed', type=int, default=1234)
+    parser.add_argument('--panels', type=int, default=0, metavar='N',
+                        help='test: write the picture grids of the first N batches per loader below OUT/panels (default: none)')
     return parser
 
 
@@ -83,6 +86,8 @@ def parse_args(argv=None):
         raise SystemExit('--limit-batches must be positive')
     if args.shard_size < 1:
         raise SystemExit('--shard-size must be positive')
+    if args.panels < 0 or (args.panels and args.mode != 'test'):
+        raise SystemExit('--panels takes a non-negative count and goes with --mode test')
     return args
 
 
@@ -190,11 +195,12 @@ def seed_batch(module, seed, loader_idx, i):
 
 
 def run(cfg, device, out_dir, mode, loaders=None, limit_batches=None, shard_size=500, seed=1234, hook=None, dataset_root=None,
-        data=None, module=None, log=print):
+        data=None, module=None, log=print, panels=0):
     """Runs one mode and returns what it wrote: {'files': [...], 'batches': {loader: n}, 'metrics': {...}, 'confusion': {...} (test)}.
     hook(i, batch, output, output_imagine): called per batch with the device tensors (test mode: output_imagine is the list
     of imagined samples).  data: a set-up DataModule to take the test loaders from (default: one over dataset_root /
-    cfg.DATASET.DATAROOT); module: a WorldModelTrainer to use instead of building one from cfg."""
+    cfg.DATASET.DATAROOT); module: a WorldModelTrainer to use instead of building one from cfg.  panels (test): the picture grids
+    of the first `panels` batches of every loader go to PNG files below out_dir/panels (muvo_amd/visualise.py)."""
     refuse_multi_process()
     if mode not in ('test', 'sim'):
         raise ValueError(f'mode {mode!r}: test or sim')
@@ -213,8 +219,12 @@ def run(cfg, device, out_dir, mode, loaders=None, limit_batches=None, shard_size
     which = chosen_loaders(mode, None) if loaders is None else [int(v) for v in loaders]
     if mode == 'sim' and len(which) != 1:
         raise ValueError('mode sim runs over one loader')
-    fn = _run_test if mode == 'test' else _run_sim
-    return fn(cfg, module, {idx: test_loaders[idx] for idx in which}, out_dir, limit_batches, shard_size, seed, hook, log)
+    chosen = {idx: test_loaders[idx] for idx in which}
+    if mode == 'sim':
+        if panels:
+            raise ValueError('panels are written in mode test')
+        return _run_sim(cfg, module, chosen, out_dir, limit_batches, shard_size, seed, hook, log)
+    return _run_test(cfg, module, chosen, out_dir, limit_batches, shard_size, seed, hook, log, panels)
 
 
 def _batches(loader, limit):
@@ -224,16 +234,24 @@ def _batches(loader, limit):
         yield i, batch
 
 
-def _run_test(cfg, module, loaders, out_dir, limit_batches, shard_size, seed, hook, log):
+def _run_test(cfg, module, loaders, out_dir, limit_batches, shard_size, seed, hook, log, panels=0):
     counts = {}
-    for idx, loader in loaders.items():
-        counts[idx] = 0
-        for i, batch in _batches(loader, limit_batches):
-            seed_batch(module, seed, idx, i)
-            output, output_imagines = module.test_step(batch, i, idx)
-            if hook is not None:
-                hook(i, batch, output, output_imagines)
-            counts[idx] += 1
+    writer, was_writer = None, module.panel_writer
+    if panels:
+        from muvo_amd.visualise import PanelWriter
+        writer = PanelWriter(os.path.join(out_dir, 'panels'))
+    try:
+        for idx, loader in loaders.items():
+            counts[idx] = 0
+            for i, batch in _batches(loader, limit_batches):
+                seed_batch(module, seed, idx, i)
+                module.panel_writer = writer if i < panels else None
+                output, output_imagines = module.test_step(batch, i, idx)
+                if hook is not None:
+                    hook(i, batch, output, output_imagines)
+                counts[idx] += 1
+    finally:
+        module.panel_writer = was_writer
     logged, confusion = {}, {}
     was_fn, module.log_fn = module.log_fn, lambda name, value: logged.__setitem__(name, float(value))
     was_cm, module.on_confusion = module.on_confusion, lambda name, matrix: confusion.__setitem__(name, matrix.tolist())
@@ -251,7 +269,7 @@ def _run_test(cfg, module, loaders, out_dir, limit_batches, shard_size, seed, ho
     with open(path, 'w') as fh:
         json.dump(result, fh, indent=1, sort_keys=True)
         fh.write('\n')
-    return {'files': [path], 'batches': counts, 'metrics': logged, 'confusion': confusion}
+    return {'files': [path] + (writer.files if writer is not None else []), 'batches': counts, 'metrics': logged, 'confusion': confusion}
 
 
 def _run_sim(cfg, module, loaders, out_dir, limit_batches, shard_size, seed, hook, log):
@@ -307,7 +325,7 @@ def main(argv=None):
     torch.cuda.set_device(0)
     device = torch.device('cuda', 0)
     run(cfg, device, args.out, args.mode, loaders=chosen_loaders(args.mode, args.loader), limit_batches=args.limit_batches,
-        shard_size=args.shard_size, seed=args.seed, dataset_root=args.dataset_root or None)
+        shard_size=args.shard_size, seed=args.seed, dataset_root=args.dataset_root or None, panels=args.panels)
 
 
 if __name__ == '__main__':

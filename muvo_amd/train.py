@@ -52,15 +52,20 @@ def load_checkpoint(module, optimizer, scheduler, path):
     return int(ck['global_step'])
 
 
-def fit(cfg, device, steps=None, resume=None, log=None, seed=1234, batch_fn=None, setup=None, dataset_root=None, input_stream=False):
+def fit(cfg, device, steps=None, resume=None, log=None, seed=1234, batch_fn=None, setup=None, dataset_root=None, input_stream=False,
+        panel_dir=None):
     """The training loop; returns (module, list of per-step loss dicts as floats).  batch_fn(micro_index) / setup(module):
     hooks for tests (own batches, e.g. switching dropout off).  dataset_root (default: cfg.DATASET.DATAROOT): batches from the
-    recordings below it instead of synthetic ones; input_stream=True prepares them on a side stream instead of the main one."""
+    recordings below it instead of synthetic ones; input_stream=True prepares them on a side stream instead of the main one.
+    panel_dir: rank 0 writes the picture grids (muvo_amd/visualise.py) of every LOG_VIDEO_INTERVAL-th step there as PNG files."""
     import torch.distributed as dist
     rank = dist.get_rank() if dist.is_initialized() else 0
     torch.manual_seed(seed)
     module = WorldModelTrainer(cfg.convert_to_dict(), device=device)
     module.train()
+    if panel_dir and rank == 0:
+        from muvo_amd.visualise import PanelWriter
+        module.panel_writer = PanelWriter(panel_dir)
     if setup is not None:
         setup(module)
     opts, scheds = module.configure_optimizers()
@@ -111,11 +116,16 @@ def fit(cfg, device, steps=None, resume=None, log=None, seed=1234, batch_fn=None
     return module, history
 
 
-def main(argv=None):
+def build_parser():
     parser = get_parser()
     parser.add_argument('--resume', default='', help='Lightning-format checkpoint to continue from')
     parser.add_argument('--dataset-root', default='', help='directory of recorded runs (overrides DATASET.DATAROOT)')
-    args = parser.parse_args(argv)
+    parser.add_argument('--panel-dir', default='', metavar='DIR', help='write the picture grids of every LOG_VIDEO_INTERVAL-th step here (rank 0)')
+    return parser
+
+
+def main(argv=None):
+    args = build_parser().parse_args(argv)
     cfg = get_cfg(args)
     import torch.distributed as dist
     world = int(os.environ.get('WORLD_SIZE', '1'))
@@ -124,7 +134,7 @@ def main(argv=None):
     device = torch.device('cuda', local_rank)
     if world > 1:
         dist.init_process_group('nccl', device_id=device)
-    fit(cfg, device, resume=args.resume or None, dataset_root=args.dataset_root or None)
+    fit(cfg, device, resume=args.resume or None, dataset_root=args.dataset_root or None, panel_dir=args.panel_dir or None)
     if world > 1:
         dist.destroy_process_group()
 

@@ -5,8 +5,9 @@ Same constructor `(hparams, path_to_conf_file=None, pretrained_path=None)`, attr
 `configure_optimizers`, `load_pretrained_weights`) as trainer.py:26-231,251-402,511-513,1022-1073.  If
 `lightning` is importable the class derives from `pl.LightningModule`, otherwise from `torch.nn.Module` with
 the same hooks so the build's own loop (bench.py / train.py / predict.py) can drive it.  The evaluation half (`validation_step`,
-`test_step`, `log_metrics`, `on_validation_epoch_end`, `on_test_epoch_end`; trainer.py:404-567,1075-1095) is here without the
-visualisation (trainer.py:569-1020); the three torchmetrics IoU metrics are muvo_amd.metrics.JaccardIndex."""
+`test_step`, `log_metrics`, `on_validation_epoch_end`, `on_test_epoch_end`; trainer.py:404-567,1075-1095) is here too; the three
+torchmetrics IoU metrics are muvo_amd.metrics.JaccardIndex.  `visualise` (trainer.py:569-957) renders the picture
+grids on the device (muvo_amd/visualise.py) and hands them to `panel_writer`; while that is None - the default - nothing is drawn."""
 import os
 
 import numpy as np
@@ -122,6 +123,7 @@ class WorldModelTrainer(_Base):
         self.logged = {}
         self.on_confusion = None       # callable(name, (C, C) host int64 matrix): the IoU heads' counts, handed over by log_metrics
         self.accumulate_now = False    # plain loop: True while a non-final micro-batch of gradient accumulation runs
+        self.panel_writer = None       # object with add_images / add_video (muvo_amd.visualise.PanelWriter): None = no panels
         # evaluation metrics per validation / test dataloader (trainer.py:51-55,100-129,191-197); created on first use
         # because they hold device accumulators
         self.metrics_vals = [{}, {}, {}]
@@ -259,18 +261,22 @@ class WorldModelTrainer(_Base):
         return loss, output, loss_imagines, output_imagines
 
     def validation_step(self, batch, batch_idx=0, dataloader_idx=0, noise=None, use_prior=None, cd_index=None):
-        """trainer.py:404-424 (visualisation/logging hooks excepted)."""
+        """trainer.py:404-424; the logging / visualisation hook runs while `panel_writer` is set."""
         loss, output, loss_imagines, output_imagines = self._eval_step(
             batch, 'val', self.metrics_vals[dataloader_idx], self.metrics_vals_imagine[dataloader_idx], noise, use_prior, cd_index)
+        if self.panel_writer is not None:
+            self.logging_and_visualisation(batch, output, output_imagines, loss, loss_imagines, batch_idx, prefix=f'val{dataloader_idx}')
         out = {f'val{dataloader_idx}_loss': self.loss_reducing(loss),
                f'val{dataloader_idx}_loss_imagine': sum(self.loss_reducing(li) for li in loss_imagines) / len(loss_imagines)}
         return out, loss, output, loss_imagines, output_imagines
 
     def test_step(self, batch, batch_idx=0, dataloader_idx=0, noise=None, use_prior=None, cd_index=None):
-        """trainer.py:1079-1095 (the visualisation excepted): the evaluation step feeding `metrics_tests` /
-        `metrics_tests_imagine`; returns (output, output_imagines)."""
+        """trainer.py:1079-1095: the evaluation step feeding `metrics_tests` / `metrics_tests_imagine`; returns (output,
+        output_imagines).  While `panel_writer` is set every batch is drawn (prefix `pred{dataloader_idx}`)."""
         _, output, _, output_imagines = self._eval_step(
             batch, 'test', self.metrics_tests[dataloader_idx], self.metrics_tests_imagine[dataloader_idx], noise, use_prior, cd_index)
+        if self.panel_writer is not None:
+            self.visualise(batch, output, output_imagines, batch_idx, prefix=f'pred{dataloader_idx}')
         return output, output_imagines
 
     def log_metrics(self, metrics_list, metrics_type):
@@ -468,17 +474,45 @@ class WorldModelTrainer(_Base):
         return self.loss_reducing(losses)
 
     def logging_and_visualisation(self, batch, output, output_imagine, loss, loss_imagines, batch_idx, prefix='train'):
-        """The logging half of trainer.py:492-509 (`self.log(f'{prefix}_{key}', value)` per loss term, `-global_step`);
-        the TensorBoard visualisation half (`visualise`, trainer.py:569-1020: cv2 / open3d / matplotlib) is out of scope.
-        Under Lightning `self.log` is the LightningModule's; in a plain loop the values are handed to `self.log_fn(name,
-        value)` if one is set, else kept (still device tensors: no host sync) in `self.logged`."""
-        step = getattr(self, 'global_step', 0) if pl is not None else self._global_step
+        """trainer.py:492-509: `self.log(f'{prefix}_{key}', value)` per loss term and `-global_step`, then - while `panel_writer`
+        is set - `visualise` under the reference's criterion: in training on every step that is a multiple of
+        LOG_VIDEO_INTERVAL, once per step (`vis_step`); otherwise on batch 0.  Under Lightning `self.log` is the
+        LightningModule's; in a plain loop the values are handed to `self.log_fn(name, value)` if one is set, else kept (still
+        device tensors: no host sync) in `self.logged`."""
+        step = self._step_now()
         self.log('-global_step', torch.tensor(-float(step), dtype=torch.float32))
         for key, value in loss.items():
             self.log(f'{prefix}_{key}', value)
         if loss_imagines:
             for key, value in loss_imagines[0].items():
                 self.log(f'{prefix}_{key}_imagine', value)
+        if self.panel_writer is None:
+            return
+        if prefix == 'train':
+            wanted = (step % self.cfg.LOG_VIDEO_INTERVAL == 0) and (step != self.vis_step)
+            self.vis_step = step
+        else:
+            wanted = batch_idx == 0
+        if wanted:
+            self.visualise(batch, output, output_imagine, batch_idx, prefix=prefix)
+
+    def _step_now(self):
+        return getattr(self, 'global_step', 0) if pl is not None else self._global_step
+
+    def visualise(self, batch, output, output_imagines, batch_idx, prefix='train', writer=None):
+        """trainer.py:569-957: the picture grids of one batch (muvo_amd/visualise.py: which ones, and what is left out), rendered
+        on the device from the tensors as they are, to `writer` (default `self.panel_writer`) as `{prefix}_outputs[_{batch_idx}]{suffix}`."""
+        from muvo_amd.visualise import render_panels, write_panels
+        writer = writer if writer is not None else self.panel_writer
+        if writer is None:
+            raise RuntimeError('visualise: no writer (set `panel_writer`, e.g. muvo_amd.visualise.PanelWriter(directory))')
+        name = f'{prefix}_outputs'
+        if prefix != 'train':
+            name = name + f'_{batch_idx}'
+        with torch.no_grad():
+            panels = render_panels(self.cfg, batch, output, output_imagines)
+        write_panels(writer, name, panels, self._step_now())
+        return panels
 
     if pl is None:
         def log(self, name, value, *args, **kwargs):

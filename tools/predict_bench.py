@@ -24,7 +24,18 @@ prediction equal to the label in about nine tiles of ten:
              evaluation loop runs it), `synced` = a synchronise after every call.
   reference  the reference's route restated (trainer.py:428-433 + the metric's update): torch.argmax on the device, prediction
              and label to the host, bincount of label * C + prediction there - by the host clock.
-The counts of both routes are compared once before timing."""
+The counts of both routes are compared once before timing.
+
+--what panels: the picture grids (muvo_amd/visualise.py, csrc/visualise.hip) of one base_1d test batch, b = 2 with
+RECEPTIVE_FIELD + FUTURE_HORIZON frames and PREDICTION.N_SAMPLES imagined samples, random tensors at the real sizes (camera
+3 x 320 x 832, range view 4 x 64 x 1024, voxels 2 x 192 x 192 x 64, route map 3 x 64 x 64), per head and all together:
+    python tools/predict_bench.py --what panels [--rounds 5] [--iters 20] [--host-iters 1] [--out profiles/predict_panels.txt]
+  device     render_panels between HIP events, calls back to back (allocation of the panels included).
+  to host    render_panels and the copy of every panel to the host, by the host clock around a device synchronise.
+  host       the reference's route restated: .cpu() of every source tensor, then tests/visualise_reference.render_panels - by
+             the host clock; `copy` is the .cpu() calls alone.
+`read` is the bytes of every source tensor once, `written` the bytes of the panels once; their sum over the `device` time is
+quoted as a share of the HBM peak.  The panels of both routes are compared once before timing."""
 import argparse
 import os
 import statistics
@@ -168,6 +179,104 @@ def confusion_main(a):
     return lines
 
 
+PANEL_HEADS = (('rgb', ('_rgb',)), ('lidar', ('_lidar', '_pcd_xy')), ('voxel', ('_voxel_top',)), ('route', ('_input_route_map',)))
+
+
+def make_panel_batch(cfg, b, dev):
+    g = torch.Generator(device=dev).manual_seed(3)
+    rf, fh, n = cfg.RECEPTIVE_FIELD, cfg.FUTURE_HORIZON, cfg.PREDICTION.N_SAMPLES
+    s = rf + fh
+    rand = lambda *shape: torch.rand(shape, generator=g, device=dev)
+
+    def range_view(T):
+        return torch.cat([torch.randn((b, T, 3, 64, 1024), generator=g, device=dev) * 0.4, rand(b, T, 1, 64, 1024)], dim=2)
+
+    def heads(T):
+        return {'rgb_1': rand(b, T, 3, 320, 832), 'lidar_reconstruction_1': range_view(T),
+                'voxel_1': torch.cat([lg.unsqueeze(0) for lg in (make_logits(T, 2, dev) for _ in range(b))])}
+    batch = {'rgb_label_1': rand(b, s, 3, 320, 832), 'throttle_brake': rand(b, s, 1) * 2 - 1, 'steering': rand(b, s, 1) * 2 - 1,
+             'range_view_label_1': range_view(s), 'voxel_label_1': (rand(b, s, 1, *GRID) < 0.1).to(torch.uint8),
+             'route_map': rand(b, s, 3, 64, 64) * 3 - 1}
+    return batch, heads(rf), [heads(fh) for _ in range(n)]
+
+
+def panels_main(a):
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), '..', 'tests'))
+    import visualise_reference as VR
+    from muvo_amd.config import base_1d_cfg
+    from muvo_amd.visualise import render_panels
+    dev = torch.device('cuda')
+    base = base_1d_cfg()
+    b = 2
+    batch, output, imagines = make_panel_batch(base, b, dev)
+    keys = {'rgb': ('rgb_label_1', 'throttle_brake', 'steering', 'rgb_1'), 'lidar': ('range_view_label_1', 'lidar_reconstruction_1'),
+            'voxel': ('voxel_label_1', 'voxel_1'), 'route': ('route_map',)}
+    lines = [f'# prediction panels of one base_1d test batch: b {b}, {base.RECEPTIVE_FIELD} + {base.FUTURE_HORIZON} frames, '
+             f'{len(imagines)} imagined sample(s); {a.rounds} alternating windows; device / to host: {a.iters} calls per window, host: '
+             f'{a.host_iters}; median ms per call (min .. max); torch CPU threads: {torch.get_num_threads()}']
+    for name, suffixes in PANEL_HEADS + (('all', tuple(k for _, v in PANEL_HEADS for k in v)),):
+        on = [name] if name != 'all' else [h for h, _ in PANEL_HEADS]
+        cfg = VR.panel_cfg(**{h: True for h in on})
+        used = [k for h in on for k in keys[h]]
+        sub = lambda d: {k: v for k, v in d.items() if k in used}
+        bt, out, ims = sub(batch), sub(output), [sub(i) for i in imagines]
+        # `s` and `rf` are read from the first batch entry and the last output entry: any entry has the right length
+        bt.setdefault('route_map', batch['route_map'])
+        out.setdefault('rgb_1', output['rgb_1'])
+        got = render_panels(cfg, bt, out, ims)
+        assert tuple(got) == suffixes, (tuple(got), suffixes)
+
+        def host(timing=None):
+            t0 = time.perf_counter()
+            cpu = lambda d: {k: v.cpu() for k, v in d.items()}
+            hb, ho, hi = cpu(bt), cpu(out), [cpu(i) for i in ims]
+            t1 = time.perf_counter()
+            if timing is not None:
+                timing.append(t1 - t0)
+            return VR.render_panels(cfg, hb, ho, hi)
+        want = host()
+        for k in suffixes:
+            assert np.array_equal(got[k].cpu().numpy(), want[k]), f'the two routes disagree on {k}'
+
+        def device_panels(iters):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(iters):
+                render_panels(cfg, bt, out, ims)
+            e1.record()
+            torch.cuda.synchronize()
+            return e0.elapsed_time(e1) / iters
+
+        def to_host():
+            return {k: v.cpu() for k, v in render_panels(cfg, bt, out, ims).items()}
+        device_panels(3)
+        wall(to_host, 2)
+        d_t, k_t, h_t, c_t = [], [], [], []
+        for _ in range(a.rounds):
+            d_t.append(device_panels(a.iters))
+            k_t.append(wall(to_host, max(1, a.iters // 5)))
+            if a.host_iters:
+                per = []
+                h_t.append(wall(lambda: host(per), a.host_iters))
+                c_t.append(statistics.mean(per) * 1e3)
+        read = sum(v.numel() * v.element_size() for d in [bt, out] + ims for k, v in d.items() if k in used)
+        written = sum(v.numel() for v in got.values())
+        med = statistics.median(d_t)
+        first = len(lines)
+        lines += [f'{name}  panels {" ".join(f"{k} {tuple(got[k].shape)}" for k in suffixes)}',
+                  f'  read {read / 1e6:.1f} MB  written {written / 1e6:.2f} MB',
+                  f'  device            {fmt(d_t)}   {(read + written) / med / 1e6:.0f} GB/s, '
+                  f'{100 * (read + written) / med / 1e6 / HBM_PEAK_GBS:.1f} % of the {HBM_PEAK_GBS / 1e3:.0f} TB/s HBM peak',
+                  f'  to host           {fmt(k_t)}']
+        if h_t:
+            lines += [f'  host     total    {fmt(h_t)}',
+                      f'  host     copy     {fmt(c_t)}',
+                      f'  host total / to host = {statistics.median(h_t) / statistics.median(k_t):.0f}']
+        for line in lines[first:]:
+            print(line, flush=True)
+    return lines
+
+
 def write_out(path, lines):
     if path:
         os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
@@ -177,7 +286,7 @@ def write_out(path, lines):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument('--what', choices=('export', 'confusion'), default='export')
+    ap.add_argument('--what', choices=('export', 'confusion', 'panels'), default='export')
     ap.add_argument('--rounds', type=int, default=5)
     ap.add_argument('--iters', type=int, default=50)
     ap.add_argument('--host-iters', type=int, default=1)
@@ -187,6 +296,9 @@ def main():
     dev = torch.device('cuda')
     if a.what == 'confusion':
         write_out(a.out, confusion_main(a))
+        return
+    if a.what == 'panels':
+        write_out(a.out, panels_main(a))
         return
     lines = [f'# voxel export routes, {GRID[0]} x {GRID[1]} x {GRID[2]} voxels per frame; {a.rounds} alternating windows; kernels: '
              f'{a.iters} calls per window, host: {a.host_iters}; median ms per call (min .. max); torch CPU threads: {torch.get_num_threads()}']
