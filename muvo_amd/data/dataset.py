@@ -301,20 +301,25 @@ class BatchLoader:
             return collate_raw(raws, slot)
 
         with ThreadPoolExecutor(max_workers=self.n_threads) as pool:
+            queued = {}
+
             def submit(k):
                 # one task per frame file set, queued before the `stage` task that waits for them (so it cannot starve them)
                 reads = [[pool.submit(ds.read_frame, ds.data_pointers[i][0], t) for t in ds.data_pointers[i][1]] for i in batches[k]]
+                queued[k] = reads
                 return pool.submit(stage, reads, slots[k % self.SLOTS])
 
             staged = {k: submit(k) for k in range(min(2, len(batches)))}
             try:
                 ready = self._upload_slot(staged.pop(0).result(), slots[0])
+                queued.pop(0)
                 for k in range(len(batches)):
                     cur, ev = ready
                     if k + 2 < len(batches):
                         staged[k + 2] = submit(k + 2)
                     if k + 1 < len(batches):      # queued before step k is: copy and preparation overlap it
                         ready = self._upload_slot(staged.pop(k + 1).result(), slots[(k + 1) % self.SLOTS])
+                        queued.pop(k + 1)
                     if self._stream is not None:
                         main = torch.cuda.current_stream(self.device)
                         main.wait_event(ev)
@@ -322,8 +327,14 @@ class BatchLoader:
                             v.record_stream(main)
                     yield cur
             finally:
+                # a consumer that stops early (validation takes the first batches of a loader): what is still queued is dropped -
+                # the staging tasks and the file reads behind them - so the pool's threads end with the reads that are running
                 for f in staged.values():
                     f.cancel()
+                for reads in queued.values():
+                    for seq in reads:
+                        for r in seq:
+                            r.cancel()
 
     def _upload_slot(self, host, slot):
         batch, ev = self.upload(host)

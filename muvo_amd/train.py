@@ -53,11 +53,21 @@ def load_checkpoint(module, optimizer, scheduler, path):
 
 
 def fit(cfg, device, steps=None, resume=None, log=None, seed=1234, batch_fn=None, setup=None, dataset_root=None, input_stream=False,
-        panel_dir=None):
+        panel_dir=None, validate=False, limit_val_batches=3, sanity_val_steps=2, val_batch_fn=None, metrics_log=None):
     """The training loop; returns (module, list of per-step loss dicts as floats).  batch_fn(micro_index) / setup(module):
     hooks for tests (own batches, e.g. switching dropout off).  dataset_root (default: cfg.DATASET.DATAROOT): batches from the
     recordings below it instead of synthetic ones; input_stream=True prepares them on a side stream instead of the main one.
-    panel_dir: rank 0 writes the picture grids (muvo_amd/visualise.py) of every LOG_VIDEO_INTERVAL-th step there as PNG files."""
+    panel_dir: rank 0 writes the picture grids (muvo_amd/visualise.py) of every LOG_VIDEO_INTERVAL-th step there as PNG files.
+
+    validate=True (train.py:104-110 under Lightning): before the first step a sanity pass of `sanity_val_steps` batches per
+    validation loader whose results are dropped (not in a resumed run); after every optimizer step that is a multiple of
+    VAL_CHECK_INTERVAL - and after that step's checkpoint is written, Lightning's order - one pass of
+    `muvo_amd.validate.run_validation` over the first `limit_val_batches` batches of every loader.  The loaders: `val_batch_fn(idx)`
+    -> iterable, asked again at every pass (idx 0, 1, 2; None or nothing to iterate: no such loader); else the three of
+    `DataModule.val_dataloader()` below dataset_root; else one loader of synthetic batches whose seeds no training batch has.
+    Every rank runs the same batches; rank 0 logs `validation {json}`.  The records are `module.val_history`.
+    metrics_log: rank 0 appends one JSON object per line to this file, {"step", "split": "train", ...} for every training
+    record and {"step", "split": "val", ...} for every pass."""
     import torch.distributed as dist
     rank = dist.get_rank() if dist.is_initialized() else 0
     torch.manual_seed(seed)
@@ -79,12 +89,31 @@ def fit(cfg, device, steps=None, resume=None, log=None, seed=1234, batch_fn=None
     world = dist.get_world_size() if dist.is_initialized() else 1
     history, micro = [], global_step * accum
     dataset_root = dataset_root or cfg.DATASET.DATAROOT
+    data = None
     if dataset_root and batch_fn is None:
         from muvo_amd.data.dataset import DataModule
         data = DataModule(cfg, dataset_root, device=device, rank=rank, world_size=world, seed=seed, input_stream=input_stream)
         data.setup()
         recorded = data.train_batches(start=micro)        # a resumed run continues the order of the interrupted one
         batch_fn = lambda _micro: next(recorded)          # noqa: E731
+    module.val_history = []
+    metrics_file = None
+    if metrics_log and rank == 0:
+        from muvo_amd.validate import JsonLines
+        metrics_file = JsonLines(metrics_log)
+    if validate:
+        from muvo_amd import validate as V
+        say = (log or print) if rank == 0 else (lambda line: None)
+        if val_batch_fn is not None:
+            val_loaders = lambda: [val_batch_fn(idx) for idx in range(3)]         # noqa: E731
+        elif data is not None:
+            recorded_val = data.val_dataloader()          # made once: every pass iterates them from their start, in the same slots
+            val_loaders = lambda: recorded_val            # noqa: E731
+        else:
+            val_loaders = lambda: [V.SyntheticLoader(cfg, max(limit_val_batches, sanity_val_steps), seed, device)]   # noqa: E731
+        if not resume and sanity_val_steps > 0:
+            sanity = V.run_validation(module, val_loaders(), limit_batches=sanity_val_steps, seed=seed, panels=False)
+            say(f'sanity validation: {json.dumps(V.jsonable(sanity)["batches"])}')
     t0 = time.time()
     while global_step < steps:
         # every optimizer step starts from its own seed: a resumed run draws the same RSSM noise / augmentation as the
@@ -110,9 +139,23 @@ def fit(cfg, device, steps=None, resume=None, log=None, seed=1234, batch_fn=None
                 total = sum(v for k, v in rec.items() if k.startswith('train_'))
                 line = json.dumps({'step': global_step, 'loss': total, 'lr': rec['lr'], 's_per_step': (time.time() - t0) / len(history)})
                 (log or print)(line)
+                if metrics_file is not None:
+                    metrics_file.write(global_step, 'train', rec)
         if cfg.VAL_CHECK_INTERVAL and global_step % cfg.VAL_CHECK_INTERVAL == 0 and rank == 0:
             name = save_checkpoint(module, optimizer, scheduler, global_step, cfg.LOG_DIR)
             (log or print)(f'checkpoint {name}')
+        if validate and V.validates_at(global_step, cfg.VAL_CHECK_INTERVAL):
+            # after the checkpoint (Lightning: ModelCheckpoint.on_train_batch_end, then the validation loop): the file of step k
+            # holds what this pass runs on, but for the BatchNorm running buffers, which validation moves (trainer.py:405)
+            tv = time.time()
+            result = V.run_validation(module, val_loaders(), limit_batches=limit_val_batches, seed=seed)
+            record = {'step': global_step, **result}          # (the pass ends with the read of its sums: the device is idle)
+            module.val_history.append(record)
+            line = {**V.jsonable(record), 's_per_pass': time.time() - tv}
+            say('validation ' + json.dumps(line))
+            if metrics_file is not None:
+                metrics_file.write(global_step, 'val', line)
+            t0 += time.time() - tv                # s_per_step of the training lines stays the training loop's
     return module, history
 
 
@@ -121,6 +164,11 @@ def build_parser():
     parser.add_argument('--resume', default='', help='Lightning-format checkpoint to continue from')
     parser.add_argument('--dataset-root', default='', help='directory of recorded runs (overrides DATASET.DATAROOT)')
     parser.add_argument('--panel-dir', default='', metavar='DIR', help='write the picture grids of every LOG_VIDEO_INTERVAL-th step here (rank 0)')
+    parser.add_argument('--validate', action='store_true',
+                        help='validate every VAL_CHECK_INTERVAL steps (after that step\'s checkpoint), with a sanity pass before the first step')
+    parser.add_argument('--limit-val-batches', type=int, default=3, metavar='N', help='batches per validation loader and pass (default 3)')
+    parser.add_argument('--sanity-val-steps', type=int, default=2, metavar='N', help='batches per loader of the sanity pass (default 2; 0: none)')
+    parser.add_argument('--metrics-log', default='', metavar='FILE', help='append the training and validation records here, one JSON object per line (rank 0)')
     return parser
 
 
@@ -134,7 +182,9 @@ def main(argv=None):
     device = torch.device('cuda', local_rank)
     if world > 1:
         dist.init_process_group('nccl', device_id=device)
-    fit(cfg, device, resume=args.resume or None, dataset_root=args.dataset_root or None, panel_dir=args.panel_dir or None)
+    fit(cfg, device, resume=args.resume or None, dataset_root=args.dataset_root or None, panel_dir=args.panel_dir or None,
+        validate=args.validate, limit_val_batches=args.limit_val_batches, sanity_val_steps=args.sanity_val_steps,
+        metrics_log=args.metrics_log or None)
     if world > 1:
         dist.destroy_process_group()
 
