@@ -417,6 +417,23 @@ int muvo_kl_loss_bwd(const float* prior_mu, const float* prior_sigma, const floa
 int muvo_adamw_step(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2, float eps,
                     float weight_decay, int step, float grad_scale, void* stream);
 
+/* ---- Chamfer-distance training loss (chamfer.hip): CDLoss, muvo/losses.py:352-367 with reducer = mean -----------------------
+ * pred (F,Cp,n), target (F,Ct,n) channel-planar fp32; x, y, z are planes 0, 1, 2 and further planes are never read.
+ * loss[0] = weight * mean_f ( mean_j min_i |p_i - t_j| + mean_i min_j |p_i - t_j| ).  The nearest neighbour is chosen by the
+ * fp32 squared distance of the coordinate differences, the lowest index wins a tie, the square root is taken for the winner.
+ * ws: muvo_chamfer_loss_ws_doubles(F, n) doubles of scratch (written, then read; no need to clear).  idx_pt / idx_tp: (F,n)
+ * int32 each - idx_pt[f,i] = the target nearest to prediction point i, idx_tp[f,j] = the prediction point nearest to target
+ * j - or both NULL when no backward follows (the loss value is bit-identical either way).
+ * Backward: dpred (F,Cp,n) is written completely, planes >= 3 with zeros; d|a - b| = (a - b)/|a - b| and exactly 0 where the
+ * two points coincide; gout = the upstream gradient of the scalar, on the device.  The mean_j min_i term is a scatter into the
+ * selected prediction points (fp32 atomics, equal destinations of a wave combined first); in deterministic mode every
+ * prediction point sums its senders in index order instead and the result is bit-reproducible.  F <= 65535, n <= 2^30. */
+int64_t muvo_chamfer_loss_ws_doubles(int64_t F, int64_t n);
+int muvo_chamfer_loss_fwd(const float* pred, const float* target, int64_t F, int Cp, int Ct, int64_t n, float weight, double* ws,
+                          int32_t* idx_pt, int32_t* idx_tp, float* loss, void* stream);
+int muvo_chamfer_loss_bwd(const float* pred, const float* target, const int32_t* idx_pt, const int32_t* idx_tp, float* dpred, int64_t F,
+                          int Cp, int Ct, int64_t n, float weight, const float* gout, void* stream);
+
 /* ---- evaluation metrics of the validation path (muvo/metrics.py via muvo/trainer.py:426-490) ----------------------------
  * All accumulators are caller-zeroed device buffers the kernels ADD into (several batches may share them).
  * muvo_ssim_frames: sums[n] += sum over (c, y, x) of the SSIM map of frame n (valid 11x11 Gaussian window given as 121

@@ -15,7 +15,13 @@ TOLERATED_EXTRA_KEYS = ('CML_DATASET_VERSION', 'MODEL.TRANSFORMER_TRANSITION', '
 #   MODEL.CONSTANT_SIZE.{RGB,LIDAR,VOXEL} - the seed sizes the reference hard-codes as (5, 13), (1, 16) and (3, 3, 1)
 #   (muvo/models/mile.py:322-336,391-396): every decoder output is 64x its seed, so (1, 32) gives the 64 x 2048 range view and
 #   (4, 4, 1) the 256 x 256 x 64 voxel grid BASELINE.json names.  Parity for non-default values: own oracle only ("unpinned").
-EXTENSION_KEYS = ('MODEL.CONSTANT_SIZE', 'MODEL.CONSTANT_SIZE.RGB', 'MODEL.CONSTANT_SIZE.LIDAR', 'MODEL.CONSTANT_SIZE.VOXEL')
+#   LOSSES.LIDAR_CD.{WEIGHT,FACTORS} - the Chamfer-distance loss of the lidar reconstruction head, which the reference defines
+#   (CDLoss, muvo/losses.py:352-367) but only constructs in a comment (muvo/trainer.py:116).  WEIGHT (float; absent = 0 = off)
+#   multiplies, FACTORS (a list drawn from 1, 2, 4; absent = [2, 4]) names the output scales that get a term
+#   `lidar_cd_{f}` = WEIGHT / f x CD(lidar_reconstruction_f[:, :, :3], range_view_label_f[:, :, :3]).  The search is brute force:
+#   factor 1 (65,536 points a frame) is left out of the default list for its cost.  Needs LIDAR_RE.ENABLED.
+EXTENSION_KEYS = ('MODEL.CONSTANT_SIZE', 'MODEL.CONSTANT_SIZE.RGB', 'MODEL.CONSTANT_SIZE.LIDAR', 'MODEL.CONSTANT_SIZE.VOXEL',
+                  'LOSSES.LIDAR_CD', 'LOSSES.LIDAR_CD.WEIGHT', 'LOSSES.LIDAR_CD.FACTORS')
 DEFAULT_CONSTANT_SIZE = {'RGB': (5, 13), 'LIDAR': (1, 16), 'VOXEL': (3, 3, 1)}
 
 
@@ -29,6 +35,24 @@ def constant_sizes(cfg):
             raise ValueError(f'MODEL.CONSTANT_SIZE.{k} must be {len(DEFAULT_CONSTANT_SIZE[k])} positive integers, got {v}')
         out.append(v)
     return tuple(out)
+
+
+DEFAULT_LIDAR_CD_FACTORS = (2, 4)
+
+
+def lidar_cd(cfg):
+    """(weight, factors) of the Chamfer-distance loss: LOSSES.LIDAR_CD.* if given, else (0.0, (2, 4)); weight 0 = no such term."""
+    node = cfg.LOSSES.get('LIDAR_CD', None) or {}
+    weight = node.get('WEIGHT', 0.0)
+    if isinstance(weight, bool) or not isinstance(weight, (int, float)) or not weight >= 0:
+        raise ValueError(f'LOSSES.LIDAR_CD.WEIGHT must be a number >= 0, got {weight!r}')
+    factors = node.get('FACTORS', DEFAULT_LIDAR_CD_FACTORS)
+    if not isinstance(factors, (list, tuple)) or any(isinstance(f, bool) or f not in (1, 2, 4) for f in factors) \
+            or len(set(factors)) != len(factors):
+        raise ValueError(f'LOSSES.LIDAR_CD.FACTORS must be a list of distinct factors drawn from 1, 2, 4, got {factors!r}')
+    if weight > 0 and not cfg.LIDAR_RE.ENABLED:
+        raise ValueError('LOSSES.LIDAR_CD.WEIGHT > 0 needs LIDAR_RE.ENABLED: the loss is on the lidar reconstruction head')
+    return float(weight), tuple(int(f) for f in factors)
 
 
 class CfgNode(dict):

@@ -96,6 +96,24 @@ class GeoScalLoss(_VoxelTriple):
     index = 2
 
 
+class CDLoss(nn.Module):
+    """muvo/losses.py:352-367: Chamfer distance between point clouds (b, s, n, 3), mean over the points of both directions and
+    over the frames.  The kernels read channel-planar points, so this drop-in form makes that view (one transposed copy);
+    `WorldModelTrainer.compute_loss` hands the head's planar tensors to ops.chamfer_loss directly."""
+
+    def __init__(self, reducer=torch.mean):
+        super().__init__()
+        if reducer is not torch.mean:
+            raise NotImplementedError('the kernels implement reducer = torch.mean (the reference default, losses.py:353)')
+        self.reducer = reducer
+
+    def forward(self, prediction, target):
+        b, s, n, d = prediction.shape
+        if d != 3 or target.shape != prediction.shape:
+            raise ValueError(f'Expected (b, s, n, 3) point clouds of equal shape, got {tuple(prediction.shape)} and {tuple(target.shape)}')
+        p = prediction.float().permute(0, 1, 3, 2).reshape(b, s, 3, 1, n)
+        t = target.float().permute(0, 1, 3, 2).reshape(b, s, 3, 1, n)
+        return ops.chamfer_loss(p, t, 1.0)[0]
 
 
 class SegmentationLoss(nn.Module):

@@ -62,7 +62,7 @@ EXPORTS = [
     'muvo_rssm_sample_fwd', 'muvo_rssm_sample_bwd',
     'muvo_spatial_loss_fwd', 'muvo_spatial_loss_bwd', 'muvo_spatial_loss_masked_fwd', 'muvo_spatial_loss_masked_bwd', 'muvo_voxel_loss_stats_doubles', 'muvo_voxel_loss_coef_floats',
     'muvo_voxel_loss_fwd', 'muvo_voxel_loss_bwd', 'muvo_l1_rows_fwd', 'muvo_l1_rows_bwd', 'muvo_kl_loss_fwd',
-    'muvo_kl_loss_bwd', 'muvo_adamw_step',
+    'muvo_kl_loss_bwd', 'muvo_adamw_step', 'muvo_chamfer_loss_ws_doubles', 'muvo_chamfer_loss_fwd', 'muvo_chamfer_loss_bwd',
     'muvo_ssim_frames', 'muvo_sqdiff_frames', 'muvo_chamfer_sums', 'muvo_ssc_counts', 'muvo_seg_confusion', 'muvo_seg_confusion_index',
     'muvo_frustum_cells', 'muvo_frustum_pool_fwd', 'muvo_frustum_pool_bwd', 'muvo_depth_expectation',
     'muvo_resize_bilinear_bwd', 'muvo_softmax_channel_fwd', 'muvo_softmax_channel_bwd',
@@ -106,6 +106,7 @@ def lib():
                 L.muvo_rssm_scratch_floats.restype = C.c_int64
                 L.muvo_voxelize_scratch_bytes.restype = C.c_int64
                 L.muvo_voxel_rows_scratch_bytes.restype = C.c_int64
+                L.muvo_chamfer_loss_ws_doubles.restype = C.c_int64
                 for name in EXPORTS:
                     getattr(L, name)  # AttributeError if a declared symbol is missing
                 _lib = L
@@ -2735,6 +2736,59 @@ class KLLossFn(torch.autograd.Function):
 
 def kl_loss(pm, ps, qm, qs, weight, alpha, terms=False):
     return KLLossFn.apply(pm, ps, qm, qs, weight, alpha, terms)
+
+
+def _chamfer_forward(pred, target, weight, with_indices):
+    pred, target = pred.contiguous(), target.contiguous()
+    b, s, cp, h, w = pred.shape
+    ct = target.shape[2]
+    assert target.shape[:2] == (b, s) and target.shape[3:] == (h, w), 'prediction and target must hold the same number of points'
+    f, n = b * s, h * w
+    L = lib()
+    ws = torch.empty(max(1, L.muvo_chamfer_loss_ws_doubles(_i64(f), _i64(n))), device=pred.device, dtype=torch.float64)
+    idx = torch.empty(2, f, n, device=pred.device, dtype=torch.int32) if with_indices else None
+    loss = torch.empty(1, device=pred.device, dtype=torch.float32)
+    _ck(L.muvo_chamfer_loss_fwd(_f(pred), _f(target), _i64(f), cp, ct, _i64(n), _fl(weight), _p(ws),
+                                _p(idx[0]) if with_indices else _p(None), _p(idx[1]) if with_indices else _p(None), _f(loss), _st()))
+    return pred, target, loss, idx, (f, cp, ct, n)
+
+
+class ChamferLossFn(torch.autograd.Function):
+    """weight * CDLoss (muvo/losses.py:352-367, reducer = mean) between the points of two (B,S,C,H,W) tensors: x, y, z are
+    channels 0..2, further channels are never read (C may differ between the two).  The gradient goes to the prediction only;
+    its channels >= 3 are exactly zero.  The nearest-neighbour indices are kept only when a backward can follow: under
+    torch.no_grad() the search writes none, and the value is bit-identical."""
+
+    @staticmethod
+    def forward(ctx, pred, target, weight, terms=False, grad_enabled=True):
+        # grad_enabled: the caller's grad mode (inside forward it is always off, and needs_input_grad stays True under no_grad)
+        need = ctx.needs_input_grad[0] and grad_enabled
+        pred, target, loss, idx, (f, cp, ct, n) = _chamfer_forward(pred, target, weight, need)
+        ctx.dims, ctx.weight = (f, cp, ct, n), weight
+        if need:
+            ctx.save_for_backward(pred, target, idx)
+        return _as_terms(ctx, loss, terms)
+
+    @staticmethod
+    def backward(ctx, g):
+        pred, target, idx = ctx.saved_tensors
+        f, cp, ct, n = ctx.dims
+        g = torch.zeros(1, device=pred.device) if g is None else g.reshape(1)
+        dpred = torch.empty_like(pred)
+        _ck(lib().muvo_chamfer_loss_bwd(_f(pred), _f(target), _p(idx[0]), _p(idx[1]), _f(dpred), _i64(f), cp, ct, _i64(n),
+                                        _fl(ctx.weight), _f(g.contiguous()), _st()))
+        return dpred, None, None, None, None
+
+
+def chamfer_loss(pred, target, weight, terms=False):
+    """terms=True: a 1-tuple holding the 0-d loss instead of the (1,) tensor (as the other loss entry points)"""
+    return ChamferLossFn.apply(pred, target, weight, terms, torch.is_grad_enabled())
+
+
+def chamfer_nearest(pred, target):
+    """The selections the loss differentiates, (2, B*S, n) int32: [0][f, i] = the target point nearest to prediction point i,
+    [1][f, j] = the prediction point nearest to target point j (lowest index on a tie)."""
+    return _chamfer_forward(pred.detach(), target.detach(), 1.0, True)[3]
 
 
 # ================================================================================================ optimiser

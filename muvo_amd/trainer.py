@@ -14,7 +14,7 @@ import numpy as np
 import torch
 
 from muvo_amd import ops
-from muvo_amd.config import get_cfg
+from muvo_amd.config import get_cfg, lidar_cd
 from muvo_amd.models.mile import Mile
 from muvo_amd.models.preprocess import PreProcess
 from muvo_amd.optim import FusedAdamW
@@ -436,6 +436,13 @@ class WorldModelTrainer(_Base):
                     losses[f'voxel_{f}'] = three[0]
                 losses[f'sem_scal_{f}'] = three[1]
                 losses[f'geo_scal_{f}'] = three[2]
+        # the Chamfer distance of the lidar head (CDLoss, losses.py:352-367; the reference constructs it only in a comment,
+        # trainer.py:116): after the reference's terms, so that their order - and the order of the total's sum - stays as it is
+        w_cd, cd_factors = lidar_cd(cfg)
+        if w_cd > 0:                              # extension (config.py: LOSSES.LIDAR_CD), absent = off: no term, no launch
+            for f in cd_factors:                  # x, y, z = channels 0..2 of both tensors, in the scaled units of lidar_re_*
+                losses[f'lidar_cd_{f}'] = ops.chamfer_loss(output[f'lidar_reconstruction_{f}'], batch[f'range_view_label_{f}'],
+                                                           w_cd * (1 / f), terms=True)[0]
         return losses
 
     def _seg_loss(self, tag, c, is_bev=False):
