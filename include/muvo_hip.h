@@ -681,6 +681,45 @@ int muvo_panel_voxel_top_logits(const float* logits, int F, int C, int X, int Y,
 int muvo_panel_voxel_top_grid(const uint8_t* grid, int F, int X, int Y, int Z, const uint8_t* palette, int pad, int padbyte, uint8_t* panel,
                               int64_t panel_bytes, const MuvoTilePlace* place, void* stream);
 
+/* ---- point-to-point ICP between lidar frames (icp.hip): the registration behind the reference's `_traj` panel -----------------
+ * (compute_pcd_transformation, geometry_utils.py:248-267: open3d registration_icp, point-to-point, identity start).
+ * src (Fs,Cs,n), tgt (Ft,Ct,n) channel-planar fp32 (the same tensor twice is fine); planes 0..2 = x, y, z, plane 3 = range; a
+ * point is valid iff range > 0 (NaN: invalid) and the coordinates of invalid points never reach a result.  Coordinates are
+ * multiplied by `scale` in fp32 on load.  Work list: P pairs, pair p registers frame src_frames[p] of src (the moving cloud)
+ * onto frame tgt_frames[p] of tgt; both lists are device int32.
+ * state: P x muvo_icp_state_doubles() doubles per pair - [0..11] T (3x4 row-major, target ~ T [source; 1]), [12] fitness =
+ *   inliers / valid queries, [13] inlier_rmse, [14] [15] the same of the previous evaluation, [16] inliers, [17] iterations
+ *   (= rigid fits applied), [18] status (MUVO_ICP_*), [19] evaluations, [20] valid queries, [21] valid target points.
+ * done: P int32, non-zero once the pair has stopped; its state is never written again and its workgroups return at once.
+ * muvo_icp_init: T = init (P x 12 doubles) or the identity (init NULL); a pair without a valid query or without a valid target
+ *   point stops at once with the identity (MUVO_ICP_EMPTY; a frame index outside its tensor: MUVO_ICP_BAD_FRAME).  Queries are
+ *   the source points 0, stride, 2 stride, ...
+ * muvo_icp_iterate: `count` times { correspond; update }.  correspond: every valid query, moved by T (fp64, rounded to fp32),
+ *   takes the valid target point with the smallest fp32 squared distance of the coordinate differences (lowest index on a tie)
+ *   and is an inlier iff d^2 <= threshold^2 (fp32); per workgroup 17 fp64 sums over the inliers go to ws
+ *   (muvo_icp_ws_doubles(P, n, stride) doubles, written then read) with plain stores.  update: sums them in block order, sets
+ *   fitness / rmse, then stops the pair - fewer than 3 inliers (MUVO_ICP_FEW_INLIERS), not the first evaluation and
+ *   |d fitness| < 1e-6 and |d rmse| < 1e-6 (MUVO_ICP_CONVERGED), iterations == max_iteration (MUVO_ICP_MAX_ITERATION) - with T
+ *   unchanged, or sets T <- U T with U the least-squares rigid motion of the inlier pairs (Horn's quaternion form in fp64: a
+ *   proper rotation always).  No atomics anywhere: results do not depend on scheduling.
+ *   corr (P,n) int32 or NULL: the target index of every query of the LAST correspond that ran for the pair, -1 = invalid or
+ *   gated out (entries of non-query points are left alone); sums (P,17) or NULL: count, sum d^2, sum s (3), sum q (3),
+ *   sum s q^T (9, row = component of s) of that evaluation, s = the moved query, q = its target point.
+ * n <= 2^24, P <= 65535. */
+#define MUVO_ICP_RUNNING 0
+#define MUVO_ICP_CONVERGED 1
+#define MUVO_ICP_MAX_ITERATION 2
+#define MUVO_ICP_FEW_INLIERS 3
+#define MUVO_ICP_EMPTY 4
+#define MUVO_ICP_BAD_FRAME 5
+int64_t muvo_icp_state_doubles(void);
+int64_t muvo_icp_ws_doubles(int64_t P, int64_t n, int64_t stride);
+int muvo_icp_init(const float* src, const float* tgt, int64_t Fs, int64_t Ft, int Cs, int Ct, int64_t n, const int32_t* src_frames,
+                  const int32_t* tgt_frames, int64_t P, int64_t stride, const double* init, double* state, int32_t* done, void* stream);
+int muvo_icp_iterate(const float* src, const float* tgt, int Cs, int Ct, int64_t n, const int32_t* src_frames, const int32_t* tgt_frames,
+                     int64_t P, float scale, float threshold, int64_t stride, int max_iteration, int count, double* ws, double* state,
+                     int32_t* done, int32_t* corr, double* sums, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

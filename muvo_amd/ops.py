@@ -84,6 +84,7 @@ EXPORTS = [
     'muvo_voxel_rows_scratch_bytes', 'muvo_voxel_rows_logits', 'muvo_voxel_rows_grid', 'muvo_voxel_rows_write', 'muvo_image_u8',
     'muvo_panel_image', 'muvo_panel_logits', 'muvo_panel_labels', 'muvo_panel_fill', 'muvo_panel_bars', 'muvo_panel_scatter',
     'muvo_panel_voxel_top_logits', 'muvo_panel_voxel_top_grid',
+    'muvo_icp_state_doubles', 'muvo_icp_ws_doubles', 'muvo_icp_init', 'muvo_icp_iterate',
 ]
 
 
@@ -107,6 +108,8 @@ def lib():
                 L.muvo_voxelize_scratch_bytes.restype = C.c_int64
                 L.muvo_voxel_rows_scratch_bytes.restype = C.c_int64
                 L.muvo_chamfer_loss_ws_doubles.restype = C.c_int64
+                L.muvo_icp_state_doubles.restype = C.c_int64
+                L.muvo_icp_ws_doubles.restype = C.c_int64
                 for name in EXPORTS:
                     getattr(L, name)  # AttributeError if a declared symbol is missing
                 _lib = L
@@ -2789,6 +2792,102 @@ def chamfer_nearest(pred, target):
     """The selections the loss differentiates, (2, B*S, n) int32: [0][f, i] = the target point nearest to prediction point i,
     [1][f, j] = the prediction point nearest to target point j (lowest index on a tie)."""
     return _chamfer_forward(pred.detach(), target.detach(), 1.0, True)[3]
+
+
+# ================================================================================================ ICP between lidar frames
+ICP_RUNNING, ICP_CONVERGED, ICP_MAX_ITERATION, ICP_FEW_INLIERS, ICP_EMPTY, ICP_BAD_FRAME = 0, 1, 2, 3, 4, 5
+ICP_CHUNK = 8                      # iterations queued between two looks at the `done` words
+IcpResult = collections.namedtuple('IcpResult', 'T fitness inlier_rmse iterations converged status')
+
+
+def _icp_setup(src, tgt, src_frames, tgt_frames, scale, threshold, init, source_stride):
+    assert src.dim() == 3 and tgt.dim() == 3 and src.shape[2] == tgt.shape[2], 'icp: planar (F, C, n) tensors of one n'
+    assert src.shape[1] >= 4 and tgt.shape[1] >= 4, 'icp: x, y, z, range are planes 0..3'
+    assert src.device == tgt.device
+    if src.dtype != torch.float32 or tgt.dtype != torch.float32:
+        raise ValueError(f'icp: float32 tensors, got {src.dtype} and {tgt.dtype}')
+    if int(source_stride) < 1 or int(source_stride) > src.shape[2]:
+        raise ValueError(f'icp: source_stride {source_stride} outside [1, n]')
+    if not (float(scale) > 0 and float(threshold) > 0):
+        raise ValueError(f'icp: scale {scale} and threshold {threshold} must be positive')
+    dev, n = src.device, src.shape[2]
+    sf = [int(v) for v in (src_frames.tolist() if torch.is_tensor(src_frames) else src_frames)]
+    tf = [int(v) for v in (tgt_frames.tolist() if torch.is_tensor(tgt_frames) else tgt_frames)]
+    if len(sf) != len(tf) or not sf:
+        raise ValueError('icp: src_frames and tgt_frames must be two non-empty lists of one length')
+    if min(sf) < 0 or max(sf) >= src.shape[0] or min(tf) < 0 or max(tf) >= tgt.shape[0]:
+        raise ValueError('icp: a frame index outside its tensor')
+    P, L = len(sf), lib()
+    frames = torch.tensor([sf, tf], dtype=torch.int32).to(dev)
+    state = torch.empty(P, int(L.muvo_icp_state_doubles()), device=dev, dtype=torch.float64)
+    done = torch.empty(P, device=dev, dtype=torch.int32)
+    ws = torch.empty(max(1, L.muvo_icp_ws_doubles(_i64(P), _i64(n), _i64(source_stride))), device=dev, dtype=torch.float64)
+    if init is not None:
+        init = torch.as_tensor(init, dtype=torch.float64).reshape(P, 4, 4)[:, :3].contiguous().to(dev)
+    _ck(L.muvo_icp_init(_f(src), _f(tgt), _i64(src.shape[0]), _i64(tgt.shape[0]), int(src.shape[1]), int(tgt.shape[1]), _i64(n),
+                        _p(frames[0]), _p(frames[1]), _i64(P), _i64(source_stride), _p(init), _p(state), _p(done), _st()))
+    return frames, state, done, ws, P, n
+
+
+def _icp_iterate(src, tgt, frames, P, n, scale, threshold, stride, max_iteration, count, ws, state, done, corr=None, sums=None):
+    _ck(lib().muvo_icp_iterate(_f(src), _f(tgt), int(src.shape[1]), int(tgt.shape[1]), _i64(n), _p(frames[0]), _p(frames[1]), _i64(P),
+                               _fl(scale), _fl(threshold), _i64(stride), int(max_iteration), int(count), _p(ws), _p(state), _p(done),
+                               _p(corr), _p(sums), _st()))
+
+
+def _icp_result(state):
+    T = torch.zeros(state.shape[0], 4, 4, dtype=torch.float64, device=state.device)
+    T[:, :3] = state[:, :12].view(-1, 3, 4)
+    T[:, 3, 3] = 1.0
+    status = state[:, 18].long()
+    return IcpResult(T, state[:, 12].clone(), state[:, 13].clone(), state[:, 17].long(), status == ICP_CONVERGED, status)
+
+
+def icp_register(src, tgt, src_frames, tgt_frames, scale, threshold, max_iteration=2000, init=None, source_stride=1):
+    """Point-to-point ICP (include/muvo_hip.h: muvo_icp_*) of P frame pairs: pair p moves frame src_frames[p] of src (F, C, n)
+    onto frame tgt_frames[p] of tgt (the same tensor twice is fine: no copy).  Planes 0..2 = x, y, z (times `scale`), plane 3 =
+    range, valid iff range > 0.  Returns IcpResult of device tensors: T (P, 4, 4) float64 (target ~ T [source; 1]), fitness,
+    inlier_rmse (P,) float64, iterations (P,) int64, converged (P,) bool (stopped by the 1e-6 deltas) and status (ICP_*).
+    The host queues ICP_CHUNK iterations at a time and then reads the P done words: no sync per iteration.  init: (P, 4, 4)
+    start poses (default identity); source_stride k: only source points 0, k, 2k ... are queries (cost knob, 1 = exact)."""
+    return _icp_run(src, tgt, src_frames, tgt_frames, scale, threshold, max_iteration, init, source_stride)
+
+
+def _icp_run(src, tgt, src_frames, tgt_frames, scale, threshold, max_iteration=2000, init=None, source_stride=1, on_chunk=None):
+    """icp_register; on_chunk(state, done) is called after every chunk (tests look at the state between chunks)"""
+    if int(max_iteration) < 0:
+        raise ValueError(f'icp: max_iteration {max_iteration} is negative')
+    src, tgt = src.contiguous(), tgt.contiguous()
+    frames, state, done, ws, P, n = _icp_setup(src, tgt, src_frames, tgt_frames, scale, threshold, init, source_stride)
+    queued = 0
+    while queued < max_iteration + 1:             # max_iteration fits need max_iteration + 1 evaluations
+        count = min(ICP_CHUNK, max_iteration + 1 - queued)
+        _icp_iterate(src, tgt, frames, P, n, scale, threshold, source_stride, max_iteration, count, ws, state, done)
+        queued += count
+        if on_chunk is not None:
+            on_chunk(state, done)
+        if bool(done.cpu().all()):
+            break
+    return _icp_result(state)
+
+
+def icp_step(src, tgt, src_frames, tgt_frames, scale, threshold, init=None, source_stride=1, out=None):
+    """One evaluation at `init` (default identity) and the fit that follows it: (corr (P, n) int32 - the target index of every
+    source point, -1 = invalid, gated out or no query -, sums (P, 17) float64 over the inliers - count, sum d^2, sum s, sum q,
+    sum s q^T -, IcpResult after the step).  Pairs that are empty report zeros and -1.  out = (corr, sums): contiguous device
+    tensors of those shapes and types to write into (they are initialised here)."""
+    src, tgt = src.contiguous(), tgt.contiguous()
+    frames, state, done, ws, P, n = _icp_setup(src, tgt, src_frames, tgt_frames, scale, threshold, init, source_stride)
+    if out is None:
+        out = (torch.empty((P, n), device=src.device, dtype=torch.int32), torch.empty(P, 17, device=src.device, dtype=torch.float64))
+    corr, sums = out
+    if (corr.shape, corr.dtype, sums.shape, sums.dtype) != ((P, n), torch.int32, (P, 17), torch.float64):
+        raise ValueError(f'icp_step: out must be ({P}, {n}) int32 and ({P}, 17) float64')
+    corr.fill_(-1)
+    sums.zero_()
+    _icp_iterate(src, tgt, frames, P, n, scale, threshold, source_stride, 2000, 1, ws, state, done, corr, sums)
+    return corr, sums, _icp_result(state)
+
 
 
 # ================================================================================================ optimiser

@@ -124,6 +124,8 @@ class WorldModelTrainer(_Base):
         self.on_confusion = None       # callable(name, (C, C) host int64 matrix): the IoU heads' counts, handed over by log_metrics
         self.accumulate_now = False    # plain loop: True while a non-final micro-batch of gradient accumulation runs
         self.panel_writer = None       # object with add_images / add_video (muvo_amd.visualise.PanelWriter): None = no panels
+        self.traj_panels = False       # with a writer and LIDAR_RE: also `_traj` (muvo_amd/odometry.py, ICP between lidar frames)
+        self.traj_options = {}         # threshold / source_stride / max_iteration of that ICP (default: 5 m, 1, 2000)
         # evaluation metrics per validation / test dataloader (trainer.py:51-55,100-129,191-197); created on first use
         # because they hold device accumulators
         self.metrics_vals = [{}, {}, {}]
@@ -519,6 +521,10 @@ class WorldModelTrainer(_Base):
         with torch.no_grad():
             panels = render_panels(self.cfg, batch, output, output_imagines)
         write_panels(writer, name, panels, self._step_now())
+        if self.traj_panels and self.cfg.LIDAR_RE.ENABLED:
+            from muvo_amd.odometry import traj_panel
+            with torch.no_grad():
+                writer.add_images(f'{name}_traj', traj_panel(self.cfg, batch, output, output_imagines, **self.traj_options), global_step=self._step_now())
         return panels
 
     if pl is None:

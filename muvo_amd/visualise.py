@@ -25,8 +25,9 @@ the steps left to right and puts one all-255 block of width `sep` before step rf
     _depth            DEPTH                video (b, T, 1, 2h, w): prediction above depth_label_1 (trainer.py:919)
 
 Float images become bytes by the rule of `ops.image_u8` - trunc(x * 255) saturated, what TensorBoard's writer does to a float
-image.  Not built: `_flow` (cv2 Farneback), `_traj` (open3d ICP), the numbers cv2.putText prints into the bars, the matplotlib
-voxel figures (`_voxel_top` stands in for them) and TensorBoard's tiling of the batch into one grid."""
+image.  `_traj` is not one of these panels: it is opt-in (`WorldModelTrainer.traj_panels`) and lives in muvo_amd/odometry.py
+(ICP between consecutive lidar frames on the device).  Not built: `_flow` (cv2 Farneback), the numbers cv2.putText prints into
+the bars, the matplotlib voxel figures (`_voxel_top` stands in for them) and TensorBoard's tiling of the batch into one grid."""
 import os
 import struct
 import zlib
