@@ -720,6 +720,53 @@ int muvo_icp_iterate(const float* src, const float* tgt, int Cs, int Ct, int64_t
                      int64_t P, float scale, float threshold, int64_t stride, int max_iteration, int count, double* ws, double* state,
                      int32_t* done, int32_t* corr, double* sums, void* stream);
 
+/* ---- dense optical flow between camera frames (flow.hip): the flow behind the reference's `_flow` panel ------------------------
+ * The reference calls cv2.calcOpticalFlowFarneback(img1, img2, None, 0.5, 3, 15, 3, 5, 1.2, 0) (trainer.py:1009-1020).  This is
+ * Farneback's two-frame method (polynomial expansion, SCIA 2003) with those parameters, but the numbers are OUR DEFINITION:
+ * parity with cv2's output is not pinned anywhere.  tests/flow_reference.py restates the definition in numpy.
+ * Input: two stacks of RGB frames (F, 3, h, w) float32 (the same tensor twice is fine) and P pairs; pair p goes from frame
+ *   pairs_a[p] of frames_a to frame pairs_b[p] of frames_b.  pairs_a / pairs_b are HOST int32 arrays: they are validated before
+ *   anything is launched and travel as kernel arguments, P <= muvo_flow_max_pairs() per call.  Index -1 is an all-white frame.
+ *   Bytes by the rule of muvo_image_u8; grey = (4899 R + 9617 G + 1868 B + 8192) >> 14 on the bytes, then fp32.
+ * Pyramid: L = 3 levels, dropped from the top while min(h, w) 0.5^(L-1) < 32.  Level k is (h + 2^(k-1)) >> k rows (round half
+ *   up; columns alike).  Level k > 0 is the level-0 grey image blurred with a normalised Gaussian of sigma = (2^k - 1) / 2 and
+ *   max(round(5 sigma) | 1, 3) taps (3 and 9; along x, then along y, replicated border), then resized bilinearly: source
+ *   coordinate (o + 0.5) (n_in / n_out) - 0.5 clamped to [0, n_in - 1], second tap min(i + 1, n_in - 1), value
+ *   (1 - fy) ((1 - fx) v00 + fx v01) + fy ((1 - fx) v10 + fx v11).  The coarsest level starts from zero flow; a finer level from
+ *   the coarser flow resized the same way and multiplied by 2.
+ * Polynomial expansion: per pixel the weighted least-squares fit of 1, x, y, x^2, y^2, xy over the 11 x 11 neighbourhood
+ *   (replicated border), weight g(x) g(y), g the normalised Gaussian of sigma 1.2.  Moments: vertically sum g f, y g f, y^2 g f,
+ *   then horizontally; the constant 6 x 6 normal matrix is inverted on the host in float64.  Kept: b_x, b_y, A_xx, A_yy and
+ *   A_xy = half the xy coefficient.
+ * One iteration (3 per level), flow d: the second frame's five values are sampled bilinearly at (x + dx, y + dy) with weights
+ *   (1-a)(1-b), a(1-b), (1-a)b, ab, summed in that order.  Inside (0 <= x + dx < w - 1 and 0 <= y + dy < h - 1): A = (A0 + A1) / 2,
+ *   db = (b0 - b1) / 2; outside: A = A0, db = 0.  b = db + A d.  The five values are multiplied by s(y) s(x), s = 0.14, 0.14,
+ *   0.4472, 0.4472, 0.4472 for the five outermost rows / columns and 1 elsewhere.  The products Axx^2 + Axy^2, Axy (Axx + Ayy),
+ *   Ayy^2 + Axy^2, Axx bx + Axy by, Axy bx + Ayy by are averaged over the 15 x 15 box (replicated border; 15 vertical sums, then
+ *   15 horizontal, times 1/225) to g11, g12, g22, h1, h2 and d = ((g22 h1 - g12 h2), (g11 h2 - g12 h1)) / (g11 g22 - g12^2 + 1e-3).
+ * fp32 throughout, uncontracted, every sum in ascending tap order, no atomics: a call is bit-reproducible and a pair's flow
+ * does not depend on the other pairs.  flow: (P, 2, h, w) float32, [dx, dy] with frame_b(x + d) ~ frame_a(x).
+ * h, w in 16..8192; ws: muvo_flow_workspace_bytes(P, h, w) bytes (-1 for sizes the entry refuses), 4-byte aligned.
+ * muvo_flow_colour: the colour coding of trainer.py:1014-1020 (again our definition) of P flow fields as padded tiles of a
+ *   3-channel panel (MuvoTilePlace as above, frame = pair): magnitude m = sqrtf(dx^2 + dy^2), angle = atan2f(dy, dx) in degrees
+ *   in [0, 360); hue = trunc(angle / 2) (at most 179); saturation = trunc((m - min) 255 / (max - min)) with min / max over the
+ *   pair's field, 0 when max = min; value 255; RGB by the 8-bit sextant formula in integers: i = hue / 30, r = hue % 30,
+ *   p = 255 - sat, q = 255 - (2 sat r + 30) / 60, t = 255 - (2 sat (30 - r) + 30) / 60, (v,t,p) (q,v,p) (p,v,t) (p,q,v) (t,p,v)
+ *   (v,p,q) for i = 0 .. 5.  A zero field is an all-255 tile.  Tiles are written in 2-pixel groups: every tile must start at an
+ *   even panel column.  ws: muvo_flow_colour_ws_bytes(P) bytes.
+ * muvo_flow_epe: acc[0] += sum |a - b|, acc[1] += sum |a|, acc[2] += the number of pixels, over the pixels at least 5 from the
+ *   border of P pairs of flow fields (P, 2, h, w); |.| in fp32, sums in fp64 per workgroup (ws: muvo_flow_epe_ws_doubles(P)
+ *   doubles), added to the device doubles acc[0..2] in a fixed order. */
+int64_t muvo_flow_max_pairs(void);
+int64_t muvo_flow_workspace_bytes(int64_t P, int h, int w);
+int muvo_flow_farneback(const float* frames_a, int64_t Fa, const float* frames_b, int64_t Fb, int h, int w, const int32_t* pairs_a,
+                        const int32_t* pairs_b, int64_t P, void* ws, int64_t ws_bytes, float* flow, void* stream);
+int64_t muvo_flow_colour_ws_bytes(int64_t P);
+int muvo_flow_colour(const float* flow, int64_t P, int h, int w, void* ws, int64_t ws_bytes, int pad, int padbyte, uint8_t* panel,
+                     int64_t panel_bytes, const MuvoTilePlace* place, void* stream);
+int64_t muvo_flow_epe_ws_doubles(int64_t P);
+int muvo_flow_epe(const float* flow_a, const float* flow_b, int64_t P, int h, int w, double* ws, int64_t ws_doubles, double* acc, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

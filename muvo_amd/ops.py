@@ -85,6 +85,8 @@ EXPORTS = [
     'muvo_panel_image', 'muvo_panel_logits', 'muvo_panel_labels', 'muvo_panel_fill', 'muvo_panel_bars', 'muvo_panel_scatter',
     'muvo_panel_voxel_top_logits', 'muvo_panel_voxel_top_grid',
     'muvo_icp_state_doubles', 'muvo_icp_ws_doubles', 'muvo_icp_init', 'muvo_icp_iterate',
+    'muvo_flow_max_pairs', 'muvo_flow_workspace_bytes', 'muvo_flow_farneback', 'muvo_flow_colour_ws_bytes', 'muvo_flow_colour',
+    'muvo_flow_epe_ws_doubles', 'muvo_flow_epe',
 ]
 
 
@@ -110,6 +112,8 @@ def lib():
                 L.muvo_chamfer_loss_ws_doubles.restype = C.c_int64
                 L.muvo_icp_state_doubles.restype = C.c_int64
                 L.muvo_icp_ws_doubles.restype = C.c_int64
+                for name in ('muvo_flow_max_pairs', 'muvo_flow_workspace_bytes', 'muvo_flow_colour_ws_bytes', 'muvo_flow_epe_ws_doubles'):
+                    getattr(L, name).restype = C.c_int64
                 for name in EXPORTS:
                     getattr(L, name)  # AttributeError if a declared symbol is missing
                 _lib = L
@@ -2887,6 +2891,66 @@ def icp_step(src, tgt, src_frames, tgt_frames, scale, threshold, init=None, sour
     sums.zero_()
     _icp_iterate(src, tgt, frames, P, n, scale, threshold, source_stride, 2000, 1, ws, state, done, corr, sums)
     return corr, sums, _icp_result(state)
+
+
+# ================================================================================================ optical flow between camera frames
+FLOW_WORKSPACE_CAP = 512 << 20     # bytes of workspace a call may hold: the pairs run in chunks below it (at least one pair)
+
+
+def _flow_indices(v, what):
+    v = [int(i) for i in (v.tolist() if torch.is_tensor(v) else v)]
+    if not v:
+        raise ValueError(f'optical_flow: {what} is empty')
+    return v
+
+
+def optical_flow(frames_a, frames_b, pairs_a, pairs_b, out=None):
+    """Dense Farneback flow (include/muvo_hip.h: muvo_flow_farneback, our definition) of P frame pairs: pair p goes from frame
+    pairs_a[p] of frames_a (Fa, 3, h, w) float32 to frame pairs_b[p] of frames_b (the same tensor twice is fine: no frame is
+    copied); index -1 is an all-white frame.  Returns (P, 2, h, w) float32 [dx, dy] on the device.  The pairs run in chunks of at
+    most muvo_flow_max_pairs() whose workspace stays below FLOW_WORKSPACE_CAP; the workspace is kept between calls."""
+    if frames_a.dtype != torch.float32 or frames_b.dtype != torch.float32:
+        raise ValueError(f'optical_flow: float32 frames, got {frames_a.dtype} and {frames_b.dtype}')
+    if frames_a.dim() != 4 or frames_b.dim() != 4 or frames_a.shape[1] != 3 or frames_a.shape[1:] != frames_b.shape[1:]:
+        raise ValueError(f'optical_flow: two stacks (F, 3, h, w) of one frame size, got {tuple(frames_a.shape)} and {tuple(frames_b.shape)}')
+    assert frames_a.device == frames_b.device
+    frames_a, frames_b = frames_a.contiguous(), frames_b.contiguous()
+    pa, pb = _flow_indices(pairs_a, 'pairs_a'), _flow_indices(pairs_b, 'pairs_b')
+    if len(pa) != len(pb):
+        raise ValueError('optical_flow: pairs_a and pairs_b must have one length')
+    L, P, (h, w) = lib(), len(pa), frames_a.shape[2:]
+    one = int(L.muvo_flow_workspace_bytes(_i64(1), int(h), int(w)))
+    if one < 0:
+        raise ValueError(f'optical_flow: frames of {h} x {w} (16..8192 on both axes)')
+    chunk = max(1, min(int(L.muvo_flow_max_pairs()), FLOW_WORKSPACE_CAP // one, P))
+    ws = scratch('optical_flow', (chunk * one + 3) // 4, frames_a.device)
+    flow = out if out is not None else torch.empty((P, 2, h, w), dtype=torch.float32, device=frames_a.device)
+    assert flow.shape == (P, 2, h, w) and flow.dtype == torch.float32 and flow.is_contiguous()
+    for at in range(0, P, chunk):
+        n = min(chunk, P - at)
+        ia, ib = (C.c_int32 * n)(*pa[at:at + n]), (C.c_int32 * n)(*pb[at:at + n])
+        _ck(L.muvo_flow_farneback(_f(frames_a), _i64(frames_a.shape[0]), _f(frames_b), _i64(frames_b.shape[0]), int(h), int(w), ia, ib, _i64(n),
+                                  _p(ws), _i64(ws.numel() * 4), _f(flow[at:at + n]), _st()))
+    return flow
+
+
+def flow_colour(flow, panel, place, pad=5, padbyte=204):
+    """Colour-coded tiles (include/muvo_hip.h: muvo_flow_colour) of P flow fields (P, 2, h, w) float32 in a 3-channel panel."""
+    assert flow.dtype == torch.float32 and flow.dim() == 4 and flow.shape[1] == 2 and flow.is_contiguous()
+    assert panel.dim() == 4 and panel.shape[1] == 3
+    P, _, h, w = flow.shape
+    ws = scratch('flow_colour', max(1, lib().muvo_flow_colour_ws_bytes(_i64(P)) // 4), flow.device)
+    _ck(lib().muvo_flow_colour(_f(flow), _i64(P), int(h), int(w), _p(ws), _i64(ws.numel() * 4), int(pad), int(padbyte), *_panel_args(panel, place)))
+
+
+def flow_epe(flow_a, flow_b, acc):
+    """acc (3,) float64 on the device += (sum |a - b|, sum |a|, pixels) over the pixels at least 5 from the border of the P pairs
+    of flow fields (P, 2, h, w) float32 (include/muvo_hip.h: muvo_flow_epe); nothing is read back."""
+    assert flow_a.shape == flow_b.shape and flow_a.dtype == flow_b.dtype == torch.float32 and flow_a.is_contiguous() and flow_b.is_contiguous()
+    assert acc.dtype == torch.float64 and acc.numel() == 3 and acc.is_contiguous()
+    P, _, h, w = flow_a.shape
+    ws = scratch('flow_epe', max(1, lib().muvo_flow_epe_ws_doubles(_i64(P))), flow_a.device, torch.float64)
+    _ck(lib().muvo_flow_epe(_f(flow_a), _f(flow_b), _i64(P), int(h), int(w), _p(ws), _i64(ws.numel()), _p(acc), _st()))
 
 
 

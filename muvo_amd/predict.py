@@ -78,6 +78,9 @@ def build_parser():
     parser.add_argument('--panels', type=int, default=0, metavar='N',
                         help='test: write the picture grids of the first N batches per loader below OUT/panels (default: none)')
     parser.add_argument('--traj', action='store_true', help='with --panels: also the ego-trajectory panel `_traj` (ICP between lidar frames)')
+    parser.add_argument('--flow', action='store_true', help='with --panels: also the optical-flow panel `_flow` (dense Farneback flow between camera frames)')
+    parser.add_argument('--optical-flow', action='store_true',
+                        help='test: endpoint error between the flow of the recorded and of the predicted camera frames -> OUT/optical_flow.json')
     parser.add_argument('--ego-motion', action='store_true',
                         help='test: drift of the ego path implied by the predicted lidar from the one implied by the recorded lidar -> OUT/ego_motion.json')
     parser.add_argument('--ego-threshold', type=float, default=5.0, metavar='M', help='ICP inlier distance in metres of --ego-motion and --traj (default 5, the reference)')
@@ -98,6 +101,10 @@ def parse_args(argv=None):
         raise SystemExit('--ego-motion and --traj go with --mode test')
     if args.traj and not args.panels:
         raise SystemExit('--traj goes with --panels N')
+    if (args.flow or args.optical_flow) and args.mode != 'test':
+        raise SystemExit('--flow and --optical-flow go with --mode test')
+    if args.flow and not args.panels:
+        raise SystemExit('--flow goes with --panels N')
     if args.ego_threshold <= 0 or args.ego_stride < 1 or args.ego_max_iteration < 0:
         raise SystemExit('--ego-threshold must be positive, --ego-stride at least 1, --ego-max-iteration non-negative')
     return args
@@ -207,7 +214,7 @@ def seed_batch(module, seed, loader_idx, i):
 
 
 def run(cfg, device, out_dir, mode, loaders=None, limit_batches=None, shard_size=500, seed=1234, hook=None, dataset_root=None,
-        data=None, module=None, log=print, panels=0, traj=False, ego_motion=None, icp_options=None):
+        data=None, module=None, log=print, panels=0, traj=False, ego_motion=None, icp_options=None, flow=False, optical_flow=False):
     """Runs one mode and returns what it wrote: {'files': [...], 'batches': {loader: n}, 'metrics': {...}, 'confusion': {...} (test)}.
     hook(i, batch, output, output_imagine): called per batch with the device tensors (test mode: output_imagine is the list
     of imagined samples).  data: a set-up DataModule to take the test loaders from (default: one over dataset_root /
@@ -215,7 +222,9 @@ def run(cfg, device, out_dir, mode, loaders=None, limit_batches=None, shard_size
     of the first `panels` batches of every loader go to PNG files below out_dir/panels (muvo_amd/visualise.py), with traj also
     `_traj`.  ego_motion (test): dict(threshold, stride, max_iteration) - muvo_amd.odometry.EgoMotionMetric runs behind `hook` on every
     batch and writes out_dir/ego_motion.json; metrics.json does not change.  icp_options: dict(threshold, source_stride,
-    max_iteration) of the ICP behind the `_traj` panel (default: 5 m, 1, 2000)."""
+    max_iteration) of the ICP behind the `_traj` panel (default: 5 m, 1, 2000).  flow (test, with panels): also the `_flow` panel;
+    optical_flow (test): muvo_amd.flow.FlowMetric runs on every batch and writes out_dir/optical_flow.json; metrics.json does
+    not change."""
     refuse_multi_process()
     if mode not in ('test', 'sim'):
         raise ValueError(f'mode {mode!r}: test or sim')
@@ -236,10 +245,10 @@ def run(cfg, device, out_dir, mode, loaders=None, limit_batches=None, shard_size
         raise ValueError('mode sim runs over one loader')
     chosen = {idx: test_loaders[idx] for idx in which}
     if mode == 'sim':
-        if panels or traj or ego_motion is not None:
-            raise ValueError('panels and the ego-motion metric belong to mode test')
+        if panels or traj or ego_motion is not None or flow or optical_flow:
+            raise ValueError('panels, the ego-motion metric and the optical-flow metric belong to mode test')
         return _run_sim(cfg, module, chosen, out_dir, limit_batches, shard_size, seed, hook, log)
-    return _run_test(cfg, module, chosen, out_dir, limit_batches, shard_size, seed, hook, log, panels, traj, ego_motion, icp_options)
+    return _run_test(cfg, module, chosen, out_dir, limit_batches, shard_size, seed, hook, log, panels, traj, ego_motion, icp_options, flow, optical_flow)
 
 
 def _batches(loader, limit):
@@ -249,10 +258,16 @@ def _batches(loader, limit):
         yield i, batch
 
 
-def _run_test(cfg, module, loaders, out_dir, limit_batches, shard_size, seed, hook, log, panels=0, traj=False, ego_motion=None, icp_options=None):
+def _run_test(cfg, module, loaders, out_dir, limit_batches, shard_size, seed, hook, log, panels=0, traj=False, ego_motion=None, icp_options=None,
+              flow=False, optical_flow=False):
     counts = {}
     writer, was_writer, was_traj, was_opt = None, module.panel_writer, module.traj_panels, module.traj_options
-    ego = None
+    ego, flow_metric, was_flow = None, None, module.flow_panels
+    if (flow or optical_flow) and not cfg.EVAL.RGB_SUPERVISION:
+        raise ValueError('the optical-flow metric and the `_flow` panel need the camera head (EVAL.RGB_SUPERVISION)')
+    if optical_flow:
+        from muvo_amd.flow import FlowMetric
+        flow_metric = FlowMetric(cfg)
     if (ego_motion is not None or traj) and not cfg.LIDAR_RE.ENABLED:
         raise ValueError('the ego-motion metric and the `_traj` panel need the lidar reconstruction head (LIDAR_RE.ENABLED)')
     if ego_motion is not None:
@@ -268,18 +283,23 @@ def _run_test(cfg, module, loaders, out_dir, limit_batches, shard_size, seed, ho
             counts[idx] = 0
             if ego is not None:
                 ego.start_loader(idx)
+            if flow_metric is not None:
+                flow_metric.start_loader(idx)
             for i, batch in _batches(loader, limit_batches):
                 seed_batch(module, seed, idx, i)
                 module.panel_writer = writer if i < panels else None
                 module.traj_panels = bool(traj)
+                module.flow_panels = bool(flow)
                 output, output_imagines = module.test_step(batch, i, idx)
                 if hook is not None:
                     hook(i, batch, output, output_imagines)
                 if ego is not None:
                     ego.update(i, batch, output, output_imagines)
+                if flow_metric is not None:
+                    flow_metric.update(i, batch, output, output_imagines)
                 counts[idx] += 1
     finally:
-        module.panel_writer, module.traj_panels, module.traj_options = was_writer, was_traj, was_opt
+        module.panel_writer, module.traj_panels, module.traj_options, module.flow_panels = was_writer, was_traj, was_opt, was_flow
     logged, confusion = {}, {}
     was_fn, module.log_fn = module.log_fn, lambda name, value: logged.__setitem__(name, float(value))
     was_cm, module.on_confusion = module.on_confusion, lambda name, matrix: confusion.__setitem__(name, matrix.tolist())
@@ -303,6 +323,10 @@ def _run_test(cfg, module, loaders, out_dir, limit_batches, shard_size, seed, ho
         files.append(ego.write(out_dir))
         out['ego_motion'] = ego.result()
         log(json.dumps({'ego_motion': out['ego_motion']}))
+    if flow_metric is not None:
+        files.append(flow_metric.write(out_dir))
+        out['optical_flow'] = flow_metric.result()
+        log(json.dumps({'optical_flow': out['optical_flow']}))
     return out
 
 
@@ -361,7 +385,8 @@ def main(argv=None):
     run(cfg, device, args.out, args.mode, loaders=chosen_loaders(args.mode, args.loader), limit_batches=args.limit_batches,
         shard_size=args.shard_size, seed=args.seed, dataset_root=args.dataset_root or None, panels=args.panels, traj=args.traj,
         ego_motion=dict(threshold=args.ego_threshold, stride=args.ego_stride, max_iteration=args.ego_max_iteration) if args.ego_motion else None,
-        icp_options=dict(threshold=args.ego_threshold, source_stride=args.ego_stride, max_iteration=args.ego_max_iteration))
+        icp_options=dict(threshold=args.ego_threshold, source_stride=args.ego_stride, max_iteration=args.ego_max_iteration),
+        flow=args.flow, optical_flow=args.optical_flow)
 
 
 if __name__ == '__main__':

@@ -126,6 +126,7 @@ class WorldModelTrainer(_Base):
         self.panel_writer = None       # object with add_images / add_video (muvo_amd.visualise.PanelWriter): None = no panels
         self.traj_panels = False       # with a writer and LIDAR_RE: also `_traj` (muvo_amd/odometry.py, ICP between lidar frames)
         self.traj_options = {}         # threshold / source_stride / max_iteration of that ICP (default: 5 m, 1, 2000)
+        self.flow_panels = False       # with a writer and EVAL.RGB_SUPERVISION: also `_flow` (muvo_amd/flow.py, dense optical flow)
         # evaluation metrics per validation / test dataloader (trainer.py:51-55,100-129,191-197); created on first use
         # because they hold device accumulators
         self.metrics_vals = [{}, {}, {}]
@@ -525,6 +526,10 @@ class WorldModelTrainer(_Base):
             from muvo_amd.odometry import traj_panel
             with torch.no_grad():
                 writer.add_images(f'{name}_traj', traj_panel(self.cfg, batch, output, output_imagines, **self.traj_options), global_step=self._step_now())
+        if self.flow_panels and self.cfg.EVAL.RGB_SUPERVISION:
+            from muvo_amd.flow import flow_panel
+            with torch.no_grad():
+                writer.add_images(f'{name}_flow', flow_panel(batch, output, output_imagines), global_step=self._step_now())
         return panels
 
     if pl is None:
