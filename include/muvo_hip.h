@@ -767,6 +767,52 @@ int muvo_flow_colour(const float* flow, int64_t P, int h, int w, void* ws, int64
 int64_t muvo_flow_epe_ws_doubles(int64_t P);
 int muvo_flow_epe(const float* flow_a, const float* flow_b, int64_t P, int h, int w, double* ws, int64_t ws_doubles, double* acc, void* stream);
 
+/* ---- first-hit ray casting through voxel class grids (raycast.hip): the `_voxel` panel and the RayIoU metric --------------------
+ * OUR DEFINITION (the reference draws its voxel figures with matplotlib and has no ray metric); tests/raycast_reference.py restates
+ * it in numpy float32 and the kernels equal that restatement bit for bit.
+ * Grid cell (x, y, z) of a class grid (X, Y, Z) uint8 is the unit cube [x, x+1) x [y, y+1) x [z, z+1) in grid coordinates and is
+ * occupied when its class is not 0.  A ray is seven fp32 numbers ox oy oz dx dy dz tmax; d need not have unit length.  Everything
+ * is fp32 with + - x /, comparisons and floorf only, uncontracted, with correctly rounded division, in this order:
+ *   1 slabs: t0 = 0, t1 = tmax, entry = 3.  For a = x, y, z with d_a != 0: inv_a = 1 / d_a; ta = (0 - o_a) inv_a; tb = (N_a - o_a) inv_a;
+ *     (lo, hi) = (ta, tb) if ta <= tb else (tb, ta); the ray misses unless lo <= hi (only a NaN fails this); if lo > t0: t0 = lo and
+ *     entry = a; if hi < t1: t1 = hi.  For d_a == 0 the ray misses unless 0 <= o_a < N_a.  The ray misses if every d_a is 0 and
+ *     unless t0 < t1.  A NaN anywhere (origin, direction, tmax) therefore ends in a miss, an infinite direction component too.
+ *   2 start cell: c_a = floorf(o_a + d_a t0) clamped to [0, N_a - 1] (compared as floats, then converted); t = t0, face = entry -
+ *     face 3: the ray starts inside the grid.
+ *   3 loop, at most X + Y + Z + 3 iterations whatever the input: an occupied cell is the hit - its linear index (x Y + y) Z + z, t,
+ *     face.  Otherwise best = +inf and, for a = x, y, z with d_a != 0: tn_a = ((float)(c_a + (d_a > 0 ? 1 : 0)) - o_a) inv_a (fresh
+ *     from the cell, never accumulated); if tn_a < best: best = tn_a, axis = a (strict: ties go x before y before z).  A miss if no
+ *     axis was taken or best > t1; the axis' cell moves by sign(d_a), a miss if it leaves the grid; t = best, face = axis.
+ * A miss is index -1, t 0, face 0.
+ * Bricks: the occupancy of a frame as one uint64 per 4 x 4 x 4 block, (ceil(X/4), ceil(Y/4), ceil(Z/4)) words, bit
+ *   (x&3) 16 + (y&3) 4 + (z&3); cells past the grid are 0.  muvo_raycast_brick_words: the words of F frames (-1 for sizes the
+ *   entries refuse: F in 1..65535, every axis in 1..2048, fewer than 2^30 voxels).  muvo_raycast_bricks_grid packs (F, X, Y, Z)
+ *   uint8; muvo_raycast_bricks_logits takes logits (F, C, X, Y, Z) float32, 2 <= C <= 16, class = first maximum over C (strict >, the
+ *   rule of muvo_panel_logits), and also writes that class grid (F, X, Y, Z) uint8: the march never reads the logits.
+ * muvo_raycast: rays (R, 7) on the device, the same table for all F frames -> hit (F, R) int32, t (F, R) float32, face (F, R)
+ *   uint8.  The march takes occupancy from the words and reads a class byte only at a hit.  R <= 2^24.
+ * muvo_panel_voxel_view: march + shading of an R x R ray table (ray i R + j is pixel (i, j)) as padded tiles of a 3-channel panel
+ *   (MuvoTilePlace as above): a miss is palette[0]; a hit per channel (palette[class][ch] S[face] (96 + (159 z) / max(Z - 1, 1)))
+ *   / 65025 in integers, S = (176, 208, 255, 255).  R <= 4096.
+ * muvo_ray_iou_counts: every ray through a label grid and a prediction grid of one size, counts (3, C, 3) uint64 = threshold x class
+ *   x (tp, fp, fn) on the device, added to: with the label's hit (cl, tl) and the prediction's (cp, tp), per threshold k - both hit,
+ *   cl == cp and fabsf(tp - tl) res <= thresholds[k] (fp32): tp[cl] += 1; otherwise fn[cl] += 1 if the label hit and fp[cp] += 1 if
+ *   the prediction hit; nothing when both miss.  Classes >= C are not counted.  thresholds: 3 HOST floats.  Integer atomics: the
+ *   counts do not depend on scheduling.  depth[0] += sum of fabsf(tp - tl) res, depth[1] += the number of rays, both over the rays
+ *   that hit in both grids: fp32 terms, fp64 partial sums per workgroup (ws: muvo_ray_iou_ws_doubles(F, R) doubles) added in a
+ *   fixed order. */
+int64_t muvo_raycast_brick_words(int F, int X, int Y, int Z);
+int muvo_raycast_bricks_grid(const uint8_t* grid, int F, int X, int Y, int Z, uint64_t* bricks, int64_t words, void* stream);
+int muvo_raycast_bricks_logits(const float* logits, int F, int C, int X, int Y, int Z, uint8_t* grid, uint64_t* bricks, int64_t words, void* stream);
+int muvo_raycast(const uint8_t* grid, const uint64_t* bricks, int F, int X, int Y, int Z, const float* rays, int64_t R, int32_t* hit, float* t,
+                 uint8_t* face, void* stream);
+int muvo_panel_voxel_view(const uint8_t* grid, const uint64_t* bricks, int F, int X, int Y, int Z, const float* rays, int R, const uint8_t* palette, int pad,
+                          int padbyte, uint8_t* panel, int64_t panel_bytes, const MuvoTilePlace* place, void* stream);
+int64_t muvo_ray_iou_ws_doubles(int64_t F, int64_t R);
+int muvo_ray_iou_counts(const uint8_t* label, const uint64_t* label_bricks, const uint8_t* pred, const uint64_t* pred_bricks, int F, int C, int X, int Y,
+                        int Z, const float* rays, int64_t R, float res, const float* thresholds, uint64_t* counts, double* ws, int64_t ws_doubles,
+                        double* depth, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

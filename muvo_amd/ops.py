@@ -87,6 +87,8 @@ EXPORTS = [
     'muvo_icp_state_doubles', 'muvo_icp_ws_doubles', 'muvo_icp_init', 'muvo_icp_iterate',
     'muvo_flow_max_pairs', 'muvo_flow_workspace_bytes', 'muvo_flow_farneback', 'muvo_flow_colour_ws_bytes', 'muvo_flow_colour',
     'muvo_flow_epe_ws_doubles', 'muvo_flow_epe',
+    'muvo_raycast_brick_words', 'muvo_raycast_bricks_grid', 'muvo_raycast_bricks_logits', 'muvo_raycast', 'muvo_panel_voxel_view',
+    'muvo_ray_iou_ws_doubles', 'muvo_ray_iou_counts',
 ]
 
 
@@ -112,7 +114,8 @@ def lib():
                 L.muvo_chamfer_loss_ws_doubles.restype = C.c_int64
                 L.muvo_icp_state_doubles.restype = C.c_int64
                 L.muvo_icp_ws_doubles.restype = C.c_int64
-                for name in ('muvo_flow_max_pairs', 'muvo_flow_workspace_bytes', 'muvo_flow_colour_ws_bytes', 'muvo_flow_epe_ws_doubles'):
+                for name in ('muvo_flow_max_pairs', 'muvo_flow_workspace_bytes', 'muvo_flow_colour_ws_bytes', 'muvo_flow_epe_ws_doubles',
+                             'muvo_raycast_brick_words', 'muvo_ray_iou_ws_doubles'):
                     getattr(L, name).restype = C.c_int64
                 for name in EXPORTS:
                     getattr(L, name)  # AttributeError if a declared symbol is missing
@@ -3282,3 +3285,74 @@ def panel_voxel_top(src, palette, panel, place, pad=0, padbyte=0):
         _ck(lib().muvo_panel_voxel_top_grid(_p(src), int(F), int(X), int(Y), int(Z), pal, int(pad), int(padbyte), *_panel_args(panel, place)))
     else:
         raise ValueError(f'panel_voxel_top: logits (F, C, X, Y, Z) float32 or a grid (F, X, Y, Z) uint8, got {tuple(src.shape)} {src.dtype}')
+
+
+# ---- ray casting through voxel grids (csrc/raycast.hip; include/muvo_hip.h: muvo_raycast, our definition) -------------------------
+def raycast_bricks(src):
+    """(class grid (F, X, Y, Z) uint8, occupancy bricks (F, words) int64 holding the uint64 words) of src = logits (F, C, X, Y, Z)
+    float32 (first maximum over C; the class grid is written by the same kernel) or a class grid (F, X, Y, Z) uint8 (returned as
+    it is)."""
+    src = src.contiguous()
+    L = lib()
+    if src.dtype == torch.float32 and src.dim() == 5:
+        F, Cn, X, Y, Z = src.shape
+        logits = True
+    elif src.dtype == torch.uint8 and src.dim() == 4:
+        F, X, Y, Z = src.shape
+        logits = False
+    else:
+        raise ValueError(f'raycast_bricks: logits (F, C, X, Y, Z) float32 or a grid (F, X, Y, Z) uint8, got {tuple(src.shape)} {src.dtype}')
+    words = int(L.muvo_raycast_brick_words(int(F), int(X), int(Y), int(Z)))
+    if words < 0:
+        raise ValueError(f'raycast_bricks: {F} frames of {X} x {Y} x {Z} (1..65535 frames, 1..2048 per axis)')
+    bricks = torch.empty((F, words // F), dtype=torch.int64, device=src.device)
+    if logits:
+        grid = torch.empty((F, X, Y, Z), dtype=torch.uint8, device=src.device)
+        _ck(L.muvo_raycast_bricks_logits(_f(src), int(F), int(Cn), int(X), int(Y), int(Z), _p(grid), _p(bricks), _i64(words), _st()))
+        return grid, bricks
+    _ck(L.muvo_raycast_bricks_grid(_p(src), int(F), int(X), int(Y), int(Z), _p(bricks), _i64(words), _st()))
+    return src, bricks
+
+
+def _ray_args(grid, bricks, rays):
+    assert grid.dtype == torch.uint8 and grid.dim() == 4 and grid.is_contiguous()
+    assert bricks.dtype == torch.int64 and bricks.is_contiguous() and bricks.shape[0] == grid.shape[0]
+    assert rays.dtype == torch.float32 and rays.dim() == 2 and rays.shape[1] == 7 and rays.is_contiguous() and rays.device == grid.device
+    return tuple(int(v) for v in grid.shape)
+
+
+def raycast(grid, bricks, rays):
+    """First hits of the R rays (R, 7) float32 in each of the F frames of `raycast_bricks`: (hit (F, R) int32 linear cell index or
+    -1, t (F, R) float32, face (F, R) uint8)."""
+    F, X, Y, Z = _ray_args(grid, bricks, rays)
+    R = rays.shape[0]
+    hit = torch.empty((F, R), dtype=torch.int32, device=grid.device)
+    t = torch.empty((F, R), dtype=torch.float32, device=grid.device)
+    face = torch.empty((F, R), dtype=torch.uint8, device=grid.device)
+    _ck(lib().muvo_raycast(_p(grid), _p(bricks), F, X, Y, Z, _f(rays), _i64(R), _p(hit), _f(t), _p(face), _st()))
+    return hit, t, face
+
+
+def panel_voxel_view(grid, bricks, rays, palette, panel, place, pad=0, padbyte=0):
+    """Shaded first-hit view of voxel grids through an R x R ray table (R * R, 7): an R x R tile each in a 3-channel panel."""
+    F, X, Y, Z = _ray_args(grid, bricks, rays)
+    R = math.isqrt(rays.shape[0])
+    assert R * R == rays.shape[0], 'panel_voxel_view: a square ray table'
+    assert panel.dim() == 4 and panel.shape[1] == 3
+    _ck(lib().muvo_panel_voxel_view(_p(grid), _p(bricks), F, X, Y, Z, _f(rays), int(R), _palette(palette, grid.device), int(pad), int(padbyte),
+                                    *_panel_args(panel, place)))
+
+
+def ray_iou_counts(label, label_bricks, pred, pred_bricks, rays, n_classes, resolution, counts, depth, thresholds=(1.0, 2.0, 4.0)):
+    """counts (3, C, 3) int64 (threshold x class x tp / fp / fn) and depth (2,) float64 (sum of |dt| in metres, rays) on the
+    device are added to, over the R rays through F label and F prediction frames (include/muvo_hip.h: muvo_ray_iou_counts);
+    nothing is read back."""
+    F, X, Y, Z = _ray_args(label, label_bricks, rays)
+    assert _ray_args(pred, pred_bricks, rays) == (F, X, Y, Z), 'ray_iou_counts: label and prediction of one shape'
+    Cn = int(n_classes)
+    assert counts.dtype == torch.int64 and tuple(counts.shape) == (3, Cn, 3) and counts.is_contiguous()
+    assert depth.dtype == torch.float64 and tuple(depth.shape) == (2,)
+    R = rays.shape[0]
+    ws = scratch('ray_iou', max(1, lib().muvo_ray_iou_ws_doubles(_i64(F), _i64(R))), label.device, torch.float64)
+    _ck(lib().muvo_ray_iou_counts(_p(label), _p(label_bricks), _p(pred), _p(pred_bricks), F, Cn, X, Y, Z, _f(rays), _i64(R), _fl(resolution),
+                                  (C.c_float * 3)(*[float(v) for v in thresholds]), _p(counts), _p(ws), _i64(ws.numel()), _p(depth), _st()))

@@ -81,6 +81,11 @@ def build_parser():
     parser.add_argument('--flow', action='store_true', help='with --panels: also the optical-flow panel `_flow` (dense Farneback flow between camera frames)')
     parser.add_argument('--optical-flow', action='store_true',
                         help='test: endpoint error between the flow of the recorded and of the predicted camera frames -> OUT/optical_flow.json')
+    parser.add_argument('--voxel', action='store_true', help='with --panels: also the 3-D voxel panel `_voxel` (the grids ray-cast on the device)')
+    parser.add_argument('--voxel-size', type=int, default=256, metavar='R', help='--voxel: pixels a side of one tile (default 256)')
+    parser.add_argument('--ray-iou', action='store_true',
+                        help='test: ray-based IoU of the voxel head (first hits of lidar-like rays through label and prediction) -> OUT/ray_iou.json')
+    parser.add_argument('--ray-stride', type=int, default=4, metavar='K', help='--ray-iou: every K-th azimuth of the range view is a ray (default 4)')
     parser.add_argument('--ego-motion', action='store_true',
                         help='test: drift of the ego path implied by the predicted lidar from the one implied by the recorded lidar -> OUT/ego_motion.json')
     parser.add_argument('--ego-threshold', type=float, default=5.0, metavar='M', help='ICP inlier distance in metres of --ego-motion and --traj (default 5, the reference)')
@@ -105,6 +110,12 @@ def parse_args(argv=None):
         raise SystemExit('--flow and --optical-flow go with --mode test')
     if args.flow and not args.panels:
         raise SystemExit('--flow goes with --panels N')
+    if (args.voxel or args.ray_iou) and args.mode != 'test':
+        raise SystemExit('--voxel and --ray-iou go with --mode test')
+    if args.voxel and not args.panels:
+        raise SystemExit('--voxel goes with --panels N')
+    if args.voxel_size < 1 or args.ray_stride < 1:
+        raise SystemExit('--voxel-size and --ray-stride must be positive')
     if args.ego_threshold <= 0 or args.ego_stride < 1 or args.ego_max_iteration < 0:
         raise SystemExit('--ego-threshold must be positive, --ego-stride at least 1, --ego-max-iteration non-negative')
     return args
@@ -214,7 +225,8 @@ def seed_batch(module, seed, loader_idx, i):
 
 
 def run(cfg, device, out_dir, mode, loaders=None, limit_batches=None, shard_size=500, seed=1234, hook=None, dataset_root=None,
-        data=None, module=None, log=print, panels=0, traj=False, ego_motion=None, icp_options=None, flow=False, optical_flow=False):
+        data=None, module=None, log=print, panels=0, traj=False, ego_motion=None, icp_options=None, flow=False, optical_flow=False,
+        voxel=False, voxel_size=256, ray_iou=None):
     """Runs one mode and returns what it wrote: {'files': [...], 'batches': {loader: n}, 'metrics': {...}, 'confusion': {...} (test)}.
     hook(i, batch, output, output_imagine): called per batch with the device tensors (test mode: output_imagine is the list
     of imagined samples).  data: a set-up DataModule to take the test loaders from (default: one over dataset_root /
@@ -224,7 +236,8 @@ def run(cfg, device, out_dir, mode, loaders=None, limit_batches=None, shard_size
     batch and writes out_dir/ego_motion.json; metrics.json does not change.  icp_options: dict(threshold, source_stride,
     max_iteration) of the ICP behind the `_traj` panel (default: 5 m, 1, 2000).  flow (test, with panels): also the `_flow` panel;
     optical_flow (test): muvo_amd.flow.FlowMetric runs on every batch and writes out_dir/optical_flow.json; metrics.json does
-    not change."""
+    not change.  voxel (test, with panels): also the `_voxel` panel with tiles of voxel_size pixels; ray_iou (test): dict(stride) -
+    muvo_amd.voxel_view.RayIoUMetric runs on every batch and writes out_dir/ray_iou.json; metrics.json does not change."""
     refuse_multi_process()
     if mode not in ('test', 'sim'):
         raise ValueError(f'mode {mode!r}: test or sim')
@@ -245,10 +258,11 @@ def run(cfg, device, out_dir, mode, loaders=None, limit_batches=None, shard_size
         raise ValueError('mode sim runs over one loader')
     chosen = {idx: test_loaders[idx] for idx in which}
     if mode == 'sim':
-        if panels or traj or ego_motion is not None or flow or optical_flow:
-            raise ValueError('panels, the ego-motion metric and the optical-flow metric belong to mode test')
+        if panels or traj or ego_motion is not None or flow or optical_flow or voxel or ray_iou is not None:
+            raise ValueError('panels, the ego-motion metric, the optical-flow metric and the ray IoU belong to mode test')
         return _run_sim(cfg, module, chosen, out_dir, limit_batches, shard_size, seed, hook, log)
-    return _run_test(cfg, module, chosen, out_dir, limit_batches, shard_size, seed, hook, log, panels, traj, ego_motion, icp_options, flow, optical_flow)
+    return _run_test(cfg, module, chosen, out_dir, limit_batches, shard_size, seed, hook, log, panels, traj, ego_motion, icp_options, flow, optical_flow,
+                     voxel, voxel_size, ray_iou)
 
 
 def _batches(loader, limit):
@@ -259,10 +273,18 @@ def _batches(loader, limit):
 
 
 def _run_test(cfg, module, loaders, out_dir, limit_batches, shard_size, seed, hook, log, panels=0, traj=False, ego_motion=None, icp_options=None,
-              flow=False, optical_flow=False):
+              flow=False, optical_flow=False, voxel=False, voxel_size=256, ray_iou=None):
     counts = {}
     writer, was_writer, was_traj, was_opt = None, module.panel_writer, module.traj_panels, module.traj_options
     ego, flow_metric, was_flow = None, None, module.flow_panels
+    ray_metric, was_voxel, was_vopt = None, module.voxel_panels, module.voxel_options
+    if (voxel or ray_iou is not None) and not cfg.VOXEL_SEG.ENABLED:
+        raise ValueError('the ray IoU and the `_voxel` panel need the voxel head (VOXEL_SEG.ENABLED)')
+    if ray_iou is not None:
+        from muvo_amd.voxel_view import RayIoUMetric
+        ray_metric = RayIoUMetric(cfg, **ray_iou)
+    if voxel:
+        module.voxel_options = dict(size=int(voxel_size))
     if (flow or optical_flow) and not cfg.EVAL.RGB_SUPERVISION:
         raise ValueError('the optical-flow metric and the `_flow` panel need the camera head (EVAL.RGB_SUPERVISION)')
     if optical_flow:
@@ -285,11 +307,14 @@ def _run_test(cfg, module, loaders, out_dir, limit_batches, shard_size, seed, ho
                 ego.start_loader(idx)
             if flow_metric is not None:
                 flow_metric.start_loader(idx)
+            if ray_metric is not None:
+                ray_metric.start_loader(idx)
             for i, batch in _batches(loader, limit_batches):
                 seed_batch(module, seed, idx, i)
                 module.panel_writer = writer if i < panels else None
                 module.traj_panels = bool(traj)
                 module.flow_panels = bool(flow)
+                module.voxel_panels = bool(voxel)
                 output, output_imagines = module.test_step(batch, i, idx)
                 if hook is not None:
                     hook(i, batch, output, output_imagines)
@@ -297,9 +322,12 @@ def _run_test(cfg, module, loaders, out_dir, limit_batches, shard_size, seed, ho
                     ego.update(i, batch, output, output_imagines)
                 if flow_metric is not None:
                     flow_metric.update(i, batch, output, output_imagines)
+                if ray_metric is not None:
+                    ray_metric.update(i, batch, output, output_imagines)
                 counts[idx] += 1
     finally:
         module.panel_writer, module.traj_panels, module.traj_options, module.flow_panels = was_writer, was_traj, was_opt, was_flow
+        module.voxel_panels, module.voxel_options = was_voxel, was_vopt
     logged, confusion = {}, {}
     was_fn, module.log_fn = module.log_fn, lambda name, value: logged.__setitem__(name, float(value))
     was_cm, module.on_confusion = module.on_confusion, lambda name, matrix: confusion.__setitem__(name, matrix.tolist())
@@ -327,6 +355,10 @@ def _run_test(cfg, module, loaders, out_dir, limit_batches, shard_size, seed, ho
         files.append(flow_metric.write(out_dir))
         out['optical_flow'] = flow_metric.result()
         log(json.dumps({'optical_flow': out['optical_flow']}))
+    if ray_metric is not None:
+        files.append(ray_metric.write(out_dir))
+        out['ray_iou'] = ray_metric.result()
+        log(json.dumps({'ray_iou': out['ray_iou']}))
     return out
 
 
@@ -386,7 +418,8 @@ def main(argv=None):
         shard_size=args.shard_size, seed=args.seed, dataset_root=args.dataset_root or None, panels=args.panels, traj=args.traj,
         ego_motion=dict(threshold=args.ego_threshold, stride=args.ego_stride, max_iteration=args.ego_max_iteration) if args.ego_motion else None,
         icp_options=dict(threshold=args.ego_threshold, source_stride=args.ego_stride, max_iteration=args.ego_max_iteration),
-        flow=args.flow, optical_flow=args.optical_flow)
+        flow=args.flow, optical_flow=args.optical_flow, voxel=args.voxel, voxel_size=args.voxel_size,
+        ray_iou=dict(stride=args.ray_stride) if args.ray_iou else None)
 
 
 if __name__ == '__main__':

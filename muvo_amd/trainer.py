@@ -127,6 +127,8 @@ class WorldModelTrainer(_Base):
         self.traj_panels = False       # with a writer and LIDAR_RE: also `_traj` (muvo_amd/odometry.py, ICP between lidar frames)
         self.traj_options = {}         # threshold / source_stride / max_iteration of that ICP (default: 5 m, 1, 2000)
         self.flow_panels = False       # with a writer and EVAL.RGB_SUPERVISION: also `_flow` (muvo_amd/flow.py, dense optical flow)
+        self.voxel_panels = False      # with a writer and VOXEL_SEG: also `_voxel` (muvo_amd/voxel_view.py, ray-cast 3-D view)
+        self.voxel_options = {}        # size of that panel's tiles (default 256)
         # evaluation metrics per validation / test dataloader (trainer.py:51-55,100-129,191-197); created on first use
         # because they hold device accumulators
         self.metrics_vals = [{}, {}, {}]
@@ -530,6 +532,11 @@ class WorldModelTrainer(_Base):
             from muvo_amd.flow import flow_panel
             with torch.no_grad():
                 writer.add_images(f'{name}_flow', flow_panel(batch, output, output_imagines), global_step=self._step_now())
+        if getattr(self, 'voxel_panels', False) and self.cfg.VOXEL_SEG.ENABLED:
+            from muvo_amd.voxel_view import voxel_panel
+            with torch.no_grad():
+                writer.add_images(f'{name}_voxel', voxel_panel(self.cfg, batch, output, output_imagines, **getattr(self, 'voxel_options', {})),
+                                  global_step=self._step_now())
         return panels
 
     if pl is None:

@@ -27,7 +27,9 @@ the steps left to right and puts one all-255 block of width `sep` before step rf
 Float images become bytes by the rule of `ops.image_u8` - trunc(x * 255) saturated, what TensorBoard's writer does to a float
 image.  `_traj` is not one of these panels: it is opt-in (`WorldModelTrainer.traj_panels`) and lives in muvo_amd/odometry.py
 (ICP between consecutive lidar frames on the device); `_flow` likewise (`WorldModelTrainer.flow_panels`, muvo_amd/flow.py: dense
-optical flow between consecutive camera frames on the device).  Not built: the numbers cv2.putText prints into the bars, the matplotlib voxel figures (`_voxel_top` stands in for them) and TensorBoard's tiling of the batch into one grid."""
+optical flow between consecutive camera frames on the device); the reference's matplotlib voxel figures likewise: `_voxel`
+(`WorldModelTrainer.voxel_panels`, muvo_amd/voxel_view.py: the grids ray-cast in 3-D on the device, next to `_voxel_top`).  Not built:
+the numbers cv2.putText prints into the bars and TensorBoard's tiling of the batch into one grid."""
 import os
 import struct
 import zlib
