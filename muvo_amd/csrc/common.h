@@ -41,6 +41,16 @@ unsigned* muvo_det_ticket(hipStream_t st);
 static inline int cdiv(long a, long b) { return (int)((a + b - 1) / b); }
 static inline int roundup(int a, int b) { return ((a + b - 1) / b) * b; }
 
+// Tuning thresholds from the environment (DESIGN.md lists them); callers keep the value in a `static const`, so each is read once.
+static inline int env_int(const char* name, int dflt) {
+  const char* e = getenv(name);
+  return e ? atoi(e) : dflt;
+}
+static inline double env_double(const char* name, double dflt) {
+  const char* e = getenv(name);
+  return e ? atof(e) : dflt;
+}
+
 // Grid size for a grid-stride elementwise kernel: enough blocks to fill 256 CUs x 8.
 static inline int ew_grid(long n, int block = 256) {
   long g = (n + block - 1) / block;

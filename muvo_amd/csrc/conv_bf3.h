@@ -13,10 +13,11 @@ long bf3_workspace_bytes(int N, int C, long S);
 int bf3_split_input(const float* x, void* ws, int N, int C, long S, hipStream_t st, const float* yact = nullptr, int act = 0,
                     float slope = 0.f, float* dbias = nullptr, const float* dhead = nullptr, const float* head_w = nullptr, int CO = 0,
                     float* dhead_w = nullptr, float* dhead_b = nullptr);
+// fused 1x1 head of a forward launch on the eight-wave tiles: out = b + W y, W [co][Msub]
+struct Bf3Head { const float* w; const float* b; float* out; int co; };
+// head (optional): only the eight-wave tiles without split-K form it (muvo_conv_forward_head_supported); other launches ignore it
 int bf3_launch_fwd_phase(const ConvPhase& g, const void* ws, const float* wp, const float* bias, float* out, int act,
-                         float slope, hipStream_t st, int ksplit = 1);
-// fused 1x1 head of the NEXT forward launches on the eight-wave tiles (thread-local; co = 0 clears it): logits = b + W y, W [co][Msub]
-void bf3_set_fused_head(const float* w, const float* b, float* out, int co);
+                         float slope, hipStream_t st, int ksplit = 1, const Bf3Head* head = nullptr);
 void bf3_set_products(int n);   // 3: bf16x3 split products (default); 1: hi * hi only (plain bf16 arithmetic)
 int bf3_get_products();
 // split-K factor the caller should use for this phase (1: none; > 1: zero the output first, finish bias / activation after)

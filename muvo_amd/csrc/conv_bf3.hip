@@ -258,8 +258,7 @@ conv_bf3_kernel(const ConvPhase g, const uint4* __restrict__ xs, long plane_u4, 
   // Every LDS read is requested one MFMA group (12 instructions, >= 384 clocks) before its use, the global loads have a
   // whole step to land, and the stage of step kt is free for step kt+2 as soon as everybody holds its second slice in
   // registers — which is what the mid-step barrier certifies.  s_waitcnt 0xC07F = lgkmcnt(0) only (gfx9 encoding).
-  static_assert(BKC == 4 && (NST == 2 || NST == 3), "two k-slices per step; two LDS stages, or three for the ping-pong schedule");
-  const int fragA = wm * (TM * 32) + (lane & 31);
+  static_assert(BKC == 4 && (NST == 2 || NST == 3), "two k-slices per step; two LDS stages, or three for the ping-pong schedule");  const int fragA = wm * (TM * 32) + (lane & 31);
   const int fragB = 2 * BKC * BM + (wn * (TN * 32) + (lane & 31)) * 4 + ((lane >> 5) ^ ((lane >> 2) & 3));   // ks 0; ks 1: ^ 2
   auto load_frags = [&](int stage, int ks, bf16x8 (&ah)[TM], bf16x8 (&al)[TM], bf16x8 (&bh)[TN], bf16x8 (&bl)[TN]) {
     const uint4* S = smem + stage * STAGE;
@@ -438,8 +437,8 @@ conv_bf3_kernel(const ConvPhase g, const uint4* __restrict__ xs, long plane_u4, 
 #if defined(MUVO_BF3_STAMPS) && MUVO_BF3_STAMPS != 3
   if (threadIdx.x == 0 && blockIdx.x < 16384) g_bf3_stamps[blockIdx.x * 8 + 7] = __builtin_amdgcn_s_memtime() - clk0;
 #endif
-#define BF3_STORE(ACT) conv_tile_store<ACT, true, true>(g, acc, bias, out, slope, bx * BN, m_tile, wm, wn, lane, sbias, head_lds, head_co, head_b, head_out)
-  if (ksplit > 1) conv_tile_atomic<true>(g, acc, out, bx * BN, m_tile, wm, wn, lane);
+#define BF3_STORE(ACT) conv_tile_store<ACT, true>(g, acc, bias, out, slope, bx * BN, m_tile, wm, wn, lane, sbias, head_lds, head_co, head_b, head_out)
+  if (ksplit > 1) conv_tile_atomic(g, acc, out, bx * BN, m_tile, wm, wn, lane);
   else { MUVO_ACT_SWITCH(act, BF3_STORE) }
   BF3_STAMP(4);
 #if defined(MUVO_BF3_STAMPS) && MUVO_BF3_STAMPS == 2
@@ -491,7 +490,8 @@ __global__ void __launch_bounds__(64 * WM * WN * WK)
 conv_bf3_wgrad_kernel(const ConvPhase g, const uint4* __restrict__ xs, long xplane_u4, int xc8, const uint4* __restrict__ dzs,
                       long dzplane_u4, int dzc8, float* __restrict__ wg, int steps_per_split,
                       const uint4* __restrict__ zero16, int xcd_order) {
-  constexpr int BK = 32, NW = WM * WN * WK;         // WK = 2: two wave groups split the 32 pixels of a step
+  static_assert(WK == 2, "two wave groups split the 32 pixels of a step (the eight-wave tiles are conv_bf3_wgrad_pp_kernel)");
+  constexpr int BK = 32, NW = WM * WN * WK;
   constexpr int TI = BM / (32 * WM), TJ = BN / (32 * WN);   // 32 x 32 MFMA blocks of a wave tile
   static_assert(TI >= 1 && TJ >= 1 && TI * 32 * WM == BM && TJ * 32 * WN == BN, "wave tiles must tile the workgroup tile");
   constexpr int CA = BM / 8, CB = BN / 8;           // 8-channel chunks per pixel row
@@ -610,6 +610,8 @@ conv_bf3_wgrad_kernel(const ConvPhase g, const uint4* __restrict__ xs, long xpla
     const char* Al = Ah + (size_t)CA * 512;
     const char* Bh = S + (size_t)2 * CA * 512 + (size_t)(wn * TJ * 4) * 512;
     const char* Bl = Bh + (size_t)CB * 512;
+    // (one trip, ks = wk, now that WK is pinned to 2.  The loop form stays: written as a plain block the 32x64 and 64x64 tiles
+    // come out with another instruction order.)
 #pragma unroll
     for (int ks0 = 0; ks0 < 2 / WK; ++ks0) {
       const int ks = WK == 2 ? wk : ks0;
@@ -1430,8 +1432,8 @@ int bf3_split_input(const float* x, void* ws, int N, int C, long S, hipStream_t 
     muvo_set_error("bf3_split_input: the fused head weight gradient needs the head gradient and the activation output");
     return MUVO_ERR_INVALID_ARG;
   }
-  static const int split_v4 = getenv("MUVO_SPLIT_V4") ? atoi(getenv("MUVO_SPLIT_V4")) : 2;   // 2: also the fused dy * act'(y) form, 1: plain splits only, 0: 4-byte kernel everywhere
-  const bool v4 = split_v4 && (!yact || split_v4 >= 2) && S % 4 == 0 && S >= 1024 && (((uintptr_t)x | (uintptr_t)yact) & 15) == 0;   // 5.5 vs 4.5 TB/s (profiles/r02b_hbm.txt)
+  // the 16-byte kernel (plain splits and the fused dy * act'(y) form) wherever its shape and alignment conditions hold
+  const bool v4 = S % 4 == 0 && S >= 1024 && (((uintptr_t)x | (uintptr_t)yact) & 15) == 0;   // 5.5 vs 4.5 TB/s (profiles/r02b_hbm.txt)
   const dim3 grid = v4 ? dim3(cdiv(S, 256), cdiv(Cp, 64), N) : dim3(cdiv(cdiv(S, 64), SPLIT_TILES), cdiv(Cp, 64), N);
   // partial-sum replicas: BIAS_REPLICAS shared ones, or (deterministic mode) one per workgroup of a channel group
   const int nrep = muvo_det() ? (int)(grid.x * grid.z) : BIAS_REPLICAS;
@@ -1443,7 +1445,7 @@ int bf3_split_input(const float* x, void* ws, int N, int C, long S, hipStream_t 
       return MUVO_ERR_HIP;
     }
   }
-  if (dhead != nullptr && !(split_v4 >= 2 && S % 4 == 0 && S >= 1024 && CO >= 1 && CO <= 4 &&
+  if (dhead != nullptr && !(S % 4 == 0 && S >= 1024 && CO >= 1 && CO <= 4 &&
                             (((uintptr_t)x | (uintptr_t)yact | (uintptr_t)dhead) & 15) == 0)) {
     muvo_set_error("bf3_split_input: the head-gradient form needs S %% 4 == 0, S >= 1024, <= 4 head channels and 16-byte aligned tensors");
     return MUVO_ERR_INVALID_ARG;
@@ -1491,9 +1493,6 @@ int bf3_split_rows(const float* x, void* ws, long rows, int C, hipStream_t st) {
   return MUVO_OK;
 }
 
-struct Bf3Head { const float* w; const float* b; float* out; int co; };     // fused 1x1 head of a forward launch (co = 0: none)
-static thread_local Bf3Head t_bf3_head = {nullptr, nullptr, nullptr, 0};
-
 // products per fp32 product: 3 (default, fp32-equivalent) or 1 (plain bf16: muvo_conv_set_products)
 static int g_bf3_products = 3;
 void bf3_set_products(int n) { g_bf3_products = n == 1 ? 1 : 3; }
@@ -1501,11 +1500,11 @@ int bf3_get_products() { return g_bf3_products; }
 
 template <int BM, int BN, int WM, int WN, int BKC, int NST, bool ONE>
 static int bf3_launch_t(const ConvPhase& g, const void* ws, const float* wp, const float* bias, float* out, int act,
-                        float slope, hipStream_t st, int ksplit) {
+                        float slope, hipStream_t st, int ksplit, const Bf3Head* head) {
   constexpr size_t lds0 = (size_t)NST * 2 * BKC * (BM + BN) * 16 + 512 + 4 * BM * WN;   // stages + tap tables + bias rows per wave
   static_assert(lds0 <= 160 * 1024, "LDS budget");
   constexpr size_t HEAD_LDS = NST == 3 ? 4096 : 0;        // eight-wave tiles: room for the weights of a fused head (<= 1024 floats)
-  const Bf3Head hd = (NST == 3 && ksplit <= 1) ? t_bf3_head : Bf3Head{nullptr, nullptr, nullptr, 0};
+  const Bf3Head hd = (NST == 3 && ksplit <= 1 && head != nullptr) ? *head : Bf3Head{nullptr, nullptr, nullptr, 0};
   const size_t lds = lds0 + (hd.co > 0 ? HEAD_LDS : 0);
   static_assert(lds0 + HEAD_LDS <= 160 * 1024, "LDS budget with a fused head");
   static bool attr_set = false;
@@ -1528,16 +1527,16 @@ static int bf3_launch_t(const ConvPhase& g, const void* ws, const float* wp, con
 }
 template <int BM, int BN, int WM, int WN, int BKC, int NST>
 static int bf3_launch(const ConvPhase& g, const void* ws, const float* wp, const float* bias, float* out, int act,
-                      float slope, hipStream_t st, int ksplit = 1) {
-  return g_bf3_products == 1 ? bf3_launch_t<BM, BN, WM, WN, BKC, NST, true>(g, ws, wp, bias, out, act, slope, st, ksplit)
-                             : bf3_launch_t<BM, BN, WM, WN, BKC, NST, false>(g, ws, wp, bias, out, act, slope, st, ksplit);
+                      float slope, hipStream_t st, int ksplit, const Bf3Head* head) {
+  return g_bf3_products == 1 ? bf3_launch_t<BM, BN, WM, WN, BKC, NST, true>(g, ws, wp, bias, out, act, slope, st, ksplit, head)
+                             : bf3_launch_t<BM, BN, WM, WN, BKC, NST, false>(g, ws, wp, bias, out, act, slope, st, ksplit, head);
 }
 
 // does this phase run on the eight-wave ping-pong tiles (256x128 / 128x256) or on the four-wave 64x128 tile?
 bool bf3_fwd_uses_pp(const ConvPhase& g) {
   if (g.M <= 64) return false;
   const long big = g.M > 128 ? (long)cdiv(g.npix, 128) * cdiv(g.M, 256) : (long)cdiv(g.npix, 256) * cdiv(g.M, 128);
-  static const int min_blocks = getenv("MUVO_BF3_PP_MIN_BLOCKS") ? atoi(getenv("MUVO_BF3_PP_MIN_BLOCKS")) : 128;
+  static const int min_blocks = env_int("MUVO_BF3_PP_MIN_BLOCKS", 128);
   return big >= min_blocks;
 }
 bool bf3_wgrad_uses_pp(const ConvPhase& g) { return g.M > 128 || (g.M > 64 && g.C > 64); }
@@ -1547,8 +1546,8 @@ bool bf3_wgrad_uses_pp(const ConvPhase& g) { return g.M > 128 || (g.M > 64 && g.
 // into >= 16-step pieces until ~512 workgroups exist.  The caller zeroes the output and runs the bias / activation pass.
 int bf3_fwd_ksplit(const ConvPhase& g) {
   if (g.npix <= 0 || bf3_fwd_uses_pp(g) || muvo_det()) return 1;     // deterministic mode: no float atomics over K ranges
-  static const int tgt = getenv("MUVO_BF3_KSPLIT_BLOCKS") ? atoi(getenv("MUVO_BF3_KSPLIT_BLOCKS")) : 512;
-  static const int min_steps = getenv("MUVO_BF3_KSPLIT_MIN_STEPS") ? atoi(getenv("MUVO_BF3_KSPLIT_MIN_STEPS")) : 16;
+  static const int tgt = env_int("MUVO_BF3_KSPLIT_BLOCKS", 512);
+  static const int min_steps = env_int("MUVO_BF3_KSPLIT_MIN_STEPS", 16);
   const long tiles = (long)cdiv(g.npix, 128) * cdiv(g.M, 64);
   const int nk = g.Kp / 32;
   if (tiles >= 192 || nk < 2 * min_steps) return 1;
@@ -1557,28 +1556,29 @@ int bf3_fwd_ksplit(const ConvPhase& g) {
   return ks < 1 ? 1 : ks;
 }
 
-void bf3_set_fused_head(const float* w, const float* b, float* out, int co) { t_bf3_head = Bf3Head{w, b, out, co}; }
-
 int bf3_launch_fwd_phase(const ConvPhase& g, const void* ws, const float* wp, const float* bias, float* out, int act,
-                         float slope, hipStream_t st, int ksplit) {
+                         float slope, hipStream_t st, int ksplit, const Bf3Head* head) {
   if (g.npix <= 0) return MUVO_OK;
-  if (ksplit > 1) return bf3_launch<64, 128, 1, 4, 4, 2>(g, ws, wp, nullptr, out, MUVO_ACT_NONE, 0.f, st, ksplit);
-  // eight-wave tiles run the ping-pong schedule (three LDS stages); MUVO_BF3_VARIANT=2 selects the in-phase two-stage
-  // schedule for comparison.  64-row tiles have four waves (one per SIMD) and keep the two-stage schedule.
-  static const int variant = getenv("MUVO_BF3_VARIANT") ? atoi(getenv("MUVO_BF3_VARIANT")) : 0;   // tuning switch
+  if (ksplit > 1) return bf3_launch<64, 128, 1, 4, 4, 2>(g, ws, wp, nullptr, out, MUVO_ACT_NONE, 0.f, st, ksplit, nullptr);
+  // eight-wave tiles run the ping-pong schedule (three LDS stages); 64-row tiles have four waves (one per SIMD) and keep the
+  // two-stage schedule.  MUVO_BF3_VARIANT=2 selects the in-phase two-stage schedule for the eight-wave tiles.  Nothing sets it
+  // and the ping-pong schedule superseded it, but the switch and its two instantiations stay: without them in this translation
+  // unit the compiler emits the 256x128 ping-pong kernel with another instruction order in its prologue (the other kernels do
+  // not change), and the refactor that retired the remaining variants promised unchanged machine code.
+  static const int variant = env_int("MUVO_BF3_VARIANT", 0);
   if (variant == 2) {
-    if (g.M > 128) return bf3_launch<256, 128, 4, 2, 4, 2>(g, ws, wp, bias, out, act, slope, st);
-    if (g.M > 64) return bf3_launch<128, 256, 2, 4, 4, 2>(g, ws, wp, bias, out, act, slope, st);
+    if (g.M > 128) return bf3_launch<256, 128, 4, 2, 4, 2>(g, ws, wp, bias, out, act, slope, st, 1, nullptr);
+    if (g.M > 64) return bf3_launch<128, 256, 2, 4, 4, 2>(g, ws, wp, bias, out, act, slope, st, 1, nullptr);
   }
   // Launches whose eight-wave tiles (one 147 KB workgroup per CU) would cover less than half of the 256 CUs, and all
   // 64-row launches, use the four-wave 64x128 tile: 49 KB of LDS, three workgroups per CU.  Measured per layer
   // (profiles/r01q_tile_choice.txt): 64x128 beats 64x256 (one workgroup per CU) by 1.4-1.6x on every 64-row layer and
   // the big tiles by 1.2-1.35x below 128 workgroups; a four-wave 128x128 tile lost to the ping-pong tiles everywhere.
   if (bf3_fwd_uses_pp(g)) {
-    if (g.M > 128) return bf3_launch<256, 128, 4, 2, 4, 3>(g, ws, wp, bias, out, act, slope, st);
-    return bf3_launch<128, 256, 2, 4, 4, 3>(g, ws, wp, bias, out, act, slope, st);
+    if (g.M > 128) return bf3_launch<256, 128, 4, 2, 4, 3>(g, ws, wp, bias, out, act, slope, st, 1, head);
+    return bf3_launch<128, 256, 2, 4, 4, 3>(g, ws, wp, bias, out, act, slope, st, 1, head);
   }
-  return bf3_launch<64, 128, 1, 4, 4, 2>(g, ws, wp, bias, out, act, slope, st);
+  return bf3_launch<64, 128, 1, 4, 4, 2>(g, ws, wp, bias, out, act, slope, st, 1, nullptr);
 }
 
 // Split-K factor of a weight-gradient launch.  Many tiles: the measured default (about `tgt` workgroups, >= `minst` steps each).
@@ -1591,8 +1591,7 @@ static int bf3_wgrad_ksplit(long tiles, int nsteps, int tgt, int minst, int slot
   int ksplit = cdiv(tgt, tiles);
   if (ksplit > cdiv(nsteps, minst)) ksplit = cdiv(nsteps, minst);
   if (ksplit < 1) ksplit = 1;
-  static const int quant = getenv("MUVO_BF3_WGRAD_QUANT") ? atoi(getenv("MUVO_BF3_WGRAD_QUANT")) : 1;   // A/B switch
-  if (quant && tiles * ksplit < 4L * slots) {
+  if (tiles * ksplit < 4L * slots) {
     const int kmax = nsteps / 12 > 1 ? nsteps / 12 : 1;
     double best = 1e30;
     for (int ks = 1; ks <= kmax && tiles * ks <= 8L * slots; ++ks) {
@@ -1605,10 +1604,9 @@ static int bf3_wgrad_ksplit(long tiles, int nsteps, int tgt, int minst, int slot
   return ksplit;
 }
 
-static int bf3_wgrad_xcd_order() {
-  static const int v = getenv("MUVO_BF3_WGRAD_XCD") ? atoi(getenv("MUVO_BF3_WGRAD_XCD")) : 1;   // A/B switch
-  return v;
-}
+// The weight-gradient kernels always walk their workgroups in XCD order (wgrad_block).  The choice stays a kernel argument, passed
+// this constant, so that the kernels keep the machine code their measurements were taken with.
+constexpr int BF3_WGRAD_XCD_ORDER = 1;
 
 template <int BM, int BN, int WM, int WN, bool ONE>
 static int bf3_wgrad_pp_launch_t(const ConvPhase& g, const void* ws_x, int Cin_total, const void* ws_dz, int Cout_total,
@@ -1629,14 +1627,14 @@ static int bf3_wgrad_pp_launch_t(const ConvPhase& g, const void* ws_x, int Cin_t
   const long xplane = (long)g.N * g.ID * g.IH * g.IW * xc8, dzplane = (long)g.N * g.OD * g.OH * g.OW * dzc8;
   const int ctiles = cdiv(g.C, BN), mtiles = cdiv(g.M, BM);
   const int nsteps = cdiv(g.npix, 32);
-  static const int tgt = getenv("MUVO_BF3_WGRAD_PP_BLOCKS") ? atoi(getenv("MUVO_BF3_WGRAD_PP_BLOCKS")) : 2048;
-  static const int minst = getenv("MUVO_BF3_WGRAD_PP_MINSTEPS") ? atoi(getenv("MUVO_BF3_WGRAD_PP_MINSTEPS")) : 32;   // measured: 16.2 -> 15.5 ms/step over all ping-pong weight gradients vs (1536, 16): fewer split-K atomics per tile
+  static const int tgt = env_int("MUVO_BF3_WGRAD_PP_BLOCKS", 2048);
+  static const int minst = env_int("MUVO_BF3_WGRAD_PP_MINSTEPS", 32);   // measured: 16.2 -> 15.5 ms/step over all ping-pong weight gradients vs (1536, 16): fewer split-K atomics per tile
   int ksplit = bf3_wgrad_ksplit((long)ctiles * g.T * mtiles, nsteps, tgt, minst, 256);   // one 147-KB workgroup per CU
   const int sps = cdiv(nsteps, ksplit);
   ksplit = cdiv(nsteps, sps);
   dim3 grid(ctiles * g.T, mtiles, ksplit);
   hipLaunchKernelGGL((conv_bf3_wgrad_pp_kernel<BM, BN, WM, WN, ONE>), grid, dim3(64 * WM * WN), lds, st, p, (const uint4*)ws_x, xplane,
-                     xc8, (const uint4*)ws_dz, dzplane, dzc8, wg, sps, bf3_wgrad_xcd_order());
+                     xc8, (const uint4*)ws_dz, dzplane, dzc8, wg, sps, BF3_WGRAD_XCD_ORDER);
   MUVO_CHECK_LAUNCH("conv_bf3_wgrad_pp_kernel");
   return MUVO_OK;
 }
@@ -1668,14 +1666,14 @@ static int bf3_wgrad_launch_t(const ConvPhase& g, const void* ws_x, int Cin_tota
   const long xplane = (long)g.N * g.ID * g.IH * g.IW * xc8, dzplane = (long)g.N * g.OD * g.OH * g.OW * dzc8;
   const int ctiles = cdiv(g.C, BN), mtiles = cdiv(g.M, BM);
   const int nsteps = cdiv(g.npix, 32);
-  static const int tgt = getenv("MUVO_BF3_WGRAD_BLOCKS") ? atoi(getenv("MUVO_BF3_WGRAD_BLOCKS")) : 2048;
-  static const int minst = getenv("MUVO_BF3_WGRAD_MINSTEPS") ? atoi(getenv("MUVO_BF3_WGRAD_MINSTEPS")) : 32;     // measured 3.6 -> 3.3 ms/step vs (1536, 16)
+  static const int tgt = env_int("MUVO_BF3_WGRAD_BLOCKS", 2048);
+  static const int minst = env_int("MUVO_BF3_WGRAD_MINSTEPS", 32);     // measured 3.6 -> 3.3 ms/step vs (1536, 16)
   int ksplit = bf3_wgrad_ksplit((long)ctiles * g.T * mtiles, nsteps, tgt, minst, 256 * (int)(160 * 1024 / lds));
   const int sps = cdiv(nsteps, ksplit);
   ksplit = cdiv(nsteps, sps);
   dim3 grid(ctiles * g.T, mtiles, ksplit);
   hipLaunchKernelGGL((conv_bf3_wgrad_kernel<BM, BN, WM, WN, WK, ONE>), grid, dim3(64 * WM * WN * WK), lds, st, p, (const uint4*)ws_x, xplane,
-                     xc8, (const uint4*)ws_dz, dzplane, dzc8, wg, sps, zero16, bf3_wgrad_xcd_order());
+                     xc8, (const uint4*)ws_dz, dzplane, dzc8, wg, sps, zero16, BF3_WGRAD_XCD_ORDER);
   MUVO_CHECK_LAUNCH("conv_bf3_wgrad_kernel");
   return MUVO_OK;
 }
@@ -1691,25 +1689,20 @@ int bf3_wgrad_phase(const ConvPhase& g, const void* ws_x, int Cin_total, const v
                     float* dw, hipStream_t st) {
   if (g.npix <= 0 || g.T == 0) return MUVO_OK;
   int rc;
-  static const int w64 = getenv("MUVO_BF3_WGRAD_64") ? atoi(getenv("MUVO_BF3_WGRAD_64")) : 1;
-  static const int w32 = getenv("MUVO_BF3_WGRAD_32") ? atoi(getenv("MUVO_BF3_WGRAD_32")) : 1;   // 32-row tile for <= 32 produced channels
-  static const int wvariant = getenv("MUVO_BF3_WGRAD_VARIANT") ? atoi(getenv("MUVO_BF3_WGRAD_VARIANT")) : 0;   // 1: in-phase DMA kernels
-  if (g.M > 128) rc = wvariant == 1 ? bf3_wgrad_launch<256, 128, 4, 2, 1>(g, ws_x, Cin_total, ws_dz, Cout_total, wg, st)
-                                    : bf3_wgrad_pp_launch<256, 128, 4, 2>(g, ws_x, Cin_total, ws_dz, Cout_total, wg, st);
-  else if (g.M > 64) rc = g.C > 64 ? (wvariant == 1 ? bf3_wgrad_launch<128, 256, 2, 4, 1>(g, ws_x, Cin_total, ws_dz, Cout_total, wg, st)
-                                                     : bf3_wgrad_pp_launch<128, 256, 2, 4>(g, ws_x, Cin_total, ws_dz, Cout_total, wg, st))
+  // rows (produced channels) pick the tile height, reduction channels its width; > 64 x > 64: the eight-wave ping-pong tiles
+  if (g.M > 128) rc = bf3_wgrad_pp_launch<256, 128, 4, 2>(g, ws_x, Cin_total, ws_dz, Cout_total, wg, st);
+  else if (g.M > 64) rc = g.C > 64 ? bf3_wgrad_pp_launch<128, 256, 2, 4>(g, ws_x, Cin_total, ws_dz, Cout_total, wg, st)
                                     : bf3_wgrad_launch<128, 128, 2, 2, 2>(g, ws_x, Cin_total, ws_dz, Cout_total, wg, st);
-  else if (g.M <= 32 && g.C <= 64 && w32) rc = bf3_wgrad_launch<32, 64, 1, 2, 2>(g, ws_x, Cin_total, ws_dz, Cout_total, wg, st);
+  else if (g.M <= 32 && g.C <= 64) rc = bf3_wgrad_launch<32, 64, 1, 2, 2>(g, ws_x, Cin_total, ws_dz, Cout_total, wg, st);
   else rc = g.C > 128 ? bf3_wgrad_launch<64, 256, 1, 4, 2>(g, ws_x, Cin_total, ws_dz, Cout_total, wg, st)
-            : g.C > 64 || w64 == 0 ? bf3_wgrad_launch<64, 128, 1, 2, 2>(g, ws_x, Cin_total, ws_dz, Cout_total, wg, st)
-                                   : bf3_wgrad_launch<64, 64, 1, 2, 2>(g, ws_x, Cin_total, ws_dz, Cout_total, wg, st);
+            : g.C > 64 ? bf3_wgrad_launch<64, 128, 1, 2, 2>(g, ws_x, Cin_total, ws_dz, Cout_total, wg, st)
+                       : bf3_wgrad_launch<64, 64, 1, 2, 2>(g, ws_x, Cin_total, ws_dz, Cout_total, wg, st);
   if (rc) return rc;
   const long total = (long)g.M * g.C * g.T;
-  static const int tiled = getenv("MUVO_UNPACK_TILED") ? atoi(getenv("MUVO_UNPACK_TILED")) : 1;     // A/B switch
-  if (tiled && total >= 4096) {
+  if (total >= 4096) {
     // LDS per workgroup: 6 KB fits next to a 147-KB convolution tile on the same CU (with 38-KB tiles the weight-gradient stream's
     // unpack launches waited for whole CUs: 2.8 ms per step against 1.45 element-wise and 1.08 with 6 KB)
-    static const int lds_cap = getenv("MUVO_UNPACK_LDS") ? atoi(getenv("MUVO_UNPACK_LDS")) : 6 * 1024;
+    static const int lds_cap = env_int("MUVO_UNPACK_LDS", 6 * 1024);
     int TM = 64;
     while (TM > 1 && (long)TM * g.T * 33 * 4 > lds_cap) TM >>= 1;
     while (TM > 1 && TM / 2 >= g.M) TM >>= 1;
@@ -1719,7 +1712,7 @@ int bf3_wgrad_phase(const ConvPhase& g, const void* ws_x, int Cin_total, const v
     return MUVO_OK;
   }
   // one element per thread (no grid-stride loop: its second iteration's loads would wait for the first iteration's stores)
-  static const int unpack_cap = getenv("MUVO_UNPACK_GRID_CAP") ? atoi(getenv("MUVO_UNPACK_GRID_CAP")) : (1 << 22);
+  static const int unpack_cap = env_int("MUVO_UNPACK_GRID_CAP", 1 << 22);
   const long ublocks = cdiv(total, 256);
   hipLaunchKernelGGL(bf3_unpack_wgrad_kernel, dim3((unsigned)(ublocks < unpack_cap ? ublocks : unpack_cap)), dim3(256), 0, st, g, wg, dw);
   MUVO_CHECK_LAUNCH("bf3_unpack_wgrad_kernel");

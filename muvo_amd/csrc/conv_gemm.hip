@@ -173,8 +173,8 @@ conv_fwd_kernel(const ConvPhase g, const float* __restrict__ in, const float* __
   if (ksplit > 1 && kt0 >= nk) return;
 
   // ---- epilogue, instantiated per activation (see act_dispatch in common.h)
-#define CONV_FWD_STORE(ACT) conv_tile_store<ACT, false, true>(g, acc, bias, out, slope, blockIdx.x * BN, m_tile, wm, wn, lane, s_bias[wave])
-  if (ksplit > 1) conv_tile_atomic<true>(g, acc, out, blockIdx.x * BN, m_tile, wm, wn, lane);
+#define CONV_FWD_STORE(ACT) conv_tile_store<ACT, false>(g, acc, bias, out, slope, blockIdx.x * BN, m_tile, wm, wn, lane, s_bias[wave])
+  if (ksplit > 1) conv_tile_atomic(g, acc, out, blockIdx.x * BN, m_tile, wm, wn, lane);
   else { MUVO_ACT_SWITCH(act, CONV_FWD_STORE) }
 #undef CONV_FWD_STORE
 }
@@ -458,8 +458,6 @@ static int choose_cp(int C) { return C <= 4 ? 4 : (C <= 8 ? 8 : roundup(C, 16));
 
 // 0: exact fp32 MFMA everywhere; 1: bf16x3 split-product MFMA for phases with at least 32 output channels
 static int g_conv_mode = -1;
-static thread_local int t_plan_mode = 0;
-static thread_local bool t_allow_merge = true;
 static int conv_mode() {
   if (g_conv_mode < 0) {
     const char* e = getenv("MUVO_CONV_MFMA");
@@ -483,18 +481,17 @@ static double bf3_min_gflop() {
   if (bf3_default_policy()) return 0.1;
   return g_bf3_min_gflop >= 0.0 ? g_bf3_min_gflop : atof(getenv("MUVO_BF16X3_MIN_GFLOP"));
 }
-static const int g_bf3_min_m = getenv("MUVO_BF3_MIN_M") ? atoi(getenv("MUVO_BF3_MIN_M")) : 32;   // smallest row count on bf16x3 (half of the 64-row tile idles at 32; still 1.4x the fp32 kernel)
-static thread_local int t_nphase = 1;         // sub-pixel phases of the operation being planned (work / pixels are per phase)
-static bool bf3_wants_phase(double gflop_phase, int C, double pix_phase) {
+static const int g_bf3_min_m = env_int("MUVO_BF3_MIN_M", 32);   // smallest row count on bf16x3 (half of the 64-row tile idles at 32; still 1.4x the fp32 kernel)
+// nphase: sub-pixel phases of the operation being planned (work / pixels are per phase)
+static bool bf3_wants_phase(double gflop_phase, int C, double pix_phase, int nphase) {
   if (!bf3_default_policy()) return gflop_phase >= bf3_min_gflop();
-  static const double pg = getenv("MUVO_BF16X3_POLICY_GFLOP") ? atof(getenv("MUVO_BF16X3_POLICY_GFLOP")) : 0.1;
-  static const double pp = getenv("MUVO_BF16X3_POLICY_PIXELS") ? atof(getenv("MUVO_BF16X3_POLICY_PIXELS")) : 256.0;
+  static const double pg = env_double("MUVO_BF16X3_POLICY_GFLOP", 0.1);
+  static const double pp = env_double("MUVO_BF16X3_POLICY_PIXELS", 256.0);
   // (few result pixels are fine when the reduction is long: the bf16x3 kernel then splits K, bf3_fwd_ksplit)
-  static const int long_c = getenv("MUVO_BF16X3_POLICY_LONG_C") ? atoi(getenv("MUVO_BF16X3_POLICY_LONG_C")) : 128;
-  return gflop_phase * t_nphase >= pg && (pix_phase * t_nphase >= pp || C >= long_c) && C >= 16;
+  static const int long_c = env_int("MUVO_BF16X3_POLICY_LONG_C", 128);
+  return gflop_phase * nphase >= pg && (pix_phase * nphase >= pp || C >= long_c) && C >= 16;
 }
 
-static thread_local int t_force_family = 0;   // +1 / -1: make this phase bf16x3 / fp32 regardless of its own size (see below)
 // does the small-channel 3x3x3 conv of this direction run on its bf16x3 kernel (conv_vox.hip)?  Same policy as the
 // implicit-GEMM family: bf16x3 mode and at least MUVO_BF16X3_MIN_GFLOP of work per batch item.
 static bool vox_uses_bf3(const muvo_conv_desc* d, int dgrad);
@@ -508,7 +505,14 @@ static bool vox_uses_bf3(const muvo_conv_desc* d, int dgrad) {
   return gflop >= bf3_min_gflop();
 }
 
-static double bf3_wgrad_min_gflop();
+// Weight gradients are leaves of the backward graph (their rounding error does not propagate into other gradients), so
+// they can go to bf16x3 at a lower work threshold than forward / data-gradient.
+static double bf3_wgrad_min_gflop() {
+  static const double env_v = env_double("MUVO_BF16X3_WGRAD_MIN_GFLOP", -1.0);
+  if (env_v >= 0.0) return env_v;
+  if (bf3_default_policy()) return 0.05;
+  return bf3_min_gflop() < 0.5 ? bf3_min_gflop() : 0.5;   // follows muvo_conv_set_bf16x3_min_gflop
+}
 static bool vox_wgrad_uses_bf3(const muvo_conv_desc* d) {
   // (deterministic mode: the bf16x3 voxel weight gradient reduces its tiles with LDS float atomics; the exact-fp32 kernel with
   // ordered global adds takes over)
@@ -519,18 +523,28 @@ static bool vox_wgrad_uses_bf3(const muvo_conv_desc* d) {
 // the voxel weight-gradient kernels take this shape: the fp32 / bf16x3 pair, or a shape only the plane-streaming bf16x3 kernel serves
 static bool vox_wgrad_ok(const muvo_conv_desc* d) { return vox_wgrad_applicable(d) || (vox_wgrad_ps_only(d) && vox_wgrad_uses_bf3(d)); }
 
-static void finish_phase(ConvPhase& g) {
+// What a plan is built for.  mode: 0 exact fp32 layout everywhere, 1 bf16x3 where the policy wants it; allow_merge: sub-pixel
+// phases that read the same input offsets become one GEMM; force_family: +1 / -1 makes a phase bf16x3 / fp32 regardless of
+// its own size (0: the policy decides).
+struct PlanOpts { int mode; bool allow_merge; int force_family; };
+
+// a phase the bf16x3 kernels can take at all
+static bool bf3_structural(const ConvPhase& g) { return g.M >= g_bf3_min_m && (long)g.T * g.C >= 32; }
+
+// nphase: sub-pixel phases of the operation this phase belongs to
+static void finish_phase(ConvPhase& g, const PlanOpts& o, int nphase) {
   g.bf3 = 0;
   if (g.nmerge <= 1) {
     g.nmerge = 1;
     g.Msub = g.M;
     for (int a = 0; a < 3; ++a) g.mop[0][a] = g.op[a];
   }
-  // bf16x3 only where it pays: phases with >= MUVO_BF16X3_MIN_GFLOP (default 2) GFLOP of work per batch item, i.e.
-  // the ConvDecoder stacks and the widest DecoderDS conv; the rest (encoders, voxel trunk) stays on exact fp32 MFMA.
+  // bf16x3 only where it pays (bf3_wants_phase: built-in policy from 0.1 GFLOP of work per batch item, or the explicit
+  // MUVO_BF16X3_MIN_GFLOP), i.e. the ConvDecoder stacks and the widest DecoderDS conv; the rest (encoders, voxel trunk) stays
+  // on exact fp32 MFMA.
   const double gflop = 2.0 * g.Msub * g.T * g.C * (double)g.SD * g.SH * g.SW * 1e-9;   // per original phase
-  const bool structural = g.M >= g_bf3_min_m && (long)g.T * g.C >= 32;
-  if (t_plan_mode == 1 && structural && t_force_family >= 0 && (bf3_wants_phase(gflop, g.C, (double)g.SD * g.SH * g.SW) || t_force_family > 0)) {
+  if (o.mode == 1 && bf3_structural(g) && o.force_family >= 0 &&
+      (bf3_wants_phase(gflop, g.C, (double)g.SD * g.SH * g.SW, nphase) || o.force_family > 0)) {
     g.bf3 = 1;
     bf3_finish_phase(g);
     return;
@@ -542,14 +556,30 @@ static void finish_phase(ConvPhase& g) {
   g.npix = g.N * g.SD * g.SH * g.SW;
 }
 
-// "conv form": out pixel o, in = o*stride - pad + r*dil.  in_dims/out_dims are the roles in THIS op.
-static int build_conv_form(const muvo_conv_desc* d, const int* in_dims, const int* out_dims, int C, int M,
-                           long wsm, long wsc, ConvPhase* ph) {
+// the fields both forms share: a zeroed phase with the tensor extents, strides and weight strides of this operation
+static ConvPhase phase_geometry(int N, const int* in_dims, const int* out_dims, int C, int M, long wsm, long wsc) {
   ConvPhase g;
   memset(&g, 0, sizeof(g));
-  g.N = d->N; g.C = C; g.M = M;
+  g.N = N; g.C = C; g.M = M;
   g.ID = in_dims[0]; g.IH = in_dims[1]; g.IW = in_dims[2];
   g.OD = out_dims[0]; g.OH = out_dims[1]; g.OW = out_dims[2];
+  g.in_sC = g.ID * g.IH * g.IW; g.out_sC = g.OD * g.OH * g.OW;
+  g.in_sN = (long)C * g.in_sC; g.out_sN = (long)M * g.out_sC;
+  g.wsm = wsm; g.wsc = wsc;
+  return g;
+}
+
+// ConvPhase::tap_d entry of an input offset; false when an axis is outside the packed range
+static bool pack_tap(int dz, int dy, int dx, int* packed) {
+  if (dz <= -120 || dz >= 120 || dy <= -120 || dy >= 120 || dx <= -120 || dx >= 120) return false;
+  *packed = ((dz + 128) << 16) | ((dy + 128) << 8) | (dx + 128);
+  return true;
+}
+
+// "conv form": out pixel o, in = o*stride - pad + r*dil.  in_dims/out_dims are the roles in THIS op.
+static int build_conv_form(const muvo_conv_desc* d, const int* in_dims, const int* out_dims, int C, int M,
+                           long wsm, long wsc, const PlanOpts& opts, ConvPhase* ph) {
+  ConvPhase g = phase_geometry(d->N, in_dims, out_dims, C, M, wsm, wsc);
   g.SD = g.OD; g.SH = g.OH; g.SW = g.OW;
   int T = 0;
   for (int a = 0; a < 3; ++a) { g.os[a] = 1; g.op[a] = 0; g.is[a] = d->stride[a]; g.ib[a] = -d->pad[a]; }
@@ -558,18 +588,12 @@ static int build_conv_form(const muvo_conv_desc* d, const int* in_dims, const in
   for (int kz = 0; kz < d->ksz[0]; ++kz)
     for (int ky = 0; ky < d->ksz[1]; ++ky)
       for (int kx = 0; kx < d->ksz[2]; ++kx) {
-        const int dz = kz * d->dil[0], dy = ky * d->dil[1], dx = kx * d->dil[2];
-        MUVO_CHECK_ARG(dz < 120 && dy < 120 && dx < 120, "conv: tap delta out of range");
-        g.tap_d[T] = ((dz + 128) << 16) | ((dy + 128) << 8) | (dx + 128);
+        MUVO_CHECK_ARG(pack_tap(kz * d->dil[0], ky * d->dil[1], kx * d->dil[2], &g.tap_d[T]), "conv: tap delta out of range");
         g.tap_w[T] = (kz * d->ksz[1] + ky) * d->ksz[2] + kx;
         ++T;
       }
   g.T = T;
-  g.in_sC = g.ID * g.IH * g.IW; g.out_sC = g.OD * g.OH * g.OW;
-  g.in_sN = (long)C * g.in_sC; g.out_sN = (long)M * g.out_sC;
-  g.wsm = wsm; g.wsc = wsc;
-  t_nphase = 1;
-  finish_phase(g);
+  finish_phase(g, opts, 1);
   *ph = g;
   return MUVO_OK;
 }
@@ -577,20 +601,16 @@ static int build_conv_form(const muvo_conv_desc* d, const int* in_dims, const in
 // "transposed form": for input p, out h = p*stride - pad + r*dil.  One phase per output residue.
 // Returns number of phases via *nph (phases with empty sub-grids are dropped).
 static int build_transposed_form(const muvo_conv_desc* d, const int* in_dims, const int* out_dims, int C, int M,
-                                 long wsm, long wsc, ConvPhase* phs, int* nph) {
+                                 long wsm, long wsc, const PlanOpts& opts, ConvPhase* phs, int* nph) {
   int count = 0;
   const int s0 = d->stride[0], s1 = d->stride[1], s2 = d->stride[2];
   MUVO_CHECK_ARG(s0 * s1 * s2 <= 8, "transposed form: too many phases");
-  t_nphase = s0 * s1 * s2;
+  const int nphase = s0 * s1 * s2;
   for (int p0 = 0; p0 < s0; ++p0)
     for (int p1 = 0; p1 < s1; ++p1)
       for (int p2 = 0; p2 < s2; ++p2) {
         const int php[3] = {p0, p1, p2};
-        ConvPhase g;
-        memset(&g, 0, sizeof(g));
-        g.N = d->N; g.C = C; g.M = M;
-        g.ID = in_dims[0]; g.IH = in_dims[1]; g.IW = in_dims[2];
-        g.OD = out_dims[0]; g.OH = out_dims[1]; g.OW = out_dims[2];
+        ConvPhase g = phase_geometry(d->N, in_dims, out_dims, C, M, wsm, wsc);
         int sub[3];
         bool empty = false;
         // per-axis tap lists
@@ -619,18 +639,12 @@ static int build_transposed_form(const muvo_conv_desc* d, const int* in_dims, co
         for (int a0 = 0; a0 < nt[0]; ++a0)
           for (int a1 = 0; a1 < nt[1]; ++a1)
             for (int a2 = 0; a2 < nt[2]; ++a2) {
-              const int dz = td[0][a0], dy = td[1][a1], dx = td[2][a2];
-              MUVO_CHECK_ARG(dz > -120 && dz < 120 && dy > -120 && dy < 120 && dx > -120 && dx < 120,
-                             "transposed form: tap delta out of range");
-              g.tap_d[T] = ((dz + 128) << 16) | ((dy + 128) << 8) | (dx + 128);
+              MUVO_CHECK_ARG(pack_tap(td[0][a0], td[1][a1], td[2][a2], &g.tap_d[T]), "transposed form: tap delta out of range");
               g.tap_w[T] = (tr[0][a0] * d->ksz[1] + tr[1][a1]) * d->ksz[2] + tr[2][a2];
               ++T;
             }
         g.T = T;
-        g.in_sC = g.ID * g.IH * g.IW; g.out_sC = g.OD * g.OH * g.OW;
-        g.in_sN = (long)C * g.in_sC; g.out_sN = (long)M * g.out_sC;
-        g.wsm = wsm; g.wsc = wsc;
-        finish_phase(g);
+        finish_phase(g, opts, nphase);
         phs[count++] = g;
       }
   // One arithmetic per operation: the sub-pixel phases of a strided data gradient differ in tap count (5x5 stride 2:
@@ -642,24 +656,22 @@ static int build_transposed_form(const muvo_conv_desc* d, const int* in_dims, co
     bool any = false, all_struct = true;
     for (int i = 0; i < count; ++i) {
       any = any || phs[i].bf3;
-      all_struct = all_struct && phs[i].M >= g_bf3_min_m && (long)phs[i].T * phs[i].C >= 32;
+      all_struct = all_struct && bf3_structural(phs[i]);
     }
     if (any) {
-      t_force_family = all_struct ? 1 : -1;
+      const PlanOpts forced = {opts.mode, opts.allow_merge, all_struct ? 1 : -1};
       for (int i = 0; i < count; ++i)
-        if ((phs[i].bf3 != 0) != all_struct) finish_phase(phs[i]);
-      t_force_family = 0;
+        if ((phs[i].bf3 != 0) != all_struct) finish_phase(phs[i], forced, nphase);
     }
   }
   // merge the phases into one GEMM when they all read the same input offsets (see conv_plan.h)
-  static const long merge_max_rows = getenv("MUVO_MERGE_MAX_ROWS") ? atol(getenv("MUVO_MERGE_MAX_ROWS")) : 2048;   // (1024: the 512-channel stages as four launches, +0.8 ms/step)
-  if (t_allow_merge && count > 1 && count <= 8 && M % 32 == 0 && (long)count * M <= merge_max_rows) {
+  static const long merge_max_rows = env_int("MUVO_MERGE_MAX_ROWS", 2048);   // (1024: the 512-channel stages as four launches, +0.8 ms/step)
+  if (opts.allow_merge && count > 1 && count <= 8 && M % 32 == 0 && (long)count * M <= merge_max_rows) {
     // The phases must cover sub-grids of one size.  Their tap sets may differ (5x5 stride 2: 9 / 6 / 6 / 4 taps; the data
     // gradient of a 3x3 stride-2 convolution: 1 / 2 / 2 / 4): the merged GEMM runs over the UNION of the input offsets and a
     // row group without a tap packs zero weights there (tap_wm = -1).  That is up to 1.8x the exact work, but one launch with
     // count x M rows on the big tiles instead of `count` launches of a few taps each - taken when at least half of the
-    // (group, tap) pairs are real (MUVO_MERGE_UNION=0: only identical tap sets, as before).
-    static const int allow_union = getenv("MUVO_MERGE_UNION") ? atoi(getenv("MUVO_MERGE_UNION")) : 1;
+    // (group, tap) pairs are real (MUVO_MERGE_UNION_MIN_PCT).
     bool same_grid = true, same_taps = true;
     int real = 0;
     for (int i = 0; i < count; ++i) {
@@ -676,8 +688,8 @@ static int build_transposed_form(const muvo_conv_desc* d, const int* in_dims, co
         while (k < nu && uni[k] != phs[i].tap_d[t]) ++k;
         if (k == nu) { if (nu < MAX_TAPS) uni[nu++] = phs[i].tap_d[t]; else fits = false; }
       }
-    static const int min_pct = getenv("MUVO_MERGE_UNION_MIN_PCT") ? atoi(getenv("MUVO_MERGE_UNION_MIN_PCT")) : 50;
-    const bool merge = same_grid && (same_taps || (allow_union && fits && nu > 1 && 100 * real >= min_pct * count * nu));
+    static const int min_pct = env_int("MUVO_MERGE_UNION_MIN_PCT", 50);
+    const bool merge = same_grid && (same_taps || (fits && nu > 1 && 100 * real >= min_pct * count * nu));
     if (merge) {
       ConvPhase g = phs[0];
       g.nmerge = count;
@@ -694,7 +706,7 @@ static int build_transposed_form(const muvo_conv_desc* d, const int* in_dims, co
         }
       }
       for (int t = 0; t < nu; ++t) g.tap_w[t] = g.tap_wm[0][t] >= 0 ? g.tap_wm[0][t] : 0;
-      finish_phase(g);
+      finish_phase(g, opts, nphase);
       phs[0] = g;
       count = 1;
     }
@@ -703,45 +715,45 @@ static int build_transposed_form(const muvo_conv_desc* d, const int* in_dims, co
   return MUVO_OK;
 }
 
+// operations of a convolution layer; OP_FWD / OP_DGRAD also index the two directions of a plan
+enum { OP_FWD = 0, OP_DGRAD = 1, OP_WGRAD = 2 };
+
 struct ConvPlan {
-  ConvPhase fwd[8]; int nfwd;
-  ConvPhase dgr[8]; int ndgr;
-  long fwd_floats, dgr_floats;
+  ConvPhase ph[2][8];   // [direction][phase]
+  int n[2];             // phases per direction
+  long floats[2];       // packed-weight floats per direction
 };
 
-static int build_plan(const muvo_conv_desc* d, ConvPlan* pl, int mode = -1, bool allow_merge = true) {
+static int build_plan(const muvo_conv_desc* d, ConvPlan* pl, const PlanOpts& opts) {
   int rc = check_desc(d);
   if (rc) return rc;
-  t_plan_mode = mode < 0 ? conv_mode() : mode;
-  t_allow_merge = allow_merge;
   const long taps = (long)d->ksz[0] * d->ksz[1] * d->ksz[2];
   if (!d->transposed) {
     // weight [Cout][Cin][taps]
-    pl->nfwd = 1;
-    rc = build_conv_form(d, d->in_sz, d->out_sz, d->Cin, d->Cout, d->Cin * taps, taps, &pl->fwd[0]);
+    pl->n[OP_FWD] = 1;
+    rc = build_conv_form(d, d->in_sz, d->out_sz, d->Cin, d->Cout, d->Cin * taps, taps, opts, &pl->ph[OP_FWD][0]);
     if (rc) return rc;
-    rc = build_transposed_form(d, d->out_sz, d->in_sz, d->Cout, d->Cin, taps, d->Cin * taps, pl->dgr, &pl->ndgr);
+    rc = build_transposed_form(d, d->out_sz, d->in_sz, d->Cout, d->Cin, taps, d->Cin * taps, opts, pl->ph[OP_DGRAD], &pl->n[OP_DGRAD]);
     if (rc) return rc;
   } else {
     // weight [Cin][Cout][taps]
-    rc = build_transposed_form(d, d->in_sz, d->out_sz, d->Cin, d->Cout, taps, d->Cout * taps, pl->fwd, &pl->nfwd);
+    rc = build_transposed_form(d, d->in_sz, d->out_sz, d->Cin, d->Cout, taps, d->Cout * taps, opts, pl->ph[OP_FWD], &pl->n[OP_FWD]);
     if (rc) return rc;
-    pl->ndgr = 1;
-    rc = build_conv_form(d, d->out_sz, d->in_sz, d->Cout, d->Cin, d->Cout * taps, taps, &pl->dgr[0]);
+    pl->n[OP_DGRAD] = 1;
+    rc = build_conv_form(d, d->out_sz, d->in_sz, d->Cout, d->Cin, d->Cout * taps, taps, opts, &pl->ph[OP_DGRAD][0]);
     if (rc) return rc;
   }
-  long off = 0;
-  for (int i = 0; i < pl->nfwd; ++i) { pl->fwd[i].wp_off = off; off += (long)pl->fwd[i].Kp * pl->fwd[i].Mp; }
-  pl->fwd_floats = off;
-  off = 0;
-  for (int i = 0; i < pl->ndgr; ++i) { pl->dgr[i].wp_off = off; off += (long)pl->dgr[i].Kp * pl->dgr[i].Mp; }
-  pl->dgr_floats = off;
+  for (int dir = 0; dir < 2; ++dir) {
+    long off = 0;
+    for (int i = 0; i < pl->n[dir]; ++i) { pl->ph[dir][i].wp_off = off; off += (long)pl->ph[dir][i].Kp * pl->ph[dir][i].Mp; }
+    pl->floats[dir] = off;
+  }
   return MUVO_OK;
 }
 
 // work threshold (per launch) above which the fp32-staged kernels use bf16x3 products in the bf16x3 mode
 static double f32_bf3_min_gflop() {
-  static const double v = getenv("MUVO_F32_BF3_MIN_GFLOP") ? atof(getenv("MUVO_F32_BF3_MIN_GFLOP")) : 2.0;
+  static const double v = env_double("MUVO_F32_BF3_MIN_GFLOP", 2.0);
   return v;
 }
 
@@ -765,18 +777,18 @@ static int phase_ksplit(const ConvPhase& g) {
   const int bm = g.M > 64 ? 128 : (g.M > 32 ? 64 : 32);
   const long blocks = (long)cdiv(g.npix, 128) * cdiv(g.M, bm);
   const int nk = g.Kp / 16;
-  static const int min_steps = getenv("MUVO_KSPLIT_MIN_STEPS") ? atoi(getenv("MUVO_KSPLIT_MIN_STEPS")) : 8;
+  static const int min_steps = env_int("MUVO_KSPLIT_MIN_STEPS", 8);
   if (blocks >= 192 || nk < 4 * min_steps) return 1;
-  static const int ks_tgt = getenv("MUVO_KSPLIT_BLOCKS") ? atoi(getenv("MUVO_KSPLIT_BLOCKS")) : 384;   // measured best of 128 ... 3072
+  static const int ks_tgt = env_int("MUVO_KSPLIT_BLOCKS", 384);   // measured best of 128 ... 3072
   int ks = cdiv(ks_tgt, blocks);
   if (ks > nk / min_steps) ks = nk / min_steps;
   return ks < 1 ? 1 : ks;
 }
 
 static int launch_fwd_phase(const ConvPhase& g, const float* in, const float* wp, const float* bias, float* out,
-                            int act, float slope, hipStream_t st, const void* ws, int ksplit) {
+                            int act, float slope, hipStream_t st, const void* ws, int ksplit, const Bf3Head* head) {
   if (g.npix <= 0) return MUVO_OK;
-  if (g.bf3) return bf3_launch_fwd_phase(g, ws, wp, bias, out, act, slope, st, ksplit);
+  if (g.bf3) return bf3_launch_fwd_phase(g, ws, wp, bias, out, act, slope, st, ksplit, head);
   if (g.M > 64) launch_fwd_run<128, 128, 2, 2>(g, in, wp, bias, out, act, slope, st, ksplit);
   else if (g.M > 32) launch_fwd_run<64, 128, 2, 2>(g, in, wp, bias, out, act, slope, st, ksplit);
   else launch_fwd_run<32, 128, 1, 4>(g, in, wp, bias, out, act, slope, st, ksplit);
@@ -784,37 +796,128 @@ static int launch_fwd_phase(const ConvPhase& g, const float* in, const float* wp
   return MUVO_OK;
 }
 
-static int launch_wgrad_phase(const ConvPhase& g, const float* in, const float* dout, float* dwp, hipStream_t st) {
-  if (g.npix <= 0 || g.T == 0) return MUVO_OK;
+template <int BN, int WM, int WN>
+static int launch_wgrad_tile(const ConvPhase& g, const float* in, const float* dout, float* dwp, hipStream_t st) {
   const int ntiles = cdiv(g.npix, 32);
-  const int rows = g.Kp;
-  int bm, bn;
-  if (g.M > 64) bn = 128; else if (g.M > 32) bn = 64; else bn = 32;
-  bm = 128;
-  const int gx = cdiv(rows, bm), gy = cdiv(g.M, bn);
+  const int gx = cdiv(g.Kp, 128), gy = cdiv(g.M, BN);
   // split-K: aim for >= 2048 blocks, each with >= 4 pixel tiles (these launches are latency-bound: more, shorter ranges win)
-  static const int tgt = getenv("MUVO_F32_WGRAD_BLOCKS") ? atoi(getenv("MUVO_F32_WGRAD_BLOCKS")) : 2048;
-  static const int mint = getenv("MUVO_F32_WGRAD_MINTILES") ? atoi(getenv("MUVO_F32_WGRAD_MINTILES")) : 4;    // measured 3.4 -> 2.9 ms/step vs (1024, 8)
+  static const int tgt = env_int("MUVO_F32_WGRAD_BLOCKS", 2048);
+  static const int mint = env_int("MUVO_F32_WGRAD_MINTILES", 4);    // measured 3.4 -> 2.9 ms/step vs (1024, 8)
   int nsplit = cdiv(tgt, gx * gy);
   if (nsplit > cdiv(ntiles, mint)) nsplit = cdiv(ntiles, mint);
   if (nsplit < 1 || muvo_det()) nsplit = 1;       // deterministic mode: one workgroup per tile walks all pixels
   const int tps = cdiv(ntiles, nsplit);
   nsplit = cdiv(ntiles, tps);
   dim3 grid(gx, gy, nsplit);
-  // bf16x3 mode: the products of this kernel run as three bf16 MFMAs too (MUVO_F32_WGRAD_BF3=0: fp32 MFMAs as in the exact mode)
-  static const bool want_bf3 = !getenv("MUVO_F32_WGRAD_BF3") || atoi(getenv("MUVO_F32_WGRAD_BF3")) != 0;
-  const bool b3 = want_bf3 && conv_mode() == 1 &&
+  // bf16x3 mode: the products of this kernel run as three bf16 MFMAs too
+  const bool b3 = conv_mode() == 1 &&
                   2e-9 * (double)g.M * (double)g.npix * (double)g.T * (double)g.C >= f32_bf3_min_gflop();   // large launches only (the stems)
-  if (b3) {
-    if (bn == 128) hipLaunchKernelGGL((conv_wgrad_kernel<128, 128, 2, 2, true>), grid, dim3(256), 0, st, g, in, dout, dwp, tps);
-    else if (bn == 64) hipLaunchKernelGGL((conv_wgrad_kernel<128, 64, 2, 2, true>), grid, dim3(256), 0, st, g, in, dout, dwp, tps);
-    else hipLaunchKernelGGL((conv_wgrad_kernel<128, 32, 4, 1, true>), grid, dim3(256), 0, st, g, in, dout, dwp, tps);
-  } else {
-    if (bn == 128) hipLaunchKernelGGL((conv_wgrad_kernel<128, 128, 2, 2, false>), grid, dim3(256), 0, st, g, in, dout, dwp, tps);
-    else if (bn == 64) hipLaunchKernelGGL((conv_wgrad_kernel<128, 64, 2, 2, false>), grid, dim3(256), 0, st, g, in, dout, dwp, tps);
-    else hipLaunchKernelGGL((conv_wgrad_kernel<128, 32, 4, 1, false>), grid, dim3(256), 0, st, g, in, dout, dwp, tps);
-  }
+  if (b3) hipLaunchKernelGGL((conv_wgrad_kernel<128, BN, WM, WN, true>), grid, dim3(256), 0, st, g, in, dout, dwp, tps);
+  else hipLaunchKernelGGL((conv_wgrad_kernel<128, BN, WM, WN, false>), grid, dim3(256), 0, st, g, in, dout, dwp, tps);
   MUVO_CHECK_LAUNCH("conv_wgrad_kernel");
+  return MUVO_OK;
+}
+
+static int launch_wgrad_phase(const ConvPhase& g, const float* in, const float* dout, float* dwp, hipStream_t st) {
+  if (g.npix <= 0 || g.T == 0) return MUVO_OK;
+  if (g.M > 64) return launch_wgrad_tile<128, 2, 2>(g, in, dout, dwp, st);
+  if (g.M > 32) return launch_wgrad_tile<64, 2, 2>(g, in, dout, dwp, st);
+  return launch_wgrad_tile<32, 4, 1>(g, in, dout, dwp, st);
+}
+
+// does the weight gradient of this conv run on the bf16x3 kernel (conv_bf3.hip)?  pf: a plan in the fp32 layout (mode 0), whose
+// forward phases the weight gradient walks.  Every phase must have >= 32 output and >= 32 input channels.  Explicit threshold:
+// per-phase work as for forward/dgrad; built-in policy: >= 0.05 GFLOP per batch item over the whole operation and more than
+// one tap (1x1 weight gradients are faster on the fp32 kernel).
+static const int g_bf3_wgrad_min_m = env_int("MUVO_BF3_WGRAD_MIN_M", 32);
+static bool wgrad_uses_bf3(const ConvPlan& pf) {
+  if (conv_mode() != 1) return false;
+  const bool dflt = bf3_default_policy() && !getenv("MUVO_BF16X3_WGRAD_MIN_GFLOP");
+  double total = 0.0;
+  int taps = 0;
+  for (int i = 0; i < pf.n[OP_FWD]; ++i) {
+    const ConvPhase& g = pf.ph[OP_FWD][i];
+    const double gflop = 2.0 * g.Msub * g.T * g.C * (double)g.SD * g.SH * g.SW * 1e-9;   // per original phase
+    if (g.Msub < g_bf3_wgrad_min_m || g.C < 32 || g.Msub % 16 != 0 && g.nmerge > 1) return false;
+    if (!dflt && gflop < bf3_wgrad_min_gflop()) return false;
+    total += gflop * g.nmerge;
+    taps += g.T * g.nmerge;
+  }
+  if (dflt && (total < bf3_wgrad_min_gflop() || taps <= 1)) return false;
+  return pf.n[OP_FWD] > 0;
+}
+
+// ------------------------------------------------------------------------------------------------
+// Routing: which kernel family serves (desc, op), in ONE place.  The order is: 1x1 head kernels (conv_pw.hip), the
+// small-channel Conv3d kernels (conv_vox.hip), then the implicit-GEMM phases, bf16x3 where the plan says so.  The values are
+// those of muvo_conv_kernel_family.
+// ------------------------------------------------------------------------------------------------
+enum { FAM_GEMM_F32 = 0, FAM_GEMM_BF3 = 1, FAM_VOX_F32 = 2, FAM_PW = 3, FAM_VOX_BF3 = 4 };
+static bool fam_is_vox(int fam) { return fam == FAM_VOX_F32 || fam == FAM_VOX_BF3; }
+
+// pl: the plan the op is decided on - forward / data gradient: the default plan; weight gradient: the unmerged fp32-layout plan
+static int route_family(const muvo_conv_desc* d, int op, const ConvPlan& pl) {
+  if (pw_applicable(d)) return FAM_PW;
+  if (op == OP_WGRAD) {
+    if (vox_wgrad_ok(d)) return vox_wgrad_uses_bf3(d) ? FAM_VOX_BF3 : FAM_VOX_F32;
+    return wgrad_uses_bf3(pl) ? FAM_GEMM_BF3 : FAM_GEMM_F32;
+  }
+  if (op == OP_FWD ? vox_fwd_ok(d) : vox_dgrad_ok(d)) return vox_uses_bf3(d, op) ? FAM_VOX_BF3 : FAM_VOX_F32;
+  for (int i = 0; i < pl.n[op]; ++i)
+    if (pl.ph[op][i].bf3) return FAM_GEMM_BF3;      // (the phases of one direction all run on the same family, build_transposed_form)
+  return FAM_GEMM_F32;
+}
+
+struct ConvRoute {
+  int family;
+  ConvPlan plan;          // GEMM families: the plan that is launched
+  const ConvPhase* ph;    // its phases for this op (weight gradient: the forward phases)
+  int nph;
+};
+
+static PlanOpts default_opts() { return PlanOpts{conv_mode(), true, 0}; }
+static const PlanOpts kWgradOpts = {0, false, 0};        // the weight gradient walks forward phases in the fp32 layout
+static const PlanOpts kWgradMergedOpts = {0, true, 0};
+
+// Validates the descriptor, builds the plan of the op and names its family.  Weight gradient: the unmerged plan decides; when
+// the bf16x3 kernel takes it, the merged plan is launched instead if the bf16x3 kernel takes that too (it understands merged
+// sub-pixel phases: one GEMM with nmerge * Cout rows).
+static int route_conv(const muvo_conv_desc* d, int op, ConvRoute* r) {
+  const int dir = op == OP_WGRAD ? OP_FWD : op;
+  int rc = build_plan(d, &r->plan, op == OP_WGRAD ? kWgradOpts : default_opts());
+  if (rc) return rc;
+  r->family = route_family(d, op, r->plan);
+  if (op == OP_WGRAD && r->family == FAM_GEMM_BF3) {
+    ConvPlan pm;
+    if (build_plan(d, &pm, kWgradMergedOpts) == MUVO_OK && wgrad_uses_bf3(pm)) r->plan = pm;
+  }
+  r->ph = r->plan.ph[dir];
+  r->nph = r->plan.n[dir];
+  return MUVO_OK;
+}
+
+// packs one direction of a plan from the PyTorch-layout weight
+static int pack_phases(const ConvPhase* ph, int nph, const float* w, float* wp, hipStream_t st) {
+  for (int i = 0; i < nph; ++i) {
+    const long total = (long)ph[i].Kp * ph[i].Mp;
+    if (total == 0) continue;
+    if (ph[i].bf3) {
+      const int rc = bf3_pack_phase(ph[i], w, wp, st);
+      if (rc) return rc;
+      continue;
+    }
+    hipLaunchKernelGGL(pack_weights_kernel, dim3(ew_grid(total)), dim3(256), 0, st, ph[i], w, wp);
+  }
+  return MUVO_OK;
+}
+
+// db[m] += sum_{n,s} dy[n][m][s]
+static int launch_bias_grad(const float* dy, float* db, int N, int M, long S, hipStream_t st) {
+  int chunks = cdiv((long)N * S, 65536);
+  if (chunks > 64) chunks = 64;
+  if (muvo_det()) chunks = 1;
+  hipLaunchKernelGGL(bias_grad_kernel, dim3(M, chunks), dim3(256), 0, st, dy, db, N, M, S);
+  MUVO_CHECK_LAUNCH("bias_grad_kernel");
   return MUVO_OK;
 }
 
@@ -838,30 +941,34 @@ int muvo_conv_set_bf16x3_min_gflop(double gflop_per_item) {
 }
 
 int muvo_conv_pack_sizes(const muvo_conv_desc* d, int64_t* fwd_floats, int64_t* dgrad_floats) {
-  ConvPlan pl;
-  int rc = build_plan(d, &pl);
+  ConvRoute r;
+  int rc = route_conv(d, OP_FWD, &r);
   if (rc) return rc;
-  {  // wgrad always runs on the fp32-layout plan and uses fwd_floats of scratch
+  long floats[2] = {r.plan.floats[OP_FWD], r.plan.floats[OP_DGRAD]};
+  {  // wgrad always runs on the fp32-layout plan and uses its forward floats of scratch
     ConvPlan pf;
-    rc = build_plan(d, &pf, 0, false);
+    rc = build_plan(d, &pf, kWgradOpts);
     if (rc) return rc;
-    if (pf.fwd_floats > pl.fwd_floats) pl.fwd_floats = pf.fwd_floats;
+    if (pf.floats[OP_FWD] > floats[OP_FWD]) floats[OP_FWD] = pf.floats[OP_FWD];
   }
-  // the small-channel Conv3d path (conv_vox.hip) keeps its own layout in the same buffers
-  if (vox_fwd_ok(d) && vox_pack_floats(d) > pl.fwd_floats) pl.fwd_floats = vox_pack_floats(d);
-  if (vox_dgrad_ok(d) && vox_pack_floats(d) > pl.dgr_floats) pl.dgr_floats = vox_pack_floats(d);
-  if (fwd_floats) *fwd_floats = pl.fwd_floats;
-  if (dgrad_floats) *dgrad_floats = pl.dgr_floats;
+  // the small-channel Conv3d path (conv_vox.hip) keeps its own layout in the same buffers (the 1x1 heads are no Conv3d shapes)
+  const int fam[2] = {r.family, route_family(d, OP_DGRAD, r.plan)};
+  for (int dir = 0; dir < 2; ++dir)
+    if (fam_is_vox(fam[dir]) && vox_pack_floats(d) > floats[dir]) floats[dir] = vox_pack_floats(d);
+  if (fwd_floats) *fwd_floats = floats[OP_FWD];
+  if (dgrad_floats) *dgrad_floats = floats[OP_DGRAD];
   return MUVO_OK;
 }
 
 int muvo_conv_pack_weights(const muvo_conv_desc* d, const float* w, float* wp_fwd, float* wp_dgrad, void* stream) {
-  ConvPlan pl;
-  int rc = build_plan(d, &pl);
+  ConvRoute r;
+  int rc = route_conv(d, OP_FWD, &r);
   if (rc) return rc;
   MUVO_CHECK_ARG(w != nullptr, "conv_pack_weights: w is null");
   hipStream_t st = (hipStream_t)stream;
-  if (pw_applicable(d)) {  // heads: the kernels read the PyTorch layout directly
+  float* wp[2] = {wp_fwd, wp_dgrad};
+  const int fam[2] = {r.family, route_family(d, OP_DGRAD, r.plan)};
+  if (fam[OP_FWD] == FAM_PW) {  // heads: the kernels read the PyTorch layout directly
     const size_t bytes = sizeof(float) * d->Cout * d->Cin;
     if ((wp_fwd && hipMemcpyAsync(wp_fwd, w, bytes, hipMemcpyDeviceToDevice, st) != hipSuccess) ||
         (wp_dgrad && hipMemcpyAsync(wp_dgrad, w, bytes, hipMemcpyDeviceToDevice, st) != hipSuccess)) {
@@ -870,37 +977,16 @@ int muvo_conv_pack_weights(const muvo_conv_desc* d, const float* w, float* wp_fw
     }
     return MUVO_OK;
   }
-  if (wp_fwd && vox_fwd_ok(d)) {
-    rc = vox_pack(d, w, wp_fwd, 0, st, vox_uses_bf3(d, 0));
-    if (rc) return rc;
-    wp_fwd = nullptr;
-  }
-  if (wp_dgrad && vox_dgrad_ok(d)) {
-    rc = vox_pack(d, w, wp_dgrad, 1, st, vox_uses_bf3(d, 1));
-    if (rc) return rc;
-    wp_dgrad = nullptr;
-  }
-  if (wp_fwd)
-    for (int i = 0; i < pl.nfwd; ++i) {
-      const long total = (long)pl.fwd[i].Kp * pl.fwd[i].Mp;
-      if (total == 0) continue;
-      if (pl.fwd[i].bf3) {
-        rc = bf3_pack_phase(pl.fwd[i], w, wp_fwd, st);
-        if (rc) return rc;
-        continue;
-      }
-      hipLaunchKernelGGL(pack_weights_kernel, dim3(ew_grid(total)), dim3(256), 0, st, pl.fwd[i], w, wp_fwd);
+  // each direction on its own: the voxel kernels' layout (first, as ever), or the phases of the plan
+  for (int dir = 0; dir < 2; ++dir)
+    if (wp[dir] && fam_is_vox(fam[dir])) {
+      rc = vox_pack(d, w, wp[dir], dir, st, fam[dir] == FAM_VOX_BF3);
+      if (rc) return rc;
     }
-  if (wp_dgrad)
-    for (int i = 0; i < pl.ndgr; ++i) {
-      const long total = (long)pl.dgr[i].Kp * pl.dgr[i].Mp;
-      if (total == 0) continue;
-      if (pl.dgr[i].bf3) {
-        rc = bf3_pack_phase(pl.dgr[i], w, wp_dgrad, st);
-        if (rc) return rc;
-        continue;
-      }
-      hipLaunchKernelGGL(pack_weights_kernel, dim3(ew_grid(total)), dim3(256), 0, st, pl.dgr[i], w, wp_dgrad);
+  for (int dir = 0; dir < 2; ++dir)
+    if (wp[dir] && !fam_is_vox(fam[dir])) {
+      rc = pack_phases(r.plan.ph[dir], r.plan.n[dir], w, wp[dir], st);
+      if (rc) return rc;
     }
   MUVO_CHECK_LAUNCH("pack_weights_kernel");
   return MUVO_OK;
@@ -908,76 +994,43 @@ int muvo_conv_pack_weights(const muvo_conv_desc* d, const float* w, float* wp_fw
 
 // bytes of caller-provided workspace needed by forward (op 0) / dgrad (op 1): the channels-last bf16 hi/lo copy of the
 // activation operand when a phase of that direction runs on the bf16x3 kernel, else 0
-static bool wgrad_uses_bf3(const ConvPlan& pf);
 int64_t muvo_conv_workspace_bytes(const muvo_conv_desc* d, int op) {
-  ConvPlan pl;
-  if (op >= 2) {  // weight gradient: split planes of x (op 2) and of dy (op 3)
-    if (build_plan(d, &pl, 0, false)) return -1;
-    if (pw_applicable(d) || vox_wgrad_ok(d) || !wgrad_uses_bf3(pl)) return 0;
+  ConvRoute r;
+  if (route_conv(d, op >= 2 ? OP_WGRAD : (op == 0 ? OP_FWD : OP_DGRAD), &r)) return -1;
+  if (r.family != FAM_GEMM_BF3) return 0;
+  if (op >= 2)    // weight gradient: split planes of x (op 2) and of dy (op 3)
     return op == 2 ? bf3_workspace_bytes(d->N, d->Cin, (long)d->in_sz[0] * d->in_sz[1] * d->in_sz[2])
                    : bf3_workspace_bytes(d->N, d->Cout, (long)d->out_sz[0] * d->out_sz[1] * d->out_sz[2]);
-  }
-  if (build_plan(d, &pl)) return -1;
-  const ConvPhase* ph = op == 0 ? pl.fwd : pl.dgr;
-  const int nph = op == 0 ? pl.nfwd : pl.ndgr;
-  if (pw_applicable(d)) return 0;
-  if (op == 0 ? vox_fwd_ok(d) : vox_dgrad_ok(d)) return 0;
-  for (int i = 0; i < nph; ++i)
-    if (ph[i].bf3) return bf3_workspace_bytes(ph[i].N, ph[i].C, (long)ph[i].ID * ph[i].IH * ph[i].IW);
-  return 0;
+  const ConvPhase& g = r.ph[0];
+  return bf3_workspace_bytes(g.N, g.C, (long)g.ID * g.IH * g.IW);
 }
 
 // which kernel family serves this shape: 0 fp32 implicit GEMM (conv_gemm.hip), 1 bf16x3 (conv_bf3.hip),
 // 2 small-channel Conv3d on the 4x4x1 MFMA (conv_vox.hip), 3 decoder heads (conv_pw.hip), 4 small-channel Conv3d on the
 // bf16x3 16x16x32 kernel (conv_vox.hip); op 0 fwd, 1 dgrad, 2 wgrad
 int muvo_conv_kernel_family(const muvo_conv_desc* d, int op) {
-  ConvPlan pl;
-  if (pw_applicable(d)) return 3;
-  if (op == 2) {
-    if (build_plan(d, &pl, 0, false)) return -1;
-    if (vox_wgrad_ok(d)) return vox_wgrad_uses_bf3(d) ? 4 : 2;
-    return wgrad_uses_bf3(pl) ? 1 : 0;
-  }
-  if (build_plan(d, &pl)) return -1;
-  if (op == 0 ? vox_fwd_ok(d) : vox_dgrad_ok(d)) return vox_uses_bf3(d, op) ? 4 : 2;
-  const ConvPhase* ph = op == 0 ? pl.fwd : pl.dgr;
-  const int nph = op == 0 ? pl.nfwd : pl.ndgr;
-  for (int i = 0; i < nph; ++i)
-    if (ph[i].bf3) return 1;
-  return 0;
+  ConvRoute r;
+  if (route_conv(d, op == 2 ? OP_WGRAD : (op == 0 ? OP_FWD : OP_DGRAD), &r)) return -1;
+  return r.family;
 }
 
 // 1 when muvo_conv_kernel_family(d, op) == 1 and the launch uses the eight-wave ping-pong tiles (256x128 / 128x256;
 // weight gradient: conv_bf3_wgrad_pp_kernel), 0 otherwise (four-wave 64x128 tile / the smaller weight-gradient tiles)
 int muvo_conv_kernel_variant(const muvo_conv_desc* d, int op) {
-  if (muvo_conv_kernel_family(d, op) != 1) return 0;
-  ConvPlan pl;
-  if (op == 2) {
-    if (build_plan(d, &pl, 0, true) || !wgrad_uses_bf3(pl)) {
-      if (build_plan(d, &pl, 0, false)) return 0;
-    }
-    return pl.nfwd > 0 && bf3_wgrad_uses_pp(pl.fwd[0]) ? 1 : 0;
-  }
-  if (build_plan(d, &pl)) return 0;
-  const ConvPhase* ph = op == 0 ? pl.fwd : pl.dgr;
-  const int nph = op == 0 ? pl.nfwd : pl.ndgr;
-  return nph > 0 && bf3_fwd_uses_pp(ph[0]) ? 1 : 0;
+  ConvRoute r;
+  if (route_conv(d, op == 2 ? OP_WGRAD : (op == 0 ? OP_FWD : OP_DGRAD), &r) || r.family != FAM_GEMM_BF3 || r.nph < 1) return 0;
+  return (op == 2 ? bf3_wgrad_uses_pp(r.ph[0]) : bf3_fwd_uses_pp(r.ph[0])) ? 1 : 0;
 }
 
 static int run_phases(const ConvPhase* ph, int nph, const float* in, const float* wp, const float* bias, float* out, int act,
-                      float slope, void* ws, hipStream_t st, bool ws_valid = false) {
+                      float slope, void* ws, hipStream_t st, bool ws_valid = false, const Bf3Head* head = nullptr) {
   bool split_done = ws_valid;
   // split-K needs a zeroed output and a finishing bias/activation pass for the whole tensor, so all phases of the operation
   // switch together as soon as one of them wants it (the sub-pixel phases of a strided data gradient differ in tap count: a
   // one-tap phase alone would not, and used to keep its four-tap sibling on a serial 64-step loop); a phase that would not
   // split on its own runs with two K ranges
-  static const int any_rule = getenv("MUVO_KSPLIT_ANY") ? atoi(getenv("MUVO_KSPLIT_ANY")) : 1;
-  bool use_ksplit = nph > 0 && !any_rule, any_ks = false;
-  for (int i = 0; i < nph; ++i) {
-    use_ksplit = use_ksplit && phase_ksplit(ph[i]) > 1;
-    any_ks = any_ks || phase_ksplit(ph[i]) > 1;
-  }
-  if (any_rule) use_ksplit = any_ks;
+  bool use_ksplit = false;
+  for (int i = 0; i < nph; ++i) use_ksplit = use_ksplit || phase_ksplit(ph[i]) > 1;
   const long out_total = nph > 0 ? (long)ph[0].N * ph[0].out_sN : 0;
   if (use_ksplit && hipMemsetAsync(out, 0, sizeof(float) * out_total, st) != hipSuccess) {
     muvo_set_error("conv: memset of the split-K output failed");
@@ -991,7 +1044,7 @@ static int run_phases(const ConvPhase* ph, int nph, const float* in, const float
       split_done = true;
     }
     const int ks_i = phase_ksplit(ph[i]);
-    int rc = launch_fwd_phase(ph[i], in, wp, bias, out, act, slope, st, ws, use_ksplit ? (ks_i > 1 ? ks_i : 2) : 1);
+    int rc = launch_fwd_phase(ph[i], in, wp, bias, out, act, slope, st, ws, use_ksplit ? (ks_i > 1 ? ks_i : 2) : 1, head);
     if (rc) return rc;
   }
   if (use_ksplit && (bias != nullptr || act != MUVO_ACT_NONE)) {
@@ -1004,13 +1057,13 @@ static int run_phases(const ConvPhase* ph, int nph, const float* in, const float
 
 int muvo_conv_forward(const muvo_conv_desc* d, const float* x, const float* wp_fwd, const float* bias, float* y,
                       int act, float slope, void* ws, void* stream) {
-  ConvPlan pl;
-  int rc = build_plan(d, &pl);
+  ConvRoute r;
+  int rc = route_conv(d, OP_FWD, &r);
   if (rc) return rc;
   MUVO_CHECK_ARG(x && wp_fwd && y, "conv_forward: null pointer");
-  if (pw_applicable(d)) return pw_forward(d, x, wp_fwd, bias, y, act, slope, (hipStream_t)stream);
-  if (vox_fwd_ok(d)) return vox_forward(d, x, wp_fwd, bias, y, act, slope, (hipStream_t)stream, vox_uses_bf3(d, 0));
-  return run_phases(pl.fwd, pl.nfwd, x, wp_fwd, bias, y, act, slope, ws, (hipStream_t)stream);
+  if (r.family == FAM_PW) return pw_forward(d, x, wp_fwd, bias, y, act, slope, (hipStream_t)stream);
+  if (fam_is_vox(r.family)) return vox_forward(d, x, wp_fwd, bias, y, act, slope, (hipStream_t)stream, r.family == FAM_VOX_BF3);
+  return run_phases(r.ph, r.nph, x, wp_fwd, bias, y, act, slope, ws, (hipStream_t)stream);
 }
 
 // muvo_conv_forward whose workspace may ALREADY hold the split planes of x (ws_valid != 0): written by the producer of x - the fused
@@ -1019,15 +1072,13 @@ int muvo_conv_forward(const muvo_conv_desc* d, const float* x, const float* wp_f
 int muvo_conv_forward_planes(const muvo_conv_desc* d, const float* x, const float* wp_fwd, const float* bias, float* y, int act,
                              float slope, void* ws, int ws_valid, void* stream) {
   if (!ws_valid) return muvo_conv_forward(d, x, wp_fwd, bias, y, act, slope, ws, stream);
-  ConvPlan pl;
-  int rc = build_plan(d, &pl);
+  ConvRoute r;
+  int rc = route_conv(d, OP_FWD, &r);
   if (rc) return rc;
   MUVO_CHECK_ARG(wp_fwd && y && ws, "conv_forward_planes: null pointer");
-  MUVO_CHECK_ARG(!pw_applicable(d) && !vox_fwd_ok(d), "conv_forward_planes: this shape does not read split planes");
-  bool all_bf3 = pl.nfwd > 0;
-  for (int i = 0; i < pl.nfwd; ++i) all_bf3 = all_bf3 && pl.fwd[i].bf3;
-  MUVO_CHECK_ARG(all_bf3, "conv_forward_planes: ws_valid needs every phase on the bf16x3 kernels (muvo_conv_kernel_family == 1)");
-  return run_phases(pl.fwd, pl.nfwd, x, wp_fwd, bias, y, act, slope, ws, (hipStream_t)stream, true);
+  MUVO_CHECK_ARG(r.family == FAM_GEMM_F32 || r.family == FAM_GEMM_BF3, "conv_forward_planes: this shape does not read split planes");
+  MUVO_CHECK_ARG(r.family == FAM_GEMM_BF3, "conv_forward_planes: ws_valid needs every phase on the bf16x3 kernels (muvo_conv_kernel_family == 1)");
+  return run_phases(r.ph, r.nph, x, wp_fwd, bias, y, act, slope, ws, (hipStream_t)stream, true);
 }
 
 // A decoder stage and the 1x1 head on its output in one launch per phase (ConvDecoder: trans_conv1/2/3 + head_4/2/1,
@@ -1037,12 +1088,12 @@ int muvo_conv_forward_planes(const muvo_conv_desc* d, const float* x, const floa
 // on those tiles without split-K, Cout % 64 == 0, CO * Cout <= 1024, CO <= 4 and y is below 2 GB.
 int muvo_conv_forward_head_supported(const muvo_conv_desc* d, int CO) {
   if (check_desc(d) || CO < 1 || CO > 4) return 0;
-  static const int on = getenv("MUVO_CONV_HEAD_FWD") ? atoi(getenv("MUVO_CONV_HEAD_FWD")) : 1;
-  if (!on || muvo_det() || conv_mode() != 1 || pw_applicable(d) || vox_fwd_ok(d)) return 0;   // (deterministic mode: groups of > 64 channels add their partial logits atomically)
-  ConvPlan pl;
-  if (build_plan(d, &pl) != MUVO_OK || pl.nfwd < 1) return 0;
-  for (int i = 0; i < pl.nfwd; ++i) {
-    const ConvPhase& g = pl.fwd[i];
+  static const int on = env_int("MUVO_CONV_HEAD_FWD", 1);
+  if (!on || muvo_det()) return 0;   // (deterministic mode: groups of > 64 channels add their partial logits atomically)
+  ConvRoute r;
+  if (route_conv(d, OP_FWD, &r) != MUVO_OK || r.family != FAM_GEMM_BF3) return 0;
+  for (int i = 0; i < r.nph; ++i) {
+    const ConvPhase& g = r.ph[i];
     if (!g.bf3 || !bf3_fwd_uses_pp(g) || phase_ksplit(g) > 1) return 0;
     if (g.Msub != d->Cout || g.Msub % 64 != 0 || g.M % 64 != 0 || (long)CO * g.Msub > 1024) return 0;
     if ((long)g.N * g.out_sN * 4 >= 0x7fffff00L) return 0;
@@ -1051,8 +1102,8 @@ int muvo_conv_forward_head_supported(const muvo_conv_desc* d, int CO) {
 }
 int muvo_conv_forward_head(const muvo_conv_desc* d, const float* x, const float* wp_fwd, const float* bias, float* y, int act,
                            float slope, void* ws, const float* head_w, const float* head_b, int CO, float* logits, void* stream) {
-  ConvPlan pl;
-  int rc = build_plan(d, &pl);
+  ConvRoute r;
+  int rc = route_conv(d, OP_FWD, &r);
   if (rc) return rc;
   MUVO_CHECK_ARG(x && wp_fwd && y && head_w && logits, "conv_forward_head: null pointer");
   MUVO_CHECK_ARG(muvo_conv_forward_head_supported(d, CO), "conv_forward_head: shape not served by the eight-wave bf16x3 tiles");
@@ -1064,10 +1115,8 @@ int muvo_conv_forward_head(const muvo_conv_desc* d, const float* x, const float*
       return MUVO_ERR_HIP;
     }
   }
-  bf3_set_fused_head(head_w, head_b, logits, CO);
-  rc = run_phases(pl.fwd, pl.nfwd, x, wp_fwd, bias, y, act, slope, ws, st);
-  bf3_set_fused_head(nullptr, nullptr, nullptr, 0);
-  return rc;
+  const Bf3Head head = {head_w, head_b, logits, CO};
+  return run_phases(r.ph, r.nph, x, wp_fwd, bias, y, act, slope, ws, st, false, &head);
 }
 
 int muvo_conv_forward_moments_supported(const muvo_conv_desc* d) {
@@ -1077,8 +1126,7 @@ int muvo_conv_forward_moments_supported(const muvo_conv_desc* d) {
 }
 int muvo_conv_forward_moments(const muvo_conv_desc* d, const float* x, const float* wp_fwd, const float* bias, float* y, int act,
                               float slope, double* moments, void* stream) {
-  ConvPlan pl;
-  int rc = build_plan(d, &pl);
+  int rc = check_desc(d);
   if (rc) return rc;
   MUVO_CHECK_ARG(x && wp_fwd && y && moments, "conv_forward_moments: null pointer");
   MUVO_CHECK_ARG(muvo_conv_forward_moments_supported(d), "conv_forward_moments: only the bf16x3 voxel kernels produce output moments");
@@ -1095,8 +1143,7 @@ int muvo_conv_affine_supported(const muvo_conv_desc* d) {
 }
 int muvo_conv_forward_affine(const muvo_conv_desc* d, const float* x, const float* aff, const float* wp_fwd, const float* bias,
                              float* y, int act, float slope, double* moments, void* stream) {
-  ConvPlan pl;
-  int rc = build_plan(d, &pl);
+  int rc = check_desc(d);
   if (rc) return rc;
   MUVO_CHECK_ARG(x && aff && wp_fwd && y, "conv_forward_affine: null pointer");
   MUVO_CHECK_ARG(muvo_conv_affine_supported(d), "conv_forward_affine: shape not served by the bf16x3 voxel kernels");
@@ -1104,8 +1151,7 @@ int muvo_conv_forward_affine(const muvo_conv_desc* d, const float* x, const floa
 }
 int muvo_conv_wgrad_affine(const muvo_conv_desc* d, const float* x, const float* aff, const float* dy, float* dw, float* dbias,
                            void* stream) {
-  ConvPlan pl;
-  int rc = build_plan(d, &pl, 0, false);
+  int rc = check_desc(d);
   if (rc) return rc;
   MUVO_CHECK_ARG(x && aff && dy && dw, "conv_wgrad_affine: null pointer");
   MUVO_CHECK_ARG(muvo_conv_affine_supported(d), "conv_wgrad_affine: shape not served by the bf16x3 voxel kernels");
@@ -1114,13 +1160,13 @@ int muvo_conv_wgrad_affine(const muvo_conv_desc* d, const float* x, const float*
 
 int muvo_conv_dgrad(const muvo_conv_desc* d, const float* dy, const float* wp_dgrad, float* dx, void* ws, int ws_valid,
                     void* stream) {
-  ConvPlan pl;
-  int rc = build_plan(d, &pl);
+  ConvRoute r;
+  int rc = route_conv(d, OP_DGRAD, &r);
   if (rc) return rc;
   MUVO_CHECK_ARG(dy && wp_dgrad && dx, "conv_dgrad: null pointer");
-  if (pw_applicable(d)) return pw_dgrad(d, dy, wp_dgrad, dx, (hipStream_t)stream);
-  if (vox_dgrad_ok(d)) return vox_dgrad(d, dy, wp_dgrad, dx, (hipStream_t)stream, vox_uses_bf3(d, 1));
-  return run_phases(pl.dgr, pl.ndgr, dy, wp_dgrad, nullptr, dx, MUVO_ACT_NONE, 0.f, ws, (hipStream_t)stream, ws_valid != 0);
+  if (r.family == FAM_PW) return pw_dgrad(d, dy, wp_dgrad, dx, (hipStream_t)stream);
+  if (fam_is_vox(r.family)) return vox_dgrad(d, dy, wp_dgrad, dx, (hipStream_t)stream, r.family == FAM_VOX_BF3);
+  return run_phases(r.ph, r.nph, dy, wp_dgrad, nullptr, dx, MUVO_ACT_NONE, 0.f, ws, (hipStream_t)stream, ws_valid != 0);
 }
 
 int muvo_conv_dgrad_accumulate(const muvo_conv_desc* d, const float* dy, const float* wp_dgrad, float* dx, void* stream) {
@@ -1166,66 +1212,28 @@ int muvo_conv_prepare_dy_head_supported(const muvo_conv_desc* d, int CO) {
   return CO >= 1 && CO <= 4 && S_out % 4 == 0 && S_out >= 1024;
 }
 
-// Weight gradients are leaves of the backward graph (their rounding error does not propagate into other gradients), so
-// they can go to bf16x3 at a lower work threshold than forward / data-gradient.
-static double bf3_wgrad_min_gflop() {
-  static const char* e = getenv("MUVO_BF16X3_WGRAD_MIN_GFLOP");
-  static const double env_v = e ? atof(e) : -1.0;
-  if (env_v >= 0.0) return env_v;
-  if (bf3_default_policy()) return 0.05;
-  return bf3_min_gflop() < 0.5 ? bf3_min_gflop() : 0.5;   // follows muvo_conv_set_bf16x3_min_gflop
-}
-
-// does the weight gradient of this conv run on the bf16x3 kernel (conv_bf3.hip)?  Every phase must have >= 32 output and
-// >= 32 input channels (>= 64 input channels when there are only 32 output channels).  Explicit threshold: per-phase work as for forward/dgrad; built-in policy: >= 0.05 GFLOP per
-// batch item over the whole operation and more than one tap (1x1 weight gradients are faster on the fp32 kernel).
-static const int g_bf3_wgrad_min_m = getenv("MUVO_BF3_WGRAD_MIN_M") ? atoi(getenv("MUVO_BF3_WGRAD_MIN_M")) : 32;
-static bool wgrad_uses_bf3(const ConvPlan& pf) {
-  if (conv_mode() != 1) return false;
-  const bool dflt = bf3_default_policy() && !getenv("MUVO_BF16X3_WGRAD_MIN_GFLOP");
-  double total = 0.0;
-  int taps = 0;
-  for (int i = 0; i < pf.nfwd; ++i) {
-    const ConvPhase& g = pf.fwd[i];
-    const double gflop = 2.0 * g.Msub * g.T * g.C * (double)g.SD * g.SH * g.SW * 1e-9;   // per original phase
-    if (g.Msub < g_bf3_wgrad_min_m || g.C < 32 || g.Msub % 16 != 0 && g.nmerge > 1) return false;
-    static const int allow32 = getenv("MUVO_BF3_WGRAD_32X32") ? atoi(getenv("MUVO_BF3_WGRAD_32X32")) : 1;
-    if (g.Msub <= 32 && g.C < 64 && !allow32) return false;     // (32 x 32 channels lost to the fp32 kernel on the 64-row tile; the 32-row tile wins)
-    if (!dflt && gflop < bf3_wgrad_min_gflop()) return false;
-    total += gflop * g.nmerge;
-    taps += g.T * g.nmerge;
-  }
-  if (dflt && (total < bf3_wgrad_min_gflop() || taps <= 1)) return false;
-  return pf.nfwd > 0;
-}
-
 // dw (PyTorch layout) += grad;  dbias += sum(dy).  dwp_scratch: fwd_floats floats of workspace, ALL-ZERO on entry and
 // left all-zero on exit (the split-K atomics accumulate into it; the unpack pass clears what it reads).
 // ws_x / ws_dy: muvo_conv_workspace_bytes(d, 2) / (d, 3) bytes (NULL when 0); flags bit 0 / bit 1: ws_x / ws_dy already
 // hold the split planes of x / dy (left there by muvo_conv_forward / muvo_conv_dgrad of the same tensors).
 int muvo_conv_wgrad(const muvo_conv_desc* d, const float* x, const float* dy, float* dwp_scratch, float* dw, float* dbias,
                     void* ws_x, void* ws_dy, int flags, void* stream) {
-  ConvPlan pl;
-  int rc = build_plan(d, &pl, 0, false);
+  ConvRoute r;
+  int rc = route_conv(d, OP_WGRAD, &r);
   if (rc) return rc;
   MUVO_CHECK_ARG(x && dy && dwp_scratch && dw, "conv_wgrad: null pointer");
   hipStream_t st = (hipStream_t)stream;
-  if (pw_applicable(d)) return pw_wgrad(d, x, dy, dw, dbias, st);
-  if (vox_wgrad_ok(d)) return vox_wgrad(d, x, dy, dw, dbias, st, vox_wgrad_uses_bf3(d));
+  if (r.family == FAM_PW) return pw_wgrad(d, x, dy, dw, dbias, st);
+  if (fam_is_vox(r.family)) return vox_wgrad(d, x, dy, dw, dbias, st, r.family == FAM_VOX_BF3);
   const long S_out = (long)d->out_sz[0] * d->out_sz[1] * d->out_sz[2];
-  if (wgrad_uses_bf3(pl)) {
-    // the bf16x3 kernel understands merged sub-pixel phases (one GEMM with nmerge * Cout rows): use them when they exist
-    ConvPlan pm;
-    if (build_plan(d, &pm, 0, true) == MUVO_OK && wgrad_uses_bf3(pm)) pl = pm;
+  if (r.family == FAM_GEMM_BF3) {
     MUVO_CHECK_ARG(ws_x && ws_dy, "conv_wgrad: this shape runs on the bf16x3 kernel and needs both workspaces");
     const long S_in = (long)d->in_sz[0] * d->in_sz[1] * d->in_sz[2];
     if (!(flags & 1)) { rc = bf3_split_input(x, ws_x, d->N, d->Cin, S_in, st); if (rc) return rc; }
     if (!(flags & 2)) { rc = bf3_split_input(dy, ws_dy, d->N, d->Cout, S_out, st); if (rc) return rc; }
-    long off = 0;
-    for (int i = 0; i < pl.nfwd; ++i) off += (long)pl.fwd[i].T * pl.fwd[i].M * pl.fwd[i].C;
-    off = 0;       // dwp_scratch is all-zero on entry and left all-zero by the unpack kernels
-    for (int i = 0; i < pl.nfwd; ++i) {
-      ConvPhase g = pl.fwd[i];
+    long off = 0;       // dwp_scratch is all-zero on entry and left all-zero by the unpack kernels
+    for (int i = 0; i < r.nph; ++i) {
+      ConvPhase g = r.ph[i];
       g.wp_off = off;
       off += (long)g.T * g.M * g.C;
       // in a forward-form phase "C" channels come from x (Cin) and "M" from dy (Cout)
@@ -1233,28 +1241,21 @@ int muvo_conv_wgrad(const muvo_conv_desc* d, const float* x, const float* dy, fl
       if (rc) return rc;
     }
   } else {
-    for (int i = 0; i < pl.nfwd; ++i) {
-      rc = launch_wgrad_phase(pl.fwd[i], x, dy, dwp_scratch, st);
+    for (int i = 0; i < r.nph; ++i) {
+      rc = launch_wgrad_phase(r.ph[i], x, dy, dwp_scratch, st);
       if (rc) return rc;
     }
-    for (int i = 0; i < pl.nfwd; ++i) {
-      const long total = (long)pl.fwd[i].M * pl.fwd[i].C * pl.fwd[i].T;
+    for (int i = 0; i < r.nph; ++i) {
+      const long total = (long)r.ph[i].M * r.ph[i].C * r.ph[i].T;
       if (total == 0) continue;
-      hipLaunchKernelGGL(unpack_wgrad_kernel, dim3(ew_grid(total)), dim3(256), 0, st, pl.fwd[i], dwp_scratch, dw);
+      hipLaunchKernelGGL(unpack_wgrad_kernel, dim3(ew_grid(total)), dim3(256), 0, st, r.ph[i], dwp_scratch, dw);
     }
     MUVO_CHECK_LAUNCH("unpack_wgrad_kernel");
   }
-  if (dbias) {
-    int chunks = cdiv((long)d->N * S_out, 65536);
-    if (chunks > 64) chunks = 64;
-    if (muvo_det()) chunks = 1;
-    hipLaunchKernelGGL(bias_grad_kernel, dim3(d->Cout, chunks), dim3(256), 0, st, dy, dbias, d->N, d->Cout, S_out);
-    MUVO_CHECK_LAUNCH("bias_grad_kernel");
-  }
-  return MUVO_OK;
+  return dbias ? launch_bias_grad(dy, dbias, d->N, d->Cout, S_out, st) : MUVO_OK;
 }
 
-// db[m] += sum_{n,s} dy[n][m][s]
+// the operand layout of the bf16x3 kernels on its own (include/muvo_hip.h)
 int64_t muvo_split_planes_bytes(int N, int C, int64_t S) { return bf3_workspace_bytes(N, C, (long)S); }
 int muvo_split_planes(const float* x, void* ws, int N, int C, int64_t S, const float* y, int act, float slope, float* dbias,
                       void* stream) {
@@ -1263,12 +1264,7 @@ int muvo_split_planes(const float* x, void* ws, int N, int C, int64_t S, const f
 }
 int muvo_bias_grad_nchw(const float* dy, float* db, int N, int M, int64_t S, void* stream) {
   MUVO_CHECK_ARG(dy && db && N > 0 && M > 0 && S > 0, "bias_grad_nchw: bad args");
-  int chunks = cdiv((long)N * S, 65536);
-  if (chunks > 64) chunks = 64;
-  if (muvo_det()) chunks = 1;
-  hipLaunchKernelGGL(bias_grad_kernel, dim3(M, chunks), dim3(256), 0, (hipStream_t)stream, dy, db, N, M, (long)S);
-  MUVO_CHECK_LAUNCH("bias_grad_kernel");
-  return MUVO_OK;
+  return launch_bias_grad(dy, db, N, M, (long)S, (hipStream_t)stream);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1285,11 +1281,7 @@ static int linear_phase(int rows, int c, int m, long wsm, long wsc, bool token_m
   d.nd = 2; d.N = 1; d.Cin = c; d.Cout = m;
   for (int a = 0; a < 3; ++a) { d.in_sz[a] = d.out_sz[a] = d.ksz[a] = d.stride[a] = d.dil[a] = 1; d.pad[a] = 0; }
   d.in_sz[2] = d.out_sz[2] = rows;
-  t_plan_mode = 1;
-  t_allow_merge = false;
-  t_force_family = 1;
-  const int rc = build_conv_form(&d, d.in_sz, d.out_sz, c, m, wsm, wsc, ph);
-  t_force_family = 0;
+  const int rc = build_conv_form(&d, d.in_sz, d.out_sz, c, m, wsm, wsc, PlanOpts{1, false, +1}, ph);   // bf16x3 whatever the size
   if (rc) return rc;
   ph->wp_off = 0;
   if (token_major_out) { ph->os[2] = m; ph->out_sC = 1; }   // out[pixel * m + channel]
@@ -1398,12 +1390,17 @@ int64_t muvo_pack_table_item_bytes(void) { return (int64_t)sizeof(PackItem); }
 int muvo_conv_pack_table_add(void* host_items, int capacity, int* n_items, int64_t* n_blocks, const muvo_conv_desc* d,
                              const float* w, float* wp_fwd, float* wp_dgrad) {
   MUVO_CHECK_ARG(host_items && n_items && n_blocks && d && w, "conv_pack_table_add: null pointer");
-  ConvPlan pl;
-  int rc = build_plan(d, &pl);
+  ConvRoute r;
+  int rc = route_conv(d, OP_FWD, &r);
   if (rc) return rc;
-  if (pw_applicable(d) || (wp_fwd && vox_fwd_ok(d)) || (wp_dgrad && vox_dgrad_ok(d))) return 1;
-  if (wp_fwd) { rc = table_append(host_items, capacity, n_items, n_blocks, pl.fwd, pl.nfwd, w, wp_fwd); if (rc) return rc; }
-  if (wp_dgrad) { rc = table_append(host_items, capacity, n_items, n_blocks, pl.dgr, pl.ndgr, w, wp_dgrad); if (rc) return rc; }
+  float* wp[2] = {wp_fwd, wp_dgrad};
+  const int fam[2] = {r.family, route_family(d, OP_DGRAD, r.plan)};
+  if (fam[OP_FWD] == FAM_PW || (wp_fwd && fam_is_vox(fam[OP_FWD])) || (wp_dgrad && fam_is_vox(fam[OP_DGRAD]))) return 1;
+  for (int dir = 0; dir < 2; ++dir)
+    if (wp[dir]) {
+      rc = table_append(host_items, capacity, n_items, n_blocks, r.plan.ph[dir], r.plan.n[dir], w, wp[dir]);
+      if (rc) return rc;
+    }
   return MUVO_OK;
 }
 

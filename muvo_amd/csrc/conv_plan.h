@@ -56,11 +56,11 @@ __device__ __forceinline__ void decode_pix(const ConvPhase& g, int p, int& n, in
 // raises the limit (-mllvm -instcombine-max-copied-from-constant-users) and fails the build on any scratch use.)
 // Split-K partial sums: atomic adds into the zeroed output (bias / activation run in a finishing pass).  Separate from the
 // store epilogue so that its code exists once per kernel, not once per activation.
-template <bool MERGED, int TM, int TN, class V>
+template <int TM, int TN, class V>
 __device__ __forceinline__ void conv_tile_atomic(const ConvPhase& g, const V (&acc)[TM][TN], float* __restrict__ out, int pix0,
                                                  int m_tile, int wm, int wn, int lane) {
   // output residues of the row groups as scalar values, selected by the (wave-uniform) group index
-  constexpr int NG = MERGED ? 8 : 1;
+  constexpr int NG = 8;      // row groups of a merged phase (ConvPhase::mop)
   int mopv[NG][3];
 #pragma unroll
   for (int q = 0; q < NG; ++q)
@@ -75,7 +75,7 @@ __device__ __forceinline__ void conv_tile_atomic(const ConvPhase& g, const V (&a
 #pragma unroll
     for (int i = 0; i < TM; ++i) {
       const int mb = m_tile + wm * (TM * 32) + i * 32;
-      const int grp = (MERGED && g.nmerge > 1) ? mb / g.Msub : 0;
+      const int grp = g.nmerge > 1 ? mb / g.Msub : 0;
       const int mo = mb - grp * g.Msub;
       int mz = mopv[0][0], my = mopv[0][1], mx = mopv[0][2];
 #pragma unroll
@@ -91,20 +91,18 @@ __device__ __forceinline__ void conv_tile_atomic(const ConvPhase& g, const V (&a
   }
 }
 
-// MERGED = false: for callers that never run merged sub-pixel phases (none at present; both kernel families do): one row group
-// (see the note on the residue table below)
 // Fused 1x1 head (hco > 0; ConvDecoder stage + RGBHead / LidarReHead, common.py:608-632): logits[n][k][pixel] = hb[k] +
 // sum_c hw[k][c] * y[n][c][pixel] for the hco <= 4 head channels, formed from the activated values while they are stored (hw: the
 // head weights [hco][Msub] in LDS).  A wave holds 64 channels of its 64 pixels: 4 * hco FMAs per stored value, one cross-half
 // shuffle per pixel column; layers with more than 64 channels per group add their partial sums atomically into the zeroed
 // logits (the wave with the group's first channels adds the bias).  Needs full tiles (M, Msub multiples of 64).
-template <int ACT, bool VEC4, bool MERGED, int TM, int TN, class V>
+template <int ACT, bool VEC4, int TM, int TN, class V>
 __device__ __forceinline__ void conv_tile_store(const ConvPhase& g, const V (&acc)[TM][TN], const float* __restrict__ bias,
                                                 float* __restrict__ out, float slope, int pix0, int m_tile, int wm,
                                                 int wn, int lane, float* sb, const float* hw = nullptr, int hco = 0,
                                                 const float* __restrict__ hb = nullptr, float* __restrict__ hlogits = nullptr) {
   // output residues of the row groups as scalar values, selected by the (wave-uniform) group index
-  constexpr int NG = MERGED ? 8 : 1;
+  constexpr int NG = 8;      // row groups of a merged phase (ConvPhase::mop)
   int mopv[NG][3];
 #pragma unroll
   for (int q = 0; q < NG; ++q)
@@ -114,7 +112,7 @@ __device__ __forceinline__ void conv_tile_store(const ConvPhase& g, const V (&ac
   if (use_bias) {
     if (lane < 32 * TM) {
       const int mb = m_tile + wm * (TM * 32) + (lane & ~31);
-      const int mo = mb - ((MERGED && g.nmerge > 1) ? mb / g.Msub : 0) * g.Msub;
+      const int mo = mb - (g.nmerge > 1 ? mb / g.Msub : 0) * g.Msub;
       const int rr = lane & 31;
       sb[lane] = (mb + rr < g.M && mo + rr < g.Msub) ? bias[mo + rr] : 0.f;
     }
@@ -141,7 +139,7 @@ __device__ __forceinline__ void conv_tile_store(const ConvPhase& g, const V (&ac
 #pragma unroll
       for (int i = 0; i < TM; ++i) {
         const int mb = m_tile + wm * (TM * 32) + i * 32;   // 32-row tile: inside one merged group (Msub % 32 == 0)
-        const int grp = (MERGED && g.nmerge > 1) ? mb / g.Msub : 0;
+        const int grp = g.nmerge > 1 ? mb / g.Msub : 0;
         const int mo = mb - grp * g.Msub;
         int mz = mopv[0][0], my = mopv[0][1], mx = mopv[0][2];
 #pragma unroll
@@ -180,7 +178,7 @@ __device__ __forceinline__ void conv_tile_store(const ConvPhase& g, const V (&ac
       }
       if (hco > 0) {        // (uniform) rows 4 * (lane >> 5) + {0..3} + 8 q: the two lane halves hold the two halves of a pixel's channels
         const int mb0 = m_tile + wm * (TM * 32);
-        const int mo0 = mb0 - ((MERGED && g.nmerge > 1) ? mb0 / g.Msub : 0) * g.Msub;
+        const int mo0 = mb0 - (g.nmerge > 1 ? mb0 / g.Msub : 0) * g.Msub;
         const bool split = g.Msub > TM * 32;               // the group's channels are spread over several waves / workgroups
 #pragma unroll
         for (int k = 0; k < 4; ++k)
@@ -206,7 +204,7 @@ __device__ __forceinline__ void conv_tile_store(const ConvPhase& g, const V (&ac
 #pragma unroll
     for (int i = 0; i < TM; ++i) {
       const int mb = m_tile + wm * (TM * 32) + i * 32;   // 32-row tile: inside one merged group (Msub % 32 == 0)
-      const int grp = (MERGED && g.nmerge > 1) ? mb / g.Msub : 0;
+      const int grp = g.nmerge > 1 ? mb / g.Msub : 0;
       const int mo = mb - grp * g.Msub;
       int mz = mopv[0][0], my = mopv[0][1], mx = mopv[0][2];
 #pragma unroll

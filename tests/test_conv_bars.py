@@ -293,7 +293,9 @@ def test_split_k_cases_run_unsplit_in_deterministic_mode():
 # Every instantiation / code path the launchers can take at test sizes.  conv_fwd_kernel: RUN is 4 (Cp == 4) or 8 (Cp == 8, and
 # KPT = 16 / (256 / BN) = 8 for all three tiles, whose BN is 128); split-K needs >= 32 K steps of 16, i.e. T * Cp >= 512: with
 # Cp == 4 that is more taps than MAX_TAPS, so RUN = 4 has no split-K form.  Out of reach at test sizes: the pointer-store
-# epilogue (outputs >= 2 GB), the MUVO_* tuning variants, merges refused by the 2048-row cap.
+# epilogue (outputs >= 2 GB), merges refused by the 2048-row cap, and the two-stage eight-wave forward tiles that only
+# MUVO_BF3_VARIANT=2 selects (kept for the sake of their neighbours' machine code, conv_bf3.hip: bf3_launch_fwd_phase).  The other
+# variants that MUVO_* tuning switches selected have been retired.
 REACHABLE = (
     [f'conv_fwd_kernel<{bm},128,run{r}>' for bm in (128, 64, 32) for r in (4, 8)]
     + [f'conv_fwd_kernel<{bm},128,run8> split-K' for bm in (128, 64, 32)]
