@@ -434,6 +434,25 @@ int muvo_chamfer_loss_fwd(const float* pred, const float* target, int64_t F, int
 int muvo_chamfer_loss_bwd(const float* pred, const float* target, const int32_t* idx_pt, const int32_t* idx_tp, float* dpred, int64_t F,
                           int Cp, int Ct, int64_t n, float weight, const float* gout, void* stream);
 
+/* ---- Lovasz-softmax training loss of the voxel head (lovasz.hip; an extension) -----------------------
+ * logits (F,C,V) fp32, labels (F,V) bytes, 2 <= C <= 16, F*C <= 65535, V <= 2^30.  A voxel with label >= C is ignored: absent
+ * from the ranking, gradient exactly 0.  Per frame f and class c: e_v = |[label_v == c] - softmax(logits_v)_c|, ranked descending
+ * with ties by ascending voxel index (a stable segmented radix sort on the device), L_fc = sum_i e_(i) g_i with g_i the increment
+ * of the Jaccard loss at rank i in its closed form (fp64).  loss[0] = weight / F * sum_f (sum_{c present in f} L_fc) /
+ * max(1, #present_f); class c is present in frame f iff one valid voxel of f has label c.
+ * ws: muvo_lovasz_ws_bytes(F, C, V) bytes of 16-byte aligned scratch (written, then read; no need to clear); after the call its
+ * first F*C doubles hold L_fc.  errors (F,C,V): e, 0 at ignored voxels, or NULL.  dlde (F,C,V): g at the voxel's rank - 0 at
+ * ignored voxels and for absent classes, not scaled by weight, 1/F or 1/#present - or NULL when no backward follows.  present
+ * (F,C) bytes.  The loss value is bit-identical with and without the optional outputs; no float atomics: every call on the same
+ * inputs gives the same bits.
+ * Backward: the ranking is fixed; dlogits (F,C,V) is written completely (zeros at ignored voxels) from dlde, the sign of
+ * de/dp (-1 foreground, +1 background) and the softmax Jacobian; gout = the upstream gradient of the scalar, on the device. */
+int64_t muvo_lovasz_ws_bytes(int64_t F, int C, int64_t V);
+int muvo_lovasz_fwd(const float* logits, const uint8_t* labels, int64_t F, int C, int64_t V, float weight, void* ws, float* errors,
+                    float* dlde, uint8_t* present, float* loss, void* stream);
+int muvo_lovasz_bwd(const float* logits, const uint8_t* labels, const float* dlde, const uint8_t* present, float* dlogits, int64_t F, int C,
+                    int64_t V, float weight, const float* gout, void* stream);
+
 /* ---- evaluation metrics of the validation path (muvo/metrics.py via muvo/trainer.py:426-490) ----------------------------
  * All accumulators are caller-zeroed device buffers the kernels ADD into (several batches may share them).
  * muvo_ssim_frames: sums[n] += sum over (c, y, x) of the SSIM map of frame n (valid 11x11 Gaussian window given as 121

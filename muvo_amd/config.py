@@ -20,8 +20,13 @@ TOLERATED_EXTRA_KEYS = ('CML_DATASET_VERSION', 'MODEL.TRANSFORMER_TRANSITION', '
 #   multiplies, FACTORS (a list drawn from 1, 2, 4; absent = [2, 4]) names the output scales that get a term
 #   `lidar_cd_{f}` = WEIGHT / f x CD(lidar_reconstruction_f[:, :, :3], range_view_label_f[:, :, :3]).  The search is brute force:
 #   factor 1 (65,536 points a frame) is left out of the default list for its cost.  Needs LIDAR_RE.ENABLED.
+#   LOSSES.VOXEL_LOVASZ.{WEIGHT,FACTORS} - the Lovasz-softmax loss of the voxel head (the surrogate of the IoU the head is judged
+#   by; the reference has none).  WEIGHT (float; absent = 0 = off) multiplies, FACTORS (a list drawn from 1, 2, 4; absent =
+#   [1, 2, 4]) names the output scales that get a term `voxel_lovasz_{f}` = WEIGHT / f x Lovasz(voxel_f, voxel_label_f), every
+#   frame a segment of its own, classes 'present' (DESIGN.md section 11).  Needs VOXEL_SEG.ENABLED.
 EXTENSION_KEYS = ('MODEL.CONSTANT_SIZE', 'MODEL.CONSTANT_SIZE.RGB', 'MODEL.CONSTANT_SIZE.LIDAR', 'MODEL.CONSTANT_SIZE.VOXEL',
-                  'LOSSES.LIDAR_CD', 'LOSSES.LIDAR_CD.WEIGHT', 'LOSSES.LIDAR_CD.FACTORS')
+                  'LOSSES.LIDAR_CD', 'LOSSES.LIDAR_CD.WEIGHT', 'LOSSES.LIDAR_CD.FACTORS',
+                  'LOSSES.VOXEL_LOVASZ', 'LOSSES.VOXEL_LOVASZ.WEIGHT', 'LOSSES.VOXEL_LOVASZ.FACTORS')
 DEFAULT_CONSTANT_SIZE = {'RGB': (5, 13), 'LIDAR': (1, 16), 'VOXEL': (3, 3, 1)}
 
 
@@ -52,6 +57,24 @@ def lidar_cd(cfg):
         raise ValueError(f'LOSSES.LIDAR_CD.FACTORS must be a list of distinct factors drawn from 1, 2, 4, got {factors!r}')
     if weight > 0 and not cfg.LIDAR_RE.ENABLED:
         raise ValueError('LOSSES.LIDAR_CD.WEIGHT > 0 needs LIDAR_RE.ENABLED: the loss is on the lidar reconstruction head')
+    return float(weight), tuple(int(f) for f in factors)
+
+
+DEFAULT_VOXEL_LOVASZ_FACTORS = (1, 2, 4)
+
+
+def voxel_lovasz(cfg):
+    """(weight, factors) of the Lovasz-softmax loss: LOSSES.VOXEL_LOVASZ.* if given, else (0.0, (1, 2, 4)); weight 0 = no such term."""
+    node = cfg.LOSSES.get('VOXEL_LOVASZ', None) or {}
+    weight = node.get('WEIGHT', 0.0)
+    if isinstance(weight, bool) or not isinstance(weight, (int, float)) or not weight >= 0:
+        raise ValueError(f'LOSSES.VOXEL_LOVASZ.WEIGHT must be a number >= 0, got {weight!r}')
+    factors = node.get('FACTORS', DEFAULT_VOXEL_LOVASZ_FACTORS)
+    if not isinstance(factors, (list, tuple)) or any(isinstance(f, bool) or f not in (1, 2, 4) for f in factors) \
+            or len(set(factors)) != len(factors):
+        raise ValueError(f'LOSSES.VOXEL_LOVASZ.FACTORS must be a list of distinct factors drawn from 1, 2, 4, got {factors!r}')
+    if weight > 0 and not cfg.VOXEL_SEG.ENABLED:
+        raise ValueError('LOSSES.VOXEL_LOVASZ.WEIGHT > 0 needs VOXEL_SEG.ENABLED: the loss is on the voxel head')
     return float(weight), tuple(int(f) for f in factors)
 
 

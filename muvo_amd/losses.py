@@ -96,6 +96,23 @@ class GeoScalLoss(_VoxelTriple):
     index = 2
 
 
+class LovaszSoftmaxLoss(nn.Module):
+    """Lovasz-softmax loss of voxel logits (b, s, c, x, y, z) against uint8 labels (b, s, 1, x, y, z): the convex surrogate of
+    the Jaccard index, every frame a segment of its own, classes 'present' (not in the reference).
+    Labels >= c - `ignore_index` among them - take no part."""
+
+    def __init__(self, ignore_index=255):
+        super().__init__()
+        self.ignore_index = ignore_index
+
+    def forward(self, prediction, target):
+        if prediction.dim() != 6 or target.dim() != 6:
+            raise ValueError(f'Expected 6-D logits and labels, got {tuple(prediction.shape)} and {tuple(target.shape)}')
+        if self.ignore_index < prediction.shape[2]:
+            raise ValueError(f'ignore_index {self.ignore_index} is one of the {prediction.shape[2]} classes: the kernels ignore labels >= C')
+        return ops.voxel_lovasz_loss(prediction, target, 1.0)[0]
+
+
 class CDLoss(nn.Module):
     """muvo/losses.py:352-367: Chamfer distance between point clouds (b, s, n, 3), mean over the points of both directions and
     over the frames.  The kernels read channel-planar points, so this drop-in form makes that view (one transposed copy);

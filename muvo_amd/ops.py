@@ -89,6 +89,7 @@ EXPORTS = [
     'muvo_flow_epe_ws_doubles', 'muvo_flow_epe',
     'muvo_raycast_brick_words', 'muvo_raycast_bricks_grid', 'muvo_raycast_bricks_logits', 'muvo_raycast', 'muvo_panel_voxel_view',
     'muvo_ray_iou_ws_doubles', 'muvo_ray_iou_counts',
+    'muvo_lovasz_ws_bytes', 'muvo_lovasz_fwd', 'muvo_lovasz_bwd',
 ]
 
 
@@ -115,7 +116,7 @@ def lib():
                 L.muvo_icp_state_doubles.restype = C.c_int64
                 L.muvo_icp_ws_doubles.restype = C.c_int64
                 for name in ('muvo_flow_max_pairs', 'muvo_flow_workspace_bytes', 'muvo_flow_colour_ws_bytes', 'muvo_flow_epe_ws_doubles',
-                             'muvo_raycast_brick_words', 'muvo_ray_iou_ws_doubles'):
+                             'muvo_raycast_brick_words', 'muvo_ray_iou_ws_doubles', 'muvo_lovasz_ws_bytes'):
                     getattr(L, name).restype = C.c_int64
                 for name in EXPORTS:
                     getattr(L, name)  # AttributeError if a declared symbol is missing
@@ -2799,6 +2800,60 @@ def chamfer_nearest(pred, target):
     """The selections the loss differentiates, (2, B*S, n) int32: [0][f, i] = the target point nearest to prediction point i,
     [1][f, j] = the prediction point nearest to target point j (lowest index on a tie)."""
     return _chamfer_forward(pred.detach(), target.detach(), 1.0, True)[3]
+
+
+def _lovasz_forward(logits, labels, weight, with_dlde, with_errors=False):
+    logits, labels = logits.contiguous(), labels.contiguous()
+    b, s, c = logits.shape[:3]
+    f = b * s
+    v = logits.numel() // (f * c)
+    assert labels.dtype == torch.uint8 and labels.numel() == f * v, 'labels must be uint8 (B,S,1,X,Y,Z) on the grid of the logits'
+    L = lib()
+    ws = torch.empty(max(16, L.muvo_lovasz_ws_bytes(_i64(f), c, _i64(v))), device=logits.device, dtype=torch.uint8)
+    errors = torch.empty(f, c, v, device=logits.device, dtype=torch.float32) if with_errors else None
+    dlde = torch.empty(f, c, v, device=logits.device, dtype=torch.float32) if with_dlde else None
+    present = torch.empty(f, c, device=logits.device, dtype=torch.uint8)
+    loss = torch.empty(1, device=logits.device, dtype=torch.float32)
+    _ck(L.muvo_lovasz_fwd(_f(logits), _p(labels), _i64(f), c, _i64(v), _fl(weight), _p(ws), _f(errors), _f(dlde), _p(present),
+                          _f(loss), _st()))
+    return logits, labels, loss, errors, dlde, present, ws, (f, c, v)
+
+
+class VoxelLovaszFn(torch.autograd.Function):
+    """weight * Lovasz-softmax loss for logits (B,S,C,X,Y,Z), labels u8 (B,S,1,X,Y,Z); labels >= C are
+    ignored.  Every frame is a segment of its own, classes 'present'.  The per-rank Jaccard increments are kept, in voxel order,
+    only when a backward can follow: under torch.no_grad() none are written, and the value is bit-identical."""
+
+    @staticmethod
+    def forward(ctx, logits, labels, weight, terms=False, grad_enabled=True):
+        need = ctx.needs_input_grad[0] and grad_enabled
+        logits, labels, loss, _, dlde, present, _, dims = _lovasz_forward(logits, labels, weight, need)
+        ctx.dims, ctx.weight = dims, weight
+        if need:
+            ctx.save_for_backward(logits, labels, dlde, present)
+        return _as_terms(ctx, loss, terms)
+
+    @staticmethod
+    def backward(ctx, g):
+        logits, labels, dlde, present = ctx.saved_tensors
+        f, c, v = ctx.dims
+        g = torch.zeros(1, device=logits.device) if g is None else g.reshape(1)
+        dl = torch.empty_like(logits)
+        _ck(lib().muvo_lovasz_bwd(_f(logits), _p(labels), _f(dlde), _p(present), _f(dl), _i64(f), c, _i64(v), _fl(ctx.weight),
+                                  _f(g.contiguous()), _st()))
+        return dl, None, None, None, None
+
+
+def voxel_lovasz_loss(logits, labels, weight, terms=False):
+    """terms=True: a 1-tuple holding the 0-d loss instead of the (1,) tensor (as the other loss entry points)"""
+    return VoxelLovaszFn.apply(logits, labels, weight, terms, torch.is_grad_enabled())
+
+
+def voxel_lovasz_parts(logits, labels):
+    """What the loss is made of, for tests and the benchmark: (errors (F,C,V), dlde (F,C,V), present (F,C) uint8,
+    frame_class_loss (F,C) float64 = L_fc, unweighted) for logits (B,S,C,...) and labels u8 (B,S,1,...)."""
+    _, _, _, errors, dlde, present, ws, (f, c, v) = _lovasz_forward(logits.detach(), labels, 1.0, True, True)
+    return errors, dlde, present, ws[:f * c * 8].view(torch.float64).view(f, c).clone()
 
 
 # ================================================================================================ ICP between lidar frames

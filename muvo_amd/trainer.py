@@ -14,7 +14,7 @@ import numpy as np
 import torch
 
 from muvo_amd import ops
-from muvo_amd.config import get_cfg, lidar_cd
+from muvo_amd.config import get_cfg, lidar_cd, voxel_lovasz
 from muvo_amd.models.mile import Mile
 from muvo_amd.models.preprocess import PreProcess
 from muvo_amd.optim import FusedAdamW
@@ -448,6 +448,13 @@ class WorldModelTrainer(_Base):
             for f in cd_factors:                  # x, y, z = channels 0..2 of both tensors, in the scaled units of lidar_re_*
                 losses[f'lidar_cd_{f}'] = ops.chamfer_loss(output[f'lidar_reconstruction_{f}'], batch[f'range_view_label_{f}'],
                                                            w_cd * (1 / f), terms=True)[0]
+        # the Lovasz-softmax loss of the voxel head (extension, config.py: LOSSES.VOXEL_LOVASZ; absent = off: no term, no launch),
+        # last for the same reason
+        w_lv, lv_factors = voxel_lovasz(cfg)
+        if w_lv > 0:
+            for f in lv_factors:
+                losses[f'voxel_lovasz_{f}'] = ops.voxel_lovasz_loss(output[f'voxel_{f}'], batch[f'voxel_label_{f}'], w_lv * (1 / f),
+                                                                    terms=True)[0]
         return losses
 
     def _seg_loss(self, tag, c, is_bev=False):
