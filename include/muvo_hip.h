@@ -832,6 +832,47 @@ int muvo_ray_iou_counts(const uint8_t* label, const uint64_t* label_bricks, cons
                         int Z, const float* rays, int64_t R, float res, const float* thresholds, uint64_t* counts, double* ws, int64_t ws_doubles,
                         double* depth, void* stream);
 
+/* ---- rendered first-hit depth loss of the voxel head along rays (render.hip; an extension) -------------
+ * OUR DEFINITION; tests/render_reference.py restates it.  logits (F, C, X, Y, Z) fp32, 2 <= C <= 16, V = X Y Z; rays (R, 7) fp32
+ * on the device, the rows of muvo_raycast, one table for all F frames; sizes as muvo_raycast: F in 1..65535, every axis in 1..2048,
+ * V < 2^30, R in 1..2^24.
+ * Per cell, fp32: m = max_c z_c, e_c = expf(z_c - m), occ = e_1 + ... + e_{C-1} (ascending c), s = e_0 + occ; the free probability
+ *   is q = e_0 / s and the occupied probability a = occ / s (this sum, never 1 - q: it keeps small a).
+ * Per ray, the cell sequence: the march of muvo_raycast above, steps 1 - 3 word for word, through a grid in which no cell is
+ *   occupied - the slabs, the clamped start cell, fresh boundaries with strict < and ties x, y, z, at most X + Y + Z + 3
+ *   iterations, the end at best > t1 or on leaving the grid.  It gives cells k = 0..n-1 with entry depths t_k (fp32, the bits
+ *   muvo_raycast reports as t for a hit in that cell) and the exit depth t_exit = t1.  A ray that muvo_raycast calls a miss before
+ *   its step 2 (a NaN, a zero direction, missing the box) is INVALID: it contributes nothing and has zero gradient.
+ * Rendered depth: T_0 = 1, T_{k+1} = T_k q_k, w_k = T_k a_k (fp32 products), D = sum_k w_k t_k + T_n t_exit (fp64 products and
+ *   sum, in the order of k): the expectation of the first-hit depth RayIoU measures on the prediction side when every cell is
+ *   occupied independently with probability a; a ray through nothing renders at the exit.  The march may stop where T is exactly
+ *   0 (all later terms are exactly 0); there is no approximate cut-off.
+ * Target: label_hit / label_t (F, R) are muvo_raycast's hit and t of the same rays through the label grid; t* = label_t where
+ *   label_hit >= 0, t_exit otherwise.
+ * loss[0] = weight / F * sum_f 1 / N * sum_{valid rays} |D - t*| with N = n_valid, the number of valid rays of the table (a
+ *   property of the table and the grid size, not of the data: the caller counts it once); N = 0: loss 0, gradient 0.  fp64
+ *   partial sums per workgroup, added by one workgroup in a fixed order; one fp32 device scalar, no host read.
+ * Outputs: depth (F, R) fp64 = D and target (F, R) fp32 = t*, both 0 at invalid rays (kept for the backward pass); optional, for
+ *   tests, NULL otherwise: t_last (F, R) fp32 = T_n, cells (F, R) int32 = n (-1: invalid), t_exit (F, R) fp32.  With one of them
+ *   given the march does not stop at T == 0, so n is the full count; the loss has the same bits with and without them.
+ * ws: muvo_render_ws_bytes(F, V, R) bytes (-1 for sizes the entries refuse) of 16-byte aligned scratch, written then read (q, a,
+ *   the accumulator, the partials); one size serves both entries, nothing in it is kept between them.
+ * Backward: with P_k = sum_{j<k} w_j t_j and Q_k = D - P_k - w_k t_k,  dD/dz_{k,c} = (T_{k+1} t_k - Q_k) (p_c - [c == 0]) - no
+ *   division.  q and a are recomputed; every valid ray is marched again with D from the forward pass (P and D in fp64) and
+ *   sign(D - t*) (T_{k+1} t_k - Q_k), sign(0) = 0, is added into a per-frame (F, V) accumulator of 64-BIT INTEGERS IN FIXED POINT
+ *   with 26 fraction bits, rounded to nearest: the largest power of two for which R t_max scale < 2^62 with R <= 2^24 and
+ *   t_max = 2048 sqrt(3), the longest unit-direction path through the largest grid (a contribution is clamped to +-4096 before
+ *   the conversion, so the sum cannot overflow whatever the directions' lengths).  Integer atomics are order-free: loss and
+ *   gradient have the same bits on every call, in both modes of muvo_set_deterministic.  A wave first sums neighbouring lanes that
+ *   sit in the same cell.  One dense pass then writes every element of dlogits (F, C, V) = accumulator 2^-26 x gout weight /
+ *   (F N) x (p_c - [c == 0]) (class 0: -a), zeros where no ray passed; gout = the upstream gradient of the scalar, on the device. */
+int64_t muvo_render_ws_bytes(int64_t F, int64_t V, int64_t R);
+int muvo_render_fwd(const float* logits, int64_t F, int C, int X, int Y, int Z, const float* rays, int64_t R, int64_t n_valid, const int32_t* label_hit,
+                    const float* label_t, float weight, void* ws, int64_t ws_bytes, double* depth, float* target, float* t_last, int32_t* cells,
+                    float* t_exit, float* loss, void* stream);
+int muvo_render_bwd(const float* logits, int64_t F, int C, int X, int Y, int Z, const float* rays, int64_t R, int64_t n_valid, const double* depth,
+                    const float* target, float weight, const float* gout, void* ws, int64_t ws_bytes, float* dlogits, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

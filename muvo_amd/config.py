@@ -24,9 +24,15 @@ TOLERATED_EXTRA_KEYS = ('CML_DATASET_VERSION', 'MODEL.TRANSFORMER_TRANSITION', '
 #   by; the reference has none).  WEIGHT (float; absent = 0 = off) multiplies, FACTORS (a list drawn from 1, 2, 4; absent =
 #   [1, 2, 4]) names the output scales that get a term `voxel_lovasz_{f}` = WEIGHT / f x Lovasz(voxel_f, voxel_label_f), every
 #   frame a segment of its own, classes 'present' (DESIGN.md section 11).  Needs VOXEL_SEG.ENABLED.
+#   LOSSES.VOXEL_RENDER.{WEIGHT,FACTORS,STRIDE} - the rendered first-hit depth loss of the voxel head along lidar rays (what the
+#   RayIoU metric measures; the reference has none).  WEIGHT (float; absent = 0 = off) multiplies, FACTORS (a list drawn from
+#   1, 2, 4; absent = [1, 2, 4]) names the output scales that get a term `voxel_render_{f}` = WEIGHT / f x render(voxel_f,
+#   voxel_label_f) x VOXEL.RESOLUTION f / LIDAR_RE.SCALE (the scaled depth units of lidar_depth_f), STRIDE (an integer >= 1;
+#   absent = 1) takes every STRIDE-th azimuth of the range view as a ray.  Needs VOXEL_SEG.ENABLED.
 EXTENSION_KEYS = ('MODEL.CONSTANT_SIZE', 'MODEL.CONSTANT_SIZE.RGB', 'MODEL.CONSTANT_SIZE.LIDAR', 'MODEL.CONSTANT_SIZE.VOXEL',
                   'LOSSES.LIDAR_CD', 'LOSSES.LIDAR_CD.WEIGHT', 'LOSSES.LIDAR_CD.FACTORS',
-                  'LOSSES.VOXEL_LOVASZ', 'LOSSES.VOXEL_LOVASZ.WEIGHT', 'LOSSES.VOXEL_LOVASZ.FACTORS')
+                  'LOSSES.VOXEL_LOVASZ', 'LOSSES.VOXEL_LOVASZ.WEIGHT', 'LOSSES.VOXEL_LOVASZ.FACTORS',
+                  'LOSSES.VOXEL_RENDER', 'LOSSES.VOXEL_RENDER.WEIGHT', 'LOSSES.VOXEL_RENDER.FACTORS', 'LOSSES.VOXEL_RENDER.STRIDE')
 DEFAULT_CONSTANT_SIZE = {'RGB': (5, 13), 'LIDAR': (1, 16), 'VOXEL': (3, 3, 1)}
 
 
@@ -76,6 +82,29 @@ def voxel_lovasz(cfg):
     if weight > 0 and not cfg.VOXEL_SEG.ENABLED:
         raise ValueError('LOSSES.VOXEL_LOVASZ.WEIGHT > 0 needs VOXEL_SEG.ENABLED: the loss is on the voxel head')
     return float(weight), tuple(int(f) for f in factors)
+
+
+DEFAULT_VOXEL_RENDER_FACTORS = (1, 2, 4)
+DEFAULT_VOXEL_RENDER_STRIDE = 1
+
+
+def voxel_render(cfg):
+    """(weight, factors, stride) of the rendered first-hit depth loss: LOSSES.VOXEL_RENDER.* if given, else (0.0, (1, 2, 4), 1);
+    weight 0 = no such term."""
+    node = cfg.LOSSES.get('VOXEL_RENDER', None) or {}
+    weight = node.get('WEIGHT', 0.0)
+    if isinstance(weight, bool) or not isinstance(weight, (int, float)) or not weight >= 0:
+        raise ValueError(f'LOSSES.VOXEL_RENDER.WEIGHT must be a number >= 0, got {weight!r}')
+    factors = node.get('FACTORS', DEFAULT_VOXEL_RENDER_FACTORS)
+    if not isinstance(factors, (list, tuple)) or any(isinstance(f, bool) or f not in (1, 2, 4) for f in factors) \
+            or len(set(factors)) != len(factors):
+        raise ValueError(f'LOSSES.VOXEL_RENDER.FACTORS must be a list of distinct factors drawn from 1, 2, 4, got {factors!r}')
+    stride = node.get('STRIDE', DEFAULT_VOXEL_RENDER_STRIDE)
+    if isinstance(stride, bool) or not isinstance(stride, int) or stride < 1:
+        raise ValueError(f'LOSSES.VOXEL_RENDER.STRIDE must be an integer >= 1, got {stride!r}')
+    if weight > 0 and not cfg.VOXEL_SEG.ENABLED:
+        raise ValueError('LOSSES.VOXEL_RENDER.WEIGHT > 0 needs VOXEL_SEG.ENABLED: the loss is on the voxel head')
+    return float(weight), tuple(int(f) for f in factors), int(stride)
 
 
 class CfgNode(dict):

@@ -113,6 +113,26 @@ class LovaszSoftmaxLoss(nn.Module):
         return ops.voxel_lovasz_loss(prediction, target, 1.0)[0]
 
 
+class RenderedDepthLoss(nn.Module):
+    """Rendered first-hit depth loss of voxel logits (b, s, c, x, y, z) against uint8 labels (b, s, 1, x, y, z) along the rays of
+    one table (R, 7) float32 in grid units, on the device of the logits: the mean over frames and valid rays of |D - t*|, D the
+    expected first-hit depth under the head's occupancy probabilities, t* the label's first hit or the exit (DESIGN.md section 12;
+    not in the reference).  `n_valid` = the table's valid rays on this grid (voxel_view.valid_rays); counted here when absent."""
+
+    def __init__(self, rays, n_valid=None):
+        super().__init__()
+        self.rays, self.n_valid = rays, n_valid
+
+    def forward(self, prediction, target):
+        if prediction.dim() != 6 or target.dim() != 6:
+            raise ValueError(f'Expected 6-D logits and labels, got {tuple(prediction.shape)} and {tuple(target.shape)}')
+        n = self.n_valid
+        if n is None:
+            from muvo_amd.voxel_view import valid_rays
+            n = int(valid_rays(self.rays.cpu().numpy(), *prediction.shape[3:]).sum())
+        return ops.voxel_render_loss(prediction, target, self.rays, n, 1.0)[0]
+
+
 class CDLoss(nn.Module):
     """muvo/losses.py:352-367: Chamfer distance between point clouds (b, s, n, 3), mean over the points of both directions and
     over the frames.  The kernels read channel-planar points, so this drop-in form makes that view (one transposed copy);

@@ -90,6 +90,7 @@ EXPORTS = [
     'muvo_raycast_brick_words', 'muvo_raycast_bricks_grid', 'muvo_raycast_bricks_logits', 'muvo_raycast', 'muvo_panel_voxel_view',
     'muvo_ray_iou_ws_doubles', 'muvo_ray_iou_counts',
     'muvo_lovasz_ws_bytes', 'muvo_lovasz_fwd', 'muvo_lovasz_bwd',
+    'muvo_render_ws_bytes', 'muvo_render_fwd', 'muvo_render_bwd',
 ]
 
 
@@ -116,7 +117,7 @@ def lib():
                 L.muvo_icp_state_doubles.restype = C.c_int64
                 L.muvo_icp_ws_doubles.restype = C.c_int64
                 for name in ('muvo_flow_max_pairs', 'muvo_flow_workspace_bytes', 'muvo_flow_colour_ws_bytes', 'muvo_flow_epe_ws_doubles',
-                             'muvo_raycast_brick_words', 'muvo_ray_iou_ws_doubles', 'muvo_lovasz_ws_bytes'):
+                             'muvo_raycast_brick_words', 'muvo_ray_iou_ws_doubles', 'muvo_lovasz_ws_bytes', 'muvo_render_ws_bytes'):
                     getattr(L, name).restype = C.c_int64
                 for name in EXPORTS:
                     getattr(L, name)  # AttributeError if a declared symbol is missing
@@ -2854,6 +2855,76 @@ def voxel_lovasz_parts(logits, labels):
     frame_class_loss (F,C) float64 = L_fc, unweighted) for logits (B,S,C,...) and labels u8 (B,S,1,...)."""
     _, _, _, errors, dlde, present, ws, (f, c, v) = _lovasz_forward(logits.detach(), labels, 1.0, True, True)
     return errors, dlde, present, ws[:f * c * 8].view(torch.float64).view(f, c).clone()
+
+
+def _render_ws(f, v, r, device):
+    n = int(lib().muvo_render_ws_bytes(_i64(f), _i64(v), _i64(r)))
+    if n < 0:
+        raise ValueError(f'voxel_render_loss: {f} frames of {v} voxels and {r} rays (1..65535 frames, fewer than 2^30 voxels, 1..2^24 rays)')
+    return torch.empty(max(16, n), device=device, dtype=torch.uint8), n
+
+
+def _render_forward(logits, labels, rays, n_valid, weight, parts=False):
+    logits, labels = logits.contiguous(), labels.contiguous()
+    assert logits.dim() == 6 and logits.dtype == torch.float32, 'logits must be float32 (B,S,C,X,Y,Z)'
+    b, s, c, X, Y, Z = (int(n) for n in logits.shape)
+    f, v = b * s, X * Y * Z
+    assert labels.dtype == torch.uint8 and labels.numel() == f * v, 'labels must be uint8 (B,S,1,X,Y,Z) on the grid of the logits'
+    assert rays.dtype == torch.float32 and rays.dim() == 2 and rays.shape[1] == 7 and rays.is_contiguous() and rays.device == logits.device, \
+        'rays must be a contiguous float32 (R, 7) table on the device of the logits'
+    R = int(rays.shape[0])
+    grid, bricks = raycast_bricks(labels.view(f, X, Y, Z))          # occupied = class != 0, as for the metric
+    hit, lt, _ = raycast(grid, bricks, rays)
+    dev = logits.device
+    ws, ws_bytes = _render_ws(f, v, R, dev)
+    depth = torch.empty(f, R, device=dev, dtype=torch.float64)
+    target = torch.empty(f, R, device=dev, dtype=torch.float32)
+    t_last = torch.empty(f, R, device=dev, dtype=torch.float32) if parts else None
+    cells = torch.empty(f, R, device=dev, dtype=torch.int32) if parts else None
+    t_exit = torch.empty(f, R, device=dev, dtype=torch.float32) if parts else None
+    loss = torch.empty(1, device=dev, dtype=torch.float32)
+    _ck(lib().muvo_render_fwd(_f(logits), _i64(f), c, X, Y, Z, _f(rays), _i64(R), _i64(n_valid), _p(hit), _f(lt), _fl(weight), _p(ws), _i64(ws_bytes),
+                              _p(depth), _f(target), _f(t_last), _p(cells), _f(t_exit), _f(loss), _st()))
+    return logits, loss, depth, target, t_last, cells, t_exit, (f, c, X, Y, Z, R)
+
+
+class VoxelRenderFn(torch.autograd.Function):
+    """weight * rendered first-hit depth loss (include/muvo_hip.h: muvo_render_fwd) for logits
+    (B,S,C,X,Y,Z), labels u8 (B,S,1,X,Y,Z) and a ray table (R, 7) in grid units with `n_valid` valid rays.  Kept for the backward
+    pass: the logits (q and a are recomputed), D (F, R) float64 and the label's t* (F, R)."""
+
+    @staticmethod
+    def forward(ctx, logits, labels, rays, n_valid, weight, terms=False, grad_enabled=True):
+        need = ctx.needs_input_grad[0] and grad_enabled
+        logits, loss, depth, target, _, _, _, dims = _render_forward(logits, labels, rays, n_valid, weight)
+        ctx.dims, ctx.weight, ctx.n_valid = dims, weight, int(n_valid)
+        if need:
+            ctx.save_for_backward(logits, rays, depth, target)
+        return _as_terms(ctx, loss, terms)
+
+    @staticmethod
+    def backward(ctx, g):
+        logits, rays, depth, target = ctx.saved_tensors
+        f, c, X, Y, Z, R = ctx.dims
+        g = torch.zeros(1, device=logits.device) if g is None else g.reshape(1)
+        ws, ws_bytes = _render_ws(f, X * Y * Z, R, logits.device)
+        dl = torch.empty_like(logits)
+        _ck(lib().muvo_render_bwd(_f(logits), _i64(f), c, X, Y, Z, _f(rays), _i64(R), _i64(ctx.n_valid), _p(depth), _f(target), _fl(ctx.weight),
+                                  _f(g.contiguous()), _p(ws), _i64(ws_bytes), _f(dl), _st()))
+        return dl, None, None, None, None, None, None
+
+
+def voxel_render_loss(logits, labels, rays, n_valid, weight, terms=False):
+    """terms=True: a 1-tuple holding the 0-d loss instead of the (1,) tensor (as the other loss entry points)"""
+    return VoxelRenderFn.apply(logits, labels, rays, n_valid, weight, terms, torch.is_grad_enabled())
+
+
+def voxel_render_parts(logits, labels, rays, n_valid, weight=1.0):
+    """What the loss is made of, for tests and the benchmark: (loss (1,), D (F, R) float64, t* (F, R), T_n (F, R), cells per ray
+    (F, R) int32 with -1 at invalid rays, t_exit (F, R)).  The march runs to the end of every ray here; the loss has the bits
+    of voxel_render_loss."""
+    _, loss, depth, target, t_last, cells, t_exit, _ = _render_forward(logits.detach(), labels, rays, n_valid, weight, True)
+    return loss, depth, target, t_last, cells, t_exit
 
 
 # ================================================================================================ ICP between lidar frames

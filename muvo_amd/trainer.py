@@ -14,7 +14,7 @@ import numpy as np
 import torch
 
 from muvo_amd import ops
-from muvo_amd.config import get_cfg, lidar_cd, voxel_lovasz
+from muvo_amd.config import get_cfg, lidar_cd, voxel_lovasz, voxel_render
 from muvo_amd.models.mile import Mile
 from muvo_amd.models.preprocess import PreProcess
 from muvo_amd.optim import FusedAdamW
@@ -454,6 +454,18 @@ class WorldModelTrainer(_Base):
         if w_lv > 0:
             for f in lv_factors:
                 losses[f'voxel_lovasz_{f}'] = ops.voxel_lovasz_loss(output[f'voxel_{f}'], batch[f'voxel_label_{f}'], w_lv * (1 / f),
+                                                                    terms=True)[0]
+        # the rendered first-hit depth loss of the voxel head along the lidar's rays (extension, config.py: LOSSES.VOXEL_RENDER;
+        # absent = off: no term, no launch, no table), last for the same reason.  In the scaled depth units of lidar_depth_f:
+        # grid cells of scale f are VOXEL.RESOLUTION f metres
+        w_rd, rd_factors, rd_stride = voxel_render(cfg)
+        if w_rd > 0:
+            from muvo_amd.voxel_view import render_table
+            for f in rd_factors:
+                pred = output[f'voxel_{f}']
+                rays, n_valid = render_table(cfg, f, rd_stride, tuple(pred.shape[3:]), pred.device)
+                losses[f'voxel_render_{f}'] = ops.voxel_render_loss(pred, batch[f'voxel_label_{f}'], rays, n_valid,
+                                                                    w_rd * (1 / f) * (cfg.VOXEL.RESOLUTION * f / cfg.LIDAR_RE.SCALE),
                                                                     terms=True)[0]
         return losses
 

@@ -72,6 +72,45 @@ def lidar_rays(cfg, stride=4):
     return rays.reshape(-1, 7).astype(np.float32)
 
 
+def valid_rays(rays, X, Y, Z):
+    """(R,) bool numpy: the rays (R, 7) float32 that the march of include/muvo_hip.h (muvo_raycast) does not call a miss before its
+    step 2 on a grid (X, Y, Z) - step 1, the slabs, in float32 and in its order.  The rendered depth loss averages over these."""
+    rays = np.asarray(rays, np.float32)
+    f32 = np.float32
+    with np.errstate(all='ignore'):
+        t0, t1 = np.zeros(len(rays), f32), rays[:, 6].copy()
+        ok, moving = np.ones(len(rays), bool), np.zeros(len(rays), bool)
+        for a, N in enumerate((X, Y, Z)):
+            o, d = rays[:, a], rays[:, 3 + a]
+            move = d != 0
+            inv = f32(1) / np.where(move, d, f32(1))
+            ta, tb = (f32(0) - o) * inv, (f32(N) - o) * inv
+            asc = ta <= tb
+            lo, hi = np.where(asc, ta, tb), np.where(asc, tb, ta)
+            ok &= np.where(move, lo <= hi, (f32(0) <= o) & (o < f32(N)))
+            t0 = np.where(move & (lo > t0), lo, t0)
+            t1 = np.where(move & (hi < t1), hi, t1)
+            moving |= move
+        return ok & moving & (t0 < t1)
+
+
+_RENDER_TABLES = {}
+
+
+def render_table(cfg, factor, stride, shape, device):
+    """(rays (R, 7) float32 on the device, the number of valid rays) of the rendered depth loss at output scale `factor`:
+    lidar_rays(cfg, stride) with the origin divided by the factor - the grid of scale f has cells f times as large - and the
+    directions as they are.  Cached per (geometry, factor, stride, grid size, device); the valid rays are counted once, here."""
+    key = (tuple(float(v) for v in cfg.VOXEL.EV_POSITION), tuple(float(v) for v in cfg.POINTS.LIDAR_POSITION), tuple(float(v) for v in cfg.POINTS.FOV),
+           int(cfg.POINTS.CHANNELS), int(cfg.POINTS.HORIZON_RESOLUTION), float(cfg.VOXEL.RESOLUTION), int(factor), int(stride),
+           tuple(int(n) for n in shape), str(device))
+    if key not in _RENDER_TABLES:
+        rays = lidar_rays(cfg, stride)
+        rays[:, :3] = (rays[:, :3].astype(np.float64) / factor).astype(np.float32)
+        _RENDER_TABLES[key] = (torch.from_numpy(rays).to(device), int(valid_rays(rays, *shape).sum()))
+    return _RENDER_TABLES[key]
+
+
 _CAMERAS = {}
 
 
