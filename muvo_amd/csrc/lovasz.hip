@@ -11,7 +11,7 @@
 // running count per wave and digit in LDS).  No atomics anywhere: every result is independent of the execution order.
 // Behind the sort: foreground count per tile -> scan -> g from the closed forms in fp64, e * g summed per tile into a slot,
 // g scattered back to voxel order; one workgroup adds the slots in a fixed order and applies the present-class rule.
-#include "common.h"
+#include "voxel_grid.h"
 
 #define LV_THREADS 256
 #define LV_ROUNDS 8
@@ -20,60 +20,8 @@
 #define LV_VOX (LV_THREADS * 4)                // voxels per workgroup of the key and gradient passes (4 consecutive per lane)
 #define LV_ONE 0x3F800000u
 #define LV_SENTINEL 0x3FFFFFFFu
-#define LV_MAXC 16
 #define LV_MAX_V (1l << 30)
 #define LV_GROUP_KEYS (1l << 26)               // keys sorted per round of launches: bounds the ping-pong buffers to 1 GiB
-
-// ---- 4 consecutive elements per lane: one 16-byte access when `vec` (aligned base, V % 4 == 0), guarded scalars otherwise
-__device__ __forceinline__ f32x4 lv_ld4(const float* __restrict__ p, long h0, long V, bool vec) {
-  if (vec) return *(const f32x4*)(p + h0);          // vec implies h0 + 3 < V
-  f32x4 r = {0.f, 0.f, 0.f, 0.f};
-  if (h0 < V) r.x = p[h0];
-  if (h0 + 1 < V) r.y = p[h0 + 1];
-  if (h0 + 2 < V) r.z = p[h0 + 2];
-  if (h0 + 3 < V) r.w = p[h0 + 3];
-  return r;
-}
-__device__ __forceinline__ void lv_st4(float* __restrict__ p, long h0, long V, bool vec, f32x4 v) {
-  if (vec) { *(f32x4*)(p + h0) = v; return; }
-  if (h0 < V) p[h0] = v.x;
-  if (h0 + 1 < V) p[h0 + 1] = v.y;
-  if (h0 + 2 < V) p[h0 + 2] = v.z;
-  if (h0 + 3 < V) p[h0 + 3] = v.w;
-}
-__device__ __forceinline__ void lv_st4u(uint32_t* __restrict__ p, long h0, long V, bool vec, uint4 v) {
-  if (vec) { *(uint4*)(p + h0) = v; return; }
-  if (h0 < V) p[h0] = v.x;
-  if (h0 + 1 < V) p[h0 + 1] = v.y;
-  if (h0 + 2 < V) p[h0 + 2] = v.z;
-  if (h0 + 3 < V) p[h0 + 3] = v.w;
-}
-// the labels of the 4 voxels, 255 (ignored) past the end
-__device__ __forceinline__ void lv_labels(const uint8_t* __restrict__ lab, long h0, long V, bool vec, unsigned l[4]) {
-  if (vec) {
-    const uint32_t w = *(const uint32_t*)(lab + h0);
-    l[0] = w & 255u; l[1] = (w >> 8) & 255u; l[2] = (w >> 16) & 255u; l[3] = w >> 24;
-    return;
-  }
-#pragma unroll
-  for (int k = 0; k < 4; ++k) l[k] = h0 + k < V ? lab[h0 + k] : 255u;
-}
-// softmax statistics of the 4 voxels over the C planes: m = the maximum, s = sum exp(x - m) (fp32, as torch.softmax)
-__device__ __forceinline__ void lv_softmax_stats(const float* __restrict__ lf, int C, long V, long h0, bool vec, f32x4& m, f32x4& s) {
-  m = lv_ld4(lf, h0, V, vec);
-  for (int c = 1; c < C; ++c) {
-    const f32x4 x = lv_ld4(lf + (size_t)c * V, h0, V, vec);
-    m.x = fmaxf(m.x, x.x); m.y = fmaxf(m.y, x.y); m.z = fmaxf(m.z, x.z); m.w = fmaxf(m.w, x.w);
-  }
-  s = f32x4{0.f, 0.f, 0.f, 0.f};
-  for (int c = 0; c < C; ++c) {
-    const f32x4 x = lv_ld4(lf + (size_t)c * V, h0, V, vec);
-    s.x += expf(x.x - m.x); s.y += expf(x.y - m.y); s.z += expf(x.z - m.z); s.w += expf(x.w - m.w);
-  }
-}
-__device__ __forceinline__ f32x4 lv_prob(f32x4 x, f32x4 m, f32x4 s) {
-  return f32x4{expf(x.x - m.x) / s.x, expf(x.y - m.y) / s.y, expf(x.z - m.z) / s.z, expf(x.w - m.w) / s.w};
-}
 
 // ---- key pass.  grid = (voxel blocks, frames of the group); f0 = the group's first frame.  keys / load: the group's buffers.
 __global__ void __launch_bounds__(LV_THREADS)
@@ -85,11 +33,11 @@ lovasz_key_kernel(const float* __restrict__ logits, const uint8_t* __restrict__ 
   const bool v4 = vec && h0 + 3 < V;
   const float* __restrict__ lf = logits + (size_t)f * C * V;
   unsigned l[4];
-  lv_labels(labels + (size_t)f * V, h0, V, v4, l);
-  f32x4 m, s;
-  lv_softmax_stats(lf, C, V, h0, v4, m, s);
+  vg_ld4(labels + (size_t)f * V, h0, V, v4, 255u, l);          // 255: ignored
+  const VgSoftmax st = vg_softmax_stats(lf, C, V, h0, v4);
+  const f32x4 m = st.m, s = st.sum;
   for (int c = 0; c < C; ++c) {
-    const f32x4 p = lv_prob(lv_ld4(lf + (size_t)c * V, h0, V, v4), m, s);
+    const f32x4 p = vg_prob(vg_ld4(lf + (size_t)c * V, h0, V, v4), m, s);
     const float pk[4] = {p.x, p.y, p.z, p.w};
     float e[4];
     uint32_t k[4], w[4];
@@ -100,10 +48,10 @@ lovasz_key_kernel(const float* __restrict__ logits, const uint8_t* __restrict__ 
       k[j] = valid ? LV_ONE - __float_as_uint(e[j]) : LV_SENTINEL;
       w[j] = (uint32_t)(h0 + j) | (fg ? 0x80000000u : 0u);
     }
-    if (errors != nullptr) lv_st4(errors + ((size_t)f * C + c) * V, h0, V, v4, f32x4{e[0], e[1], e[2], e[3]});
+    if (errors != nullptr) vg_st4(errors + ((size_t)f * C + c) * V, h0, V, v4, f32x4{e[0], e[1], e[2], e[3]});
     const size_t seg = (size_t)blockIdx.y * C + c;
-    lv_st4u(keys + seg * V, h0, V, v4, uint4{k[0], k[1], k[2], k[3]});
-    lv_st4u(load + seg * V, h0, V, v4, uint4{w[0], w[1], w[2], w[3]});
+    vg_st4(keys + seg * V, h0, V, v4, uint4{k[0], k[1], k[2], k[3]});
+    vg_st4(load + seg * V, h0, V, v4, uint4{w[0], w[1], w[2], w[3]});
   }
 }
 
@@ -388,13 +336,13 @@ lovasz_bwd_kernel(const float* __restrict__ logits, const uint8_t* __restrict__ 
   const float* __restrict__ gf = dlde + (size_t)f * C * V;
   float* __restrict__ df = dlogits + (size_t)f * C * V;
   unsigned l[4];
-  lv_labels(labels + (size_t)f * V, h0, V, v4, l);
-  f32x4 m, s;
-  lv_softmax_stats(lf, C, V, h0, v4, m, s);
+  vg_ld4(labels + (size_t)f * V, h0, V, v4, 255u, l);          // 255: ignored
+  const VgSoftmax st = vg_softmax_stats(lf, C, V, h0, v4);
+  const f32x4 m = st.m, s = st.sum;
   f32x4 dot = {0.f, 0.f, 0.f, 0.f};
   for (int c = 0; c < C; ++c) {
-    const f32x4 p = lv_prob(lv_ld4(lf + (size_t)c * V, h0, V, v4), m, s);
-    const f32x4 g = lv_ld4(gf + (size_t)c * V, h0, V, v4);
+    const f32x4 p = vg_prob(vg_ld4(lf + (size_t)c * V, h0, V, v4), m, s);
+    const f32x4 g = vg_ld4(gf + (size_t)c * V, h0, V, v4);
     const float sc = (pmask >> c) & 1u ? scale : 0.f;
     dot.x += (l[0] == (unsigned)c ? -sc : sc) * g.x * p.x;
     dot.y += (l[1] == (unsigned)c ? -sc : sc) * g.y * p.y;
@@ -402,15 +350,15 @@ lovasz_bwd_kernel(const float* __restrict__ logits, const uint8_t* __restrict__ 
     dot.w += (l[3] == (unsigned)c ? -sc : sc) * g.w * p.w;
   }
   for (int c = 0; c < C; ++c) {
-    const f32x4 p = lv_prob(lv_ld4(lf + (size_t)c * V, h0, V, v4), m, s);
-    const f32x4 g = lv_ld4(gf + (size_t)c * V, h0, V, v4);
+    const f32x4 p = vg_prob(vg_ld4(lf + (size_t)c * V, h0, V, v4), m, s);
+    const f32x4 g = vg_ld4(gf + (size_t)c * V, h0, V, v4);
     const float sc = (pmask >> c) & 1u ? scale : 0.f;
     f32x4 d;
     d.x = l[0] < (unsigned)C ? p.x * ((l[0] == (unsigned)c ? -sc : sc) * g.x - dot.x) : 0.f;
     d.y = l[1] < (unsigned)C ? p.y * ((l[1] == (unsigned)c ? -sc : sc) * g.y - dot.y) : 0.f;
     d.z = l[2] < (unsigned)C ? p.z * ((l[2] == (unsigned)c ? -sc : sc) * g.z - dot.z) : 0.f;
     d.w = l[3] < (unsigned)C ? p.w * ((l[3] == (unsigned)c ? -sc : sc) * g.w - dot.w) : 0.f;
-    lv_st4(df + (size_t)c * V, h0, V, v4, d);
+    vg_st4(df + (size_t)c * V, h0, V, v4, d);
   }
 }
 
@@ -444,7 +392,7 @@ inline LvLayout lv_layout(int64_t F, int64_t C, int64_t V) {
   L.total = o;
   return L;
 }
-inline bool lv_args_ok(int64_t F, int C, int64_t V) { return F > 0 && V > 0 && C >= 2 && C <= LV_MAXC && F * C <= 65535 && V <= LV_MAX_V; }
+inline bool lv_args_ok(int64_t F, int C, int64_t V) { return F > 0 && V > 0 && C >= 2 && C <= VG_MAXC && F * C <= 65535 && V <= LV_MAX_V; }
 inline bool lv_al16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
 }  // namespace
 
@@ -458,7 +406,7 @@ int64_t muvo_lovasz_ws_bytes(int64_t F, int C, int64_t V) {
 int muvo_lovasz_fwd(const float* logits, const uint8_t* labels, int64_t F, int C, int64_t V, float weight, void* ws, float* errors,
                     float* dlde, uint8_t* present, float* loss, void* stream) {
   MUVO_CHECK_ARG(logits && labels && ws && present && loss, "lovasz_fwd: null pointer");
-  MUVO_CHECK_ARG(C >= 2 && C <= LV_MAXC, "lovasz_fwd: %d classes (2..16)", C);
+  MUVO_CHECK_ARG(C >= 2 && C <= VG_MAXC, "lovasz_fwd: %d classes (2..16)", C);
   MUVO_CHECK_ARG(F > 0 && V > 0, "lovasz_fwd: bad args (F=%lld V=%lld)", (long long)F, (long long)V);
   MUVO_CHECK_ARG(F * C <= 65535, "lovasz_fwd: more than 65535 (frame, class) segments");
   MUVO_CHECK_ARG(V <= LV_MAX_V, "lovasz_fwd: more than 2^30 voxels per frame");
@@ -500,7 +448,7 @@ int muvo_lovasz_fwd(const float* logits, const uint8_t* labels, int64_t F, int C
 int muvo_lovasz_bwd(const float* logits, const uint8_t* labels, const float* dlde, const uint8_t* present, float* dlogits, int64_t F, int C,
                     int64_t V, float weight, const float* gout, void* stream) {
   MUVO_CHECK_ARG(logits && labels && dlde && present && dlogits && gout, "lovasz_bwd: null pointer");
-  MUVO_CHECK_ARG(C >= 2 && C <= LV_MAXC, "lovasz_bwd: %d classes (2..16)", C);
+  MUVO_CHECK_ARG(C >= 2 && C <= VG_MAXC, "lovasz_bwd: %d classes (2..16)", C);
   MUVO_CHECK_ARG(F > 0 && V > 0, "lovasz_bwd: bad args (F=%lld V=%lld)", (long long)F, (long long)V);
   MUVO_CHECK_ARG(F * C <= 65535, "lovasz_bwd: more than 65535 (frame, class) segments");
   MUVO_CHECK_ARG(V <= LV_MAX_V, "lovasz_bwd: more than 2^30 voxels per frame");

@@ -1,21 +1,16 @@
 // First-hit ray casting through voxel class grids (muvo_amd/voxel_view.py): the `_voxel` panel and the RayIoU metric.  The march
-// is the definition of include/muvo_hip.h (muvo_raycast), statement by statement and in its order - tests/raycast_reference.py
-// restates it in numpy float32 and the kernels are compared with it bit for bit, so nothing here may be reassociated, contracted
-// or replaced by an approximate division.
+// is the definition of include/muvo_hip.h (muvo_raycast): its walk from cell to cell is vg_start / vg_step of voxel_grid.h, which
+// render.hip takes too.
 // One thread owns one ray of one frame; the rays of a wave are neighbours of the table (adjacent pixels of the camera, adjacent
 // azimuths of a lidar beam), so they enter the grid together and diverge only where the surfaces they meet differ.  Occupancy
 // comes from 4 x 4 x 4 bricks, one uint64 each (bit (x&3) 16 + (y&3) 4 + (z&3)): the word of the current brick stays in registers
 // and is loaded again only when the ray leaves the brick - one 8-byte load per up to ~10 steps instead of one byte load per
 // step - and a frame's words (288 KiB at 192 x 192 x 64) stay in the L2 of every XCD that marches it.  The class byte is read once, at
 // the hit.  Measured against the same march testing the class bytes directly: 10 - 25 % less time, equal results.
-// The three axes are handled by the same macro three times and selected with compares: no local array is indexed dynamically
-// (the build refuses scratch memory).  The loop has the hard bound X + Y + Z + 3 whatever the input.
+// The loop has the hard bound X + Y + Z + 3 whatever the input.
 #include <algorithm>
 
-#include "common.h"
-
-#define RC_MAXC 16
-#define RC_MAXDIM 2048          // (float)N is exact and (x Y + y) Z + z stays far below 2^31 together with the voxel bound below
+#include "voxel_grid.h"
 
 struct RcGrid {
   const uint8_t* __restrict__ cls;       // (X, Y, Z) classes of this frame
@@ -29,69 +24,23 @@ struct RcHit {
   int face;
 };
 
-__device__ __forceinline__ int rc_cell(float p, int N) {
-  const float f = floorf(p);
-  return !(f >= 0.f) ? 0 : (f > (float)(N - 1) ? N - 1 : (int)f);
-}
-
-#define RC_SLAB(o, d, inv, N, a)                                                   \
-  if (d != 0.f) {                                                                  \
-    inv = 1.0f / d;                                                                \
-    const float ta = (0.0f - o) * inv, tb = ((float)(N) - o) * inv;                \
-    const bool asc = ta <= tb;                                                     \
-    const float lo = asc ? ta : tb, hi = asc ? tb : ta;                            \
-    if (!(lo <= hi)) ok = false;                                                   \
-    if (lo > t0) { t0 = lo; entry = a; }                                           \
-    if (hi < t1) t1 = hi;                                                          \
-    any = true;                                                                    \
-  } else if (!(0.0f <= o && o < (float)(N))) {                                     \
-    ok = false;                                                                    \
-  }
-
-#define RC_NEXT(o, d, inv, c, a)                                                   \
-  if (d != 0.f) {                                                                  \
-    const float tn = ((float)(c + (d > 0.f ? 1 : 0)) - o) * inv;                   \
-    if (tn < best) { best = tn; axis = a; }                                        \
-  }
-
-__device__ __forceinline__ RcHit rc_march(const RcGrid& g, float ox, float oy, float oz, float dx, float dy, float dz, float tmax) {
+// the walk of voxel_grid.h with the occupancy test in front of every step: hit.t = the entry depth of the occupied cell, hit.face =
+// the axis of the boundary crossed last (the entry face in the start cell)
+__device__ __forceinline__ RcHit rc_march(const RcGrid& g, const float* __restrict__ q) {
   const RcHit miss{-1, 0.f, 0};
-  float t0 = 0.f, t1 = tmax, ix = 0.f, iy = 0.f, iz = 0.f;
-  int entry = 3;
-  bool ok = true, any = false;
-  RC_SLAB(ox, dx, ix, g.X, 0)
-  RC_SLAB(oy, dy, iy, g.Y, 1)
-  RC_SLAB(oz, dz, iz, g.Z, 2)
-  if (!ok || !any || !(t0 < t1)) return miss;
-  int cx = rc_cell(ox + dx * t0, g.X), cy = rc_cell(oy + dy * t0, g.Y), cz = rc_cell(oz + dz * t0, g.Z);
-  float t = t0;
-  int face = entry;
+  VgRay s;
+  int face;
+  if (!vg_start(s, q, g.X, g.Y, g.Z, face)) return miss;
   int held = -1;
   uint64_t word = 0;
   const int bound = g.X + g.Y + g.Z + 3;
   for (int it = 0; it < bound; ++it) {
-    const int b = ((cx >> 2) * g.BY + (cy >> 2)) * g.BZ + (cz >> 2);
+    const int b = ((s.cx >> 2) * g.BY + (s.cy >> 2)) * g.BZ + (s.cz >> 2);
     if (b != held) { word = g.bricks[b]; held = b; }
-    const bool occupied = (word >> (((cx & 3) << 4) | ((cy & 3) << 2) | (cz & 3))) & 1ull;
-    if (occupied) return RcHit{(cx * g.Y + cy) * g.Z + cz, t, face};
-    float best = __builtin_inff();
-    int axis = -1;
-    RC_NEXT(ox, dx, ix, cx, 0)
-    RC_NEXT(oy, dy, iy, cy, 1)
-    RC_NEXT(oz, dz, iz, cz, 2)
-    if (axis < 0 || best > t1) return miss;
-    if (axis == 0) {
-      cx += dx > 0.f ? 1 : -1;
-      if (cx < 0 || cx >= g.X) return miss;
-    } else if (axis == 1) {
-      cy += dy > 0.f ? 1 : -1;
-      if (cy < 0 || cy >= g.Y) return miss;
-    } else {
-      cz += dz > 0.f ? 1 : -1;
-      if (cz < 0 || cz >= g.Z) return miss;
-    }
-    t = best;
-    face = axis;
+    const bool occupied = (word >> (((s.cx & 3) << 4) | ((s.cy & 3) << 2) | (s.cz & 3))) & 1ull;
+    if (occupied) return RcHit{(s.cx * g.Y + s.cy) * g.Z + s.cz, s.t, face};
+    face = vg_step(s, g.X, g.Y, g.Z);
+    if (face < 0) return miss;
   }
   return miss;
 }
@@ -179,7 +128,7 @@ __global__ void __launch_bounds__(256) rc_cast_kernel(RcFrames g, const float* _
   const int f = blockIdx.y;
   if (r >= R) return;
   const float* __restrict__ q = rays + r * 7;
-  const RcHit h = rc_march(g.frame(f), q[0], q[1], q[2], q[3], q[4], q[5], q[6]);
+  const RcHit h = rc_march(g.frame(f), q);
   const size_t o = (size_t)f * R + r;
   hit[o] = h.idx;
   t[o] = h.t;
@@ -202,7 +151,7 @@ __global__ void __launch_bounds__(256) rc_view_kernel(RcFrames g, const float* _
   if (i >= 0 && i < R && j >= 0 && j < R) {
     const float* __restrict__ q = rays + ((long)i * R + j) * 7;
     const RcGrid fr = g.frame(f);
-    const RcHit h = rc_march(fr, q[0], q[1], q[2], q[3], q[4], q[5], q[6]);
+    const RcHit h = rc_march(fr, q);
     if (h.idx < 0) {
       cr = palette[0]; cg = palette[1]; cb = palette[2];
     } else {
@@ -220,7 +169,7 @@ __global__ void __launch_bounds__(256) rc_view_kernel(RcFrames g, const float* _
 // integer sums, order-free.  The depth sums leave as one fp64 partial pair per workgroup (part[(f NB + block) 2 + k]).
 __global__ void __launch_bounds__(256) rc_iou_kernel(RcFrames gl, RcFrames gp, const float* __restrict__ rays, long R, int C, float res, float thr0,
                                                      float thr1, float thr2, unsigned long long* __restrict__ counts, double* __restrict__ part) {
-  __shared__ unsigned cnt[3 * RC_MAXC * 3];
+  __shared__ unsigned cnt[3 * VG_MAXC * 3];
   __shared__ double red[2][4];
   for (int k = threadIdx.x; k < 9 * C; k += 256) cnt[k] = 0;
   __syncthreads();
@@ -230,8 +179,8 @@ __global__ void __launch_bounds__(256) rc_iou_kernel(RcFrames gl, RcFrames gp, c
   if (r < R) {
     const float* __restrict__ q = rays + r * 7;
     const RcGrid fl = gl.frame(f), fp = gp.frame(f);
-    const RcHit hl = rc_march(fl, q[0], q[1], q[2], q[3], q[4], q[5], q[6]);
-    const RcHit hp = rc_march(fp, q[0], q[1], q[2], q[3], q[4], q[5], q[6]);
+    const RcHit hl = rc_march(fl, q);
+    const RcHit hp = rc_march(fp, q);
     const int cl = hl.idx >= 0 ? (int)fl.cls[hl.idx] : -1, cp = hp.idx >= 0 ? (int)fp.cls[hp.idx] : -1;
     const bool both = cl >= 0 && cp >= 0;
     const float err = both ? fabsf(hp.t - hl.t) * res : 0.f;
@@ -271,10 +220,8 @@ __global__ void __launch_bounds__(64) rc_iou_sum_kernel(const double* __restrict
 #define ST ((hipStream_t)stream)
 
 static int rc_sizes(const char* who, int F, int X, int Y, int Z) {
-  MUVO_CHECK_ARG(F >= 1 && F <= 65535, "%s: %d frames outside 1..65535", who, F);
-  MUVO_CHECK_ARG(X >= 1 && Y >= 1 && Z >= 1 && X <= RC_MAXDIM && Y <= RC_MAXDIM && Z <= RC_MAXDIM && (int64_t)X * Y * Z < (1ll << 30),
-                 "%s: grid %d x %d x %d (1..%d per axis, below 2^30 voxels)", who, X, Y, Z, RC_MAXDIM);
-  return MUVO_OK;
+  if (int rc = vg_check_frames(who, F)) return rc;
+  return vg_check_grid(who, X, Y, Z);
 }
 
 static RcFrames rc_frames(const uint8_t* cls, const uint64_t* bricks, int X, int Y, int Z) {
@@ -304,7 +251,7 @@ static int rc_bricks(const char* who, const void* src, bool logits, int F, int C
 extern "C" {
 
 int64_t muvo_raycast_brick_words(int F, int X, int Y, int Z) {
-  if (F < 1 || F > 65535 || X < 1 || Y < 1 || Z < 1 || X > RC_MAXDIM || Y > RC_MAXDIM || Z > RC_MAXDIM) return -1;
+  if (!(vg_frames_ok(F) && vg_axes_ok(X, Y, Z))) return -1;
   return (int64_t)F * ((X + 3) / 4) * ((Y + 3) / 4) * ((Z + 3) / 4);
 }
 
@@ -313,14 +260,14 @@ int muvo_raycast_bricks_grid(const uint8_t* grid, int F, int X, int Y, int Z, ui
 }
 
 int muvo_raycast_bricks_logits(const float* logits, int F, int C, int X, int Y, int Z, uint8_t* grid, uint64_t* bricks, int64_t words, void* stream) {
-  MUVO_CHECK_ARG(C >= 2 && C <= RC_MAXC, "raycast_bricks_logits: C = %d outside 2..%d", C, RC_MAXC);
+  if (int rc = vg_check_classes("raycast_bricks_logits", C)) return rc;
   return rc_bricks("raycast_bricks_logits", logits, true, F, C, X, Y, Z, grid, bricks, words, ST);
 }
 
 int muvo_raycast(const uint8_t* grid, const uint64_t* bricks, int F, int X, int Y, int Z, const float* rays, int64_t R, int32_t* hit, float* t,
                  uint8_t* face, void* stream) {
   if (int rc = rc_sizes("raycast", F, X, Y, Z)) return rc;
-  MUVO_CHECK_ARG(R >= 1 && R <= (1ll << 24), "raycast: %lld rays outside 1..2^24", (long long)R);
+  if (int rc = vg_check_rays("raycast", R)) return rc;
   MUVO_CHECK_ARG(grid && bricks && rays && hit && t && face, "raycast: null pointer");
   hipLaunchKernelGGL(rc_cast_kernel, dim3((unsigned)((R + 255) / 256), (unsigned)F), dim3(256), 0, ST, rc_frames(grid, bricks, X, Y, Z), rays, (long)R, hit, t,
                      face);
@@ -356,14 +303,14 @@ int muvo_panel_voxel_view(const uint8_t* grid, const uint64_t* bricks, int F, in
   return MUVO_OK;
 }
 
-int64_t muvo_ray_iou_ws_doubles(int64_t F, int64_t R) { return (F < 1 || F > 65535 || R < 1 || R > (1ll << 24)) ? -1 : F * ((R + 255) / 256) * 2; }
+int64_t muvo_ray_iou_ws_doubles(int64_t F, int64_t R) { return vg_frames_ok(F) && vg_rays_ok(R) ? F * ((R + 255) / 256) * 2 : -1; }
 
 int muvo_ray_iou_counts(const uint8_t* label, const uint64_t* label_bricks, const uint8_t* pred, const uint64_t* pred_bricks, int F, int C, int X, int Y,
                         int Z, const float* rays, int64_t R, float res, const float* thresholds, uint64_t* counts, double* ws, int64_t ws_doubles,
                         double* depth, void* stream) {
   if (int rc = rc_sizes("ray_iou_counts", F, X, Y, Z)) return rc;
-  MUVO_CHECK_ARG(C >= 2 && C <= RC_MAXC, "ray_iou_counts: C = %d outside 2..%d", C, RC_MAXC);
-  MUVO_CHECK_ARG(R >= 1 && R <= (1ll << 24), "ray_iou_counts: %lld rays outside 1..2^24", (long long)R);
+  if (int rc = vg_check_classes("ray_iou_counts", C)) return rc;
+  if (int rc = vg_check_rays("ray_iou_counts", R)) return rc;
   MUVO_CHECK_ARG(label && label_bricks && pred && pred_bricks && rays && thresholds && counts && ws && depth, "ray_iou_counts: null pointer");
   MUVO_CHECK_ARG(res > 0.f && thresholds[0] >= 0.f && thresholds[1] >= 0.f && thresholds[2] >= 0.f, "ray_iou_counts: resolution %g not positive or a negative threshold",
                  (double)res);

@@ -2,7 +2,7 @@
 // loss).  include/muvo_hip.h (muvo_render_fwd) is the definition; tests/render_reference.py restates it.
 //   occupancy pass  logits -> q = P(free), a = P(occupied) per cell, (F, V) pairs of fp32, 4 consecutive voxels per lane
 //   march           one thread per (ray, frame): the cell sequence of muvo_raycast through a grid in which nothing is occupied -
-//                   steps 1 - 3 of that definition word for word, fp32, uncontracted - composited front to back:
+//                   the walk raycast.hip takes, vg_start / vg_step of voxel_grid.h - composited front to back:
 //                   T in fp32, the depth sum in fp64.  |D - t*| leaves as one fp64 partial per workgroup.
 //   finish          one workgroup adds the partials in a fixed order and writes the fp32 scalar.
 //   backward        the occupancy pass again (q and a are recomputed, not kept: 8 bytes a voxel and frame), then the same march
@@ -14,129 +14,15 @@
 // distinct destinations of a wave; inside a march that loop would run up to 64 times per step once the rays have spread, so here
 // the runs are summed by a segmented shuffle reduction of fixed cost (6 steps) and the head of each run issues the atomic.  Equal
 // cells in different runs simply issue one atomic each - integer sums, the result is the same.
-// The three axes are handled by the same macro three times and selected with compares: no local array is indexed dynamically
-// (the build refuses scratch memory).  The march loop has the hard bound X + Y + Z + 3 whatever the input.
-#include "common.h"
+// The march loop has the hard bound X + Y + Z + 3 whatever the input.
+#include "voxel_grid.h"
 
 #define RN_THREADS 256
 #define RN_VOX (RN_THREADS * 4)          // voxels per workgroup of the dense passes (4 consecutive per lane)
-#define RN_MAXC 16
-#define RN_MAXDIM 2048
-#define RN_MAX_R (1ll << 24)
 #define RN_FIX_BITS 26                    // see the header: 2^24 rays x 2048 sqrt(3) x 2^26 < 2^62
 #define RN_FIX_CLAMP 4096.0               // a contribution is clamped to +-4096 before conversion (unit directions stay below 3548)
 
 typedef long long rn_i64x2 __attribute__((ext_vector_type(2)));
-
-// ---- the march of muvo_raycast, steps 1 - 3, without the occupancy test -------------------------------------------------------------
-struct RnRay {
-  float ox, oy, oz, dx, dy, dz, ix, iy, iz;
-  float t1;                                // exit depth
-  float t;                                 // entry depth of the current cell
-  int cx, cy, cz;
-};
-
-__device__ __forceinline__ int rn_cell(float p, int N) {
-  const float f = floorf(p);
-  return !(f >= 0.f) ? 0 : (f > (float)(N - 1) ? N - 1 : (int)f);
-}
-
-#define RN_SLAB(o, d, inv, N)                                                      \
-  if (d != 0.f) {                                                                  \
-    inv = 1.0f / d;                                                                \
-    const float ta = (0.0f - o) * inv, tb = ((float)(N) - o) * inv;                \
-    const bool asc = ta <= tb;                                                     \
-    const float lo = asc ? ta : tb, hi = asc ? tb : ta;                            \
-    if (!(lo <= hi)) ok = false;                                                   \
-    if (lo > t0) t0 = lo;                                                          \
-    if (hi < t1) t1 = hi;                                                          \
-    any = true;                                                                    \
-  } else if (!(0.0f <= o && o < (float)(N))) {                                     \
-    ok = false;                                                                    \
-  }
-
-#define RN_NEXT(o, d, inv, c, a)                                                   \
-  if (d != 0.f) {                                                                  \
-    const float tn = ((float)(c + (d > 0.f ? 1 : 0)) - o) * inv;                   \
-    if (tn < best) { best = tn; axis = a; }                                        \
-  }
-
-// steps 1 and 2; false: the ray is invalid (muvo_raycast calls it a miss before its step 2)
-__device__ __forceinline__ bool rn_start(RnRay& s, const float* __restrict__ q, int X, int Y, int Z) {
-  s.ox = q[0]; s.oy = q[1]; s.oz = q[2]; s.dx = q[3]; s.dy = q[4]; s.dz = q[5];
-  float t0 = 0.f, t1 = q[6];
-  s.ix = 0.f; s.iy = 0.f; s.iz = 0.f;
-  bool ok = true, any = false;
-  RN_SLAB(s.ox, s.dx, s.ix, X)
-  RN_SLAB(s.oy, s.dy, s.iy, Y)
-  RN_SLAB(s.oz, s.dz, s.iz, Z)
-  s.t1 = t1;
-  s.t = t0;
-  s.cx = 0; s.cy = 0; s.cz = 0;
-  if (!ok || !any || !(t0 < t1)) return false;
-  s.cx = rn_cell(s.ox + s.dx * t0, X);
-  s.cy = rn_cell(s.oy + s.dy * t0, Y);
-  s.cz = rn_cell(s.oz + s.dz * t0, Z);
-  return true;
-}
-
-// step 3 behind the occupancy test: to the next cell; false: the march has ended (best > t1, or the ray left the grid)
-__device__ __forceinline__ bool rn_step(RnRay& s, int X, int Y, int Z) {
-  float best = __builtin_inff();
-  int axis = -1;
-  RN_NEXT(s.ox, s.dx, s.ix, s.cx, 0)
-  RN_NEXT(s.oy, s.dy, s.iy, s.cy, 1)
-  RN_NEXT(s.oz, s.dz, s.iz, s.cz, 2)
-  if (axis < 0 || best > s.t1) return false;
-  if (axis == 0) {
-    const int c = s.cx + (s.dx > 0.f ? 1 : -1);
-    if (c < 0 || c >= X) return false;
-    s.cx = c;
-  } else if (axis == 1) {
-    const int c = s.cy + (s.dy > 0.f ? 1 : -1);
-    if (c < 0 || c >= Y) return false;
-    s.cy = c;
-  } else {
-    const int c = s.cz + (s.dz > 0.f ? 1 : -1);
-    if (c < 0 || c >= Z) return false;
-    s.cz = c;
-  }
-  s.t = best;
-  return true;
-}
-
-// ---- 4 consecutive voxels per lane: one 16-byte access when `vec` (aligned bases, V % 4 == 0), guarded scalars otherwise ---------
-__device__ __forceinline__ f32x4 rn_ld4(const float* __restrict__ p, long h0, long V, bool vec) {
-  if (vec) return *(const f32x4*)(p + h0);          // vec implies h0 + 3 < V
-  f32x4 r = {0.f, 0.f, 0.f, 0.f};
-  if (h0 < V) r.x = p[h0];
-  if (h0 + 1 < V) r.y = p[h0 + 1];
-  if (h0 + 2 < V) r.z = p[h0 + 2];
-  if (h0 + 3 < V) r.w = p[h0 + 3];
-  return r;
-}
-__device__ __forceinline__ void rn_st4(float* __restrict__ p, long h0, long V, bool vec, f32x4 v) {
-  if (vec) { *(f32x4*)(p + h0) = v; return; }
-  if (h0 < V) p[h0] = v.x;
-  if (h0 + 1 < V) p[h0 + 1] = v.y;
-  if (h0 + 2 < V) p[h0 + 2] = v.z;
-  if (h0 + 3 < V) p[h0 + 3] = v.w;
-}
-// m = the maximum over the classes, e0 = exp(x_0 - m), occ = sum_{c >= 1} exp(x_c - m) in ascending c
-__device__ __forceinline__ void rn_stats(const float* __restrict__ lf, int C, long V, long h0, bool vec, f32x4& m, f32x4& e0, f32x4& occ) {
-  const f32x4 x0 = rn_ld4(lf, h0, V, vec);
-  m = x0;
-  for (int c = 1; c < C; ++c) {
-    const f32x4 x = rn_ld4(lf + (size_t)c * V, h0, V, vec);
-    m.x = fmaxf(m.x, x.x); m.y = fmaxf(m.y, x.y); m.z = fmaxf(m.z, x.z); m.w = fmaxf(m.w, x.w);
-  }
-  e0 = f32x4{expf(x0.x - m.x), expf(x0.y - m.y), expf(x0.z - m.z), expf(x0.w - m.w)};
-  occ = f32x4{0.f, 0.f, 0.f, 0.f};
-  for (int c = 1; c < C; ++c) {
-    const f32x4 x = rn_ld4(lf + (size_t)c * V, h0, V, vec);
-    occ.x += expf(x.x - m.x); occ.y += expf(x.y - m.y); occ.z += expf(x.z - m.z); occ.w += expf(x.w - m.w);
-  }
-}
 
 // qa[cell] = (q, a) = (e0 / (e0 + occ), occ / (e0 + occ)), interleaved: a march step takes both with one 8-byte load.
 // grid = (voxel blocks, frames)
@@ -145,9 +31,8 @@ __global__ void __launch_bounds__(RN_THREADS) render_occ_kernel(const float* __r
   const long h0 = ((long)blockIdx.x * RN_THREADS + threadIdx.x) * 4;
   if (h0 >= V) return;
   const bool v4 = vec && h0 + 3 < V;
-  f32x4 m, e0, occ;
-  rn_stats(logits + (size_t)f * C * V, C, V, h0, v4, m, e0, occ);
-  const f32x4 s = e0 + occ;
+  const VgSoftmax st = vg_softmax_stats(logits + (size_t)f * C * V, C, V, h0, v4);
+  const f32x4 e0 = st.e0, occ = st.rest, s = e0 + occ;
   float2* __restrict__ o = qa + (size_t)f * V + h0;
   if (v4) {                                          // (f V + h0) 8 bytes is a multiple of 32
     *(f32x4*)o = f32x4{e0.x / s.x, occ.x / s.x, e0.y / s.y, occ.y / s.y};
@@ -173,8 +58,9 @@ render_march_kernel(const float2* __restrict__ qa, const float* __restrict__ ray
   const size_t V = (size_t)X * Y * Z;
   double err = 0.0;
   if (r < R) {
-    RnRay s;
-    const bool valid = rn_start(s, rays + r * 7, X, Y, Z);
+    VgRay s;
+    int entry;
+    const bool valid = vg_start(s, rays + r * 7, X, Y, Z, entry);
     const size_t o = (size_t)f * R + r;
     float T = 1.f;
     double P = 0.0, Dv = 0.0;
@@ -191,7 +77,7 @@ render_march_kernel(const float2* __restrict__ qa, const float* __restrict__ ray
         T = T * c.x;
         ++n;
         if (!ALL && T == 0.f) break;
-        if (!rn_step(s, X, Y, Z)) break;
+        if (vg_step(s, X, Y, Z) < 0) break;
       }
       Dv = P + (double)T * (double)s.t1;
       ts = lhit[o] >= 0 ? lt[o] : s.t1;
@@ -234,20 +120,16 @@ render_bwd_march_kernel(const float2* __restrict__ qa, const float* __restrict__
   const int f = blockIdx.y;
   const int lane = threadIdx.x & 63;
   const long V = (long)X * Y * Z;
-  RnRay s;
+  VgRay s = {};
+  int entry;
   bool active = false;
   double Dv = 0.0, sg = 0.0;
-  if (r < R) {
-    if (rn_start(s, rays + r * 7, X, Y, Z)) {
-      const size_t o = (size_t)f * R + r;
-      Dv = D[o];
-      const double d = Dv - (double)tstar[o];
-      sg = d > 0.0 ? 1.0 : (d < 0.0 ? -1.0 : 0.0);
-      active = sg != 0.0;
-    }
-  } else {
-    s.ox = s.oy = s.oz = s.dx = s.dy = s.dz = s.ix = s.iy = s.iz = s.t1 = s.t = 0.f;
-    s.cx = s.cy = s.cz = 0;
+  if (r < R && vg_start(s, rays + r * 7, X, Y, Z, entry)) {
+    const size_t o = (size_t)f * R + r;
+    Dv = D[o];
+    const double d = Dv - (double)tstar[o];
+    sg = d > 0.0 ? 1.0 : (d < 0.0 ? -1.0 : 0.0);
+    active = sg != 0.0;
   }
   const float2* __restrict__ qf = qa + (size_t)f * V;
   unsigned long long* __restrict__ accf = acc + (size_t)f * V;
@@ -269,7 +151,7 @@ render_bwd_march_kernel(const float2* __restrict__ qa, const float* __restrict__
       T = Tk;
       g = g > RN_FIX_CLAMP ? RN_FIX_CLAMP : (g < -RN_FIX_CLAMP ? -RN_FIX_CLAMP : (g == g ? g : 0.0));
       val = __double2ll_rn(g * (double)(1ll << RN_FIX_BITS));
-      if (T == 0.f || !rn_step(s, X, Y, Z)) active = false;       // behind T == 0 every contribution is exactly 0
+      if (T == 0.f || vg_step(s, X, Y, Z) < 0) active = false;      // behind T == 0 every contribution is exactly 0
     }
     if (!COMBINE) {
       if (cell >= 0 && (long)cell < V && val != 0) atomicAdd(accf + cell, (unsigned long long)val);
@@ -312,16 +194,14 @@ render_dense_kernel(const float* __restrict__ logits, const long long* __restric
   const double g0 = (double)k0 * sc, g1 = (double)k1 * sc, g2 = (double)k2 * sc, g3 = (double)k3 * sc;
   const float* __restrict__ lf = logits + (size_t)f * C * V;
   float* __restrict__ df = dlogits + (size_t)f * C * V;
-  f32x4 m, e0, occ;
-  rn_stats(lf, C, V, h0, v4, m, e0, occ);
-  const f32x4 s = e0 + occ;
+  const VgSoftmax st = vg_softmax_stats(lf, C, V, h0, v4);
+  const f32x4 occ = st.rest, s = st.e0 + occ;
   // class 0: p_0 - 1 = -a, from the same sum as the forward pass
-  rn_st4(df, h0, V, v4, f32x4{(float)(g0 * -(double)(occ.x / s.x)), (float)(g1 * -(double)(occ.y / s.y)), (float)(g2 * -(double)(occ.z / s.z)),
+  vg_st4(df, h0, V, v4, f32x4{(float)(g0 * -(double)(occ.x / s.x)), (float)(g1 * -(double)(occ.y / s.y)), (float)(g2 * -(double)(occ.z / s.z)),
                               (float)(g3 * -(double)(occ.w / s.w))});
   for (int c = 1; c < C; ++c) {
-    const f32x4 x = rn_ld4(lf + (size_t)c * V, h0, V, v4);
-    const f32x4 p = f32x4{expf(x.x - m.x) / s.x, expf(x.y - m.y) / s.y, expf(x.z - m.z) / s.z, expf(x.w - m.w) / s.w};
-    rn_st4(df + (size_t)c * V, h0, V, v4, f32x4{(float)(g0 * (double)p.x), (float)(g1 * (double)p.y), (float)(g2 * (double)p.z), (float)(g3 * (double)p.w)});
+    const f32x4 p = vg_prob(vg_ld4(lf + (size_t)c * V, h0, V, v4), st.m, s);
+    vg_st4(df + (size_t)c * V, h0, V, v4, f32x4{(float)(g0 * (double)p.x), (float)(g1 * (double)p.y), (float)(g2 * (double)p.z), (float)(g3 * (double)p.w)});
   }
 }
 
@@ -329,8 +209,6 @@ render_dense_kernel(const float* __restrict__ logits, const long long* __restric
 #define ST ((hipStream_t)stream)
 
 static inline int64_t rn_up16(int64_t n) { return (n + 15) & ~(int64_t)15; }
-
-static bool rn_sizes_ok(int64_t F, int64_t V, int64_t R) { return F >= 1 && F <= 65535 && V >= 1 && V < (1ll << 30) && R >= 1 && R <= RN_MAX_R; }
 
 struct RnWs {
   float2* qa;
@@ -344,11 +222,10 @@ static RnWs rn_ws(void* ws, int64_t F, int64_t V) {
 }
 
 static int rn_check(const char* who, int64_t F, int C, int X, int Y, int Z, int64_t R, int64_t n_valid, const void* ws, int64_t ws_bytes) {
-  MUVO_CHECK_ARG(F >= 1 && F <= 65535, "%s: %lld frames outside 1..65535", who, (long long)F);
-  MUVO_CHECK_ARG(C >= 2 && C <= RN_MAXC, "%s: C = %d outside 2..%d", who, C, RN_MAXC);
-  MUVO_CHECK_ARG(X >= 1 && Y >= 1 && Z >= 1 && X <= RN_MAXDIM && Y <= RN_MAXDIM && Z <= RN_MAXDIM && (int64_t)X * Y * Z < (1ll << 30),
-                 "%s: grid %d x %d x %d (1..%d per axis, below 2^30 voxels)", who, X, Y, Z, RN_MAXDIM);
-  MUVO_CHECK_ARG(R >= 1 && R <= RN_MAX_R, "%s: %lld rays outside 1..2^24", who, (long long)R);
+  if (int rc = vg_check_frames(who, F)) return rc;
+  if (int rc = vg_check_classes(who, C)) return rc;
+  if (int rc = vg_check_grid(who, X, Y, Z)) return rc;
+  if (int rc = vg_check_rays(who, R)) return rc;
   MUVO_CHECK_ARG(n_valid >= 0 && n_valid <= R, "%s: %lld valid rays of %lld", who, (long long)n_valid, (long long)R);
   const int64_t need = muvo_render_ws_bytes(F, (int64_t)X * Y * Z, R);
   MUVO_CHECK_ARG(ws != nullptr && ((uintptr_t)ws & 15) == 0 && ws_bytes >= need, "%s: workspace of %lld bytes, %lld needed (16-byte aligned)", who,
@@ -364,7 +241,7 @@ static void rn_occupancy(const float* logits, int64_t F, int C, int64_t V, const
 extern "C" {
 
 int64_t muvo_render_ws_bytes(int64_t F, int64_t V, int64_t R) {
-  if (!rn_sizes_ok(F, V, R)) return -1;
+  if (!(vg_frames_ok(F) && vg_voxels_ok(V) && vg_rays_ok(R))) return -1;
   return rn_up16(F * V * 8) + F * V * 8 + F * ((R + RN_THREADS - 1) / RN_THREADS) * 8;
 }
 

@@ -2571,7 +2571,10 @@ def resize_nearest(x, out_sz):
 def _grad_vector(gs, device):
     """the gradients of k scalar outputs of a loss Function (`terms=True`: returned as separate 0-d tensors, so that the caller's
     `[i]` is a tuple index and not k select_backward nodes of 2-3 launches each) as ONE (k,) device vector for the backward kernel;
-    a term nobody differentiated counts as zero.  One launch (all terms usually receive the same upstream scalar)."""
+    a term nobody differentiated counts as zero.  One launch (all terms usually receive the same upstream scalar).  The gradient
+    of the stacked 1-D output (`terms=False`) is that vector already."""
+    if len(gs) == 1 and gs[0] is not None and gs[0].dim() == 1:
+        return gs[0].contiguous()
     first = next((g for g in gs if g is not None), None)
     if first is None:
         return torch.zeros(len(gs), device=device, dtype=torch.float32)
@@ -2585,6 +2588,20 @@ def _grad_vector(gs, device):
             g = zero
         parts.append(g.reshape(()))
     return torch.stack(parts)
+
+
+def _grad_scalar(g, device):
+    """the gradient of the one scalar output of a loss Function as a (1,) device vector; nobody differentiated it: zero"""
+    return torch.zeros(1, device=device) if g is None else g.reshape(1)
+
+
+def _voxel_dims(logits, labels=None):
+    """(F, C, V) of logits (B,S,C,X,Y,Z); with labels, also checks that they are the uint8 grid of the logits"""
+    b, s, c = logits.shape[:3]
+    f = b * s
+    v = logits.numel() // (f * c)
+    assert labels is None or (labels.dtype == torch.uint8 and labels.numel() == f * v), 'labels must be uint8 (B,S,1,X,Y,Z) on the grid of the logits'
+    return f, c, v
 
 
 def _as_terms(ctx, t, terms):
@@ -2622,7 +2639,7 @@ class SpatialLossFn(torch.autograd.Function):
     def backward(ctx, *gs):
         pred, target, stats, mask = ctx.saved_tensors
         f, c, hw = ctx.dims
-        g = gs[0].contiguous() if (len(gs) == 1 and gs[0] is not None and gs[0].dim() == 1) else _grad_vector(gs, pred.device)
+        g = _grad_vector(gs, pred.device)
         covered = sum(c1 - c0 for c0, c1, _, _ in ctx.parts)
         dpred = torch.empty_like(pred) if covered == c else torch.zeros_like(pred)
         for i, (c0, c1, norm, weight) in enumerate(ctx.parts):
@@ -2643,15 +2660,14 @@ class VoxelLossFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, logits, target, weight, class_w, terms=False):
         logits, target = logits.contiguous(), target.contiguous()
-        b, s, c = logits.shape[:3]
-        v = logits.numel() // (b * s * c)
+        f, c, v = _voxel_dims(logits)
         L = lib()
         stats = torch.empty(L.muvo_voxel_loss_stats_doubles(c), device=logits.device, dtype=torch.float64)
         coef = torch.empty(L.muvo_voxel_loss_coef_floats(c), device=logits.device, dtype=torch.float32)
         loss3 = torch.empty(3, device=logits.device, dtype=torch.float32)
-        _ck(L.muvo_voxel_loss_fwd(_f(logits), _p(target), _i64(b * s), c, _i64(v), _f(class_w), _fl(weight), _p(stats),
+        _ck(L.muvo_voxel_loss_fwd(_f(logits), _p(target), _i64(f), c, _i64(v), _f(class_w), _fl(weight), _p(stats),
                                   _f(coef), _f(loss3), _st()))
-        ctx.dims, ctx.weight, ctx.class_w = (b * s, c, v), weight, class_w
+        ctx.dims, ctx.weight, ctx.class_w = (f, c, v), weight, class_w
         ctx.save_for_backward(logits, target, coef)
         return _as_terms(ctx, loss3, terms)
 
@@ -2659,7 +2675,7 @@ class VoxelLossFn(torch.autograd.Function):
     def backward(ctx, *gs):
         logits, target, coef = ctx.saved_tensors
         f, c, v = ctx.dims
-        g = gs[0].contiguous() if (len(gs) == 1 and gs[0] is not None and gs[0].dim() == 1) else _grad_vector(gs, logits.device)
+        g = _grad_vector(gs, logits.device)
         dl = torch.empty_like(logits)
         _ck(lib().muvo_voxel_loss_bwd(_f(logits), _p(target), _f(dl), _i64(f), c, _i64(v), _f(ctx.class_w),
                                       _fl(ctx.weight), _f(coef), _f(g), _st()))
@@ -2687,7 +2703,7 @@ class L1RowsFn(torch.autograd.Function):
         pred, target = ctx.saved_tensors
         rows, cols = ctx.dims
         dp = torch.empty_like(pred)
-        g = torch.zeros(1, device=pred.device) if g is None else g.reshape(1)
+        g = _grad_scalar(g, pred.device)
         _ck(lib().muvo_l1_rows_bwd(_f(pred), _f(target), _f(dp), _i64(rows), cols, _fl(ctx.weight), _f(g.contiguous()),
                                    _st()))
         return dp, None, None, None
@@ -2739,7 +2755,7 @@ class KLLossFn(torch.autograd.Function):
     def backward(ctx, g):
         pm, ps, qm, qs = ctx.saved_tensors
         b, t, s, weight, alpha = ctx.args
-        g = torch.zeros(1, device=pm.device) if g is None else g.reshape(1)
+        g = _grad_scalar(g, pm.device)
         d = [torch.empty_like(pm) for _ in range(4)]
         _ck(lib().muvo_kl_loss_bwd(_f(pm), _f(ps), _f(qm), _f(qs), _f(d[0]), _f(d[1]), _f(d[2]), _f(d[3]), b, t, s,
                                    _fl(weight), _fl(alpha), _f(g.contiguous()), _st()))
@@ -2785,7 +2801,7 @@ class ChamferLossFn(torch.autograd.Function):
     def backward(ctx, g):
         pred, target, idx = ctx.saved_tensors
         f, cp, ct, n = ctx.dims
-        g = torch.zeros(1, device=pred.device) if g is None else g.reshape(1)
+        g = _grad_scalar(g, pred.device)
         dpred = torch.empty_like(pred)
         _ck(lib().muvo_chamfer_loss_bwd(_f(pred), _f(target), _p(idx[0]), _p(idx[1]), _f(dpred), _i64(f), cp, ct, _i64(n),
                                         _fl(ctx.weight), _f(g.contiguous()), _st()))
@@ -2805,10 +2821,7 @@ def chamfer_nearest(pred, target):
 
 def _lovasz_forward(logits, labels, weight, with_dlde, with_errors=False):
     logits, labels = logits.contiguous(), labels.contiguous()
-    b, s, c = logits.shape[:3]
-    f = b * s
-    v = logits.numel() // (f * c)
-    assert labels.dtype == torch.uint8 and labels.numel() == f * v, 'labels must be uint8 (B,S,1,X,Y,Z) on the grid of the logits'
+    f, c, v = _voxel_dims(logits, labels)
     L = lib()
     ws = torch.empty(max(16, L.muvo_lovasz_ws_bytes(_i64(f), c, _i64(v))), device=logits.device, dtype=torch.uint8)
     errors = torch.empty(f, c, v, device=logits.device, dtype=torch.float32) if with_errors else None
@@ -2838,7 +2851,7 @@ class VoxelLovaszFn(torch.autograd.Function):
     def backward(ctx, g):
         logits, labels, dlde, present = ctx.saved_tensors
         f, c, v = ctx.dims
-        g = torch.zeros(1, device=logits.device) if g is None else g.reshape(1)
+        g = _grad_scalar(g, logits.device)
         dl = torch.empty_like(logits)
         _ck(lib().muvo_lovasz_bwd(_f(logits), _p(labels), _f(dlde), _p(present), _f(dl), _i64(f), c, _i64(v), _fl(ctx.weight),
                                   _f(g.contiguous()), _st()))
@@ -2867,9 +2880,8 @@ def _render_ws(f, v, r, device):
 def _render_forward(logits, labels, rays, n_valid, weight, parts=False):
     logits, labels = logits.contiguous(), labels.contiguous()
     assert logits.dim() == 6 and logits.dtype == torch.float32, 'logits must be float32 (B,S,C,X,Y,Z)'
-    b, s, c, X, Y, Z = (int(n) for n in logits.shape)
-    f, v = b * s, X * Y * Z
-    assert labels.dtype == torch.uint8 and labels.numel() == f * v, 'labels must be uint8 (B,S,1,X,Y,Z) on the grid of the logits'
+    f, c, v = _voxel_dims(logits, labels)
+    X, Y, Z = (int(n) for n in logits.shape[3:])
     assert rays.dtype == torch.float32 and rays.dim() == 2 and rays.shape[1] == 7 and rays.is_contiguous() and rays.device == logits.device, \
         'rays must be a contiguous float32 (R, 7) table on the device of the logits'
     R = int(rays.shape[0])
@@ -2906,7 +2918,7 @@ class VoxelRenderFn(torch.autograd.Function):
     def backward(ctx, g):
         logits, rays, depth, target = ctx.saved_tensors
         f, c, X, Y, Z, R = ctx.dims
-        g = torch.zeros(1, device=logits.device) if g is None else g.reshape(1)
+        g = _grad_scalar(g, logits.device)
         ws, ws_bytes = _render_ws(f, X * Y * Z, R, logits.device)
         dl = torch.empty_like(logits)
         _ck(lib().muvo_render_bwd(_f(logits), _i64(f), c, X, Y, Z, _f(rays), _i64(R), _i64(ctx.n_valid), _p(depth), _f(target), _fl(ctx.weight),
