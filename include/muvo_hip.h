@@ -873,6 +873,30 @@ int muvo_render_fwd(const float* logits, int64_t F, int C, int X, int Y, int Z, 
 int muvo_render_bwd(const float* logits, int64_t F, int C, int X, int Y, int Z, const float* rays, int64_t R, int64_t n_valid, const double* depth,
                     const float* target, float weight, const float* gout, void* ws, int64_t ws_bytes, float* dlogits, void* stream);
 
+/* ---- sensor-visibility mask of the voxel labels (visibility.hip; an extension) ----------------------------
+ * OUR DEFINITION (the reference has no visibility mask; its SemScal / GeoScal losses carry ignore_index = 255 and nothing writes
+ * one); tests/visibility_reference.py restates it and the kernels equal that restatement bit for bit.
+ * Inputs: a label grid (F, X, Y, Z) uint8, its bricks from muvo_raycast_bricks_grid (occupied is what that entry calls occupied:
+ *   class != 0) and a ray table (R, 7) fp32 on the device, the rows of muvo_raycast, one table for all F frames; sizes as
+ *   muvo_raycast: F in 1..65535, every axis in 1..2048, fewer than 2^30 voxels, R in 1..2^24.
+ * Marking: for every ray that passes step 1 of muvo_raycast, walk the cells of its steps 1 - 3, the same fp32 statements in the
+ *   same order, and mark each visited cell SEEN; stop after marking the first occupied cell, or where step 3 ends the walk
+ *   (best > t1, no axis, leaving the grid).  A ray that is a miss before step 2 (a NaN, a zero or infinite direction, missing the
+ *   box, t0 >= t1) marks nothing.  The loop runs at most X + Y + Z + 3 iterations, carried as an explicit trip count.
+ * seen: one uint64 per 4 x 4 x 4 brick and frame in the layout and bit order of the occupancy bricks (word ((x>>2) BY + (y>>2)) BZ
+ *   + (z>>2) of the frame, bit (x&3) 16 + (y&3) 4 + (z&3)); `words` >= muvo_raycast_brick_words(F, X, Y, Z), 8-byte aligned.
+ *   muvo_visibility_mark clears it on the caller's stream and sets it with 64-bit integer OR atomics: a ray collects the bits of
+ *   consecutive cells of one brick in a register and issues one atomic when the brick changes and at its end - unless the word,
+ *   read first, already holds those bits (bits are only set during a call: a stale read costs an atomic, never a bit).  OR is
+ *   order-free: the same inputs give the same bits on every call, in both modes of muvo_set_deterministic.
+ * Masked label (muvo_visibility_apply): out (F, X, Y, Z) uint8 = label where label != 0; 0 where the cell is free and SEEN; 255
+ *   where it is free and not SEEN.  Occupied cells are never masked: a sensor point put them there, whatever the discretised march
+ *   does.  counts (2,) uint64 on the device, ADDED TO by integer atomics: [0] the free-and-seen cells, [1] the unknown cells of
+ *   the call.  out may not alias label. */
+int muvo_visibility_mark(const uint8_t* grid, const uint64_t* bricks, int F, int X, int Y, int Z, const float* rays, int64_t R, uint64_t* seen,
+                         int64_t words, void* stream);
+int muvo_visibility_apply(const uint8_t* label, const uint64_t* seen, int F, int X, int Y, int Z, uint8_t* out, uint64_t* counts, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

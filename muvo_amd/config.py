@@ -29,10 +29,18 @@ TOLERATED_EXTRA_KEYS = ('CML_DATASET_VERSION', 'MODEL.TRANSFORMER_TRANSITION', '
 #   1, 2, 4; absent = [1, 2, 4]) names the output scales that get a term `voxel_render_{f}` = WEIGHT / f x render(voxel_f,
 #   voxel_label_f) x VOXEL.RESOLUTION f / LIDAR_RE.SCALE (the scaled depth units of lidar_depth_f), STRIDE (an integer >= 1;
 #   absent = 1) takes every STRIDE-th azimuth of the range view as a ray.  Needs VOXEL_SEG.ENABLED.
+#   VOXEL_SEG.VISIBILITY.{ENABLED,LIDAR_STRIDE,CAMERA_STRIDE} - the sensor-visibility mask of the voxel labels (the reference has
+#   none: its labels call every unobserved cell "free").  ENABLED (bool; absent = off: no table, no launch, no new batch key)
+#   makes PreProcess add `voxel_visible_label_{1,2,4}`: voxel_label_f with every free cell that no ray of the lidar sweep or the
+#   depth camera passes before its first occupied cell set to 255, which the dense voxel losses (cross-entropy, SemScal, GeoScal,
+#   Lovasz) and the SSC metrics ignore; evaluation then also logs `{prefix}_Voxel_Unknown_Share`.  LIDAR_STRIDE (an integer >= 1;
+#   absent = 1) takes every STRIDE-th azimuth of the range view, CAMERA_STRIDE (an integer >= 1; absent = 2) every STRIDE-th
+#   pixel of the full camera frame in both directions.  Needs VOXEL_SEG.ENABLED, refuses VOXEL_SEG.USE_TOP_K.
 EXTENSION_KEYS = ('MODEL.CONSTANT_SIZE', 'MODEL.CONSTANT_SIZE.RGB', 'MODEL.CONSTANT_SIZE.LIDAR', 'MODEL.CONSTANT_SIZE.VOXEL',
                   'LOSSES.LIDAR_CD', 'LOSSES.LIDAR_CD.WEIGHT', 'LOSSES.LIDAR_CD.FACTORS',
                   'LOSSES.VOXEL_LOVASZ', 'LOSSES.VOXEL_LOVASZ.WEIGHT', 'LOSSES.VOXEL_LOVASZ.FACTORS',
-                  'LOSSES.VOXEL_RENDER', 'LOSSES.VOXEL_RENDER.WEIGHT', 'LOSSES.VOXEL_RENDER.FACTORS', 'LOSSES.VOXEL_RENDER.STRIDE')
+                  'LOSSES.VOXEL_RENDER', 'LOSSES.VOXEL_RENDER.WEIGHT', 'LOSSES.VOXEL_RENDER.FACTORS', 'LOSSES.VOXEL_RENDER.STRIDE',
+                  'VOXEL_SEG.VISIBILITY', 'VOXEL_SEG.VISIBILITY.ENABLED', 'VOXEL_SEG.VISIBILITY.LIDAR_STRIDE', 'VOXEL_SEG.VISIBILITY.CAMERA_STRIDE')
 DEFAULT_CONSTANT_SIZE = {'RGB': (5, 13), 'LIDAR': (1, 16), 'VOXEL': (3, 3, 1)}
 
 
@@ -105,6 +113,31 @@ def voxel_render(cfg):
     if weight > 0 and not cfg.VOXEL_SEG.ENABLED:
         raise ValueError('LOSSES.VOXEL_RENDER.WEIGHT > 0 needs VOXEL_SEG.ENABLED: the loss is on the voxel head')
     return float(weight), tuple(int(f) for f in factors), int(stride)
+
+
+DEFAULT_VISIBILITY_LIDAR_STRIDE = 1
+DEFAULT_VISIBILITY_CAMERA_STRIDE = 2
+
+
+def voxel_visibility(cfg):
+    """(enabled, lidar stride, camera stride) of the sensor-visibility mask: VOXEL_SEG.VISIBILITY.* if given, else (False, 1, 2);
+    off = no table, no launch, no new batch key."""
+    node = cfg.VOXEL_SEG.get('VISIBILITY', None) or {}
+    enabled = node.get('ENABLED', False)
+    if not isinstance(enabled, bool):
+        raise ValueError(f'VOXEL_SEG.VISIBILITY.ENABLED must be true or false, got {enabled!r}')
+    strides = []
+    for key, default in (('LIDAR_STRIDE', DEFAULT_VISIBILITY_LIDAR_STRIDE), ('CAMERA_STRIDE', DEFAULT_VISIBILITY_CAMERA_STRIDE)):
+        stride = node.get(key, default)
+        if isinstance(stride, bool) or not isinstance(stride, int) or stride < 1:
+            raise ValueError(f'VOXEL_SEG.VISIBILITY.{key} must be an integer >= 1, got {stride!r}')
+        strides.append(int(stride))
+    if enabled and not cfg.VOXEL_SEG.ENABLED:
+        raise ValueError('VOXEL_SEG.VISIBILITY.ENABLED needs VOXEL_SEG.ENABLED: the mask is on the labels of the voxel head')
+    if enabled and cfg.VOXEL_SEG.USE_TOP_K:
+        raise ValueError('VOXEL_SEG.VISIBILITY.ENABLED together with VOXEL_SEG.USE_TOP_K: the top-k cross-entropy runs through a '
+                         'different kernel whose treatment of label 255 is not defined')
+    return enabled, strides[0], strides[1]
 
 
 class CfgNode(dict):

@@ -273,6 +273,31 @@ class SSCMetrics:
         self.iou_ssc = torch.zeros(self.n_classes, dtype=torch.float32, device=dev)
 
 
+class VoxelUnknownShare:
+    """`{prefix}_Voxel_Unknown_Share` (extension, config.py: VOXEL_SEG.VISIBILITY): the share of the label cells at scale 1 that
+    the visibility mask sets to 255, over the frames of one metric set.  add_batch marks and applies the frames' labels again -
+    the batch's masked labels carry no count, and a metric set sees a slice of the frames - and only queues kernels: the (2,)
+    integer counts of muvo_visibility_apply stay on the device until get_stat."""
+
+    def __init__(self):
+        self.reset()
+
+    def add_batch(self, label, rays):
+        from muvo_amd import ops
+        if not label.shape[0]:
+            return
+        if self.counts is None:
+            self.counts = torch.zeros(2, dtype=torch.int64, device=label.device)
+        ops.visible_labels(label, rays, self.counts)
+        self.cells += label.numel()
+
+    def get_stat(self):
+        return int(self.counts[1]) / self.cells if self.cells else 0.0
+
+    def reset(self):
+        self.counts, self.cells = None, 0
+
+
 class EvalMetrics:
     """The metric set of one validation dataloader on base_1d (trainer.py:426-490): ssim, psnr, cd, ssc."""
 

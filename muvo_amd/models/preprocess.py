@@ -11,6 +11,7 @@ import torch
 import torch.nn as nn
 
 from muvo_amd import ops
+from muvo_amd.config import voxel_visibility
 
 
 def bev_out_of_view_mask(fov, image_width, resolution, crop_left, crop_right, bev_w, bev_h, offset_forward, camera_forward):
@@ -47,6 +48,7 @@ class PreProcess(nn.Module):
             raise ValueError('EVAL.RESOLUTION with FACTOR != 1 needs EVAL.RGB_SUPERVISION = False: the RGB decoder reconstructs the '
                              'full-size image while rgb_label_1 is the down-scaled one (the reference fails in its loss, trainer.py:296-302)')
         self._pins = {}
+        voxel_visibility(cfg)           # raises here, not in the first step, on a bad VOXEL_SEG.VISIBILITY
         self.bev_out_of_view_mask = None
         if cfg.EVAL.MASK_VIEW:        # preprocess.py:20-21
             self.bev_out_of_view_mask = torch.from_numpy(bev_out_of_view_mask(
@@ -185,4 +187,11 @@ class PreProcess(nn.Module):
             x, y, z = batch['voxel'].shape[-3:]
             for f in (2, 4):
                 batch[f'voxel_label_{f}'] = ops.resize_nearest(batch[f'voxel_label_{f // 2}'], (x // f, y // f, z // f))
+            if voxel_visibility(cfg)[0]:     # extension (config.py: VOXEL_SEG.VISIBILITY; absent = off: no table, no launch, no key)
+                from muvo_amd.voxel_view import visibility_table
+                for f in (1, 2, 4):             # free cells no sensor ray passes become 255; voxel_label_f itself stays
+                    label = batch[f'voxel_label_{f}']
+                    grid = label.to(torch.uint8).reshape(-1, *label.shape[-3:])
+                    rays = visibility_table(cfg, f, tuple(grid.shape[1:]), grid.device)
+                    batch[f'voxel_visible_label_{f}'] = ops.visible_labels(grid, rays)[0].view(label.shape)
         return batch

@@ -91,6 +91,7 @@ EXPORTS = [
     'muvo_ray_iou_ws_doubles', 'muvo_ray_iou_counts',
     'muvo_lovasz_ws_bytes', 'muvo_lovasz_fwd', 'muvo_lovasz_bwd',
     'muvo_render_ws_bytes', 'muvo_render_fwd', 'muvo_render_bwd',
+    'muvo_visibility_mark', 'muvo_visibility_apply',
 ]
 
 
@@ -3450,6 +3451,38 @@ def raycast_bricks(src):
         return grid, bricks
     _ck(L.muvo_raycast_bricks_grid(_p(src), int(F), int(X), int(Y), int(Z), _p(bricks), _i64(words), _st()))
     return src, bricks
+
+
+def visibility_mark(grid, bricks, rays):
+    """The SEEN words (F, words) int64 - layout and bit order of `raycast_bricks` - of the R rays (R, 7) float32 through each of
+    the F frames: every cell a ray visits up to and including its first occupied one (include/muvo_hip.h: muvo_visibility_mark,
+    our definition).  The entry clears the words itself."""
+    F, X, Y, Z = _ray_args(grid, bricks, rays)
+    seen = torch.empty_like(bricks)
+    _ck(lib().muvo_visibility_mark(_p(grid), _p(bricks), F, X, Y, Z, _f(rays), _i64(rays.shape[0]), _p(seen), _i64(seen.numel()), _st()))
+    return seen
+
+
+def visibility_apply(label, seen, counts=None):
+    """The masked label (F, X, Y, Z) uint8 of `label` under the SEEN words of `visibility_mark`: label where it is not 0, 0 where a
+    free cell is seen, 255 where it is not.  counts (2,) int64 on the device (free-and-seen, unknown) is added to; None: a fresh
+    one.  Returns (masked label, counts)."""
+    assert label.dtype == torch.uint8 and label.dim() == 4 and label.is_contiguous()
+    F, X, Y, Z = (int(v) for v in label.shape)
+    assert seen.dtype == torch.int64 and seen.is_contiguous() and seen.device == label.device
+    assert tuple(seen.shape) == (F, ((X + 3) // 4) * ((Y + 3) // 4) * ((Z + 3) // 4)), 'visibility_apply: the words of visibility_mark for this grid'
+    if counts is None:
+        counts = torch.zeros(2, dtype=torch.int64, device=label.device)
+    assert counts.dtype == torch.int64 and tuple(counts.shape) == (2,) and counts.is_contiguous() and counts.device == label.device
+    out = torch.empty_like(label)
+    _ck(lib().muvo_visibility_apply(_p(label), _p(seen), F, X, Y, Z, _p(out), _p(counts), _st()))
+    return out, counts
+
+
+def visible_labels(label, rays, counts=None):
+    """bricks + mark + apply for a label grid (F, X, Y, Z) uint8: (masked label, counts)."""
+    grid, bricks = raycast_bricks(label)
+    return visibility_apply(grid, visibility_mark(grid, bricks, rays), counts)
 
 
 def _ray_args(grid, bricks, rays):

@@ -111,6 +111,55 @@ def render_table(cfg, factor, stride, shape, device):
     return _RENDER_TABLES[key]
 
 
+def camera_label_rays(cfg, stride=2):
+    """(ceil(H / stride) * ceil(W / stride), 7) float32 numpy, computed in float64: one ray per `stride`-th pixel (r, c), r = 0,
+    stride, ..., c = 0, stride, ..., row-major, of the full IMAGE.SIZE = (H, W) frame at IMAGE.FOV - the depth camera the voxel
+    labels come from.  Unit direction through the point csrc/voxelize.hip unprojects that pixel to: it takes the pixel's integer
+    coordinates (c, r) - the pixel's CORNER, not its centre - against the principal point (W / 2, H / 2), x = (c - W / 2) depth /
+    f, y = (r - H / 2) depth / f, f = W / (2 tan(FOV / 2)), and puts the point at (depth, -x, -y) from the camera in grid axes:
+    direction (1, -(c - W / 2) / f, -(r - H / 2) / f) normalised.  One origin, the camera: VOXEL.EV_POSITION + (forward, -right,
+    up) / VOXEL.RESOLUTION of IMAGE.CAMERA_POSITION (the convention of input_pipeline.voxelize_geometry); tmax = +inf."""
+    if isinstance(stride, bool) or int(stride) != stride or stride < 1:
+        raise ValueError(f'camera_label_rays: stride {stride} below 1')
+    H, W = (int(v) for v in cfg.IMAGE.SIZE)
+    f = W / (2.0 * math.tan(float(cfg.IMAGE.FOV) * math.pi / 360.0))
+    forward, right, up = (float(v) for v in cfg.IMAGE.CAMERA_POSITION)
+    res = float(cfg.VOXEL.RESOLUTION)
+    origin = np.array([float(v) for v in cfg.VOXEL.EV_POSITION]) + np.array([forward, -right, up]) / res
+    rows, cols = np.arange(0, H, stride, dtype=np.float64), np.arange(0, W, stride, dtype=np.float64)
+    d = np.empty((len(rows), len(cols), 3), np.float64)
+    d[..., 0] = 1.0
+    d[..., 1] = -(cols[None, :] - W / 2.0) / f
+    d[..., 2] = -(rows[:, None] - H / 2.0) / f
+    d /= np.sqrt((d * d).sum(-1, keepdims=True))
+    rays = np.empty((len(rows), len(cols), 7), np.float64)
+    rays[..., :3] = origin
+    rays[..., 3:6] = d
+    rays[..., 6] = np.inf
+    return rays.reshape(-1, 7).astype(np.float32)
+
+
+_VISIBILITY_TABLES = {}
+
+
+def visibility_table(cfg, factor, shape, device):
+    """rays (R, 7) float32 on the device of the visibility mask at label scale `factor`: the rows of
+    lidar_rays(cfg, LIDAR_STRIDE) followed by those of camera_label_rays(cfg, CAMERA_STRIDE) of VOXEL_SEG.VISIBILITY, origins
+    divided by the factor - the grid of scale f has cells f times as large - directions as they are.  Cached per (geometry,
+    factor, strides, grid size, device)."""
+    from muvo_amd.config import voxel_visibility
+    _, lidar_stride, camera_stride = voxel_visibility(cfg)
+    key = (tuple(float(v) for v in cfg.VOXEL.EV_POSITION), tuple(float(v) for v in cfg.POINTS.LIDAR_POSITION), tuple(float(v) for v in cfg.POINTS.FOV),
+           int(cfg.POINTS.CHANNELS), int(cfg.POINTS.HORIZON_RESOLUTION), float(cfg.VOXEL.RESOLUTION),
+           tuple(int(v) for v in cfg.IMAGE.SIZE), float(cfg.IMAGE.FOV), tuple(float(v) for v in cfg.IMAGE.CAMERA_POSITION),
+           int(factor), lidar_stride, camera_stride, tuple(int(n) for n in shape), str(device))
+    if key not in _VISIBILITY_TABLES:
+        rays = np.concatenate([lidar_rays(cfg, lidar_stride), camera_label_rays(cfg, camera_stride)])
+        rays[:, :3] = (rays[:, :3].astype(np.float64) / factor).astype(np.float32)
+        _VISIBILITY_TABLES[key] = torch.from_numpy(rays).to(device)
+    return _VISIBILITY_TABLES[key]
+
+
 _CAMERAS = {}
 
 
