@@ -165,6 +165,13 @@ int muvo_grouped_linear_fwd(const float* x, int M, int K, int L, const float* co
                             const int* N, void* stream);
 int muvo_grouped_linear_bwd(const float* x, int M, int K, int L, const float* const* W, float* const* dY, float* dx,
                             float* const* dW, float* const* db, const int* N, void* stream);
+/* Routing query of the three grouped launches (host code only): the forward row template (8 | 24) and its grid, the grids of
+ * the data-gradient (K / 64 column blocks x 128-row weight slabs) and weight-gradient (K / 256 x 16-row groups) kernels. */
+typedef struct muvo_grouped_linear_route_info {
+  int32_t fwd_rm, fwd_grid;
+  int32_t dgrad_grid[2], wgrad_grid[2];
+} muvo_grouped_linear_route_info;
+int muvo_grouped_linear_route(int M, int K, int L, const int* N, muvo_grouped_linear_route_info* out);
 /* Clock probe of the dominant kernel class (eight-wave bf16x3 implicit-GEMM tiles): shader clock (MHz) and wall time per
  * K step (32 deep, 24 MFMA 32x32x16 per wave) that workgroup 0 of the most recent launch measured over its K loop.  The
  * kernels run power-limited well below the 2.4 GHz the dense MFMA peak is quoted at; bench.py reports both. */
@@ -230,6 +237,19 @@ typedef struct muvo_gemm_desc {
   int32_t mode;
 } muvo_gemm_desc;
 int muvo_gemm(const muvo_gemm_desc* d, const float* A, const float* B, float* C, const float* bias, void* stream);
+/* Routing query: what muvo_gemm would launch for this descriptor (host code only: nothing is launched, no device is needed).
+ * A / B count only by their 16-byte alignment; has_bias as `bias != NULL` of the call.  The same MUVO_GEMM_KSPLIT_BLOCKS /
+ * MUVO_GEMM_KSPLIT_MINTILES / MUVO_SKINNY_KS_BLOCKS values and the same deterministic mode as the launch itself.
+ * kernel: MUVO_GEMM_TILED (fp32 MFMA tiles bm x bn, loaders a_lay / b_lay: 0 lanes along m / n, 1 lanes along k; ksplit K ranges,
+ * grid (n tiles, m tiles, batches * ksplit)) or one of the skinny kernels (rm: row template; bm = bn = 0, a_lay = b_lay = -1;
+ * ksplit: the KS of the n-contiguous kernel = grid[1], else 1). */
+enum { MUVO_GEMM_TILED = 0, MUVO_GEMM_SKINNY_KVEC = 1, MUVO_GEMM_SKINNY_KCONTIG = 2, MUVO_GEMM_SKINNY_NCONTIG = 3 };
+typedef struct muvo_gemm_route_info {
+  int32_t kernel, rm, bm, bn, a_lay, b_lay, ksplit;
+  int32_t grid[3];
+  int32_t block;
+} muvo_gemm_route_info;
+int muvo_gemm_route(const muvo_gemm_desc* d, const float* A, const float* B, int has_bias, muvo_gemm_route_info* out);
 
 /* ---- normalisation (norm.hip) --------------------------------------------------------------------
  * Train-mode BatchNorm2d (batch statistics over N*S, running stats momentum update, unbiased running

@@ -522,7 +522,8 @@ __global__ void __launch_bounds__(256) grouped_linear_wgrad_kernel(const Grouped
   int l = 0;
   while (l + 1 < a.L && (int)blockIdx.y >= a.blk0[l + 1]) ++l;
   const int N = a.N[l], K = a.K, M = a.M;
-  if (a.dW[l] == nullptr) return;                              // (uniform) frozen layer
+  float* __restrict__ dWl = a.dW[l];                           // null: frozen weight; its bias may still train
+  if (dWl == nullptr && (a.db[l] == nullptr || blockIdx.x != 0)) return;      // (uniform)
   const float* __restrict__ dy = a.Y[l];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int k4 = blockIdx.x * 64 + lane;                       // float4 index inside a row
@@ -545,8 +546,8 @@ __global__ void __launch_bounds__(256) grouped_linear_wgrad_kernel(const Grouped
       g.x += d[m] * xv[m].x; g.y += d[m] * xv[m].y; g.z += d[m] * xv[m].z; g.w += d[m] * xv[m].w;
       sb += d[m];
     }
-    if (kok) {
-      float4* dst = reinterpret_cast<float4*>(a.dW[l] + (long)n * K) + k4;
+    if (kok && dWl != nullptr) {
+      float4* dst = reinterpret_cast<float4*>(dWl + (long)n * K) + k4;
       float4 o = *dst;
       o.x += g.x; o.y += g.y; o.z += g.z; o.w += g.w;
       *dst = o;
@@ -573,6 +574,26 @@ static int grouped_fill(GroupedLinearArgs& a, int L, int M, int K, const float* 
   return MUVO_OK;
 }
 
+// Host decisions of the three grouped launches for checked sizes: the forward row template and the grids (the per-layer
+// workgroup counts are those grouped_fill puts into blk0 for 4 / 128 / 16 columns per workgroup).
+static void grouped_route(int M, int K, int L, const int* N, muvo_grouped_linear_route_info* r) {
+  int b4 = 0, b128 = 0, b16 = 0;
+  for (int l = 0; l < L; ++l) { b4 += cdiv(N[l], 4); b128 += cdiv(N[l], 128); b16 += cdiv(N[l], 16); }
+  r->fwd_rm = M <= 8 ? 8 : 24;
+  r->fwd_grid = b4;
+  r->dgrad_grid[0] = cdiv(K, 64); r->dgrad_grid[1] = b128;
+  r->wgrad_grid[0] = cdiv(K, 256); r->wgrad_grid[1] = b16;
+}
+
+extern "C" int muvo_grouped_linear_route(int M, int K, int L, const int* N, muvo_grouped_linear_route_info* out) {
+  MUVO_CHECK_ARG(N && out, "grouped_linear_route: null pointer");
+  MUVO_CHECK_ARG(L > 0 && L <= GL_MAX, "grouped_linear: %d layers (max %d)", L, GL_MAX);
+  MUVO_CHECK_ARG(M > 0 && M <= 24 && K >= 64 && K % 4 == 0, "grouped_linear: M=%d K=%d unsupported (M <= 24, K %% 4 == 0)", M, K);
+  for (int l = 0; l < L; ++l) MUVO_CHECK_ARG(N[l] > 0, "grouped_linear: bad layer %d", l);
+  grouped_route(M, K, L, N, out);
+  return MUVO_OK;
+}
+
 extern "C" int muvo_grouped_linear_fwd(const float* x, int M, int K, int L, const float* const* W, const float* const* b,
                                        float* const* Y, const int* N, void* stream) {
   MUVO_CHECK_ARG(x && W && Y && N && (((uintptr_t)x) & 15) == 0, "grouped_linear_fwd: bad args");
@@ -580,8 +601,10 @@ extern "C" int muvo_grouped_linear_fwd(const float* x, int M, int K, int L, cons
   int rc = grouped_fill(a, L, M, K, W, b, Y, nullptr, nullptr, N, 4);
   if (rc) return rc;
   hipStream_t st = (hipStream_t)stream;
-  if (M <= 8) hipLaunchKernelGGL((grouped_linear_fwd_kernel<8>), dim3(a.blk0[L]), dim3(512), 0, st, a, x);
-  else hipLaunchKernelGGL((grouped_linear_fwd_kernel<24>), dim3(a.blk0[L]), dim3(512), 0, st, a, x);
+  muvo_grouped_linear_route_info r;
+  grouped_route(M, K, L, N, &r);
+  if (r.fwd_rm == 8) hipLaunchKernelGGL((grouped_linear_fwd_kernel<8>), dim3(r.fwd_grid), dim3(512), 0, st, a, x);
+  else hipLaunchKernelGGL((grouped_linear_fwd_kernel<24>), dim3(r.fwd_grid), dim3(512), 0, st, a, x);
   MUVO_CHECK_LAUNCH("grouped_linear_fwd");
   return MUVO_OK;
 }
@@ -599,36 +622,116 @@ extern "C" int muvo_grouped_linear_bwd(const float* x, int M, int K, int L, cons
       muvo_set_error("grouped_linear_bwd: memset failed");
       return MUVO_ERR_HIP;
     }
-    hipLaunchKernelGGL(grouped_linear_dgrad_kernel, dim3(cdiv(K, 64), a.blk0[L]), dim3(256), 0, st, a, dx);
+    muvo_grouped_linear_route_info r;
+    grouped_route(M, K, L, N, &r);
+    hipLaunchKernelGGL(grouped_linear_dgrad_kernel, dim3(r.dgrad_grid[0], r.dgrad_grid[1]), dim3(256), 0, st, a, dx);
   }
   if (dW) {
     int rc = grouped_fill(a, L, M, K, W, nullptr, dY, dW, db, N, 16);
     if (rc) return rc;
     for (int l = 0; l < L; ++l)
       MUVO_CHECK_ARG(dW[l] == nullptr || (((uintptr_t)dW[l]) & 15) == 0, "grouped_linear_bwd: unaligned gradient buffer");
-    hipLaunchKernelGGL(grouped_linear_wgrad_kernel, dim3(cdiv(K, 256), a.blk0[L]), dim3(256), 0, st, a, x);
+    muvo_grouped_linear_route_info r;
+    grouped_route(M, K, L, N, &r);
+    hipLaunchKernelGGL(grouped_linear_wgrad_kernel, dim3(r.wgrad_grid[0], r.wgrad_grid[1]), dim3(256), 0, st, a, x);
   }
   MUVO_CHECK_LAUNCH("grouped_linear_bwd");
   return MUVO_OK;
 }
 
 template <int BM, int BN, int WM, int WN>
-static void launch_gemm_lay(const GemmArgs& g, const float* A, const float* B, float* C, dim3 grid, hipStream_t st) {
-  const int al = (g.sam == 1 && g.sak != 1) ? 0 : (g.sak == 1 ? 1 : 0);
-  const int bl = (g.sbn == 1) ? 0 : (g.sbk == 1 ? 1 : 0);
+static void launch_gemm_lay(const GemmArgs& g, int al, int bl, const float* A, const float* B, float* C, dim3 grid, hipStream_t st) {
   if (al == 0 && bl == 0) hipLaunchKernelGGL((gemm_kernel<BM, BN, WM, WN, 0, 0>), grid, dim3(256), 0, st, g, A, B, C);
   else if (al == 0 && bl == 1) hipLaunchKernelGGL((gemm_kernel<BM, BN, WM, WN, 0, 1>), grid, dim3(256), 0, st, g, A, B, C);
   else if (al == 1 && bl == 0) hipLaunchKernelGGL((gemm_kernel<BM, BN, WM, WN, 1, 0>), grid, dim3(256), 0, st, g, A, B, C);
   else hipLaunchKernelGGL((gemm_kernel<BM, BN, WM, WN, 1, 1>), grid, dim3(256), 0, st, g, A, B, C);
 }
 
-extern "C" int muvo_gemm(const muvo_gemm_desc* d, const float* A, const float* B, float* C, const float* bias,
-                         void* stream) {
-  MUVO_CHECK_ARG(d && A && B && C, "gemm: null pointer");
+static int gemm_check_desc(const muvo_gemm_desc* d, bool has_bias) {
   MUVO_CHECK_ARG(d->M > 0 && d->N > 0 && d->K >= 0, "gemm: bad sizes M=%d N=%d K=%d", d->M, d->N, d->K);
   MUVO_CHECK_ARG(d->B1 > 0 && d->B2 > 0, "gemm: bad batch sizes");
   MUVO_CHECK_ARG(d->mode == 0 || d->mode == 1, "gemm: mode must be 0 (store) or 1 (atomic add)");
-  MUVO_CHECK_ARG(!(d->mode == 1 && (bias || d->act != MUVO_ACT_NONE)), "gemm: bias/act not allowed in accumulate mode");
+  MUVO_CHECK_ARG(!(d->mode == 1 && (has_bias || d->act != MUVO_ACT_NONE)), "gemm: bias/act not allowed in accumulate mode");
+  return MUVO_OK;
+}
+
+// The whole host decision of muvo_gemm (kernel, row template or tile, loader layouts, k split, grid) for a checked descriptor;
+// the pointers count only by their alignment.  muvo_gemm launches from it, muvo_gemm_route reports it.
+static void gemm_route(const muvo_gemm_desc* d, const float* A, const float* B, bool has_bias, muvo_gemm_route_info* r) {
+  static const int skinny_ks_tgt = getenv("MUVO_SKINNY_KS_BLOCKS") ? atoi(getenv("MUVO_SKINNY_KS_BLOCKS")) : 512;
+  static const int ksplit_tgt = getenv("MUVO_GEMM_KSPLIT_BLOCKS") ? atoi(getenv("MUVO_GEMM_KSPLIT_BLOCKS")) : 768;
+  static const int ksplit_mint = getenv("MUVO_GEMM_KSPLIT_MINTILES") ? atoi(getenv("MUVO_GEMM_KSPLIT_MINTILES")) : 8;
+  const int nb = d->B1 * d->B2;
+  r->rm = r->bm = r->bn = 0;
+  r->a_lay = r->b_lay = -1;
+  r->ksplit = 1;
+  r->grid[1] = r->grid[2] = 1;
+  const bool vec_ok = d->sbk == 1 && d->sak == 1 && d->K % 4 == 0 && d->sam % 4 == 0 && d->sbn % 4 == 0 &&
+                      (((uintptr_t)A | (uintptr_t)B) & 15) == 0;
+  const bool kvec = d->M <= 32 && d->mode == 0 && nb == 1 && d->K >= 64 && vec_ok;
+  if (d->M <= 32 && d->mode == 0 && nb == 1 && ((d->N >= 64 && d->K >= 16) || kvec)) {
+    // (the k-vector kernel holds M x 4 accumulators per lane: up to 24 rows; 25..32 rows take the k-contiguous kernel)
+    if (d->M <= 24 && vec_ok) {
+      r->kernel = MUVO_GEMM_SKINNY_KVEC;
+      r->rm = d->M <= 4 ? 4 : d->M <= 8 ? 8 : d->M <= 16 ? 16 : 24;
+      r->grid[0] = cdiv(d->N, 4);
+      r->block = 512;
+    } else if (d->sbk == 1) {
+      r->kernel = MUVO_GEMM_SKINNY_KCONTIG;
+      r->rm = d->M <= 4 ? 4 : 8;
+      r->grid[0] = cdiv(d->N, 8);
+      r->block = 256;
+    } else {
+      const int blocks = cdiv(d->N, 64);
+      int ks = 1;
+      if (!has_bias && d->act == MUVO_ACT_NONE && d->scm == d->N) {   // dense C: zero it, then split k over workgroups
+        ks = cdiv(skinny_ks_tgt, blocks);
+        if (ks > d->K / 64) ks = d->K / 64;
+        if (ks < 1 || muvo_det()) ks = 1;
+      }
+      r->kernel = MUVO_GEMM_SKINNY_NCONTIG;
+      r->rm = d->M <= 4 ? 4 : d->M <= 8 ? 8 : 24;      // 24: the 20 frame rows of a step in one pass
+      r->ksplit = ks;
+      r->grid[0] = blocks;
+      r->grid[1] = ks;
+      r->block = 256;
+    }
+    return;
+  }
+  int bm, bn;
+  if (d->M <= 32) { bm = 32; bn = 128; }
+  else if (d->N <= 64) { bm = 128; bn = 64; }
+  else { bm = 128; bn = 128; }
+  const int gx = cdiv(d->N, bn), gy = cdiv(d->M, bm);
+  int ksplit = 1;
+  if (d->mode == 1) {
+    const int nkt = cdiv(d->K, 16);
+    ksplit = cdiv(ksplit_tgt, gx * gy * nb);
+    if (ksplit > cdiv(nkt, ksplit_mint)) ksplit = cdiv(nkt, ksplit_mint);
+    if (ksplit < 1 || muvo_det()) ksplit = 1;      // deterministic mode: one contributor per element of the accumulated C
+  }
+  r->kernel = MUVO_GEMM_TILED;
+  r->bm = bm; r->bn = bn;
+  r->a_lay = (d->sam == 1 && d->sak != 1) ? 0 : (d->sak == 1 ? 1 : 0);
+  r->b_lay = (d->sbn == 1) ? 0 : (d->sbk == 1 ? 1 : 0);
+  r->ksplit = ksplit;
+  r->grid[0] = gx; r->grid[1] = gy; r->grid[2] = nb * ksplit;
+  r->block = 256;
+}
+
+extern "C" int muvo_gemm_route(const muvo_gemm_desc* d, const float* A, const float* B, int has_bias, muvo_gemm_route_info* out) {
+  MUVO_CHECK_ARG(d && out, "gemm_route: null pointer");
+  int rc = gemm_check_desc(d, has_bias != 0);
+  if (rc) return rc;
+  gemm_route(d, A, B, has_bias != 0, out);
+  return MUVO_OK;
+}
+
+extern "C" int muvo_gemm(const muvo_gemm_desc* d, const float* A, const float* B, float* C, const float* bias,
+                         void* stream) {
+  MUVO_CHECK_ARG(d && A && B && C, "gemm: null pointer");
+  int rc = gemm_check_desc(d, bias != nullptr);
+  if (rc) return rc;
   static const bool log_calls = getenv("MUVO_GEMM_LOG") != nullptr;      // diagnostic: one line per call
   if (log_calls)
     fprintf(stderr, "muvo_gemm M=%d N=%d K=%d nb=%d mode=%d sam=%ld sak=%ld sbk=%ld sbn=%ld act=%d bias=%d\n", d->M, d->N, d->K,
@@ -640,64 +743,36 @@ extern "C" int muvo_gemm(const muvo_gemm_desc* d, const float* A, const float* B
   g.a_b1 = d->a_b1; g.a_b2 = d->a_b2; g.b_b1 = d->b_b1; g.b_b2 = d->b_b2; g.c_b1 = d->c_b1; g.c_b2 = d->c_b2;
   g.alpha = d->alpha; g.bias = bias; g.bias_div = d->bias_div > 0 ? d->bias_div : 1;
   g.act = d->act; g.slope = d->slope; g.mode = d->mode;
-  const int nb = d->B1 * d->B2;
   hipStream_t st = (hipStream_t)stream;
-  const bool kvec = d->M <= 32 && d->mode == 0 && nb == 1 && d->K >= 64 && d->sbk == 1 && d->sak == 1 && d->K % 4 == 0 &&
-                    d->sam % 4 == 0 && d->sbn % 4 == 0 && (((uintptr_t)A | (uintptr_t)B) & 15) == 0;
-  if (d->M <= 32 && d->mode == 0 && nb == 1 && ((d->N >= 64 && d->K >= 16) || kvec)) {
-    g.ksplit = 1;
-    // (the k-vector kernel holds M x 4 accumulators per lane: up to 24 rows; 25..32 rows take the k-contiguous kernel)
-    const bool vec = d->M <= 24 && d->sbk == 1 && d->sak == 1 && d->K % 4 == 0 && d->sam % 4 == 0 && d->sbn % 4 == 0 &&
-                     (((uintptr_t)A | (uintptr_t)B) & 15) == 0;
-    if (vec) {
-      const dim3 grid(cdiv(d->N, 4));
-      if (d->M <= 4) hipLaunchKernelGGL((gemm_skinny_kvec_kernel<4>), grid, dim3(512), 0, st, g, A, B, C);
-      else if (d->M <= 8) hipLaunchKernelGGL((gemm_skinny_kvec_kernel<8>), grid, dim3(512), 0, st, g, A, B, C);
-      else if (d->M <= 16) hipLaunchKernelGGL((gemm_skinny_kvec_kernel<16>), grid, dim3(512), 0, st, g, A, B, C);
-      else hipLaunchKernelGGL((gemm_skinny_kvec_kernel<24>), grid, dim3(512), 0, st, g, A, B, C);
-    } else if (d->sbk == 1) {
-      const int blocks = cdiv(d->N, 8);
-      if (d->M <= 4) hipLaunchKernelGGL((gemm_skinny_kcontig_kernel<4>), dim3(blocks), dim3(256), 0, st, g, A, B, C);
-      else hipLaunchKernelGGL((gemm_skinny_kcontig_kernel<8>), dim3(blocks), dim3(256), 0, st, g, A, B, C);
-    } else {
-      const int blocks = cdiv(d->N, 64);
-      int ks = 1;
-      if (!bias && d->act == MUVO_ACT_NONE && d->scm == d->N) {   // dense C: zero it, then split k over workgroups
-        static const int ks_tgt = getenv("MUVO_SKINNY_KS_BLOCKS") ? atoi(getenv("MUVO_SKINNY_KS_BLOCKS")) : 512;
-        ks = cdiv(ks_tgt, blocks);
-        if (ks > d->K / 64) ks = d->K / 64;
-        if (ks < 1 || muvo_det()) ks = 1;
-      }
-      if (ks > 1 && hipMemsetAsync(C, 0, sizeof(float) * (size_t)d->M * d->N, st) != hipSuccess) {
-        muvo_set_error("gemm_skinny: memset failed");
-        return MUVO_ERR_HIP;
-      }
-      if (d->M <= 4) hipLaunchKernelGGL((gemm_skinny_ncontig_kernel<4>), dim3(blocks, ks), dim3(256), 0, st, g, A, B, C, ks);
-      else if (d->M <= 8) hipLaunchKernelGGL((gemm_skinny_ncontig_kernel<8>), dim3(blocks, ks), dim3(256), 0, st, g, A, B, C, ks);
-      else hipLaunchKernelGGL((gemm_skinny_ncontig_kernel<24>), dim3(blocks, ks), dim3(256), 0, st, g, A, B, C, ks);   // the 20 frame rows of a step in one pass
-    }
+  muvo_gemm_route_info r;
+  gemm_route(d, A, B, bias != nullptr, &r);
+  g.ksplit = r.kernel == MUVO_GEMM_TILED ? r.ksplit : 1;
+  const dim3 grid(r.grid[0], r.grid[1], r.grid[2]);
+  if (r.kernel == MUVO_GEMM_SKINNY_KVEC) {
+    if (r.rm == 4) hipLaunchKernelGGL((gemm_skinny_kvec_kernel<4>), grid, dim3(512), 0, st, g, A, B, C);
+    else if (r.rm == 8) hipLaunchKernelGGL((gemm_skinny_kvec_kernel<8>), grid, dim3(512), 0, st, g, A, B, C);
+    else if (r.rm == 16) hipLaunchKernelGGL((gemm_skinny_kvec_kernel<16>), grid, dim3(512), 0, st, g, A, B, C);
+    else hipLaunchKernelGGL((gemm_skinny_kvec_kernel<24>), grid, dim3(512), 0, st, g, A, B, C);
     MUVO_CHECK_LAUNCH("gemm_skinny_kernel");
-    return MUVO_OK;
+  } else if (r.kernel == MUVO_GEMM_SKINNY_KCONTIG) {
+    if (r.rm == 4) hipLaunchKernelGGL((gemm_skinny_kcontig_kernel<4>), grid, dim3(256), 0, st, g, A, B, C);
+    else hipLaunchKernelGGL((gemm_skinny_kcontig_kernel<8>), grid, dim3(256), 0, st, g, A, B, C);
+    MUVO_CHECK_LAUNCH("gemm_skinny_kernel");
+  } else if (r.kernel == MUVO_GEMM_SKINNY_NCONTIG) {
+    const int ks = r.ksplit;
+    if (ks > 1 && hipMemsetAsync(C, 0, sizeof(float) * (size_t)d->M * d->N, st) != hipSuccess) {
+      muvo_set_error("gemm_skinny: memset failed");
+      return MUVO_ERR_HIP;
+    }
+    if (r.rm == 4) hipLaunchKernelGGL((gemm_skinny_ncontig_kernel<4>), grid, dim3(256), 0, st, g, A, B, C, ks);
+    else if (r.rm == 8) hipLaunchKernelGGL((gemm_skinny_ncontig_kernel<8>), grid, dim3(256), 0, st, g, A, B, C, ks);
+    else hipLaunchKernelGGL((gemm_skinny_ncontig_kernel<24>), grid, dim3(256), 0, st, g, A, B, C, ks);
+    MUVO_CHECK_LAUNCH("gemm_skinny_kernel");
+  } else {
+    if (r.bm == 32) launch_gemm_lay<32, 128, 1, 4>(g, r.a_lay, r.b_lay, A, B, C, grid, st);
+    else if (r.bn == 64) launch_gemm_lay<128, 64, 2, 2>(g, r.a_lay, r.b_lay, A, B, C, grid, st);
+    else launch_gemm_lay<128, 128, 2, 2>(g, r.a_lay, r.b_lay, A, B, C, grid, st);
+    MUVO_CHECK_LAUNCH("gemm_kernel");
   }
-  int bm, bn;
-  if (d->M <= 32) { bm = 32; bn = 128; }
-  else if (d->N <= 64) { bm = 128; bn = 64; }
-  else { bm = 128; bn = 128; }
-  const int gx = cdiv(d->N, bn), gy = cdiv(d->M, bm);
-  int ksplit = 1;
-  if (d->mode == 1) {
-    const int nkt = cdiv(d->K, 16);
-    static const int tgt = getenv("MUVO_GEMM_KSPLIT_BLOCKS") ? atoi(getenv("MUVO_GEMM_KSPLIT_BLOCKS")) : 768;
-    static const int mint = getenv("MUVO_GEMM_KSPLIT_MINTILES") ? atoi(getenv("MUVO_GEMM_KSPLIT_MINTILES")) : 8;
-    ksplit = cdiv(tgt, gx * gy * nb);
-    if (ksplit > cdiv(nkt, mint)) ksplit = cdiv(nkt, mint);
-    if (ksplit < 1 || muvo_det()) ksplit = 1;      // deterministic mode: one contributor per element of the accumulated C
-  }
-  g.ksplit = ksplit;
-  dim3 grid(gx, gy, nb * ksplit);
-  if (bm == 32) launch_gemm_lay<32, 128, 1, 4>(g, A, B, C, grid, st);
-  else if (bn == 64) launch_gemm_lay<128, 64, 2, 2>(g, A, B, C, grid, st);
-  else launch_gemm_lay<128, 128, 2, 2>(g, A, B, C, grid, st);
-  MUVO_CHECK_LAUNCH("gemm_kernel");
   return MUVO_OK;
 }

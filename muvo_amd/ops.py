@@ -43,12 +43,21 @@ class GemmDesc(C.Structure):
                 ('mode', C.c_int32)]
 
 
+class GemmRouteInfo(C.Structure):
+    _fields_ = [('kernel', C.c_int32), ('rm', C.c_int32), ('bm', C.c_int32), ('bn', C.c_int32), ('a_lay', C.c_int32),
+                ('b_lay', C.c_int32), ('ksplit', C.c_int32), ('grid', C.c_int32 * 3), ('block', C.c_int32)]
+
+
+class GroupedLinearRouteInfo(C.Structure):
+    _fields_ = [('fwd_rm', C.c_int32), ('fwd_grid', C.c_int32), ('dgrad_grid', C.c_int32 * 2), ('wgrad_grid', C.c_int32 * 2)]
+
+
 # every exported symbol of include/muvo_hip.h (tests/test_abi.py checks this list against the header)
 EXPORTS = [
     'muvo_last_error', 'muvo_abi_version', 'muvo_selftest_mfma', 'muvo_set_deterministic', 'muvo_get_deterministic', 'muvo_reset_accumulators',
     'muvo_conv_set_products', 'muvo_conv_get_products',
     'muvo_conv_set_mode', 'muvo_conv_get_mode', 'muvo_conv_set_bf16x3_min_gflop', 'muvo_conv_pack_sizes', 'muvo_conv_workspace_bytes', 'muvo_conv_kernel_family', 'muvo_conv_kernel_variant', 'muvo_conv_pack_weights', 'muvo_conv_forward', 'muvo_conv_dgrad', 'muvo_conv_prepare_dy', 'muvo_conv_wgrad', 'muvo_bias_grad_nchw',
-    'muvo_gemm',
+    'muvo_gemm', 'muvo_gemm_route', 'muvo_grouped_linear_route',
     'muvo_pack_table_item_bytes', 'muvo_conv_pack_table_add', 'muvo_linear_bf16x3_pack_table_add', 'muvo_pack_table_run',
     'muvo_linear_bf16x3_pack_floats', 'muvo_linear_bf16x3_pack', 'muvo_linear_bf16x3_workspace_bytes', 'muvo_linear_bf16x3_split',
     'muvo_linear_bf16x3_forward', 'muvo_linear_bf16x3_dgrad', 'muvo_linear_bf16x3_wgrad',
@@ -663,6 +672,26 @@ def gemm(A, B, Cout, M, N, K, sam, sak, sbk, sbn, scm, bias=None, alpha=1.0, act
     pb = C.c_void_p(B.data_ptr() + 4 * b_off)
     pc = C.c_void_p(Cout.data_ptr() + 4 * c_off)
     _ck(lib().muvo_gemm(C.byref(d), pa, pb, pc, _f(bias), _st()))
+
+
+GEMM_KERNELS = ('tiled', 'skinny_kvec', 'skinny_kcontig', 'skinny_ncontig')
+
+
+def gemm_route(M, N, K, sam, sak, sbk, sbn, scm, has_bias=False, act=ACT_NONE, mode=0, B1=1, B2=1, a_addr=0, b_addr=0):
+    """What `gemm` would launch for these arguments (host code only, no device): dict(kernel, rm, tile, lay, ksplit, grid,
+    block).  a_addr / b_addr: the byte addresses of the operands (data_ptr() + 4 * offset); only their alignment counts."""
+    d = GemmDesc(M, N, K, sam, sak, sbk, sbn, scm, B1, B2, 0, 0, 0, 0, 0, 0, 1.0, 1, act, 0.0, mode)
+    r = GemmRouteInfo()
+    _ck(lib().muvo_gemm_route(C.byref(d), C.c_void_p(a_addr), C.c_void_p(b_addr), int(bool(has_bias)), C.byref(r)))
+    return {'kernel': GEMM_KERNELS[r.kernel], 'rm': r.rm, 'tile': (r.bm, r.bn), 'lay': (r.a_lay, r.b_lay), 'ksplit': r.ksplit,
+            'grid': tuple(r.grid), 'block': r.block}
+
+
+def grouped_linear_route(m, k, ns):
+    """The launches of GroupedLinearFn for (m, k) inputs and layer widths ns (host code only, no device)."""
+    r = GroupedLinearRouteInfo()
+    _ck(lib().muvo_grouped_linear_route(m, k, len(ns), (C.c_int * len(ns))(*ns), C.byref(r)))
+    return {'fwd_rm': r.fwd_rm, 'fwd_grid': r.fwd_grid, 'dgrad_grid': tuple(r.dgrad_grid), 'wgrad_grid': tuple(r.wgrad_grid)}
 
 
 class LinearFn(torch.autograd.Function):
