@@ -893,6 +893,48 @@ int muvo_render_fwd(const float* logits, int64_t F, int C, int X, int Y, int Z, 
 int muvo_render_bwd(const float* logits, int64_t F, int C, int X, int Y, int Z, const float* rays, int64_t R, int64_t n_valid, const double* depth,
                     const float* target, float weight, const float* gout, void* ws, int64_t ws_bytes, float* dlogits, void* stream);
 
+/* ---- rendered first-hit class loss of the voxel head along rays (render_class.hip; an extension) ---------
+ * OUR DEFINITION; tests/render_class_reference.py restates it.  Inputs as muvo_render_fwd: logits (F, C, X, Y, Z) fp32,
+ * 2 <= C <= 16, V = X Y Z; labels (F, X, Y, Z) uint8; rays (R, 7) fp32 on the device, the rows of muvo_raycast, one table for all F
+ * frames; F in 1..65535, every axis in 1..2048, V < 2^30, R in 1..2^24.
+ * Per cell, fp32: m, e_c, occ and s = e_0 + occ as muvo_render_fwd has them; p_c = e_c / s, q = p_0.
+ * Per ray: the cell sequence k = 0..n-1 and the validity rule of muvo_render_fwd (the march of muvo_raycast, steps 1 - 3, through a
+ *   grid in which nothing is occupied).  An INVALID ray contributes nothing and has zero gradient.  T_0 = 1, T_{k+1} = T_k q_k (fp32
+ *   products).
+ * Target class y: label_hit (F, R) is muvo_raycast's hit of the same rays through the label grid; y = the class byte of the label
+ *   at the hit cell, y = 0 where the label ray misses.  A class byte >= C at a hit cannot be refused without reading device memory
+ *   on the host, so such a ray is IGNORED: it is reported as y = -1 and contributes nothing, like an invalid ray (it still counts
+ *   in N).
+ * Rendered mass: y >= 1: S_y = sum_k T_k p_{k,y}; y = 0: S_0 = T_n, the ray leaves the grid unhit.  Products and sum in fp64, in the
+ *   order of k.  sum_c S_c = 1 by telescoping.  The march may stop where T is exactly 0 (all later terms are exactly 0); there is no
+ *   approximate cut-off.
+ * Loss of a ray: l = -log((S_y + eps) / (1 + eps)), eps = 2^-10, fp64: log(1025) = 6.93 without mass on the class, 0 for a perfect ray.
+ * loss[0] = weight / F * sum_f 1 / N * sum_{valid rays} l with N = n_valid as for muvo_render_fwd; N = 0: loss 0, gradient 0.  fp64
+ *   partial sums per workgroup, added by one workgroup in a fixed order; one fp32 device scalar, no host read.
+ * Outputs: mass (F, R) fp64 = S_y and target (F, R) int32 = y - mass 0 and target -1 at invalid and ignored rays - kept for the backward pass;
+ *   optional, for tests, NULL otherwise: t_last (F, R) fp32 = T_n (0: invalid), cells (F, R) int32 = n (-1: invalid).  With one of
+ *   them given the march does not stop at T == 0, so n is the full count; the loss has the same bits with and without them.
+ * ws: muvo_render_class_ws_bytes(F, C, V, R) bytes (-1 for sizes the entries refuse) of 16-byte aligned scratch, written then read
+ *   (the probabilities cell-major (F, V, C) fp32, the accumulator (F, C, V) int64, the partials); one size serves both entries,
+ *   nothing in it is kept between them.
+ * Backward: A_j = T_j p_{j,y} and B_j = S_y - sum_{k<=j} A_k for y >= 1 (the exact tail of the forward's own fp64 sum: the ray is
+ *   marched again with S_y from the forward pass); A_j = 0 and B_j = T_n = S_0 for y = 0.
+ *   dS_y/dz_{j,c} = A_j [c = y] + B_j [c = 0] - p_{j,c} (A_j + B_j) and dl/dS_y = -r, r = 1 / (S_y + eps) in fp64, once per ray.
+ *   A visit adds -A_j r to slot y and -B_j r to slot 0 of a per-cell vector of C slots, an (F, C, V) accumulator of 64-BIT INTEGERS
+ *   IN FIXED POINT with 37 fraction bits, rounded to nearest (at most 2^-38 per add): every contribution has magnitude below 1
+ *   (A_j <= S_y, B_j <= S_y), and 37 is the largest number of bits for which R x 1 x 2^37 < 2^62 with R <= 2^24 - the sum of a slot,
+ *   and of the C slots of a cell (at most two adds per visit: < 2^63), cannot overflow.  A contribution is clamped to +-1 and a NaN
+ *   becomes 0 before the conversion.  Integer atomics are order-free: loss and gradient have the same bits on every call, in both
+ *   modes of muvo_set_deterministic.  A wave first sums neighbouring lanes with the same destination.  One dense pass then writes
+ *   every element of dlogits (F, C, V): dz_{j,c} = (acc_c - p_c sum_c' acc_c') 2^-37 x gout weight / (F N), the sum over the slots
+ *   in integers; zeros where no ray passed; gout = the upstream gradient of the scalar, on the device. */
+int64_t muvo_render_class_ws_bytes(int64_t F, int C, int64_t V, int64_t R);
+int muvo_render_class_fwd(const float* logits, const uint8_t* labels, int64_t F, int C, int X, int Y, int Z, const float* rays, int64_t R, int64_t n_valid,
+                          const int32_t* label_hit, float weight, void* ws, int64_t ws_bytes, double* mass, int32_t* target, float* t_last,
+                          int32_t* cells, float* loss, void* stream);
+int muvo_render_class_bwd(const float* logits, int64_t F, int C, int X, int Y, int Z, const float* rays, int64_t R, int64_t n_valid, const double* mass,
+                          const int32_t* target, float weight, const float* gout, void* ws, int64_t ws_bytes, float* dlogits, void* stream);
+
 /* ---- sensor-visibility mask of the voxel labels (visibility.hip; an extension) ----------------------------
  * OUR DEFINITION (the reference has no visibility mask; its SemScal / GeoScal losses carry ignore_index = 255 and nothing writes
  * one); tests/visibility_reference.py restates it and the kernels equal that restatement bit for bit.

@@ -29,6 +29,11 @@ TOLERATED_EXTRA_KEYS = ('CML_DATASET_VERSION', 'MODEL.TRANSFORMER_TRANSITION', '
 #   1, 2, 4; absent = [1, 2, 4]) names the output scales that get a term `voxel_render_{f}` = WEIGHT / f x render(voxel_f,
 #   voxel_label_f) x VOXEL.RESOLUTION f / LIDAR_RE.SCALE (the scaled depth units of lidar_depth_f), STRIDE (an integer >= 1;
 #   absent = 1) takes every STRIDE-th azimuth of the range view as a ray.  Needs VOXEL_SEG.ENABLED.
+#   LOSSES.VOXEL_RENDER_CLASS.{WEIGHT,FACTORS,STRIDE} - the rendered first-hit class loss of the voxel head along the same rays
+#   (the class half of RayIoU; the reference has none).  WEIGHT (float; absent = 0 = off) multiplies, FACTORS (a list drawn from
+#   1, 2, 4; absent = [1, 2, 4]) names the output scales that get a term `voxel_render_class_{f}` = WEIGHT / f x
+#   render_class(voxel_f, voxel_label_f), STRIDE (an integer >= 1; absent = 1) takes every STRIDE-th azimuth of the range view as
+#   a ray - the table LOSSES.VOXEL_RENDER uses at the same stride.  Needs VOXEL_SEG.ENABLED.
 #   VOXEL_SEG.VISIBILITY.{ENABLED,LIDAR_STRIDE,CAMERA_STRIDE} - the sensor-visibility mask of the voxel labels (the reference has
 #   none: its labels call every unobserved cell "free").  ENABLED (bool; absent = off: no table, no launch, no new batch key)
 #   makes PreProcess add `voxel_visible_label_{1,2,4}`: voxel_label_f with every free cell that no ray of the lidar sweep or the
@@ -40,6 +45,8 @@ EXTENSION_KEYS = ('MODEL.CONSTANT_SIZE', 'MODEL.CONSTANT_SIZE.RGB', 'MODEL.CONST
                   'LOSSES.LIDAR_CD', 'LOSSES.LIDAR_CD.WEIGHT', 'LOSSES.LIDAR_CD.FACTORS',
                   'LOSSES.VOXEL_LOVASZ', 'LOSSES.VOXEL_LOVASZ.WEIGHT', 'LOSSES.VOXEL_LOVASZ.FACTORS',
                   'LOSSES.VOXEL_RENDER', 'LOSSES.VOXEL_RENDER.WEIGHT', 'LOSSES.VOXEL_RENDER.FACTORS', 'LOSSES.VOXEL_RENDER.STRIDE',
+                  'LOSSES.VOXEL_RENDER_CLASS', 'LOSSES.VOXEL_RENDER_CLASS.WEIGHT', 'LOSSES.VOXEL_RENDER_CLASS.FACTORS',
+                  'LOSSES.VOXEL_RENDER_CLASS.STRIDE',
                   'VOXEL_SEG.VISIBILITY', 'VOXEL_SEG.VISIBILITY.ENABLED', 'VOXEL_SEG.VISIBILITY.LIDAR_STRIDE', 'VOXEL_SEG.VISIBILITY.CAMERA_STRIDE')
 DEFAULT_CONSTANT_SIZE = {'RGB': (5, 13), 'LIDAR': (1, 16), 'VOXEL': (3, 3, 1)}
 
@@ -96,23 +103,37 @@ DEFAULT_VOXEL_RENDER_FACTORS = (1, 2, 4)
 DEFAULT_VOXEL_RENDER_STRIDE = 1
 
 
+def _rendered_loss(cfg, key, default_factors, default_stride):
+    node = cfg.LOSSES.get(key, None) or {}
+    weight = node.get('WEIGHT', 0.0)
+    if isinstance(weight, bool) or not isinstance(weight, (int, float)) or not weight >= 0:
+        raise ValueError(f'LOSSES.{key}.WEIGHT must be a number >= 0, got {weight!r}')
+    factors = node.get('FACTORS', default_factors)
+    if not isinstance(factors, (list, tuple)) or any(isinstance(f, bool) or f not in (1, 2, 4) for f in factors) \
+            or len(set(factors)) != len(factors):
+        raise ValueError(f'LOSSES.{key}.FACTORS must be a list of distinct factors drawn from 1, 2, 4, got {factors!r}')
+    stride = node.get('STRIDE', default_stride)
+    if isinstance(stride, bool) or not isinstance(stride, int) or stride < 1:
+        raise ValueError(f'LOSSES.{key}.STRIDE must be an integer >= 1, got {stride!r}')
+    if weight > 0 and not cfg.VOXEL_SEG.ENABLED:
+        raise ValueError(f'LOSSES.{key}.WEIGHT > 0 needs VOXEL_SEG.ENABLED: the loss is on the voxel head')
+    return float(weight), tuple(int(f) for f in factors), int(stride)
+
+
 def voxel_render(cfg):
     """(weight, factors, stride) of the rendered first-hit depth loss: LOSSES.VOXEL_RENDER.* if given, else (0.0, (1, 2, 4), 1);
     weight 0 = no such term."""
-    node = cfg.LOSSES.get('VOXEL_RENDER', None) or {}
-    weight = node.get('WEIGHT', 0.0)
-    if isinstance(weight, bool) or not isinstance(weight, (int, float)) or not weight >= 0:
-        raise ValueError(f'LOSSES.VOXEL_RENDER.WEIGHT must be a number >= 0, got {weight!r}')
-    factors = node.get('FACTORS', DEFAULT_VOXEL_RENDER_FACTORS)
-    if not isinstance(factors, (list, tuple)) or any(isinstance(f, bool) or f not in (1, 2, 4) for f in factors) \
-            or len(set(factors)) != len(factors):
-        raise ValueError(f'LOSSES.VOXEL_RENDER.FACTORS must be a list of distinct factors drawn from 1, 2, 4, got {factors!r}')
-    stride = node.get('STRIDE', DEFAULT_VOXEL_RENDER_STRIDE)
-    if isinstance(stride, bool) or not isinstance(stride, int) or stride < 1:
-        raise ValueError(f'LOSSES.VOXEL_RENDER.STRIDE must be an integer >= 1, got {stride!r}')
-    if weight > 0 and not cfg.VOXEL_SEG.ENABLED:
-        raise ValueError('LOSSES.VOXEL_RENDER.WEIGHT > 0 needs VOXEL_SEG.ENABLED: the loss is on the voxel head')
-    return float(weight), tuple(int(f) for f in factors), int(stride)
+    return _rendered_loss(cfg, 'VOXEL_RENDER', DEFAULT_VOXEL_RENDER_FACTORS, DEFAULT_VOXEL_RENDER_STRIDE)
+
+
+DEFAULT_VOXEL_RENDER_CLASS_FACTORS = (1, 2, 4)
+DEFAULT_VOXEL_RENDER_CLASS_STRIDE = 1
+
+
+def voxel_render_class(cfg):
+    """(weight, factors, stride) of the rendered first-hit class loss: LOSSES.VOXEL_RENDER_CLASS.* if given, else
+    (0.0, (1, 2, 4), 1); weight 0 = no such term.  The rules and texts of voxel_render."""
+    return _rendered_loss(cfg, 'VOXEL_RENDER_CLASS', DEFAULT_VOXEL_RENDER_CLASS_FACTORS, DEFAULT_VOXEL_RENDER_CLASS_STRIDE)
 
 
 DEFAULT_VISIBILITY_LIDAR_STRIDE = 1

@@ -4,7 +4,7 @@
 //   march           one thread per (ray, frame): the cell sequence of muvo_raycast through a grid in which nothing is occupied -
 //                   the walk raycast.hip takes, vg_start / vg_step of voxel_grid.h - composited front to back:
 //                   T in fp32, the depth sum in fp64.  |D - t*| leaves as one fp64 partial per workgroup.
-//   finish          one workgroup adds the partials in a fixed order and writes the fp32 scalar.
+//   finish          one workgroup adds the partials in a fixed order and writes the fp32 scalar (vg_finish_kernel of voxel_grid.h).
 //   backward        the occupancy pass again (q and a are recomputed, not kept: 8 bytes a voxel and frame), then the same march
 //                   with D from the forward pass, adding sign (T_{k+1} t_k - Q_k) per visited cell into an (F, V) accumulator
 //                   of 64-bit integers in fixed point, then one dense pass accumulator -> dlogits.
@@ -97,18 +97,6 @@ render_march_kernel(const float2* __restrict__ qa, const float* __restrict__ ray
   if (threadIdx.x == 0) part[(size_t)f * gridDim.x + blockIdx.x] = ((red[0] + red[1]) + red[2]) + red[3];
 }
 
-// one workgroup: thread l adds the partials l, l + 256, ... in order, the lanes of a wave are added by a fixed butterfly, the four
-// waves in their order
-__global__ void __launch_bounds__(RN_THREADS) render_finish_kernel(const double* __restrict__ part, long P, float weight, long F, long N, float* __restrict__ loss) {
-  __shared__ double red[4];
-  double s = 0.0;
-  for (long p = threadIdx.x; p < P; p += RN_THREADS) s += part[p];
-  s = wave_sum_d(s);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-  __syncthreads();
-  if (threadIdx.x == 0) loss[0] = N > 0 ? (float)((double)weight * (((red[0] + red[1]) + red[2]) + red[3]) / ((double)F * (double)N)) : 0.f;
-}
-
 // ---- backward march.  The loop is wave-uniform (it ends when no lane of the wave marches any more): every lane takes part in the
 // shuffles of the combine.  COMBINE = false (MUVO_RENDER_COMBINE=0, for measurements: DESIGN.md section 12) issues one atomic per
 // lane and step instead; the sums are integers, the results are the same bits.
@@ -157,16 +145,9 @@ render_bwd_march_kernel(const float2* __restrict__ qa, const float* __restrict__
       if (cell >= 0 && (long)cell < V && val != 0) atomicAdd(accf + cell, (unsigned long long)val);
       continue;
     }
-    // runs of neighbouring lanes in the same cell: lane i + o belongs to the run of lane i iff no run starts in (i, i + o]
-    const int prev = __shfl_up(cell, 1, 64);
+    const int prev = __shfl_up(cell, 1, 64);                                    // runs of neighbouring lanes in the same cell
     const bool head = lane == 0 || prev != cell;
-    const unsigned long long heads = __ballot(head);
-    const unsigned long long after = lane < 63 ? heads >> (lane + 1) : 0ull;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const long long u = __shfl_down(val, o, 64);
-      if (lane + o < 64 && (after & ((1ull << o) - 1ull)) == 0ull) val += u;
-    }
+    val = vg_run_sum(val, head, lane);
     if (head && cell >= 0 && (long)cell < V && val != 0) atomicAdd(accf + cell, (unsigned long long)val);
   }
 }
@@ -261,7 +242,7 @@ int muvo_render_fwd(const float* logits, int64_t F, int C, int X, int Y, int Z, 
   else
     hipLaunchKernelGGL(render_march_kernel<false>, dim3(nb, (unsigned)F), dim3(RN_THREADS), 0, ST, (const float2*)w.qa, rays, (long)R, X, Y, Z,
                        label_hit, label_t, depth, target, (float*)nullptr, (int32_t*)nullptr, (float*)nullptr, w.part);
-  hipLaunchKernelGGL(render_finish_kernel, dim3(1), dim3(RN_THREADS), 0, ST, (const double*)w.part, (long)nb * (long)F, weight, (long)F, (long)n_valid, loss);
+  hipLaunchKernelGGL(vg_finish_kernel, dim3(1), dim3(256), 0, ST, (const double*)w.part, (long)nb * (long)F, weight, (long)F, (long)n_valid, loss);
   MUVO_CHECK_LAUNCH("render_fwd");
   return MUVO_OK;
 }

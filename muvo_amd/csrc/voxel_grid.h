@@ -1,5 +1,6 @@
-// What the voxel-head units (raycast.hip, render.hip, lovasz.hip) share: the limits and their host checks, the ray walk of
-// muvo_raycast, the access to 4 consecutive voxels per lane, and the per-voxel softmax statistics over the class planes.
+// What the voxel-head units (raycast.hip, render.hip, render_class.hip, lovasz.hip) share: the limits and their host checks, the ray
+// walk of muvo_raycast, the access to 4 consecutive voxels per lane, the per-voxel softmax statistics over the class planes, and
+// what the two rendered losses share: the sum over runs of lanes before an atomic and the finish of the loss.
 #pragma once
 #include "common.h"
 
@@ -176,4 +177,30 @@ __device__ __forceinline__ VgSoftmax vg_softmax_stats(const float* __restrict__ 
 }
 __device__ __forceinline__ f32x4 vg_prob(f32x4 x, f32x4 m, f32x4 s) {
   return f32x4{expf(x.x - m.x) / s.x, expf(x.y - m.y) / s.y, expf(x.z - m.z) / s.z, expf(x.w - m.w) / s.w};
+}
+
+// ---- the rendered losses (render.hip, render_class.hip) ---------------------------------------------------------------------------
+// Sums `val` over runs of neighbouring lanes - a run starts at every lane with `head` - by a segmented shuffle reduction of fixed
+// cost (6 steps); the head lane of a run holds its sum.  Every lane of the wave must take part.
+__device__ __forceinline__ long long vg_run_sum(long long val, bool head, int lane) {
+  const unsigned long long heads = __ballot(head);
+  const unsigned long long after = lane < 63 ? heads >> (lane + 1) : 0ull;      // lane i + o belongs to the run of lane i iff no run starts in (i, i + o]
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const long long u = __shfl_down(val, o, 64);
+    if (lane + o < 64 && (after & ((1ull << o) - 1ull)) == 0ull) val += u;
+  }
+  return val;
+}
+
+// loss[0] = weight / (F N) x the sum of the P fp64 partials.  One workgroup of 256: thread l adds the partials l, l + 256, ... in
+// order, the lanes of a wave are added by a fixed butterfly, the four waves in their order
+static __global__ void __launch_bounds__(256) vg_finish_kernel(const double* __restrict__ part, long P, float weight, long F, long N, float* __restrict__ loss) {
+  __shared__ double red[4];
+  double s = 0.0;
+  for (long p = threadIdx.x; p < P; p += 256) s += part[p];
+  s = wave_sum_d(s);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
+  __syncthreads();
+  if (threadIdx.x == 0) loss[0] = N > 0 ? (float)((double)weight * (((red[0] + red[1]) + red[2]) + red[3]) / ((double)F * (double)N)) : 0.f;
 }

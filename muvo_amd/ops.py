@@ -100,6 +100,7 @@ EXPORTS = [
     'muvo_ray_iou_ws_doubles', 'muvo_ray_iou_counts',
     'muvo_lovasz_ws_bytes', 'muvo_lovasz_fwd', 'muvo_lovasz_bwd',
     'muvo_render_ws_bytes', 'muvo_render_fwd', 'muvo_render_bwd',
+    'muvo_render_class_ws_bytes', 'muvo_render_class_fwd', 'muvo_render_class_bwd',
     'muvo_visibility_mark', 'muvo_visibility_apply',
 ]
 
@@ -127,7 +128,8 @@ def lib():
                 L.muvo_icp_state_doubles.restype = C.c_int64
                 L.muvo_icp_ws_doubles.restype = C.c_int64
                 for name in ('muvo_flow_max_pairs', 'muvo_flow_workspace_bytes', 'muvo_flow_colour_ws_bytes', 'muvo_flow_epe_ws_doubles',
-                             'muvo_raycast_brick_words', 'muvo_ray_iou_ws_doubles', 'muvo_lovasz_ws_bytes', 'muvo_render_ws_bytes'):
+                             'muvo_raycast_brick_words', 'muvo_ray_iou_ws_doubles', 'muvo_lovasz_ws_bytes', 'muvo_render_ws_bytes',
+                             'muvo_render_class_ws_bytes'):
                     getattr(L, name).restype = C.c_int64
                 for name in EXPORTS:
                     getattr(L, name)  # AttributeError if a declared symbol is missing
@@ -2907,7 +2909,9 @@ def _render_ws(f, v, r, device):
     return torch.empty(max(16, n), device=device, dtype=torch.uint8), n
 
 
-def _render_forward(logits, labels, rays, n_valid, weight, parts=False):
+def _render_label_pass(logits, labels, rays):
+    """What both rendered losses start with: the contiguous inputs, their sizes, and muvo_raycast's (hit, t) of the table's rays
+    through the label grid."""
     logits, labels = logits.contiguous(), labels.contiguous()
     assert logits.dim() == 6 and logits.dtype == torch.float32, 'logits must be float32 (B,S,C,X,Y,Z)'
     f, c, v = _voxel_dims(logits, labels)
@@ -2917,6 +2921,12 @@ def _render_forward(logits, labels, rays, n_valid, weight, parts=False):
     R = int(rays.shape[0])
     grid, bricks = raycast_bricks(labels.view(f, X, Y, Z))          # occupied = class != 0, as for the metric
     hit, lt, _ = raycast(grid, bricks, rays)
+    return logits, grid, hit, lt, (f, c, X, Y, Z, R)
+
+
+def _render_forward(logits, labels, rays, n_valid, weight, parts=False):
+    logits, _, hit, lt, (f, c, X, Y, Z, R) = _render_label_pass(logits, labels, rays)
+    v = X * Y * Z
     dev = logits.device
     ws, ws_bytes = _render_ws(f, v, R, dev)
     depth = torch.empty(f, R, device=dev, dtype=torch.float64)
@@ -2967,6 +2977,68 @@ def voxel_render_parts(logits, labels, rays, n_valid, weight=1.0):
     of voxel_render_loss."""
     _, loss, depth, target, t_last, cells, t_exit, _ = _render_forward(logits.detach(), labels, rays, n_valid, weight, True)
     return loss, depth, target, t_last, cells, t_exit
+
+
+def _render_class_ws(f, c, v, r, device):
+    n = int(lib().muvo_render_class_ws_bytes(_i64(f), c, _i64(v), _i64(r)))
+    if n < 0:
+        raise ValueError(f'voxel_render_class_loss: {f} frames of {c} classes, {v} voxels and {r} rays (1..65535 frames, 2..16 classes, '
+                         'fewer than 2^30 voxels, 1..2^24 rays)')
+    return torch.empty(max(16, n), device=device, dtype=torch.uint8), n        # from the caching allocator, as _render_ws
+
+
+def _render_class_forward(logits, labels, rays, n_valid, weight, parts=False):
+    logits, grid, hit, _, (f, c, X, Y, Z, R) = _render_label_pass(logits, labels, rays)
+    dev = logits.device
+    ws, ws_bytes = _render_class_ws(f, c, X * Y * Z, R, dev)
+    mass = torch.empty(f, R, device=dev, dtype=torch.float64)
+    target = torch.empty(f, R, device=dev, dtype=torch.int32)
+    t_last = torch.empty(f, R, device=dev, dtype=torch.float32) if parts else None
+    cells = torch.empty(f, R, device=dev, dtype=torch.int32) if parts else None
+    loss = torch.empty(1, device=dev, dtype=torch.float32)
+    _ck(lib().muvo_render_class_fwd(_f(logits), _p(grid), _i64(f), c, X, Y, Z, _f(rays), _i64(R), _i64(n_valid), _p(hit), _fl(weight), _p(ws),
+                                    _i64(ws_bytes), _p(mass), _p(target), _f(t_last), _p(cells), _f(loss), _st()))
+    return logits, loss, mass, target, t_last, cells, (f, c, X, Y, Z, R)
+
+
+class VoxelRenderClassFn(torch.autograd.Function):
+    """weight * rendered first-hit class loss (include/muvo_hip.h: muvo_render_class_fwd) for logits
+    (B,S,C,X,Y,Z), labels u8 (B,S,1,X,Y,Z) and a ray table (R, 7) in grid units with `n_valid` valid rays.  A label class >= C at a
+    ray's first hit makes the loss ignore that ray (the labels stay on the device: nothing is read back to refuse them).  Kept
+    for the backward pass: the logits (the probabilities are recomputed), S_y (F, R) float64 and y (F, R) int32."""
+
+    @staticmethod
+    def forward(ctx, logits, labels, rays, n_valid, weight, terms=False, grad_enabled=True):
+        need = ctx.needs_input_grad[0] and grad_enabled
+        logits, loss, mass, target, _, _, dims = _render_class_forward(logits, labels, rays, n_valid, weight)
+        ctx.dims, ctx.weight, ctx.n_valid = dims, weight, int(n_valid)
+        if need:
+            ctx.save_for_backward(logits, rays, mass, target)
+        return _as_terms(ctx, loss, terms)
+
+    @staticmethod
+    def backward(ctx, g):
+        logits, rays, mass, target = ctx.saved_tensors
+        f, c, X, Y, Z, R = ctx.dims
+        g = _grad_scalar(g, logits.device)
+        ws, ws_bytes = _render_class_ws(f, c, X * Y * Z, R, logits.device)
+        dl = torch.empty_like(logits)
+        _ck(lib().muvo_render_class_bwd(_f(logits), _i64(f), c, X, Y, Z, _f(rays), _i64(R), _i64(ctx.n_valid), _p(mass), _p(target), _fl(ctx.weight),
+                                        _f(g.contiguous()), _p(ws), _i64(ws_bytes), _f(dl), _st()))
+        return dl, None, None, None, None, None, None
+
+
+def voxel_render_class_loss(logits, labels, rays, n_valid, weight, terms=False):
+    """terms=True: a 1-tuple holding the 0-d loss instead of the (1,) tensor (as the other loss entry points)"""
+    return VoxelRenderClassFn.apply(logits, labels, rays, n_valid, weight, terms, torch.is_grad_enabled())
+
+
+def voxel_render_class_parts(logits, labels, rays, n_valid, weight=1.0):
+    """What the loss is made of, for tests and the benchmark: (loss (1,), S_y (F, R) float64, y (F, R) int32 with -1 at invalid and
+    ignored rays, T_n (F, R), cells per ray (F, R) int32 with -1 at invalid rays).  The march runs to the end of every ray here;
+    the loss has the bits of voxel_render_class_loss."""
+    _, loss, mass, target, t_last, cells, _ = _render_class_forward(logits.detach(), labels, rays, n_valid, weight, True)
+    return loss, mass, target, t_last, cells
 
 
 # ================================================================================================ ICP between lidar frames
