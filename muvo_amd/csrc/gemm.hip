@@ -9,6 +9,7 @@
 // ("lanes along k" when the operand is k-contiguous, else "lanes along m/n"); both produce the same
 // k-major LDS tiles consumed by v_mfma_f32_32x32x2_f32.  mode 1 = float-atomic accumulate (split-K and
 // gradient accumulation into .grad buffers).
+#include <type_traits>
 #include "common.h"
 
 struct GemmArgs {
@@ -179,6 +180,11 @@ __global__ void __launch_bounds__(256) gemm_kernel(const GemmArgs g, const float
 // transition.py:108-127) and the small MLPs.  These are weight-bandwidth bound: B (the weight) is streamed exactly once
 // by as many workgroups as possible; A (a few rows) is re-read from L1/L2.  Two variants by the contiguous axis of B.
 // ------------------------------------------------------------------------------------------------
+// The output value act(alpha * s + bias[n / bias_div]) of the skinny kernels (runtime activation).
+__device__ __forceinline__ float skinny_out(const GemmArgs& g, float s, int n) {
+  return act_apply(g.alpha * s + (g.bias ? g.bias[n / g.bias_div] : 0.f), g.act, g.slope);
+}
+
 // B k-contiguous (nn.Linear forward: B(k,n) = W[n][k]).  One wave per pair of output columns, lanes stride over k.
 template <int RM>
 __global__ void __launch_bounds__(256) gemm_skinny_kcontig_kernel(const GemmArgs g, const float* __restrict__ A,
@@ -206,12 +212,8 @@ __global__ void __launch_bounds__(256) gemm_skinny_kcontig_kernel(const GemmArgs
     for (int r = 0; r < RM; ++r) {
       const float s0 = wave_sum(acc0[r]), s1 = wave_sum(acc1[r]);
       if (lane == 0 && r0 + r < g.M) {
-        const float bv0 = g.bias ? g.bias[n0 / g.bias_div] : 0.f;
-        C[(long)(r0 + r) * g.scm + n0] = act_apply(g.alpha * s0 + bv0, g.act, g.slope);
-        if (two) {
-          const float bv1 = g.bias ? g.bias[(n0 + 1) / g.bias_div] : 0.f;
-          C[(long)(r0 + r) * g.scm + n0 + 1] = act_apply(g.alpha * s1 + bv1, g.act, g.slope);
-        }
+        C[(long)(r0 + r) * g.scm + n0] = skinny_out(g, s0, n0);
+        if (two) C[(long)(r0 + r) * g.scm + n0 + 1] = skinny_out(g, s1, n0 + 1);
       }
     }
   }
@@ -220,16 +222,16 @@ __global__ void __launch_bounds__(256) gemm_skinny_kcontig_kernel(const GemmArgs
 // Same product for 16-byte aligned, k-contiguous A and B with K % 4 == 0 (every nn.Linear forward of the model).  A
 // workgroup owns four output columns and ALL rows: its four waves split k (lanes read float4), so the weight is streamed
 // from HBM exactly once and A is re-read from L2 once per four columns (the two-column kernel above re-read it per column
-// pair and made several passes over the weight for M > 8).
+// pair and made several passes over the weight for M > 8).  The work of one 512-thread workgroup, columns n0 .. n0 + 3 of C
+// (g.M <= RM); grouped_linear_fwd_kernel is the same function on a layer of its table.
 template <int RM>
-__global__ void __launch_bounds__(512, 2) gemm_skinny_kvec_kernel(const GemmArgs g, const float* __restrict__ A,
-                                                               const float* __restrict__ B, float* __restrict__ C) {
+__device__ __forceinline__ void skinny_kvec_tile(const GemmArgs& g, const float* __restrict__ A, const float* __restrict__ B,
+                                                 float* __restrict__ C, int n0) {
   // eight waves x two k chunks x four columns of float4 in flight per workgroup: a cold 68 MB weight needs ~8 MB of
   // outstanding loads to approach HBM speed (HBM latency x bandwidth)
   __shared__ float red[8][RM][4];
   __shared__ float tr[8][64 * 33];         // per wave: 64 lanes x (up to) 32 values, row stride 33 floats (conflict-free columns)
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int n0 = blockIdx.x * 4;
   float acc[RM][4];
 #pragma unroll
   for (int r = 0; r < RM; ++r)
@@ -299,10 +301,15 @@ __global__ void __launch_bounds__(512, 2) gemm_skinny_kvec_kernel(const GemmArgs
       float sum = 0.f;
 #pragma unroll
       for (int w8 = 0; w8 < 8; ++w8) sum += red[w8][r][c];
-      const float bv = g.bias ? g.bias[(n0 + c) / g.bias_div] : 0.f;
-      C[(long)r * g.scm + n0 + c] = act_apply(g.alpha * sum + bv, g.act, g.slope);
+      C[(long)r * g.scm + n0 + c] = skinny_out(g, sum, n0 + c);
     }
   }
+}
+
+template <int RM>
+__global__ void __launch_bounds__(512, 2) gemm_skinny_kvec_kernel(const GemmArgs g, const float* __restrict__ A,
+                                                               const float* __restrict__ B, float* __restrict__ C) {
+  skinny_kvec_tile<RM>(g, A, B, C, blockIdx.x * 4);
 }
 
 // B n-contiguous (data gradient of nn.Linear: B(k,n) = W[k][n]).  Lanes along n (coalesced weight rows); the workgroup
@@ -310,14 +317,54 @@ __global__ void __launch_bounds__(512, 2) gemm_skinny_kvec_kernel(const GemmArgs
 // each of the four waves takes 32 k of the chunk, four k per pass: four weight loads in flight, the wave-uniform A operands
 // come as one broadcast 16-byte LDS read per row.  (A from global memory meant a scalar load per row and k with a wait per
 // basic block; the 68-MB Linear of the model ran at 0.5 TB/s.)  KS > 1: partial sums are added into the pre-zeroed C with
-// float atomics (only offered without bias/activation).
+// float atomics (only offered without bias/activation).  One chunk: acc[r] += sum over k in [kc, min(kc + 128, kend)) of A(r0 + r, k) * B(k, nc), this wave's quarter of it.  The
+// caller makes sure (barrier) that every wave has finished with the previous contents of sA.  grouped_linear_dgrad_kernel runs
+// the same step on a 128-row slab of a layer's weight.
+constexpr int SKINNY_KC = 128;
+template <int RM>
+__device__ __forceinline__ void skinny_nc_chunk(const GemmArgs& g, const float* __restrict__ A, const float* __restrict__ B, int r0,
+                                                int nc, int kc, int kend, float (&sA)[RM][SKINNY_KC], float (&acc)[RM]) {
+  constexpr int KC = SKINNY_KC;
+  const int wave = threadIdx.x >> 6;
+  for (int i = threadIdx.x; i < RM * KC; i += 256) {
+    const int r = i / KC, kk = i - r * KC;
+    const bool ok = r0 + r < g.M && kc + kk < kend;
+    const float v = A[(long)(ok ? r0 + r : 0) * g.sam + (long)(ok ? kc + kk : 0) * g.sak];     // unconditional load
+    sA[r][kk] = ok ? v : 0.f;
+  }
+  __syncthreads();
+#pragma unroll 2
+  for (int kk = wave * 32; kk < wave * 32 + 32; kk += 4) {
+    float w[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const int k = kc + kk + u;
+      w[u] = B[(long)(k < g.K ? k : g.K - 1) * g.sbk + (long)nc * g.sbn];      // past kend: multiplied by the zeros in sA
+    }
+#pragma unroll
+    for (int r = 0; r < RM; ++r) {
+      const float4 a = *reinterpret_cast<const float4*>(&sA[r][kk]);
+      acc[r] += (a.x * w[0] + a.y * w[1]) + (a.z * w[2] + a.w * w[3]);
+    }
+  }
+}
+// The four waves' partial sums of a 64-column block meet in LDS; wave w then calls out(r, sum) for rows w, w + 4, ..
+template <int RM, class F>
+__device__ __forceinline__ void skinny_nc_reduce(const float (&acc)[RM], float (&red)[4][RM][64], F out) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+  for (int r = 0; r < RM; ++r) red[wave][r][lane] = acc[r];
+  __syncthreads();
+  for (int r = wave; r < RM; r += 4) out(r, red[0][r][lane] + red[1][r][lane] + red[2][r][lane] + red[3][r][lane]);
+}
+
 template <int RM>
 __global__ void __launch_bounds__(256) gemm_skinny_ncontig_kernel(const GemmArgs g, const float* __restrict__ A,
                                                                   const float* __restrict__ B, float* __restrict__ C, int KS) {
-  constexpr int KC = 128;
+  constexpr int KC = SKINNY_KC;
   __shared__ float red[4][RM][64];
   __shared__ __attribute__((aligned(16))) float sA[RM][KC];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int lane = threadIdx.x & 63;
   const int n = blockIdx.x * 64 + lane;
   const bool nok = n < g.N;
   const int nc = nok ? n : g.N - 1;
@@ -331,44 +378,16 @@ __global__ void __launch_bounds__(256) gemm_skinny_ncontig_kernel(const GemmArgs
     for (int r = 0; r < RM; ++r) acc[r] = 0.f;
     for (int kc = kbeg; kc < kend; kc += KC) {
       __syncthreads();                                             // the previous chunk has been consumed
-      for (int i = threadIdx.x; i < RM * KC; i += 256) {
-        const int r = i / KC, kk = i - r * KC;
-        const bool ok = r0 + r < g.M && kc + kk < kend;
-        const float v = A[(long)(ok ? r0 + r : 0) * g.sam + (long)(ok ? kc + kk : 0) * g.sak];     // unconditional load
-        sA[r][kk] = ok ? v : 0.f;
-      }
-      __syncthreads();
-#pragma unroll 2
-      for (int kk = wave * 32; kk < wave * 32 + 32; kk += 4) {
-        float w[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-          const int k = kc + kk + u;
-          w[u] = B[(long)(k < g.K ? k : g.K - 1) * g.sbk + (long)nc * g.sbn];      // past kend: multiplied by the zeros in sA
-        }
-#pragma unroll
-        for (int r = 0; r < RM; ++r) {
-          const float4 a = *reinterpret_cast<const float4*>(&sA[r][kk]);
-          acc[r] += (a.x * w[0] + a.y * w[1]) + (a.z * w[2] + a.w * w[3]);
-        }
-      }
+      skinny_nc_chunk<RM>(g, A, B, r0, nc, kc, kend, sA, acc);
     }
-    __syncthreads();
-#pragma unroll
-    for (int r = 0; r < RM; ++r) red[wave][r][lane] = acc[r];
-    __syncthreads();
-    for (int r = wave; r < RM; r += 4) {
+    __syncthreads();                                               // the previous row group's sums have been read
+    skinny_nc_reduce<RM>(acc, red, [&](int r, float s) {
       if (r0 + r < g.M && nok) {
-        const float s = red[0][r][lane] + red[1][r][lane] + red[2][r][lane] + red[3][r][lane];
         float* dst = C + (long)(r0 + r) * g.scm + n;
-        if (KS > 1) {
-          atomicAdd(dst, g.alpha * s);
-        } else {
-          const float bv = g.bias ? g.bias[n / g.bias_div] : 0.f;
-          *dst = act_apply(g.alpha * s + bv, g.act, g.slope);
-        }
+        if (KS > 1) atomicAdd(dst, g.alpha * s);
+        else *dst = skinny_out(g, s, n);
       }
-    }
+    });
   }
 }
 
@@ -396,123 +415,37 @@ struct GroupedLinearArgs {
 
 template <int RM>
 __global__ void __launch_bounds__(512, 2) grouped_linear_fwd_kernel(const GroupedLinearArgs a, const float* __restrict__ x) {
-  __shared__ float red[8][RM][4];
-  __shared__ float tr[8][64 * 33];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   int l = 0;
   while (l + 1 < a.L && (int)blockIdx.x >= a.blk0[l + 1]) ++l;
-  const int n0 = ((int)blockIdx.x - a.blk0[l]) * 4, N = a.N[l], K = a.K, M = a.M;
-  const float* __restrict__ B = a.W[l];
-  float acc[RM][4];
-#pragma unroll
-  for (int r = 0; r < RM; ++r)
-#pragma unroll
-    for (int c = 0; c < 4; ++c) acc[r][c] = 0.f;
-  const float4 zero4 = make_float4(0.f, 0.f, 0.f, 0.f);
-  const int mlast = M - 1;
-  for (int k = (wave * 64 + lane) * 4; k < K; k += 4096) {
-    const bool has2 = k + 2048 < K;
-    const int k2 = has2 ? k + 2048 : k;
-    float4 w[2][4];
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-      const float* bp = B + (long)(n0 + c < N ? n0 + c : n0) * K;
-      w[0][c] = *reinterpret_cast<const float4*>(bp + k);
-      const float4 t = *reinterpret_cast<const float4*>(bp + k2);
-      w[1][c] = has2 ? t : zero4;
-    }
-#pragma unroll
-    for (int rg = 0; rg < RM; rg += 4) {
-      float4 a0[4], a1[4];
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const float* ar = x + (long)(rg + q < mlast ? rg + q : mlast) * K;
-        a0[q] = *reinterpret_cast<const float4*>(ar + k);
-        a1[q] = *reinterpret_cast<const float4*>(ar + k2);
-      }
-#pragma unroll
-      for (int q = 0; q < 4; ++q)
-#pragma unroll
-        for (int c = 0; c < 4; ++c)
-          acc[rg + q][c] += a0[q].x * w[0][c].x + a0[q].y * w[0][c].y + a0[q].z * w[0][c].z + a0[q].w * w[0][c].w +
-                            a1[q].x * w[1][c].x + a1[q].y * w[1][c].y + a1[q].z * w[1][c].z + a1[q].w * w[1][c].w;
-      __builtin_amdgcn_sched_barrier(0);
-    }
-  }
-  constexpr int NV = RM * 4, CH = NV < 32 ? NV : 32;
-  float* trw = tr[wave];
-#pragma unroll
-  for (int c0 = 0; c0 < NV; c0 += CH) {
-    if (c0) __syncthreads();
-#pragma unroll
-    for (int v = 0; v < CH; ++v) trw[lane * 33 + v] = acc[(c0 + v) >> 2][(c0 + v) & 3];
-    __syncthreads();
-    if (lane < CH) {
-      float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
-#pragma unroll
-      for (int q = 0; q < 64; q += 4) {
-        s0 += trw[q * 33 + lane]; s1 += trw[(q + 1) * 33 + lane];
-        s2 += trw[(q + 2) * 33 + lane]; s3 += trw[(q + 3) * 33 + lane];
-      }
-      red[wave][(c0 + lane) >> 2][(c0 + lane) & 3] = (s0 + s1) + (s2 + s3);
-    }
-  }
-  __syncthreads();
-  float* __restrict__ Y = a.Y[l];
-  const float* __restrict__ bias = a.b[l];
-  for (int i = threadIdx.x; i < RM * 4; i += 512) {
-    const int r = i >> 2, c = i & 3;
-    if (r < M && n0 + c < N) {
-      float sum = 0.f;
-#pragma unroll
-      for (int w8 = 0; w8 < 8; ++w8) sum += red[w8][r][c];
-      Y[(long)r * N + n0 + c] = sum + (bias ? bias[n0 + c] : 0.f);
-    }
-  }
+  // Y_l = x W_l^T + b_l as a GEMM of the k-vector kernel: alpha = 1, bias_div = 1, no activation (with -ffp-contract=off,
+  // 1.0f * s + b has the bits of s + b)
+  GemmArgs g = {};
+  g.M = a.M; g.N = a.N[l]; g.K = a.K;
+  g.sam = g.sbn = a.K; g.scm = g.N;
+  g.alpha = 1.f; g.bias = a.b[l]; g.bias_div = 1; g.act = MUVO_ACT_NONE;
+  skinny_kvec_tile<RM>(g, x, a.W[l], a.Y[l], ((int)blockIdx.x - a.blk0[l]) * 4);
 }
 
-// dx[m][k] += sum over a 128-row slab of W_l:  dy_l[m][n] * W_l[n][k];  grid.x = K / 64 column blocks, grid.y = slabs
+// dx[m][k] += sum over a 128-row slab of W_l:  dy_l[m][n] * W_l[n][k];  grid.x = K / 64 column blocks, grid.y = slabs.
+// One chunk of the n-contiguous kernel on the GEMM dx (M x K) = dy_l (M x N_l) W_l: the slab's rows of W_l are its k.
 __global__ void __launch_bounds__(256) grouped_linear_dgrad_kernel(const GroupedLinearArgs a, float* __restrict__ dx) {
-  constexpr int RM = 24, NC = 128;
+  constexpr int RM = 24, NC = SKINNY_KC;
   __shared__ float red[4][RM][64];
   __shared__ __attribute__((aligned(16))) float sA[RM][NC];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   int l = 0;
   while (l + 1 < a.L && (int)blockIdx.y >= a.blk0[l + 1]) ++l;
-  const int nb = ((int)blockIdx.y - a.blk0[l]) * NC, N = a.N[l], K = a.K, M = a.M;
-  const float* __restrict__ W = a.W[l];
-  const float* __restrict__ dy = a.Y[l];
-  const int k = blockIdx.x * 64 + lane;
-  const int kc = k < K ? k : K - 1;
-  for (int i = threadIdx.x; i < RM * NC; i += 256) {          // dy slab -> LDS (zero past M / N)
-    const int r = i / NC, nn = i - r * NC;
-    const bool ok = r < M && nb + nn < N;
-    const float v = dy[(long)(ok ? r : 0) * N + (ok ? nb + nn : 0)];
-    sA[r][nn] = ok ? v : 0.f;
-  }
-  __syncthreads();
+  GemmArgs g = {};
+  g.M = a.M; g.N = a.K; g.K = a.N[l];
+  g.sam = g.K; g.sak = 1; g.sbk = g.N; g.sbn = 1;
+  const int nb = ((int)blockIdx.y - a.blk0[l]) * NC;
+  const int n = blockIdx.x * 64 + (threadIdx.x & 63);          // column of dx
   float acc[RM];
 #pragma unroll
   for (int r = 0; r < RM; ++r) acc[r] = 0.f;
-#pragma unroll 2
-  for (int nn = wave * 32; nn < wave * 32 + 32; nn += 4) {
-    float w[4];
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      const int n = nb + nn + u;
-      w[u] = W[(long)(n < N ? n : N - 1) * K + kc];             // rows past N meet the zeros in sA
-    }
-#pragma unroll
-    for (int r = 0; r < RM; ++r) {
-      const float4 d = *reinterpret_cast<const float4*>(&sA[r][nn]);
-      acc[r] += (d.x * w[0] + d.y * w[1]) + (d.z * w[2] + d.w * w[3]);
-    }
-  }
-#pragma unroll
-  for (int r = 0; r < RM; ++r) red[wave][r][lane] = acc[r];
-  __syncthreads();
-  for (int r = wave; r < RM; r += 4)
-    if (r < M && k < K) atomicAdd(dx + (long)r * K + k, red[0][r][lane] + red[1][r][lane] + red[2][r][lane] + red[3][r][lane]);
+  skinny_nc_chunk<RM>(g, a.Y[l], a.W[l], 0, n < g.N ? n : g.N - 1, nb, nb + NC < g.K ? nb + NC : g.K, sA, acc);
+  skinny_nc_reduce<RM>(acc, red, [&](int r, float s) {
+    if (r < g.M && n < g.N) atomicAdd(dx + (long)r * g.N + n, s);
+  });
 }
 
 // dW_l[n][k .. k+3] += sum_m dy_l[m][n] * x[m][k .. k+3]  (one float4 per lane, 16 weight rows per workgroup pass);
@@ -556,26 +489,24 @@ __global__ void __launch_bounds__(256) grouped_linear_wgrad_kernel(const Grouped
   }
 }
 
-static int grouped_fill(GroupedLinearArgs& a, int L, int M, int K, const float* const* W, const float* const* b, float* const* Y,
-                        float* const* dW, float* const* db, const int* N, int cols_per_block) {
+// Runtime integer -> template argument: f(std::integral_constant<int, V>()) for the V of the list that equals v (the last
+// one otherwise), so that a launch names exactly the instantiations it can reach.
+template <int V, int... MORE, class F>
+static void with_const(int v, F f) {
+  if constexpr (sizeof...(MORE) > 0)
+    if (v != V) return with_const<MORE...>(v, f);
+  f(std::integral_constant<int, V>());
+}
+#define LAUNCH_RM(KERNEL, ...) [&](auto rm) { hipLaunchKernelGGL((KERNEL<decltype(rm)::value>), __VA_ARGS__); }
+
+static int grouped_check_sizes(int L, int M, int K) {
   MUVO_CHECK_ARG(L > 0 && L <= GL_MAX, "grouped_linear: %d layers (max %d)", L, GL_MAX);
   MUVO_CHECK_ARG(M > 0 && M <= 24 && K >= 64 && K % 4 == 0, "grouped_linear: M=%d K=%d unsupported (M <= 24, K %% 4 == 0)", M, K);
-  a.L = L; a.M = M; a.K = K;
-  int blk = 0;
-  for (int l = 0; l < L; ++l) {
-    MUVO_CHECK_ARG(W[l] && Y[l] && N[l] > 0 && (((uintptr_t)W[l]) & 15) == 0, "grouped_linear: bad layer %d", l);
-    a.W[l] = W[l]; a.b[l] = b ? b[l] : nullptr; a.Y[l] = Y[l];
-    a.dW[l] = dW ? dW[l] : nullptr; a.db[l] = db ? db[l] : nullptr;
-    a.N[l] = N[l];
-    a.blk0[l] = blk;
-    blk += cdiv(N[l], cols_per_block);
-  }
-  a.blk0[L] = blk;
   return MUVO_OK;
 }
 
 // Host decisions of the three grouped launches for checked sizes: the forward row template and the grids (the per-layer
-// workgroup counts are those grouped_fill puts into blk0 for 4 / 128 / 16 columns per workgroup).
+// workgroup counts are those of grouped_blk0 for 4 / 128 / 16 columns per workgroup).
 static void grouped_route(int M, int K, int L, const int* N, muvo_grouped_linear_route_info* r) {
   int b4 = 0, b128 = 0, b16 = 0;
   for (int l = 0; l < L; ++l) { b4 += cdiv(N[l], 4); b128 += cdiv(N[l], 128); b16 += cdiv(N[l], 16); }
@@ -585,10 +516,32 @@ static void grouped_route(int M, int K, int L, const int* N, muvo_grouped_linear
   r->wgrad_grid[0] = cdiv(K, 256); r->wgrad_grid[1] = b16;
 }
 
+// the checked layer table and the route; blk0 depends on the launch (grouped_blk0)
+static int grouped_fill(GroupedLinearArgs& a, int L, int M, int K, const float* const* W, const float* const* b, float* const* Y,
+                        float* const* dW, float* const* db, const int* N, muvo_grouped_linear_route_info* r) {
+  int rc = grouped_check_sizes(L, M, K);
+  if (rc) return rc;
+  a.L = L; a.M = M; a.K = K;
+  for (int l = 0; l < L; ++l) {
+    MUVO_CHECK_ARG(W[l] && Y[l] && N[l] > 0 && (((uintptr_t)W[l]) & 15) == 0, "grouped_linear: bad layer %d", l);
+    a.W[l] = W[l]; a.b[l] = b ? b[l] : nullptr; a.Y[l] = Y[l];
+    a.dW[l] = dW ? dW[l] : nullptr; a.db[l] = db ? db[l] : nullptr;
+    a.N[l] = N[l];
+  }
+  grouped_route(M, K, L, N, r);
+  return MUVO_OK;
+}
+
+// blk0 of a launch whose workgroups take `cols` columns of one layer each
+static void grouped_blk0(GroupedLinearArgs& a, int cols) {
+  a.blk0[0] = 0;
+  for (int l = 0; l < a.L; ++l) a.blk0[l + 1] = a.blk0[l] + cdiv(a.N[l], cols);
+}
+
 extern "C" int muvo_grouped_linear_route(int M, int K, int L, const int* N, muvo_grouped_linear_route_info* out) {
   MUVO_CHECK_ARG(N && out, "grouped_linear_route: null pointer");
-  MUVO_CHECK_ARG(L > 0 && L <= GL_MAX, "grouped_linear: %d layers (max %d)", L, GL_MAX);
-  MUVO_CHECK_ARG(M > 0 && M <= 24 && K >= 64 && K % 4 == 0, "grouped_linear: M=%d K=%d unsupported (M <= 24, K %% 4 == 0)", M, K);
+  int rc = grouped_check_sizes(L, M, K);
+  if (rc) return rc;
   for (int l = 0; l < L; ++l) MUVO_CHECK_ARG(N[l] > 0, "grouped_linear: bad layer %d", l);
   grouped_route(M, K, L, N, out);
   return MUVO_OK;
@@ -598,13 +551,11 @@ extern "C" int muvo_grouped_linear_fwd(const float* x, int M, int K, int L, cons
                                        float* const* Y, const int* N, void* stream) {
   MUVO_CHECK_ARG(x && W && Y && N && (((uintptr_t)x) & 15) == 0, "grouped_linear_fwd: bad args");
   GroupedLinearArgs a;
-  int rc = grouped_fill(a, L, M, K, W, b, Y, nullptr, nullptr, N, 4);
-  if (rc) return rc;
-  hipStream_t st = (hipStream_t)stream;
   muvo_grouped_linear_route_info r;
-  grouped_route(M, K, L, N, &r);
-  if (r.fwd_rm == 8) hipLaunchKernelGGL((grouped_linear_fwd_kernel<8>), dim3(r.fwd_grid), dim3(512), 0, st, a, x);
-  else hipLaunchKernelGGL((grouped_linear_fwd_kernel<24>), dim3(r.fwd_grid), dim3(512), 0, st, a, x);
+  int rc = grouped_fill(a, L, M, K, W, b, Y, nullptr, nullptr, N, &r);
+  if (rc) return rc;
+  grouped_blk0(a, 4);
+  with_const<8, 24>(r.fwd_rm, LAUNCH_RM(grouped_linear_fwd_kernel, dim3(r.fwd_grid), dim3(512), 0, (hipStream_t)stream, a, x));
   MUVO_CHECK_LAUNCH("grouped_linear_fwd");
   return MUVO_OK;
 }
@@ -613,26 +564,24 @@ extern "C" int muvo_grouped_linear_fwd(const float* x, int M, int K, int L, cons
 extern "C" int muvo_grouped_linear_bwd(const float* x, int M, int K, int L, const float* const* W, float* const* dY, float* dx,
                                        float* const* dW, float* const* db, const int* N, void* stream) {
   MUVO_CHECK_ARG(x && W && dY && N && (((uintptr_t)x) & 15) == 0, "grouped_linear_bwd: bad args");
+  if (!dx && !dW) return MUVO_OK;
   hipStream_t st = (hipStream_t)stream;
   GroupedLinearArgs a;
+  muvo_grouped_linear_route_info r;
+  int rc = grouped_fill(a, L, M, K, W, nullptr, dY, dW, db, N, &r);
+  if (rc) return rc;
   if (dx) {
-    int rc = grouped_fill(a, L, M, K, W, nullptr, dY, nullptr, nullptr, N, 128);
-    if (rc) return rc;
     if (hipMemsetAsync(dx, 0, sizeof(float) * (size_t)M * K, st) != hipSuccess) {
       muvo_set_error("grouped_linear_bwd: memset failed");
       return MUVO_ERR_HIP;
     }
-    muvo_grouped_linear_route_info r;
-    grouped_route(M, K, L, N, &r);
+    grouped_blk0(a, 128);
     hipLaunchKernelGGL(grouped_linear_dgrad_kernel, dim3(r.dgrad_grid[0], r.dgrad_grid[1]), dim3(256), 0, st, a, dx);
   }
   if (dW) {
-    int rc = grouped_fill(a, L, M, K, W, nullptr, dY, dW, db, N, 16);
-    if (rc) return rc;
     for (int l = 0; l < L; ++l)
       MUVO_CHECK_ARG(dW[l] == nullptr || (((uintptr_t)dW[l]) & 15) == 0, "grouped_linear_bwd: unaligned gradient buffer");
-    muvo_grouped_linear_route_info r;
-    grouped_route(M, K, L, N, &r);
+    grouped_blk0(a, 16);
     hipLaunchKernelGGL(grouped_linear_wgrad_kernel, dim3(r.wgrad_grid[0], r.wgrad_grid[1]), dim3(256), 0, st, a, x);
   }
   MUVO_CHECK_LAUNCH("grouped_linear_bwd");
@@ -640,11 +589,12 @@ extern "C" int muvo_grouped_linear_bwd(const float* x, int M, int K, int L, cons
 }
 
 template <int BM, int BN, int WM, int WN>
-static void launch_gemm_lay(const GemmArgs& g, int al, int bl, const float* A, const float* B, float* C, dim3 grid, hipStream_t st) {
-  if (al == 0 && bl == 0) hipLaunchKernelGGL((gemm_kernel<BM, BN, WM, WN, 0, 0>), grid, dim3(256), 0, st, g, A, B, C);
-  else if (al == 0 && bl == 1) hipLaunchKernelGGL((gemm_kernel<BM, BN, WM, WN, 0, 1>), grid, dim3(256), 0, st, g, A, B, C);
-  else if (al == 1 && bl == 0) hipLaunchKernelGGL((gemm_kernel<BM, BN, WM, WN, 1, 0>), grid, dim3(256), 0, st, g, A, B, C);
-  else hipLaunchKernelGGL((gemm_kernel<BM, BN, WM, WN, 1, 1>), grid, dim3(256), 0, st, g, A, B, C);
+static void launch_gemm_lay(const GemmArgs& g, int al, int bl, const float* A, const float* B, float* C, dim3 grid, dim3 block,
+                            hipStream_t st) {
+  if (al == 0 && bl == 0) hipLaunchKernelGGL((gemm_kernel<BM, BN, WM, WN, 0, 0>), grid, block, 0, st, g, A, B, C);
+  else if (al == 0 && bl == 1) hipLaunchKernelGGL((gemm_kernel<BM, BN, WM, WN, 0, 1>), grid, block, 0, st, g, A, B, C);
+  else if (al == 1 && bl == 0) hipLaunchKernelGGL((gemm_kernel<BM, BN, WM, WN, 1, 0>), grid, block, 0, st, g, A, B, C);
+  else hipLaunchKernelGGL((gemm_kernel<BM, BN, WM, WN, 1, 1>), grid, block, 0, st, g, A, B, C);
 }
 
 static int gemm_check_desc(const muvo_gemm_desc* d, bool has_bias) {
@@ -736,43 +686,32 @@ extern "C" int muvo_gemm(const muvo_gemm_desc* d, const float* A, const float* B
   if (log_calls)
     fprintf(stderr, "muvo_gemm M=%d N=%d K=%d nb=%d mode=%d sam=%ld sak=%ld sbk=%ld sbn=%ld act=%d bias=%d\n", d->M, d->N, d->K,
             d->B1 * d->B2, d->mode, (long)d->sam, (long)d->sak, (long)d->sbk, (long)d->sbn, d->act, bias != nullptr);
-  GemmArgs g;
-  g.M = d->M; g.N = d->N; g.K = d->K;
-  g.sam = d->sam; g.sak = d->sak; g.sbk = d->sbk; g.sbn = d->sbn; g.scm = d->scm;
-  g.B1 = d->B1; g.B2 = d->B2;
-  g.a_b1 = d->a_b1; g.a_b2 = d->a_b2; g.b_b1 = d->b_b1; g.b_b2 = d->b_b2; g.c_b1 = d->c_b1; g.c_b2 = d->c_b2;
-  g.alpha = d->alpha; g.bias = bias; g.bias_div = d->bias_div > 0 ? d->bias_div : 1;
-  g.act = d->act; g.slope = d->slope; g.mode = d->mode;
   hipStream_t st = (hipStream_t)stream;
   muvo_gemm_route_info r;
   gemm_route(d, A, B, bias != nullptr, &r);
-  g.ksplit = r.kernel == MUVO_GEMM_TILED ? r.ksplit : 1;
-  const dim3 grid(r.grid[0], r.grid[1], r.grid[2]);
+  // (embedding the descriptor would move `bias` and with it the SGPR counts of gemm_kernel: the layout stays)
+  const GemmArgs g = {d->M, d->N, d->K, d->sam, d->sak, d->sbk, d->sbn, d->scm, d->B1, d->B2, d->a_b1, d->a_b2, d->b_b1, d->b_b2,
+                      d->c_b1, d->c_b2, d->alpha, bias, d->bias_div > 0 ? d->bias_div : 1, d->act, d->slope, d->mode,
+                      r.kernel == MUVO_GEMM_TILED ? r.ksplit : 1};
+  const dim3 grid(r.grid[0], r.grid[1], r.grid[2]), block(r.block);
+  if (r.kernel == MUVO_GEMM_TILED) {
+    if (r.bm == 32) launch_gemm_lay<32, 128, 1, 4>(g, r.a_lay, r.b_lay, A, B, C, grid, block, st);
+    else if (r.bn == 64) launch_gemm_lay<128, 64, 2, 2>(g, r.a_lay, r.b_lay, A, B, C, grid, block, st);
+    else launch_gemm_lay<128, 128, 2, 2>(g, r.a_lay, r.b_lay, A, B, C, grid, block, st);
+    MUVO_CHECK_LAUNCH("gemm_kernel");
+    return MUVO_OK;
+  }
   if (r.kernel == MUVO_GEMM_SKINNY_KVEC) {
-    if (r.rm == 4) hipLaunchKernelGGL((gemm_skinny_kvec_kernel<4>), grid, dim3(512), 0, st, g, A, B, C);
-    else if (r.rm == 8) hipLaunchKernelGGL((gemm_skinny_kvec_kernel<8>), grid, dim3(512), 0, st, g, A, B, C);
-    else if (r.rm == 16) hipLaunchKernelGGL((gemm_skinny_kvec_kernel<16>), grid, dim3(512), 0, st, g, A, B, C);
-    else hipLaunchKernelGGL((gemm_skinny_kvec_kernel<24>), grid, dim3(512), 0, st, g, A, B, C);
-    MUVO_CHECK_LAUNCH("gemm_skinny_kernel");
+    with_const<4, 8, 16, 24>(r.rm, LAUNCH_RM(gemm_skinny_kvec_kernel, grid, block, 0, st, g, A, B, C));
   } else if (r.kernel == MUVO_GEMM_SKINNY_KCONTIG) {
-    if (r.rm == 4) hipLaunchKernelGGL((gemm_skinny_kcontig_kernel<4>), grid, dim3(256), 0, st, g, A, B, C);
-    else hipLaunchKernelGGL((gemm_skinny_kcontig_kernel<8>), grid, dim3(256), 0, st, g, A, B, C);
-    MUVO_CHECK_LAUNCH("gemm_skinny_kernel");
-  } else if (r.kernel == MUVO_GEMM_SKINNY_NCONTIG) {
-    const int ks = r.ksplit;
-    if (ks > 1 && hipMemsetAsync(C, 0, sizeof(float) * (size_t)d->M * d->N, st) != hipSuccess) {
+    with_const<4, 8>(r.rm, LAUNCH_RM(gemm_skinny_kcontig_kernel, grid, block, 0, st, g, A, B, C));
+  } else {
+    if (r.ksplit > 1 && hipMemsetAsync(C, 0, sizeof(float) * (size_t)d->M * d->N, st) != hipSuccess) {
       muvo_set_error("gemm_skinny: memset failed");
       return MUVO_ERR_HIP;
     }
-    if (r.rm == 4) hipLaunchKernelGGL((gemm_skinny_ncontig_kernel<4>), grid, dim3(256), 0, st, g, A, B, C, ks);
-    else if (r.rm == 8) hipLaunchKernelGGL((gemm_skinny_ncontig_kernel<8>), grid, dim3(256), 0, st, g, A, B, C, ks);
-    else hipLaunchKernelGGL((gemm_skinny_ncontig_kernel<24>), grid, dim3(256), 0, st, g, A, B, C, ks);
-    MUVO_CHECK_LAUNCH("gemm_skinny_kernel");
-  } else {
-    if (r.bm == 32) launch_gemm_lay<32, 128, 1, 4>(g, r.a_lay, r.b_lay, A, B, C, grid, st);
-    else if (r.bn == 64) launch_gemm_lay<128, 64, 2, 2>(g, r.a_lay, r.b_lay, A, B, C, grid, st);
-    else launch_gemm_lay<128, 128, 2, 2>(g, r.a_lay, r.b_lay, A, B, C, grid, st);
-    MUVO_CHECK_LAUNCH("gemm_kernel");
+    with_const<4, 8, 24>(r.rm, LAUNCH_RM(gemm_skinny_ncontig_kernel, grid, block, 0, st, g, A, B, C, r.ksplit));
   }
+  MUVO_CHECK_LAUNCH("gemm_skinny_kernel");
   return MUVO_OK;
 }

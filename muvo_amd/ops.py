@@ -676,6 +676,20 @@ def gemm(A, B, Cout, M, N, K, sam, sak, sbk, sbn, scm, bias=None, alpha=1.0, act
     _ck(lib().muvo_gemm(C.byref(d), pa, pb, pc, _f(bias), _st()))
 
 
+def act_bwd(y, dy, act, slope):
+    """dz = dy * act'(y) from the saved output y of a fused activation; dy itself when there is none"""
+    if act == ACT_NONE:
+        return dy
+    dz = torch.empty_like(dy)
+    _ck(lib().muvo_act_bwd(_f(y), _f(dy), _f(dz), _i64(dy.numel()), act, _fl(slope), _st()))
+    return dz
+
+
+def bias_grad_acc(dz, bias, rows, out_f):
+    """bias.grad += column sums of the contiguous (rows, out_f) matrix dz"""
+    _ck(lib().muvo_colsum_acc(_f(dz), _f(grad_of(bias)), _i64(rows), _i64(out_f), _i64(out_f), _st()))
+
+
 GEMM_KERNELS = ('tiled', 'skinny_kvec', 'skinny_kcontig', 'skinny_ncontig')
 
 
@@ -717,12 +731,7 @@ class LinearFn(torch.autograd.Function):
         weight, bias = ctx.weight, ctx.bias
         out_f, in_f = weight.shape
         rows = x.numel() // in_f
-        dy = dy.contiguous()
-        if ctx.act != ACT_NONE:
-            dz = torch.empty_like(dy)
-            _ck(lib().muvo_act_bwd(_f(y), _f(dy), _f(dz), _i64(dy.numel()), ctx.act, _fl(ctx.slope), _st()))
-        else:
-            dz = dy
+        dz = act_bwd(y, dy.contiguous(), ctx.act, ctx.slope)
         dx = None
         if ctx.needs_input_grad[0]:
             dx = torch.empty_like(x)
@@ -732,7 +741,7 @@ class LinearFn(torch.autograd.Function):
             # dW[o][i] += sum_r dz[r][o] x[r][i]
             gemm(dz, x, grad_of(weight), out_f, in_f, rows, 1, out_f, in_f, 1, in_f, mode=1)
             if bias is not None:
-                _ck(lib().muvo_colsum_acc(_f(dz), _f(grad_of(bias)), _i64(rows), _i64(out_f), _i64(out_f), _st()))
+                bias_grad_acc(dz, bias, rows, out_f)
         return dx, None, None, None, None
 
 
@@ -848,11 +857,7 @@ class LinearBf16x3Fn(torch.autograd.Function):
         rows, in_f, out_f, df = ctx.dims
         L = lib()
         dy = dy.contiguous()
-        if ctx.act != ACT_NONE:
-            dz = torch.empty_like(dy)
-            _ck(L.muvo_act_bwd(_f(y), _f(dy), _f(dz), _i64(dy.numel()), ctx.act, _fl(ctx.slope), _st()))
-        else:
-            dz = dy
+        dz = act_bwd(y, dy, ctx.act, ctx.slope)
         nws = (L.muvo_linear_bf16x3_workspace_bytes(_i64(rows), out_f) + 3) // 4
         ws_dz = scratch('lin_ws_dz', nws, dy.device)
         _ck(L.muvo_linear_bf16x3_split(_f(dz), _i64(rows), out_f, _p(ws_dz), _st()))
@@ -871,7 +876,7 @@ class LinearBf16x3Fn(torch.autograd.Function):
             _ck(L.muvo_linear_bf16x3_wgrad(_i64(rows), in_f, out_f, _p(ctx.ws_x), _p(ws_dz), _f(sc), _f(grad_of(weight)),
                                            _st()))
             if bias is not None:
-                _ck(L.muvo_colsum_acc(_f(dz), _f(grad_of(bias)), _i64(rows), _i64(out_f), _i64(out_f), _st()))
+                bias_grad_acc(dz, bias, rows, out_f)
         return dx, None, None, None, None
 
 
@@ -1317,11 +1322,8 @@ class ConvFn(torch.autograd.Function):
             return dyp[0], dyp[0]          # (dz: pointer stand-in)
         if fused_dy:
             return ConvFn._split_dy(ctx, plan, x, y, dy, head, use_act, dy_ws.get(plan.dy_planes_floats))
-        if use_act:
-            dz = torch.empty_like(dy)
-            _ck(lib().muvo_act_bwd(_f(y), _f(dy), _f(dz), _i64(dy.numel()), ctx.act, _fl(ctx.slope), _st()))
-            return dz, None
-        return dy, None   # no activation, or its derivative was already chained by the consumer's backward
+        # (dy itself: no activation, or its derivative was already chained by the consumer's backward)
+        return act_bwd(y, dy, ctx.act if use_act else ACT_NONE, ctx.slope), None
 
     @staticmethod
     def _split_dy(ctx, plan, x, y, dy, head, use_act, planes):
