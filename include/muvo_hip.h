@@ -304,6 +304,31 @@ int muvo_avgpool_bwd(const float* dy, float* dx, int64_t G, int64_t S, void* str
 /* F.interpolate(scale_factor=2, mode='trilinear', align_corners=False) (common.py:169) */
 int muvo_upsample3d_x2_fwd(const float* x, float* y, int64_t NC, int D, int H, int W, void* stream);
 int muvo_upsample3d_x2_bwd(const float* dy, float* dx, int64_t NC, int D, int H, int W, void* stream);
+/* Routing queries: what the pooling / upsample / softmax entry points would launch (host code only: nothing is launched, no
+ * device is needed; the same MUVO_UPSAMPLE_WALK / MUVO_MAXPOOL_BWD_V8 values as the launch itself).  Pointers count only by
+ * their alignment.  A kernel that moves 16 bytes per access of a pointer is chosen only when that pointer is 16-byte aligned.
+ * muvo_upsample3d_route: in / out = x / y forward, dy / dx backward.  Forward kernels: SCALAR, VEC (float4 stores of y), VEC8 and
+ * ROW (float4 loads of x, 16-byte stores of y); backward: SCALAR, VEC, WALK, ROW (all three: 16-byte loads of dy, 8- or 16-byte
+ * stores of dx).  segs / dseg: the d segments of the walking backward kernels and their length (1 / D otherwise). */
+enum { MUVO_UPSAMPLE_SCALAR = 0, MUVO_UPSAMPLE_VEC = 1, MUVO_UPSAMPLE_VEC8 = 2, MUVO_UPSAMPLE_WALK = 3, MUVO_UPSAMPLE_ROW = 4 };
+typedef struct muvo_upsample3d_route_info {
+  int32_t kernel;
+  int32_t grid[3], block[3];
+  int32_t segs, dseg;
+} muvo_upsample3d_route_info;
+int muvo_upsample3d_route(int backward, int64_t NC, int D, int H, int W, const void* in, const void* out,
+                          muvo_upsample3d_route_info* r);
+/* muvo_maxpool2d_route: in / out = x / y forward, dy / dx backward.  k: the template instance (3: 3/2/1, 2: 2/2/0); load16: the
+ * forward kernel reads x as aligned 16-byte pairs; v8: the backward is the eight-column 3x3 kernel (16-byte loads of dy, 4-byte
+ * loads of idx, 16-byte stores of dx) instead of the generic one. */
+typedef struct muvo_maxpool2d_route_info {
+  int32_t k, load16, v8;
+  int32_t grid[3], block[3];
+} muvo_maxpool2d_route_info;
+int muvo_maxpool2d_route(int backward, int64_t NC, int H, int W, int k, int s, int p, const void* in, const void* idx,
+                         const void* out, muvo_maxpool2d_route_info* r);
+/* the MAXV template instance (columns held per lane: 8 or 17) of muvo_softmax_dropout_fwd / _bwd; -1 for an invalid length */
+int muvo_softmax_dropout_route(int cols);
 /* PreProcess (muvo/models/preprocess.py:102-225): u8 -> /255 -> crop -> (label, ImageNet-normalised) */
 int muvo_preprocess_image(const uint8_t* img, float* label, float* norm, int64_t NC, int C, int H, int W, int top, int left,
                           int CH, int CW, const float* mean3, const float* std3, void* stream);

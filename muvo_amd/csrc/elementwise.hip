@@ -117,7 +117,8 @@ __global__ void __launch_bounds__(256) tokens_to_nchw_kernel(const float* __rest
 // output.  Thread = (4 consecutive columns, 1 row); no integer division per element (3-D grid).
 template <int K, int S, int P>
 __global__ void __launch_bounds__(256) maxpool2d_fwd_t_kernel(const float* __restrict__ x, float* __restrict__ y,
-                                                              uint8_t* __restrict__ idx, int H, int W, int OH, int OW) {
+                                                              uint8_t* __restrict__ idx, int H, int W, int OH, int OW,
+                                                              int load16) {
   const int ow0 = (blockIdx.x * 64 + threadIdx.x) * 4, oh = blockIdx.y * 4 + threadIdx.y;
   if (ow0 >= OW || oh >= OH) return;
   const long nc = blockIdx.z;
@@ -134,8 +135,9 @@ __global__ void __launch_bounds__(256) maxpool2d_fwd_t_kernel(const float* __res
     constexpr int SPAN = 3 * S + K;                 // columns touched by 4 consecutive windows
     float v[SPAN];
     const int w0 = ow0 * S - P;
-    if (S == 2 && (W & 7) == 0 && OW * 2 == W && (((uintptr_t)x) & 15) == 0) {
-      // (uniform) the eight columns 2 * ow0 .. + 7 as two aligned 16-byte loads, plus the left neighbour for the 3-wide
+    if (S == 2 && load16) {
+      // (uniform; maxpool2d_route: W % 8 == 0, OW * 2 == W, x 16-byte aligned)
+      // the eight columns 2 * ow0 .. + 7 as two aligned 16-byte loads, plus the left neighbour for the 3-wide
       // window: unconditional (clamped address, masked value) instead of nine predicated 4-byte loads per row
       const float4 q0 = *reinterpret_cast<const float4*>(row + 2 * ow0), q1 = *reinterpret_cast<const float4*>(row + 2 * ow0 + 4);
       const float qs[8] = {q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, q1.z, q1.w};
@@ -892,14 +894,54 @@ int muvo_tokens_to_nchw(const float* tokens, float* x, int N, int C, int L, int 
   MUVO_CHECK_LAUNCH("tokens_to_nchw");
   return MUVO_OK;
 }
+// The host decisions of muvo_maxpool2d_fwd / _bwd for checked arguments (the pointers count only by their alignment): the
+// launchers launch from it, muvo_maxpool2d_route reports it.
+static void maxpool2d_route(bool backward, int64_t NC, int H, int W, int k, int s, int p, const void* in, const void* idx,
+                            const void* out, muvo_maxpool2d_route_info* r) {
+  const int OH = (H + 2 * p - k) / s + 1, OW = (W + 2 * p - k) / s + 1;
+  r->k = k;
+  r->load16 = r->v8 = 0;
+  r->block[0] = 64; r->block[1] = 4; r->block[2] = 1;
+  r->grid[2] = (int32_t)NC;
+  if (!backward) {
+    r->load16 = s == 2 && (W & 7) == 0 && OW * 2 == W && (((uintptr_t)in) & 15) == 0;
+    r->grid[0] = cdiv(OW, 256); r->grid[1] = cdiv(OH, 4);
+    return;
+  }
+  static const bool v8 = !getenv("MUVO_MAXPOOL_BWD_V8") || atoi(getenv("MUVO_MAXPOOL_BWD_V8")) != 0;   // A/B switch
+  if (k == 3 && v8 && W % 8 == 0 && OW % 4 == 0 && 2 * OW == W && 2 * OH == H && ((((uintptr_t)in) | ((uintptr_t)out)) & 15) == 0 &&
+      (((uintptr_t)idx) & 3) == 0) {
+    r->v8 = 1;
+    r->grid[0] = cdiv(W / 8, 64); r->grid[1] = cdiv(H / 2, 4);
+    return;
+  }
+  r->grid[0] = cdiv(W, 256); r->grid[1] = cdiv(H, 4);
+}
+static int maxpool2d_check(int64_t NC, int H, int W, int k, int s, int p) {
+  MUVO_CHECK_ARG(NC > 0 && NC <= 2147483647L && H > 0 && W > 0, "maxpool2d: bad sizes");
+  MUVO_CHECK_ARG((k == 3 && s == 2 && p == 1) || (k == 2 && s == 2 && p == 0), "maxpool2d: only 3x3 s2 p1 and 2x2 s2 p0 are on the path");
+  MUVO_CHECK_ARG(H + 2 * p >= k && W + 2 * p >= k, "maxpool2d: window larger than the padded image");
+  return MUVO_OK;
+}
+int muvo_maxpool2d_route(int backward, int64_t NC, int H, int W, int k, int s, int p, const void* in, const void* idx,
+                         const void* out, muvo_maxpool2d_route_info* r) {
+  MUVO_CHECK_ARG(r, "maxpool2d_route: null pointer");
+  int rc = maxpool2d_check(NC, H, W, k, s, p);
+  if (rc) return rc;
+  maxpool2d_route(backward != 0, NC, H, W, k, s, p, in, idx, out, r);
+  return MUVO_OK;
+}
 int muvo_maxpool2d_fwd(const float* x, float* y, uint8_t* idx, int64_t NC, int H, int W, int OH, int OW, int k, int s, int p,
                        void* stream) {
-  MUVO_CHECK_ARG(x && y && idx && NC > 0 && NC <= 2147483647L, "maxpool2d_fwd: bad args");
-  MUVO_CHECK_ARG((k == 3 && s == 2 && p == 1) || (k == 2 && s == 2 && p == 0), "maxpool2d: only 3x3 s2 p1 and 2x2 s2 p0 are on the path");
+  MUVO_CHECK_ARG(x && y && idx, "maxpool2d_fwd: bad args");
+  int rc = maxpool2d_check(NC, H, W, k, s, p);
+  if (rc) return rc;
   MUVO_CHECK_ARG(OH == (H + 2 * p - k) / s + 1 && OW == (W + 2 * p - k) / s + 1 && cdiv(OH, 4) <= 65535, "maxpool2d_fwd: output size");
-  dim3 grid(cdiv(OW, 256), cdiv(OH, 4), (unsigned)NC), block(64, 4);
-  if (k == 3) hipLaunchKernelGGL((maxpool2d_fwd_t_kernel<3, 2, 1>), grid, block, 0, ST, x, y, idx, H, W, OH, OW);
-  else hipLaunchKernelGGL((maxpool2d_fwd_t_kernel<2, 2, 0>), grid, block, 0, ST, x, y, idx, H, W, OH, OW);
+  muvo_maxpool2d_route_info r;
+  maxpool2d_route(false, NC, H, W, k, s, p, x, idx, y, &r);
+  const dim3 grid(r.grid[0], r.grid[1], r.grid[2]), block(r.block[0], r.block[1]);
+  if (r.k == 3) hipLaunchKernelGGL((maxpool2d_fwd_t_kernel<3, 2, 1>), grid, block, 0, ST, x, y, idx, H, W, OH, OW, r.load16);
+  else hipLaunchKernelGGL((maxpool2d_fwd_t_kernel<2, 2, 0>), grid, block, 0, ST, x, y, idx, H, W, OH, OW, r.load16);
   MUVO_CHECK_LAUNCH("maxpool2d_fwd");
   return MUVO_OK;
 }
@@ -956,15 +998,16 @@ __global__ void __launch_bounds__(256) maxpool3s2_bwd_v8_kernel(const float* __r
 
 int muvo_maxpool2d_bwd(const float* dy, const uint8_t* idx, float* dx, int64_t NC, int H, int W, int OH, int OW, int k,
                        int s, int p, void* stream) {
-  MUVO_CHECK_ARG(dy && dx && idx && NC > 0 && NC <= 2147483647L, "maxpool2d_bwd: bad args");
-  MUVO_CHECK_ARG((k == 3 && s == 2 && p == 1) || (k == 2 && s == 2 && p == 0), "maxpool2d: only 3x3 s2 p1 and 2x2 s2 p0 are on the path");
+  MUVO_CHECK_ARG(dy && dx && idx, "maxpool2d_bwd: bad args");
+  int rc = maxpool2d_check(NC, H, W, k, s, p);
+  if (rc) return rc;
+  MUVO_CHECK_ARG(OH == (H + 2 * p - k) / s + 1 && OW == (W + 2 * p - k) / s + 1, "maxpool2d_bwd: output size");
   MUVO_CHECK_ARG(cdiv(H, 4) <= 65535, "maxpool2d_bwd: image too tall");
-  dim3 grid(cdiv(W, 256), cdiv(H, 4), (unsigned)NC), block(64, 4);
-  static const bool v8 = !getenv("MUVO_MAXPOOL_BWD_V8") || atoi(getenv("MUVO_MAXPOOL_BWD_V8")) != 0;   // A/B switch
-  if (k == 3 && v8 && W % 8 == 0 && OW % 4 == 0 && 2 * OW == W && 2 * OH == H && ((((uintptr_t)dy) | ((uintptr_t)dx)) & 15) == 0 &&
-      (((uintptr_t)idx) & 3) == 0) {
-    hipLaunchKernelGGL(maxpool3s2_bwd_v8_kernel, dim3(cdiv(W / 8, 64), cdiv(H / 2, 4), (unsigned)NC), block, 0, ST, dy, idx, dx, H, W, OH, OW);
-  } else if (k == 3) hipLaunchKernelGGL((maxpool2d_bwd_t_kernel<3, 2, 1>), grid, block, 0, ST, dy, idx, dx, H, W, OH, OW);
+  muvo_maxpool2d_route_info r;
+  maxpool2d_route(true, NC, H, W, k, s, p, dy, idx, dx, &r);
+  const dim3 grid(r.grid[0], r.grid[1], r.grid[2]), block(r.block[0], r.block[1]);
+  if (r.v8) hipLaunchKernelGGL(maxpool3s2_bwd_v8_kernel, grid, block, 0, ST, dy, idx, dx, H, W, OH, OW);
+  else if (r.k == 3) hipLaunchKernelGGL((maxpool2d_bwd_t_kernel<3, 2, 1>), grid, block, 0, ST, dy, idx, dx, H, W, OH, OW);
   else hipLaunchKernelGGL((maxpool2d_bwd_t_kernel<2, 2, 0>), grid, block, 0, ST, dy, idx, dx, H, W, OH, OW);
   MUVO_CHECK_LAUNCH("maxpool2d_bwd");
   return MUVO_OK;
@@ -981,61 +1024,88 @@ int muvo_avgpool_bwd(const float* dy, float* dx, int64_t G, int64_t S, void* str
   MUVO_CHECK_LAUNCH("avgpool_bwd");
   return MUVO_OK;
 }
+// The host decision of muvo_upsample3d_x2_fwd / _bwd for checked sizes: kernel, grid, block and the d segments of the walking
+// kernels.  The pointers count only by their alignment: a kernel is chosen only if every pointer it accesses with 16-byte
+// instructions is 16-byte aligned (W % 4 == 0 resp. W % 2 == 0 keeps every row start as aligned as the base), anything else
+// goes to the next kernel down, ultimately the scalar ones.  The launchers launch from it, muvo_upsample3d_route reports it.
+static void upsample3d_route(bool backward, int64_t NC, int D, int H, int W, const void* in, const void* out,
+                             muvo_upsample3d_route_info* r) {
+  const bool in16 = (((uintptr_t)in) & 15) == 0, out16 = (((uintptr_t)out) & 15) == 0;
+  const int oq = W / 2;                     // fine float4 per row
+  const int q8 = W / 4;
+  const bool oq_ok = W % 4 == 0 && oq <= 64 && (oq & (oq - 1)) == 0;
+  r->segs = 1; r->dseg = D;
+  r->grid[1] = r->grid[2] = 1;
+  r->block[0] = 256; r->block[1] = r->block[2] = 1;
+  if (!backward) {
+    if (oq_ok && D + 1 <= 65535 && NC <= 65535 && in16 && out16) {          // float4 loads of x, 16-byte stores of y
+      r->kernel = MUVO_UPSAMPLE_ROW;
+      r->grid[0] = cdiv((long)(H + 1) * oq, 256); r->grid[1] = D + 1; r->grid[2] = (int32_t)NC;
+    } else if (W % 4 == 0 && q8 <= 64 && (q8 & (q8 - 1)) == 0 && 2 * D <= 65535 && NC <= 65535 && in16 && out16) {   // the same
+      r->kernel = MUVO_UPSAMPLE_VEC8;
+      r->grid[0] = cdiv((long)2 * H * q8, 256); r->grid[1] = 2 * D; r->grid[2] = (int32_t)NC;
+    } else if (W % 2 == 0 && 2 * D <= 65535 && NC <= 65535 && out16) {      // dword loads of x, float4 stores of y
+      r->kernel = MUVO_UPSAMPLE_VEC;
+      r->grid[0] = cdiv((long)2 * H * (2 * W / 4), 256); r->grid[1] = 2 * D; r->grid[2] = (int32_t)NC;
+    } else {
+      r->kernel = MUVO_UPSAMPLE_SCALAR;
+      r->grid[0] = ew_grid(NC * D * H * W * 8);
+    }
+    return;
+  }
+  static const int walk = getenv("MUVO_UPSAMPLE_WALK") ? atoi(getenv("MUVO_UPSAMPLE_WALK")) : 2;
+  if (walk == 2 && oq_ok && NC <= 65535 && in16 && out16) {
+    const int rgroups = cdiv(H, 256 / oq);
+    int segs = 1;
+    while ((long)NC * rgroups * segs < 4096 && segs * 16 <= D) segs *= 2;
+    r->kernel = MUVO_UPSAMPLE_ROW;
+    r->dseg = cdiv(D, segs);
+    r->segs = cdiv(D, r->dseg);
+    r->grid[0] = rgroups; r->grid[1] = r->segs; r->grid[2] = (int32_t)NC;
+  } else if (walk && W % 4 == 0 && (W / 4) * H <= 1024 && (W / 4) * H >= 128 && NC <= 65535 && in16 && out16) {
+    // enough workgroups to fill the chip: split the d range (each segment recomputes its two lead-in planes)
+    int segs = 1;
+    while ((long)NC * segs < 1024 && segs * 8 <= D) segs *= 2;
+    r->kernel = MUVO_UPSAMPLE_WALK;
+    r->dseg = cdiv(D, segs);
+    r->segs = cdiv(D, r->dseg);
+    r->grid[0] = r->segs; r->grid[1] = (int32_t)NC;
+    r->block[0] = W / 4; r->block[1] = H;
+  } else if (W % 4 == 0 && D <= 65535 && NC <= 65535 && in16 && out16) {    // float4 loads of dy, float4 stores of dx
+    r->kernel = MUVO_UPSAMPLE_VEC;
+    r->grid[0] = cdiv((long)H * (W / 4), 256); r->grid[1] = D; r->grid[2] = (int32_t)NC;
+  } else {
+    r->kernel = MUVO_UPSAMPLE_SCALAR;
+    r->grid[0] = ew_grid(NC * D * H * W);
+  }
+}
+int muvo_upsample3d_route(int backward, int64_t NC, int D, int H, int W, const void* in, const void* out,
+                          muvo_upsample3d_route_info* r) {
+  MUVO_CHECK_ARG(r && NC > 0 && D > 0 && H > 0 && W > 0, "upsample3d_route: bad args");
+  upsample3d_route(backward != 0, NC, D, H, W, in, out, r);
+  return MUVO_OK;
+}
 int muvo_upsample3d_x2_fwd(const float* x, float* y, int64_t NC, int D, int H, int W, void* stream) {
   MUVO_CHECK_ARG(x && y && NC > 0 && D > 0 && H > 0 && W > 0, "upsample3d_fwd: bad args");
-  const int q8 = W / 4;
-  const int oq = W / 2;                     // output float4 per row
-  if (W % 4 == 0 && oq <= 64 && (oq & (oq - 1)) == 0 && D + 1 <= 65535 && NC <= 65535) {
-    dim3 grid(cdiv((long)(H + 1) * oq, 256), D + 1, (unsigned)NC);
-    hipLaunchKernelGGL(upsample3d_x2_fwd_row_kernel, grid, dim3(256), 0, ST, x, y, D, H, W);
-    MUVO_CHECK_LAUNCH("upsample3d_fwd_row");
-    return MUVO_OK;
-  }
-  if (W % 4 == 0 && q8 <= 64 && (q8 & (q8 - 1)) == 0 && 2 * D <= 65535 && NC <= 65535) {
-    dim3 grid(cdiv((long)2 * H * q8, 256), 2 * D, (unsigned)NC);
-    hipLaunchKernelGGL(upsample3d_x2_fwd_vec8_kernel, grid, dim3(256), 0, ST, x, y, D, H, W);
-    MUVO_CHECK_LAUNCH("upsample3d_fwd_vec8");
-    return MUVO_OK;
-  }
-  if (W % 2 == 0 && 2 * D <= 65535 && NC <= 65535) {
-    dim3 grid(cdiv((long)2 * H * (2 * W / 4), 256), 2 * D, (unsigned)NC);
-    hipLaunchKernelGGL(upsample3d_x2_fwd_vec_kernel, grid, dim3(256), 0, ST, x, y, D, H, W);
-    MUVO_CHECK_LAUNCH("upsample3d_fwd_vec");
-    return MUVO_OK;
-  }
-  hipLaunchKernelGGL(upsample3d_x2_fwd_kernel, dim3(ew_grid(NC * D * H * W * 8)), dim3(256), 0, ST, x, y, (long)NC, D, H, W);
+  muvo_upsample3d_route_info r;
+  upsample3d_route(false, NC, D, H, W, x, y, &r);
+  const dim3 grid(r.grid[0], r.grid[1], r.grid[2]), block(r.block[0], r.block[1], r.block[2]);
+  if (r.kernel == MUVO_UPSAMPLE_ROW) hipLaunchKernelGGL(upsample3d_x2_fwd_row_kernel, grid, block, 0, ST, x, y, D, H, W);
+  else if (r.kernel == MUVO_UPSAMPLE_VEC8) hipLaunchKernelGGL(upsample3d_x2_fwd_vec8_kernel, grid, block, 0, ST, x, y, D, H, W);
+  else if (r.kernel == MUVO_UPSAMPLE_VEC) hipLaunchKernelGGL(upsample3d_x2_fwd_vec_kernel, grid, block, 0, ST, x, y, D, H, W);
+  else hipLaunchKernelGGL(upsample3d_x2_fwd_kernel, grid, block, 0, ST, x, y, (long)NC, D, H, W);
   MUVO_CHECK_LAUNCH("upsample3d_fwd");
   return MUVO_OK;
 }
 int muvo_upsample3d_x2_bwd(const float* dy, float* dx, int64_t NC, int D, int H, int W, void* stream) {
   MUVO_CHECK_ARG(dy && dx && NC > 0 && D > 0 && H > 0 && W > 0, "upsample3d_bwd: bad args");
-  static const int walk = getenv("MUVO_UPSAMPLE_WALK") ? atoi(getenv("MUVO_UPSAMPLE_WALK")) : 2;
-  const int oq = W / 2;
-  if (walk == 2 && W % 4 == 0 && oq <= 64 && (oq & (oq - 1)) == 0 && NC <= 65535 && (((uintptr_t)dy | (uintptr_t)dx) & 15) == 0) {
-    const int rgroups = cdiv(H, 256 / oq);
-    int segs = 1;
-    while ((long)NC * rgroups * segs < 4096 && segs * 16 <= D) segs *= 2;
-    const int dseg = cdiv(D, segs);
-    hipLaunchKernelGGL(upsample3d_x2_bwd_row_kernel, dim3(rgroups, cdiv(D, dseg), (unsigned)NC), dim3(256), 0, ST, dy, dx, D, H, W, dseg);
-    MUVO_CHECK_LAUNCH("upsample3d_bwd_row");
-    return MUVO_OK;
-  }
-  if (walk && W % 4 == 0 && (W / 4) * H <= 1024 && (W / 4) * H >= 128 && NC <= 65535 && (((uintptr_t)dy | (uintptr_t)dx) & 15) == 0) {
-    // enough workgroups to fill the chip: split the d range (each segment recomputes its two lead-in planes)
-    int segs = 1;
-    while ((long)NC * segs < 1024 && segs * 8 <= D) segs *= 2;
-    const int dseg = cdiv(D, segs);
-    hipLaunchKernelGGL(upsample3d_x2_bwd_walk_kernel, dim3(cdiv(D, dseg), (unsigned)NC), dim3(W / 4, H), 0, ST, dy, dx, D, H, W, dseg);
-    MUVO_CHECK_LAUNCH("upsample3d_bwd_walk");
-    return MUVO_OK;
-  }
-  if (W % 4 == 0 && D <= 65535 && NC <= 65535) {
-    dim3 grid(cdiv((long)H * (W / 4), 256), D, (unsigned)NC);
-    hipLaunchKernelGGL(upsample3d_x2_bwd_vec_kernel, grid, dim3(256), 0, ST, dy, dx, D, H, W);
-    MUVO_CHECK_LAUNCH("upsample3d_bwd_vec");
-    return MUVO_OK;
-  }
-  hipLaunchKernelGGL(upsample3d_x2_bwd_kernel, dim3(ew_grid(NC * D * H * W)), dim3(256), 0, ST, dy, dx, (long)NC, D, H, W);
+  muvo_upsample3d_route_info r;
+  upsample3d_route(true, NC, D, H, W, dy, dx, &r);
+  const dim3 grid(r.grid[0], r.grid[1], r.grid[2]), block(r.block[0], r.block[1], r.block[2]);
+  if (r.kernel == MUVO_UPSAMPLE_ROW) hipLaunchKernelGGL(upsample3d_x2_bwd_row_kernel, grid, block, 0, ST, dy, dx, D, H, W, r.dseg);
+  else if (r.kernel == MUVO_UPSAMPLE_WALK) hipLaunchKernelGGL(upsample3d_x2_bwd_walk_kernel, grid, block, 0, ST, dy, dx, D, H, W, r.dseg);
+  else if (r.kernel == MUVO_UPSAMPLE_VEC) hipLaunchKernelGGL(upsample3d_x2_bwd_vec_kernel, grid, block, 0, ST, dy, dx, D, H, W);
+  else hipLaunchKernelGGL(upsample3d_x2_bwd_kernel, grid, block, 0, ST, dy, dx, (long)NC, D, H, W);
   MUVO_CHECK_LAUNCH("upsample3d_bwd");
   return MUVO_OK;
 }
@@ -1083,10 +1153,16 @@ int muvo_resize_nearest_u8(const uint8_t* x, uint8_t* y, int64_t NC, int D, int 
   MUVO_CHECK_LAUNCH("resize_nearest_u8");
   return MUVO_OK;
 }
+// the MAXV instance of the softmax kernels for a checked row length (the launchers and muvo_softmax_dropout_route)
+static int softmax_dropout_maxv(int cols) { return cols <= 512 ? 8 : SOFTMAX_MAXV; }
+int muvo_softmax_dropout_route(int cols) {
+  MUVO_CHECK_ARG(cols > 0 && cols <= 64 * SOFTMAX_MAXV, "softmax_route: bad args (cols=%d, max %d)", cols, 64 * SOFTMAX_MAXV);
+  return softmax_dropout_maxv(cols);
+}
 int muvo_softmax_dropout_fwd(const float* S, float* P, float* Pd, int64_t rows, int cols, float p, uint64_t seed,
                              void* stream) {
   MUVO_CHECK_ARG(S && P && rows > 0 && cols > 0 && cols <= 64 * SOFTMAX_MAXV, "softmax_fwd: bad args (cols=%d, max %d)", cols, 64 * SOFTMAX_MAXV);
-  if (cols <= 512)
+  if (softmax_dropout_maxv(cols) == 8)
     hipLaunchKernelGGL((softmax_dropout_fwd_kernel<8>), dim3(cdiv(rows, 4)), dim3(256), 0, ST, S, P, Pd, (long)rows, cols, p, seed);
   else
     hipLaunchKernelGGL((softmax_dropout_fwd_kernel<SOFTMAX_MAXV>), dim3(cdiv(rows, 4)), dim3(256), 0, ST, S, P, Pd, (long)rows, cols, p, seed);
@@ -1096,7 +1172,7 @@ int muvo_softmax_dropout_fwd(const float* S, float* P, float* Pd, int64_t rows, 
 int muvo_softmax_dropout_bwd(const float* P, const float* dPd, float* dS, int64_t rows, int cols, float p, uint64_t seed,
                              void* stream) {
   MUVO_CHECK_ARG(P && dPd && dS && rows > 0 && cols > 0 && cols <= 64 * SOFTMAX_MAXV, "softmax_bwd: bad args");
-  if (cols <= 512)
+  if (softmax_dropout_maxv(cols) == 8)
     hipLaunchKernelGGL((softmax_dropout_bwd_kernel<8>), dim3(cdiv(rows, 4)), dim3(256), 0, ST, P, dPd, dS, (long)rows, cols, p, seed);
   else
     hipLaunchKernelGGL((softmax_dropout_bwd_kernel<SOFTMAX_MAXV>), dim3(cdiv(rows, 4)), dim3(256), 0, ST, P, dPd, dS, (long)rows, cols, p, seed);

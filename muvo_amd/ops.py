@@ -52,6 +52,14 @@ class GroupedLinearRouteInfo(C.Structure):
     _fields_ = [('fwd_rm', C.c_int32), ('fwd_grid', C.c_int32), ('dgrad_grid', C.c_int32 * 2), ('wgrad_grid', C.c_int32 * 2)]
 
 
+class Upsample3dRouteInfo(C.Structure):
+    _fields_ = [('kernel', C.c_int32), ('grid', C.c_int32 * 3), ('block', C.c_int32 * 3), ('segs', C.c_int32), ('dseg', C.c_int32)]
+
+
+class MaxPool2dRouteInfo(C.Structure):
+    _fields_ = [('k', C.c_int32), ('load16', C.c_int32), ('v8', C.c_int32), ('grid', C.c_int32 * 3), ('block', C.c_int32 * 3)]
+
+
 # every exported symbol of include/muvo_hip.h (tests/test_abi.py checks this list against the header)
 EXPORTS = [
     'muvo_last_error', 'muvo_abi_version', 'muvo_selftest_mfma', 'muvo_set_deterministic', 'muvo_get_deterministic', 'muvo_reset_accumulators',
@@ -66,6 +74,7 @@ EXPORTS = [
     'muvo_act_fwd', 'muvo_act_bwd', 'muvo_dropout', 'muvo_axpby', 'muvo_copy2d', 'muvo_colsum_acc', 'muvo_batchsum',
     'muvo_nchw_to_tokens', 'muvo_tokens_to_nchw', 'muvo_maxpool2d_fwd', 'muvo_maxpool2d_bwd', 'muvo_avgpool_fwd',
     'muvo_avgpool_bwd', 'muvo_upsample3d_x2_fwd', 'muvo_upsample3d_x2_bwd', 'muvo_preprocess_image',
+    'muvo_upsample3d_route', 'muvo_maxpool2d_route', 'muvo_softmax_dropout_route',
     'muvo_preprocess_route', 'muvo_divide_scalar', 'muvo_resize_bilinear', 'muvo_resize_nearest_f32',
     'muvo_resize_nearest_u8', 'muvo_softmax_dropout_fwd', 'muvo_softmax_dropout_bwd', 'muvo_gru_fwd', 'muvo_gru_bwd',
     'muvo_rssm_sample_fwd', 'muvo_rssm_sample_bwd',
@@ -2105,6 +2114,34 @@ class Upsample3dFn(torch.autograd.Function):
 
 def upsample3d_x2(x):
     return Upsample3dFn.apply(x)
+
+
+UPSAMPLE_KERNELS = ('scalar', 'vec', 'vec8', 'walk', 'row')
+
+
+def upsample3d_route(backward, nc, d, h, w, in_addr=0, out_addr=0):
+    """What upsample3d_x2 would launch forward (in / out = x / y) or backward (dy / dx), host code only, no device:
+    dict(kernel, grid, block, segs, dseg).  The byte addresses count only by their 16-byte alignment."""
+    r = Upsample3dRouteInfo()
+    _ck(lib().muvo_upsample3d_route(int(bool(backward)), _i64(nc), d, h, w, C.c_void_p(in_addr), C.c_void_p(out_addr), C.byref(r)))
+    return {'kernel': UPSAMPLE_KERNELS[r.kernel], 'grid': tuple(r.grid), 'block': tuple(r.block), 'segs': r.segs, 'dseg': r.dseg}
+
+
+def maxpool2d_route(backward, nc, h, w, k, s, p, in_addr=0, idx_addr=0, out_addr=0):
+    """What max_pool2d would launch forward (in / out = x / y) or backward (dy / dx), host code only, no device:
+    dict(k, load16, v8, grid, block)."""
+    r = MaxPool2dRouteInfo()
+    _ck(lib().muvo_maxpool2d_route(int(bool(backward)), _i64(nc), h, w, k, s, p, C.c_void_p(in_addr), C.c_void_p(idx_addr),
+                                   C.c_void_p(out_addr), C.byref(r)))
+    return {'k': r.k, 'load16': bool(r.load16), 'v8': bool(r.v8), 'grid': tuple(r.grid), 'block': tuple(r.block)}
+
+
+def softmax_dropout_route(cols):
+    """The MAXV template instance (8 or 17) of the softmax(+dropout) kernels for rows of `cols` columns (host code only)."""
+    r = lib().muvo_softmax_dropout_route(int(cols))
+    if r < 0:
+        _ck(r)
+    return {'maxv': r}
 
 
 # ================================================================================================ attention
