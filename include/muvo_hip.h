@@ -305,12 +305,12 @@ int muvo_avgpool_bwd(const float* dy, float* dx, int64_t G, int64_t S, void* str
 int muvo_upsample3d_x2_fwd(const float* x, float* y, int64_t NC, int D, int H, int W, void* stream);
 int muvo_upsample3d_x2_bwd(const float* dy, float* dx, int64_t NC, int D, int H, int W, void* stream);
 /* Routing queries: what the pooling / upsample / softmax entry points would launch (host code only: nothing is launched, no
- * device is needed; the same MUVO_UPSAMPLE_WALK / MUVO_MAXPOOL_BWD_V8 values as the launch itself).  Pointers count only by
- * their alignment.  A kernel that moves 16 bytes per access of a pointer is chosen only when that pointer is 16-byte aligned.
- * muvo_upsample3d_route: in / out = x / y forward, dy / dx backward.  Forward kernels: SCALAR, VEC (float4 stores of y), VEC8 and
- * ROW (float4 loads of x, 16-byte stores of y); backward: SCALAR, VEC, WALK, ROW (all three: 16-byte loads of dy, 8- or 16-byte
- * stores of dx).  segs / dseg: the d segments of the walking backward kernels and their length (1 / D otherwise). */
-enum { MUVO_UPSAMPLE_SCALAR = 0, MUVO_UPSAMPLE_VEC = 1, MUVO_UPSAMPLE_VEC8 = 2, MUVO_UPSAMPLE_WALK = 3, MUVO_UPSAMPLE_ROW = 4 };
+ * device is needed; the launchers launch from the same decision).  Pointers count only by their alignment.  A kernel that moves
+ * 16 bytes per access of a pointer is chosen only when that pointer is 16-byte aligned.
+ * muvo_upsample3d_route: in / out = x / y forward, dy / dx backward.  Three kernels per direction.  Forward: SCALAR, VEC (float4
+ * stores of y) and ROW (float4 loads of x, 16-byte stores of y); backward: SCALAR, VEC and ROW (both: 16-byte loads of dy, 16- resp.
+ * 8-byte stores of dx).  segs / dseg: the d segments of the backward ROW kernel and their length (1 / D otherwise). */
+enum { MUVO_UPSAMPLE_SCALAR = 0, MUVO_UPSAMPLE_VEC = 1, MUVO_UPSAMPLE_ROW = 2 };
 typedef struct muvo_upsample3d_route_info {
   int32_t kernel;
   int32_t grid[3], block[3];

@@ -7,7 +7,7 @@
 // Every random decision is an explicit input: the host draws them in the reference's RNG call order
 // (muvo_amd/augment.py) and hands over one small parameter table.  HBM-bound elementwise / small-stencil work: one
 // coalesced pass per stage, frames without augmentation are skipped entirely.
-#include "common.h"
+#include "resample.h"
 
 #define ST ((hipStream_t)stream)
 #define GRID_STRIDE(i, n) for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < (n); i += (long)gridDim.x * blockDim.x)
@@ -163,16 +163,12 @@ __global__ void clear_doubles_kernel(double* p, int n) {
 // parameter row of one SAMPLE (MUVO_ROUTEAUG_STRIDE floats): [0] mode 0 none / 1 drop / 2 end of route / 3 affine,
 // [1] number of leading rows zeroed (mode 2), [2..7] inverse affine matrix (output pixel -> input pixel, centred coordinates)
 __global__ void route_aug_kernel(const uint8_t* __restrict__ img, float* __restrict__ out, const float* __restrict__ params,
-                                 int B, int S, int H, int W, int OH, int OW, float m0, float m1, float m2, float s0, float s1,
-                                 float s2) {
+                                 int B, int S, int H, int W, int OH, int OW, Norm3 ms) {
   const long n = (long)B * S * 3 * OH * OW;
   const float sh = (float)H / (float)OH, sw = (float)W / (float)OW;
   GRID_STRIDE(i, n) {
-    const int x = (int)(i % OW);
-    long r = i / OW;
-    const int y = (int)(r % OH);
-    const long nc = r / OH;
-    const int c = (int)(nc % 3);
+    int y, x;
+    const long nc = split_index(i, OH, OW, y, x);
     const int b = (int)(nc / (3L * S));
     const float* P = params ? params + (long)b * MUVO_ROUTEAUG_STRIDE : nullptr;
     const int mode = P ? (int)P[0] : 0;
@@ -195,13 +191,8 @@ __global__ void route_aug_kernel(const uint8_t* __restrict__ img, float* __restr
       zero = qx < 0 || qx >= OW || qy < 0 || qy >= OH;
     }
     float v = 0.f;
-    if (!zero) {
-      int sy = (int)floorf((float)qy * sh); if (sy > H - 1) sy = H - 1;
-      int sx = (int)floorf((float)qx * sw); if (sx > W - 1) sx = W - 1;
-      v = (float)img[(nc * H + sy) * W + sx] / 255.f;
-    }
-    const float m = c == 0 ? m0 : (c == 1 ? m1 : m2), s = c == 0 ? s0 : (c == 1 ? s1 : s2);
-    out[i] = (v - m) / s;
+    if (!zero) v = (float)img[(nc * H + nearest_src(qy, H, sh)) * W + nearest_src(qx, W, sw)] / 255.f;
+    out[i] = normalise3(ms, (int)(nc % 3), v);
   }
 }
 
@@ -223,7 +214,7 @@ int muvo_preprocess_route_aug(const uint8_t* img, float* out, const float* param
                               const float* mean3, const float* std3, void* stream) {
   MUVO_CHECK_ARG(img && out && mean3 && std3 && C == 3 && B > 0 && S > 0, "preprocess_route_aug: bad args");
   hipLaunchKernelGGL(route_aug_kernel, dim3(ew_grid((long)B * S * 3 * OH * OW)), dim3(256), 0, ST, img, out, params, B, S, H, W,
-                     OH, OW, mean3[0], mean3[1], mean3[2], std3[0], std3[1], std3[2]);
+                     OH, OW, norm3_of(mean3, std3));
   MUVO_CHECK_LAUNCH("preprocess_route_aug");
   return MUVO_OK;
 }

@@ -4,7 +4,7 @@
 // Here: one pass computes the cell of every frustum point (geometry only), the forward kernel forms depth * feature on the
 // fly and adds it into a channels-last BEV accumulator with coalesced float atomics (lanes = channels), and the backward
 // kernel is a deterministic gather over the same point list.  HBM-bound; the accumulator (B x cells x C) stays in L2.
-#include "common.h"
+#include "resample.h"
 
 #define BEV_TP 64      // pixels per workgroup tile
 #define BEV_MAXD 48    // depth bins (reference: 37)
@@ -191,8 +191,8 @@ resize_bilinear_bwd_kernel(const float* __restrict__ dy, float* __restrict__ dx,
   const float sh = (float)H / (float)OH, sw = (float)W / (float)OW;
   const float ish = (float)OH / (float)H, isw = (float)OW / (float)W;
   for (long i = blockIdx.x * 256L + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
-    const int ix = (int)(i % W), iy = (int)((i / W) % H);
-    const long nc = i / ((long)W * H);
+    int iy, ix;
+    const long nc = split_index(i, H, W, iy, ix);
     // outputs whose source coordinate lies in [iy - 1, iy + 1) (and the clamped borders): a conservative index window
     int oy0 = (int)floorf(((float)iy - 0.5f) * ish - 0.5f) - 1, oy1 = (int)ceilf(((float)iy + 1.5f) * ish - 0.5f) + 1;
     int ox0 = (int)floorf(((float)ix - 0.5f) * isw - 0.5f) - 1, ox1 = (int)ceilf(((float)ix + 1.5f) * isw - 0.5f) + 1;
@@ -203,19 +203,10 @@ resize_bilinear_bwd_kernel(const float* __restrict__ dy, float* __restrict__ dx,
     const float* g = dy + nc * OH * OW;
     float acc = 0.f;
     for (int oy = oy0; oy <= oy1; ++oy) {
-      float fy = sh * ((float)oy + 0.5f) - 0.5f; if (fy < 0.f) fy = 0.f;
-      const int y0 = (int)fy, y1 = y0 + (y0 < H - 1 ? 1 : 0);
-      const float ly = fy - (float)y0;
-      const float wy = (y0 == iy ? 1.f - ly : 0.f) + (y1 == iy ? ly : 0.f);
+      const float wy = lin_w(oy, iy, H, sh);
       if (wy == 0.f) continue;
       float row = 0.f;
-      for (int ox = ox0; ox <= ox1; ++ox) {
-        float fx = sw * ((float)ox + 0.5f) - 0.5f; if (fx < 0.f) fx = 0.f;
-        const int x0 = (int)fx, x1 = x0 + (x0 < W - 1 ? 1 : 0);
-        const float lx = fx - (float)x0;
-        const float wx = (x0 == ix ? 1.f - lx : 0.f) + (x1 == ix ? lx : 0.f);
-        row += wx * g[(long)oy * OW + ox];
-      }
+      for (int ox = ox0; ox <= ox1; ++ox) row += lin_w(ox, ix, W, sw) * g[(long)oy * OW + ox];
       acc += wy * row;
     }
     dx[i] = acc;

@@ -87,13 +87,14 @@ __device__ __forceinline__ void det_turn_done(unsigned* ticket) {
 }
 
 // ---- activations -----------------------------------------------------------------------------
+__device__ __forceinline__ float sigmoidf_(float x) { return 1.f / (1.f + expf(-x)); }
 __device__ __forceinline__ float act_apply(float v, int act, float slope) {
   switch (act) {
     case MUVO_ACT_RELU: return v > 0.f ? v : 0.f;
     case MUVO_ACT_LEAKY: return v > 0.f ? v : v * slope;
     case MUVO_ACT_ELU: return v > 0.f ? v : expm1f(v);
     case MUVO_ACT_TANH: return tanhf(v);
-    case MUVO_ACT_SIGMOID: return 1.f / (1.f + expf(-v));
+    case MUVO_ACT_SIGMOID: return sigmoidf_(v);
     default: return v;
   }
 }
@@ -107,7 +108,7 @@ __device__ __forceinline__ float act_apply_c(float v, float slope) {
   else if constexpr (ACT == MUVO_ACT_LEAKY) return v > 0.f ? v : v * slope;
   else if constexpr (ACT == MUVO_ACT_ELU) return v > 0.f ? v : expm1f(v);
   else if constexpr (ACT == MUVO_ACT_TANH) return tanhf(v);
-  else if constexpr (ACT == MUVO_ACT_SIGMOID) return 1.f / (1.f + expf(-v));
+  else if constexpr (ACT == MUVO_ACT_SIGMOID) return sigmoidf_(v);
   else return v;
 }
 template <int ACT> struct ActTag { static constexpr int value = ACT; };

@@ -3,7 +3,7 @@
 // max/avg pooling (timm ResNet stem, common.py:127, mile.py:107), trilinear x2 upsampling
 // (common.py:169), PreProcess (preprocess.py:102-225), attention softmax(+dropout), GRU / RSSM pointwise
 // math (transition.py:18-24,160-181).  All coalesced, grid-stride.
-#include "common.h"
+#include "resample.h"
 
 #define GRID_STRIDE(i, n) for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < (n); i += (long)gridDim.x * blockDim.x)
 
@@ -217,6 +217,56 @@ __global__ void __launch_bounds__(256) maxpool2d_bwd_t_kernel(const float* __res
     for (int e = 0; e < 4; ++e) if (w0 + e < W) o[e] = g[e];
   }
 }
+// 3x3 stride-2 pad-1 form for W % 8 == 0, OW % 4 == 0, H = 2 OH (the ResNet stems): a lane owns EIGHT consecutive input columns
+// of the ROW PAIR (2r, 2r+1).  They are touched by the five windows 4l .. 4l+4 of the window rows r (rows 2r-1 .. 2r+1) and r+1
+// (row 2r+1 only): per window row one 16-byte gradient load, one 4-byte winner load and one scalar pair for the fifth window -
+// instead of 2 x 3 scalar pairs per four columns of one row - and four 16-byte stores.  Standalone on 20 x 64 x 160 x 416:
+// 96 us against 134 us with one row per lane (tools/dev/maxpool_bwd_probe.hip; stores alone 54 us); it is the last memory-bound
+// pass on the main stream before the stem's weight gradient.
+__global__ void __launch_bounds__(256) maxpool3s2_bwd_v8_kernel(const float* __restrict__ dy, const uint8_t* __restrict__ idx,
+                                                                 float* __restrict__ dx, int H, int W, int OH, int OW) {
+  const int l = blockIdx.x * 64 + threadIdx.x, w0 = 8 * l, r = blockIdx.y * 4 + threadIdx.y;
+  if (w0 >= W || 2 * r >= H) return;
+  const long nc = blockIdx.z;
+  float g0[8], g1[8];
+#pragma unroll
+  for (int e = 0; e < 8; ++e) g0[e] = g1[e] = 0.f;
+  const int j4 = min(4 * l + 4, OW - 1);                              // fifth window (clamped; masked below)
+  const bool live4 = 4 * l + 4 <= OW - 1;
+#pragma unroll
+  for (int i = 0; i < 2; ++i) {
+    const int oh = min(r + i, OH - 1);
+    const bool live = r + i <= OH - 1;
+    const long ro = (nc * OH + oh) * (long)OW;
+    const float4 d4 = *(const float4*)(dy + ro + 4 * l);
+    const uchar4 i4 = *(const uchar4*)(idx + ro + 4 * l);
+    const float dd[5] = {d4.x, d4.y, d4.z, d4.w, dy[ro + j4]};
+    const int ww[5] = {i4.x, i4.y, i4.z, i4.w, idx[ro + j4]};
+#pragma unroll
+    for (int j = 0; j < 5; ++j) {
+      const bool lv = live && (j < 4 || live4);
+      const int a0 = ww[j] / 3, b0 = ww[j] - 3 * a0;                   // winner (row, column) inside the window
+#pragma unroll
+      for (int b = 0; b < 3; ++b) {
+        const int e = 2 * j - 1 + b;                                   // window 4l+j covers columns 2j-1 .. 2j+1 of this lane
+        if (e >= 0 && e < 8 && lv && b0 == b) {
+          // window row r: input rows 2r-1 (a = 0, another lane's pair), 2r (a = 1), 2r+1 (a = 2); window row r+1: row 2r+1 is a = 0
+          if (i == 0) {
+            if (a0 == 1) g0[e] += dd[j];
+            if (a0 == 2) g1[e] += dd[j];
+          } else if (a0 == 0) {
+            g1[e] += dd[j];
+          }
+        }
+      }
+    }
+  }
+  float* o = dx + (nc * H + 2 * r) * (long)W + w0;
+  *(float4*)o = make_float4(g0[0], g0[1], g0[2], g0[3]);
+  *(float4*)(o + 4) = make_float4(g0[4], g0[5], g0[6], g0[7]);
+  *(float4*)(o + W) = make_float4(g1[0], g1[1], g1[2], g1[3]);
+  *(float4*)(o + W + 4) = make_float4(g1[4], g1[5], g1[6], g1[7]);
+}
 // y[g] = mean_s x[g*S + s]; one wave per group
 __global__ void __launch_bounds__(256) avgpool_fwd_kernel(const float* __restrict__ x, float* __restrict__ y, long G, long S) {
   const long g = blockIdx.x * 4L + (threadIdx.x >> 6);
@@ -234,68 +284,65 @@ __global__ void avgpool_bwd_kernel(const float* __restrict__ dy, float* __restri
 }
 
 // ------------------------------------------------------------------------- trilinear x2 upsample
-__device__ __forceinline__ void lin_src(int d, int n_in, int& i0, int& i1, float& w1) {
-  float src = 0.5f * ((float)d + 0.5f) - 0.5f;
-  if (src < 0.f) src = 0.f;
-  i0 = (int)src;
-  i1 = i0 + (i0 < n_in - 1 ? 1 : 0);
-  w1 = src - (float)i0;
+// The per-element steps of this section.  The x2 source coordinate is lin_src / lin_w of resample.h with the scale 0.5f.
+// The eight corners [d][h][w] of an output combined in the nested form a (b (c v + fw v) + fh (..)) + fd (..)
+__device__ __forceinline__ float trilerp(float fd, float fh, float fw, float v000, float v001, float v010, float v011, float v100,
+                                         float v101, float v110, float v111) {
+  const float a = 1.f - fd, b = 1.f - fh, c = 1.f - fw;
+  return a * (b * (c * v000 + fw * v001) + fh * (c * v010 + fw * v011)) +
+         fd * (b * (c * v100 + fw * v101) + fh * (c * v110 + fw * v111));
 }
+// weights with which input index i (of n) receives output indices 2i-1 .. 2i+2 (out-of-range outputs get 0)
+__device__ __forceinline__ void up2_bwd_weights(int i, int n, float (&w)[4]) {
+  w[0] = i > 0 ? 0.25f : 0.f;
+  w[1] = i > 0 ? 0.75f : 1.f;
+  w[2] = i < n - 1 ? 0.75f : 1.f;
+  w[3] = i < n - 1 ? 0.25f : 0.f;
+}
+// the column adjoint of the vectorised backward kernels: coarse column w (of W) receives the fine columns 2w-1 .. 2w+2 = g0 .. g3,
+// a fine column that does not exist passed as 0; the two inner weights are 1 where the forward clamps
+__device__ __forceinline__ float up2_col_adjoint(int w, int W, float g0, float g1, float g2, float g3) {
+  const float w1 = w > 0 ? 0.75f : 1.f, w2 = w < W - 1 ? 0.75f : 1.f;
+  return (0.25f * g0 + w1 * g1) + (w2 * g2 + 0.25f * g3);
+}
+
 __global__ void upsample3d_x2_fwd_kernel(const float* __restrict__ x, float* __restrict__ y, long NC, int D, int H, int W) {
   const int OD = 2 * D, OH = 2 * H, OW = 2 * W;
   const long n = NC * OD * OH * OW;
   GRID_STRIDE(i, n) {
-    const int ow = (int)(i % OW);
-    long r = i / OW;
-    const int oh = (int)(r % OH);
-    r /= OH;
-    const int od = (int)(r % OD);
-    const long nc = r / OD;
+    int od, oh, ow;
+    const long nc = split_index(i, OD, OH, OW, od, oh, ow);
     int d0, d1, h0, h1, w0, w1;
     float fd, fh, fw;
-    lin_src(od, D, d0, d1, fd);
-    lin_src(oh, H, h0, h1, fh);
-    lin_src(ow, W, w0, w1, fw);
+    lin_src(od, D, 0.5f, d0, d1, fd);
+    lin_src(oh, H, 0.5f, h0, h1, fh);
+    lin_src(ow, W, 0.5f, w0, w1, fw);
     const float* xp = x + nc * D * H * W;
-    const float v000 = xp[(d0 * H + h0) * W + w0], v001 = xp[(d0 * H + h0) * W + w1];
-    const float v010 = xp[(d0 * H + h1) * W + w0], v011 = xp[(d0 * H + h1) * W + w1];
-    const float v100 = xp[(d1 * H + h0) * W + w0], v101 = xp[(d1 * H + h0) * W + w1];
-    const float v110 = xp[(d1 * H + h1) * W + w0], v111 = xp[(d1 * H + h1) * W + w1];
-    const float a = (1.f - fd), b = (1.f - fh), c = (1.f - fw);
-    y[i] = a * (b * (c * v000 + fw * v001) + fh * (c * v010 + fw * v011)) +
-           fd * (b * (c * v100 + fw * v101) + fh * (c * v110 + fw * v111));
+    y[i] = trilerp(fd, fh, fw, xp[(d0 * H + h0) * W + w0], xp[(d0 * H + h0) * W + w1], xp[(d0 * H + h1) * W + w0],
+                   xp[(d0 * H + h1) * W + w1], xp[(d1 * H + h0) * W + w0], xp[(d1 * H + h0) * W + w1],
+                   xp[(d1 * H + h1) * W + w0], xp[(d1 * H + h1) * W + w1]);
   }
-}
-// per-axis weight with which output index d reads input index i
-__device__ __forceinline__ float lin_w(int d, int i, int n_in) {
-  int i0, i1; float w1;
-  lin_src(d, n_in, i0, i1, w1);
-  return (i0 == i ? 1.f - w1 : 0.f) + (i1 == i ? w1 : 0.f);
 }
 __global__ void upsample3d_x2_bwd_kernel(const float* __restrict__ dy, float* __restrict__ dx, long NC, int D, int H, int W) {
   const int OD = 2 * D, OH = 2 * H, OW = 2 * W;
   const long n = NC * D * H * W;
   GRID_STRIDE(i, n) {
-    const int w = (int)(i % W);
-    long r = i / W;
-    const int h = (int)(r % H);
-    r /= H;
-    const int d = (int)(r % D);
-    const long nc = r / D;
+    int d, h, w;
+    const long nc = split_index(i, D, H, W, d, h, w);
     const float* gp = dy + nc * OD * OH * OW;
     float acc = 0.f;
     for (int a = 2 * d - 1; a <= 2 * d + 2; ++a) {
       if ((unsigned)a >= (unsigned)OD) continue;
-      const float wa = lin_w(a, d, D);
+      const float wa = lin_w(a, d, D, 0.5f);
       if (wa == 0.f) continue;
       for (int b = 2 * h - 1; b <= 2 * h + 2; ++b) {
         if ((unsigned)b >= (unsigned)OH) continue;
-        const float wb = lin_w(b, h, H);
+        const float wb = lin_w(b, h, H, 0.5f);
         if (wb == 0.f) continue;
         float row = 0.f;
         for (int c = 2 * w - 1; c <= 2 * w + 2; ++c) {
           if ((unsigned)c >= (unsigned)OW) continue;
-          row += lin_w(c, w, W) * gp[((long)a * OH + b) * OW + c];
+          row += lin_w(c, w, W, 0.5f) * gp[((long)a * OH + b) * OW + c];
         }
         acc += wa * wb * row;
       }
@@ -316,8 +363,8 @@ __global__ void __launch_bounds__(256) upsample3d_x2_fwd_vec_kernel(const float*
   const long nc = blockIdx.z;
   int d0, d1, h0, h1;
   float fd, fh;
-  lin_src(od, D, d0, d1, fd);
-  lin_src(oh, H, h0, h1, fh);
+  lin_src(od, D, 0.5f, d0, d1, fd);
+  lin_src(oh, H, 0.5f, h0, h1, fh);
   const float* xp = x + nc * D * H * W;
   // input columns 2j-1 .. 2j+2 (clamped): the four outputs 4j+e read slots (0,1) (1,2) (1,2) (2,3)
   int wi[4];
@@ -333,69 +380,23 @@ __global__ void __launch_bounds__(256) upsample3d_x2_fwd_vec_kernel(const float*
 #pragma unroll
     for (int s4 = 0; s4 < 4; ++s4) r[q][s4] = rows[q][wi[s4]];
   float o[4];
-  const float a = 1.f - fd, b = 1.f - fh;
 #pragma unroll
   for (int e = 0; e < 4; ++e) {
     int i0, i1;
     float fw;
-    lin_src(4 * j + e, W, i0, i1, fw);   // only the weight is used; the slots hold x[i0], x[i1]
+    lin_src(4 * j + e, W, 0.5f, i0, i1, fw);   // only the weight is used; the slots hold x[i0], x[i1]
     const int s0 = (e + 1) >> 1, s1 = s0 + 1;
-    const float c = 1.f - fw;
-    o[e] = a * (b * (c * r[0][s0] + fw * r[0][s1]) + fh * (c * r[1][s0] + fw * r[1][s1])) +
-           fd * (b * (c * r[2][s0] + fw * r[2][s1]) + fh * (c * r[3][s0] + fw * r[3][s1]));
+    o[e] = trilerp(fd, fh, fw, r[0][s0], r[0][s1], r[1][s0], r[1][s1], r[2][s0], r[2][s1], r[3][s0], r[3][s1]);
   }
   float4* yp = (float4*)(y + ((nc * (2 * D) + od) * OH + oh) * (long)OW) + j;
   *yp = make_float4(o[0], o[1], o[2], o[3]);
 }
 
-// Eight outputs per lane (W % 4 == 0 and W / 4 a power of two <= 64, so a row of lanes never straddles a wave): each of the
-// four corner rows is ONE aligned float4 load per lane, the two neighbour columns come from the adjacent lanes (or the
-// lane's own edge value where the reference clamps).  The four-outputs variant above issued 16 strided dword loads per
-// float4 store and ran at 1.9 TB/s of the ~4 TB/s a pure streaming write reaches.
-__global__ void __launch_bounds__(256) upsample3d_x2_fwd_vec8_kernel(const float* __restrict__ x, float* __restrict__ y, int D,
-                                                                     int H, int W) {
-  const int OH = 2 * H, OW = 2 * W, Q = W / 4;
-  const int idx = blockIdx.x * 256 + threadIdx.x;
-  const bool live = idx < OH * Q;
-  const int oh = live ? idx / Q : 0, j = live ? idx - oh * Q : 0;
-  const int od = blockIdx.y;
-  const long nc = blockIdx.z;
-  int d0, d1, h0, h1;
-  float fd, fh;
-  lin_src(od, D, d0, d1, fd);
-  lin_src(oh, H, h0, h1, fh);
-  const float* xp = x + nc * D * H * W + 4 * j;
-  const float4 r00 = *(const float4*)(xp + (d0 * H + h0) * W), r01 = *(const float4*)(xp + (d0 * H + h1) * W);
-  const float4 r10 = *(const float4*)(xp + (d1 * H + h0) * W), r11 = *(const float4*)(xp + (d1 * H + h1) * W);
-  // the (d, h) interpolation is the same for all columns: blend the four rows first
-  const float a = 1.f - fd, b = 1.f - fh;
-  const float w00 = a * b, w01 = a * fh, w10 = fd * b, w11 = fd * fh;
-  float c[6];      // blended input columns 4j-1 .. 4j+4
-  c[1] = w00 * r00.x + w01 * r01.x + w10 * r10.x + w11 * r11.x;
-  c[2] = w00 * r00.y + w01 * r01.y + w10 * r10.y + w11 * r11.y;
-  c[3] = w00 * r00.z + w01 * r01.z + w10 * r10.z + w11 * r11.z;
-  c[4] = w00 * r00.w + w01 * r01.w + w10 * r10.w + w11 * r11.w;
-  const float lft = __shfl_up(c[4], 1), rgt = __shfl_down(c[1], 1);
-  c[0] = j > 0 ? lft : c[1];               // clamped at the borders (src < 0 -> column 0; i1 = i0 at the last column)
-  c[5] = j < Q - 1 ? rgt : c[4];
-  if (!live) return;
-  float o[8];
-#pragma unroll
-  for (int e = 0; e < 4; ++e) {             // input column i = 4j + e -> outputs 2i (0.25 left + 0.75 own), 2i+1 (0.75 own + 0.25 right)
-    o[2 * e] = 0.25f * c[e] + 0.75f * c[e + 1];
-    o[2 * e + 1] = 0.75f * c[e + 1] + 0.25f * c[e + 2];
-  }
-  float4* yp = (float4*)(y + ((nc * (2 * D) + od) * OH + oh) * (long)OW) + 2 * j;
-  typedef float nt_f4 __attribute__((ext_vector_type(4)));
-  __builtin_nontemporal_store((nt_f4){o[0], o[1], o[2], o[3]}, (nt_f4*)yp);
-  __builtin_nontemporal_store((nt_f4){o[4], o[5], o[6], o[7]}, (nt_f4*)yp + 1);
-}
-
 // A 2 x 2 block of output (depth, row) positions per lane, ONE output float4 per position: lane = (row block ph, output float4
 // f).  Outputs od = 2 pd - 1 and 2 pd read the SAME two input planes (pd - 1, pd, clamped) with weights (0.75, 0.25) and
 // (0.25, 0.75), and likewise for rows: four float4 loads feed four float4 stores, and every store instruction of a wave
-// writes whole 256-byte output rows.  In the eight-outputs kernel above a lane's two float4 leave in two instructions that
-// each cover every other 16 bytes of a row: 3.0 TB/s; this kernel: 5.4 TB/s on the 3-GB top level (a plain fill: 6.9).
+// writes whole 256-byte output rows: 5.4 TB/s on the 3-GB top level (a plain fill: 6.9; the four-outputs kernel above, with its
+// 16 strided dword loads per float4 store: 1.9).
 // Output columns 4 f .. 4 f + 3 come from input columns 2 f - 1 .. 2 f + 2: the lane pair (f, f ^ 1) loads the same aligned
 // input float4 f >> 1 and takes the one missing column from its neighbour lane.  Blocks pd = 0 .. D, ph = 0 .. H; the
 // positions that fall outside the output are skipped.
@@ -440,13 +441,6 @@ __global__ void __launch_bounds__(256) upsample3d_x2_fwd_row_kernel(const float*
   }
 }
 
-// weights with which input index i (of n) receives output indices 2i-1 .. 2i+2 (out-of-range outputs get 0)
-__device__ __forceinline__ void up2_bwd_weights(int i, int n, float (&w)[4]) {
-  w[0] = i > 0 ? 0.25f : 0.f;
-  w[1] = i > 0 ? 0.75f : 1.f;
-  w[2] = i < n - 1 ? 0.75f : 1.f;
-  w[3] = i < n - 1 ? 0.25f : 0.f;
-}
 __global__ void __launch_bounds__(256) upsample3d_x2_bwd_vec_kernel(const float* __restrict__ dy, float* __restrict__ dx, int D,
                                                                     int H, int W) {
   const int OH = 2 * H, OW = 2 * W, Q = W / 4;
@@ -475,76 +469,19 @@ __global__ void __launch_bounds__(256) upsample3d_x2_bwd_vec_kernel(const float*
       const float g[10] = {gl, m0.x, m0.y, m0.z, m0.w, m1.x, m1.y, m1.z, m1.w, gr};
       const float wab = wa[ia] * wb[ib];
 #pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        // input column w = 4j+e receives outputs 2w-1 .. 2w+2 = g[2e .. 2e+3]
-        const int w = 4 * j + e;
-        const float w1 = w > 0 ? 0.75f : 1.f, w2 = w < W - 1 ? 0.75f : 1.f;
-        acc[e] += wab * ((0.25f * g[2 * e] + w1 * g[2 * e + 1]) + (w2 * g[2 * e + 2] + 0.25f * g[2 * e + 3]));
-      }
+      for (int e = 0; e < 4; ++e)       // input column w = 4j+e receives outputs 2w-1 .. 2w+2 = g[2e .. 2e+3]
+        acc[e] += wab * up2_col_adjoint(4 * j + e, W, g[2 * e], g[2 * e + 1], g[2 * e + 2], g[2 * e + 3]);
     }
   }
   float4* xp = (float4*)(dx + ((nc * D + d) * H + h) * (long)W) + j;
   *xp = make_float4(acc[0], acc[1], acc[2], acc[3]);
 }
 
-// The same adjoint with every fine element fetched from HBM once: a workgroup owns the whole (h, w) plane of one (n, c) and
-// WALKS along d.  A thread keeps the (w, h)-reduced contributions P_a of the last two fine planes in registers; coarse plane
-// d = 0.25 P_{2d-1} + 0.75 P_{2d} + 0.75 P_{2d+1} + 0.25 P_{2d+2} needs only the two new planes per step (the gather form
-// above reads each fine row four times over and ran at 1.85 TB/s).  block = (W/4, H) threads, grid = (d segments, N*C).
-__device__ __forceinline__ float4 up2_plane_contrib(const float* __restrict__ plane, int OH, int OW, int h, int j, const float (&wb)[4],
-                                                    int W, bool left, bool right) {
-  float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
-#pragma unroll
-  for (int ib = 0; ib < 4; ++ib) {
-    if (wb[ib] == 0.f) continue;
-    const float* row = plane + (long)(2 * h - 1 + ib) * OW + 8 * j;
-    const float4 m0 = *(const float4*)row, m1 = *(const float4*)(row + 4);
-    const float gl = left ? row[-1] : 0.f, gr = right ? row[8] : 0.f;
-    const float g[10] = {gl, m0.x, m0.y, m0.z, m0.w, m1.x, m1.y, m1.z, m1.w, gr};
-    float r[4];
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      const int w = 4 * j + e;
-      const float w1 = w > 0 ? 0.75f : 1.f, w2 = w < W - 1 ? 0.75f : 1.f;
-      r[e] = wb[ib] * ((0.25f * g[2 * e] + w1 * g[2 * e + 1]) + (w2 * g[2 * e + 2] + 0.25f * g[2 * e + 3]));
-    }
-    acc.x += r[0]; acc.y += r[1]; acc.z += r[2]; acc.w += r[3];
-  }
-  return acc;
-}
-__global__ void __launch_bounds__(1024) upsample3d_x2_bwd_walk_kernel(const float* __restrict__ dy, float* __restrict__ dx, int D,
-                                                                     int H, int W, int dseg) {
-  const int OH = 2 * H, OW = 2 * W;
-  const int j = threadIdx.x, h = threadIdx.y;
-  const long nc = blockIdx.y;
-  const int d0 = blockIdx.x * dseg, d1 = min(d0 + dseg, D);
-  float wb[4];
-  up2_bwd_weights(h, H, wb);
-  const bool left = j > 0, right = 8 * j + 8 < OW;
-  const float* gp = dy + nc * (2L * D) * OH * OW;
-  const long ps = (long)OH * OW;
-  auto contrib = [&](int a) -> float4 {
-    if (a < 0 || a >= 2 * D) return make_float4(0.f, 0.f, 0.f, 0.f);
-    return up2_plane_contrib(gp + (long)a * ps, OH, OW, h, j, wb, W, left, right);
-  };
-  float4 pm1 = contrib(2 * d0 - 1), p0 = contrib(2 * d0);
-  for (int d = d0; d < d1; ++d) {
-    const float4 p1 = contrib(2 * d + 1), p2 = contrib(2 * d + 2);
-    float wa[4];
-    up2_bwd_weights(d, D, wa);
-    float4 o;
-    o.x = (wa[0] * pm1.x + wa[1] * p0.x) + (wa[2] * p1.x + wa[3] * p2.x);
-    o.y = (wa[0] * pm1.y + wa[1] * p0.y) + (wa[2] * p1.y + wa[3] * p2.y);
-    o.z = (wa[0] * pm1.z + wa[1] * p0.z) + (wa[2] * p1.z + wa[3] * p2.z);
-    o.w = (wa[0] * pm1.w + wa[1] * p0.w) + (wa[2] * p1.w + wa[3] * p2.w);
-    *((float4*)(dx + ((nc * D + d) * H + h) * (long)W) + j) = o;
-    pm1 = p1; p0 = p2;
-  }
-}
-
-// The walking adjoint with one FINE float4 per lane and row: lane = (coarse row h, fine float4 f), so a load instruction of a
-// wave reads whole 256-byte fine rows (above: two float4 with a 32-byte stride plus two scalar neighbours per lane) and the
-// coarse result leaves as a float2 per lane, i.e. whole coarse rows per store instruction.  Fine columns 4 f .. 4 f + 3 feed
+// The same adjoint with every fine element fetched from HBM once: a workgroup WALKS along d.  A lane keeps the (w, h)-reduced
+// contributions P_a of the last two fine planes in registers; coarse plane d = 0.25 P_{2d-1} + 0.75 P_{2d} + 0.75 P_{2d+1} +
+// 0.25 P_{2d+2} needs only the two new planes per step (the gather form above reads each fine row four times over and ran at
+// 1.85 TB/s).  One FINE float4 per lane and row: lane = (coarse row h, fine float4 f), so a load instruction of a wave reads
+// whole 256-byte fine rows and the coarse result leaves as a float2 per lane, i.e. whole coarse rows per store instruction.  Fine columns 4 f .. 4 f + 3 feed
 // the coarse columns 2 f and 2 f + 1; the two missing fine neighbours (4 f - 1, 4 f + 4) come from the adjacent lanes.
 // 256 threads = 256 / (W / 2) coarse rows; grid = (row groups, d segments, N * C).
 __global__ void __launch_bounds__(256) upsample3d_x2_bwd_row_kernel(const float* __restrict__ dy, float* __restrict__ dx, int D,
@@ -558,7 +495,6 @@ __global__ void __launch_bounds__(256) upsample3d_x2_bwd_row_kernel(const float*
   const int d0 = blockIdx.y * dseg, d1 = min(d0 + dseg, D);
   float wb[4];
   up2_bwd_weights(h, H, wb);
-  const float w1a = f > 0 ? 0.75f : 1.f, w2b = 2 * f + 1 < W - 1 ? 0.75f : 1.f, w2a = 2 * f < W - 1 ? 0.75f : 1.f;
   const float* gp = dy + nc * (2L * D) * OH * OW + 4 * f;
   const long ps = (long)OH * OW;
   // the four fine rows of plane a that this lane's coarse row receives (clamped row / plane: masked by the weights below)
@@ -580,8 +516,8 @@ __global__ void __launch_bounds__(256) upsample3d_x2_bwd_row_kernel(const float*
       const float lft = __shfl_up(g[ib].w, 1), rgt = __shfl_down(g[ib].x, 1);
       const float gl = f > 0 ? lft : 0.f, gr = f < OQ - 1 ? rgt : 0.f;
       const float wgt = wb[ib] * pw;                          // 0 for the rows that do not exist
-      acc.x += wgt * ((0.25f * gl + w1a * g[ib].x) + (w2a * g[ib].y + 0.25f * g[ib].z));
-      acc.y += wgt * ((0.25f * g[ib].y + 0.75f * g[ib].z) + (w2b * g[ib].w + 0.25f * gr));
+      acc.x += wgt * up2_col_adjoint(2 * f, W, gl, g[ib].x, g[ib].y, g[ib].z);
+      acc.y += wgt * up2_col_adjoint(2 * f + 1, W, g[ib].y, g[ib].z, g[ib].w, gr);
     }
     return acc;
   };
@@ -609,36 +545,26 @@ __global__ void __launch_bounds__(256) upsample3d_x2_bwd_row_kernel(const float*
 // u8 (NC, H, W) -> crop (top,left,CH,CW) -> /255 -> label ; (label-mean[c])/std[c] -> normalised
 __global__ void preprocess_image_kernel(const uint8_t* __restrict__ img, float* __restrict__ label,
                                         float* __restrict__ norm, long NC, int C, int H, int W, int top, int left, int CH,
-                                        int CW, float m0, float m1, float m2, float s0, float s1, float s2) {
+                                        int CW, Norm3 ms) {
   const long n = NC * CH * CW;
   GRID_STRIDE(i, n) {
-    const int x = (int)(i % CW);
-    long r = i / CW;
-    const int y = (int)(r % CH);
-    const long nc = r / CH;
-    const int c = (int)(nc % C);
+    int y, x;
+    const long nc = split_index(i, CH, CW, y, x);
     const float v = (float)img[(nc * H + (y + top)) * W + (x + left)] / 255.f;
     if (label) label[i] = v;
-    const float m = c == 0 ? m0 : (c == 1 ? m1 : m2), s = c == 0 ? s0 : (c == 1 ? s1 : s2);
-    norm[i] = (v - m) / s;
+    norm[i] = normalise3(ms, (int)(nc % C), v);
   }
 }
 // route map: u8 (NC,H,W) -> /255 -> nearest resize (OH,OW) -> normalise
 __global__ void preprocess_route_kernel(const uint8_t* __restrict__ img, float* __restrict__ norm, long NC, int C, int H,
-                                        int W, int OH, int OW, float m0, float m1, float m2, float s0, float s1, float s2) {
+                                        int W, int OH, int OW, Norm3 ms) {
   const long n = NC * OH * OW;
   const float sh = (float)H / (float)OH, sw = (float)W / (float)OW;
   GRID_STRIDE(i, n) {
-    const int x = (int)(i % OW);
-    long r = i / OW;
-    const int y = (int)(r % OH);
-    const long nc = r / OH;
-    const int c = (int)(nc % C);
-    int sy = (int)floorf((float)y * sh); if (sy > H - 1) sy = H - 1;
-    int sx = (int)floorf((float)x * sw); if (sx > W - 1) sx = W - 1;
-    const float v = (float)img[(nc * H + sy) * W + sx] / 255.f;
-    const float m = c == 0 ? m0 : (c == 1 ? m1 : m2), s = c == 0 ? s0 : (c == 1 ? s1 : s2);
-    norm[i] = (v - m) / s;
+    int y, x;
+    const long nc = split_index(i, OH, OW, y, x);
+    const float v = (float)img[(nc * H + nearest_src(y, H, sh)) * W + nearest_src(x, W, sw)] / 255.f;
+    norm[i] = normalise3(ms, (int)(nc % C), v);
   }
 }
 __global__ void scale_kernel(const float* __restrict__ x, float* __restrict__ y, long n, float inv) {
@@ -650,15 +576,11 @@ __global__ void resize_bilinear_kernel(const float* __restrict__ x, float* __res
   const long n = NC * OH * OW;
   const float sh = (float)H / (float)OH, sw = (float)W / (float)OW;
   GRID_STRIDE(i, n) {
-    const int ox = (int)(i % OW);
-    long r = i / OW;
-    const int oy = (int)(r % OH);
-    const long nc = r / OH;
-    float fy = sh * ((float)oy + 0.5f) - 0.5f; if (fy < 0.f) fy = 0.f;
-    float fx = sw * ((float)ox + 0.5f) - 0.5f; if (fx < 0.f) fx = 0.f;
-    const int y0 = (int)fy, x0 = (int)fx;
-    const int y1 = y0 + (y0 < H - 1 ? 1 : 0), x1 = x0 + (x0 < W - 1 ? 1 : 0);
-    const float ly = fy - (float)y0, lx = fx - (float)x0;
+    int oy, ox, y0, y1, x0, x1;
+    float ly, lx;
+    const long nc = split_index(i, OH, OW, oy, ox);
+    lin_src(oy, H, sh, y0, y1, ly);
+    lin_src(ox, W, sw, x0, x1, lx);
     const float hy = 1.f - ly, hx = 1.f - lx;
     const float* xp = x + nc * H * W;
     y[i] = hy * (hx * xp[y0 * W + x0] + lx * xp[y0 * W + x1]) + ly * (hx * xp[y1 * W + x0] + lx * xp[y1 * W + x1]);
@@ -671,16 +593,57 @@ __global__ void resize_nearest_kernel(const T* __restrict__ x, T* __restrict__ y
   const long n = NC * OD * OH * OW;
   const float sd = (float)D / (float)OD, sh = (float)H / (float)OH, sw = (float)W / (float)OW;
   GRID_STRIDE(i, n) {
-    const int ox = (int)(i % OW);
-    long r = i / OW;
-    const int oy = (int)(r % OH);
-    r /= OH;
-    const int oz = (int)(r % OD);
-    const long nc = r / OD;
-    int z = (int)floorf((float)oz * sd); if (z > D - 1) z = D - 1;
-    int yy = (int)floorf((float)oy * sh); if (yy > H - 1) yy = H - 1;
-    int xx = (int)floorf((float)ox * sw); if (xx > W - 1) xx = W - 1;
-    y[i] = x[((nc * D + z) * H + yy) * W + xx];
+    int oz, oy, ox;
+    const long nc = split_index(i, OD, OH, OW, oz, oy, ox);
+    y[i] = x[((nc * D + nearest_src(oz, D, sd)) * H + nearest_src(oy, H, sh)) * W + nearest_src(ox, W, sw)];
+  }
+}
+// Antialiased linear resize of (NC, H, W) float planes (include/muvo_hip.h: muvo_resize_bilinear_aa): EVAL.RESOLUTION of
+// PreProcess.forward (preprocess.py:209-210,252-273: torchvision 0.15.2 resize(antialias=True) = ATen _upsample_bilinear2d_aa).
+// One thread per output pixel; per axis the taps [lo, hi) and triangle weights of ATen's _compute_indices_min_size_weights_aa in
+// float32, normalised; horizontal sums first, then the vertical combination (the order of the separable reference kernel).
+struct AaTaps { int lo, n; float center, inv, total; };
+__device__ __forceinline__ AaTaps aa_taps(int o, int in_size, float scale) {
+  const float support = scale >= 1.f ? scale : 1.f;
+  AaTaps t;
+  t.inv = scale >= 1.f ? 1.f / scale : 1.f;
+  t.center = scale * ((float)o + 0.5f);
+  int lo = (int)(t.center - support + 0.5f), hi = (int)(t.center + support + 0.5f);
+  lo = lo < 0 ? 0 : lo;
+  hi = hi > in_size ? in_size : hi;
+  t.lo = lo;
+  t.n = hi - lo;
+  float tot = 0.f;
+  for (int j = 0; j < t.n; ++j) {
+    const float w = 1.f - fabsf(((float)(j + lo) - t.center + 0.5f) * t.inv);
+    tot += w > 0.f ? w : 0.f;
+  }
+  t.total = tot;
+  return t;
+}
+__device__ __forceinline__ float aa_weight(const AaTaps& t, int j) {
+  const float w = 1.f - fabsf(((float)(j + t.lo) - t.center + 0.5f) * t.inv);
+  return (w > 0.f ? w : 0.f) / t.total;
+}
+__global__ void __launch_bounds__(256) resize_bilinear_aa_kernel(const float* __restrict__ x, float* __restrict__ y,
+                                                                 float* __restrict__ ynorm, Norm3 ms, long NC, int C, int H, int W,
+                                                                 int OH, int OW) {
+  const float sh = (float)H / (float)OH, sw = (float)W / (float)OW;
+  const long total = NC * OH * OW;
+  GRID_STRIDE(i, total) {
+    int oy, ox;
+    const long nc = split_index(i, OH, OW, oy, ox);
+    const AaTaps tx = aa_taps(ox, W, sw), ty = aa_taps(oy, H, sh);
+    const float* p = x + nc * (long)H * W;
+    float acc = 0.f;
+    for (int r = 0; r < ty.n; ++r) {
+      const float* row = p + (long)(ty.lo + r) * W + tx.lo;
+      float rs = 0.f;
+      for (int j = 0; j < tx.n; ++j) rs += row[j] * aa_weight(tx, j);
+      acc += rs * aa_weight(ty, r);
+    }
+    y[i] = acc;
+    if (ynorm) ynorm[i] = normalise3(ms, (int)(nc % C), acc);
   }
 }
 
@@ -754,19 +717,24 @@ __global__ void __launch_bounds__(256) softmax_dropout_bwd_kernel(const float* _
 }
 
 // ---------------------------------------------------------------------------------------- RSSM
-__device__ __forceinline__ float sigmoidf_(float x) { return 1.f / (1.f + expf(-x)); }
 // torch.nn.GRUCell: r = s(gi_r+gh_r), z = s(gi_z+gh_z), n = tanh(gi_n + r*gh_n), h' = (1-z)*n + z*h
+struct GruGates { float r, z, n, ghn; };
+// the gates of element j of a sequence whose rows of gi / gh (3 H floats: r | z | n) start at a / c
+__device__ __forceinline__ GruGates gru_gates(const float* __restrict__ a, const float* __restrict__ c, int H, long j) {
+  GruGates g;
+  g.r = sigmoidf_(a[j] + c[j]);
+  g.z = sigmoidf_(a[H + j] + c[H + j]);
+  g.ghn = c[2 * H + j];
+  g.n = tanhf(a[2 * H + j] + g.r * g.ghn);
+  return g;
+}
 __global__ void gru_fwd_kernel(const float* __restrict__ gi, const float* __restrict__ gh, const float* __restrict__ h,
                                float* __restrict__ hn, int B, int H) {
   const long n = (long)B * H;
   GRID_STRIDE(i, n) {
     const long b = i / H, j = i - b * H;
-    const float* a = gi + b * 3 * H;
-    const float* c = gh + b * 3 * H;
-    const float r = sigmoidf_(a[j] + c[j]);
-    const float z = sigmoidf_(a[H + j] + c[H + j]);
-    const float nn = tanhf(a[2 * H + j] + r * c[2 * H + j]);
-    hn[i] = (1.f - z) * nn + z * h[i];
+    const GruGates q = gru_gates(gi + b * 3 * H, gh + b * 3 * H, H, j);
+    hn[i] = (1.f - q.z) * q.n + q.z * h[i];
   }
 }
 __global__ void gru_bwd_kernel(const float* __restrict__ gi, const float* __restrict__ gh, const float* __restrict__ h,
@@ -775,12 +743,8 @@ __global__ void gru_bwd_kernel(const float* __restrict__ gi, const float* __rest
   const long n = (long)B * H;
   GRID_STRIDE(i, n) {
     const long b = i / H, j = i - b * H;
-    const float* a = gi + b * 3 * H;
-    const float* c = gh + b * 3 * H;
-    const float r = sigmoidf_(a[j] + c[j]);
-    const float z = sigmoidf_(a[H + j] + c[H + j]);
-    const float ghn = c[2 * H + j];
-    const float nn = tanhf(a[2 * H + j] + r * ghn);
+    const GruGates q = gru_gates(gi + b * 3 * H, gh + b * 3 * H, H, j);
+    const float r = q.r, z = q.z, nn = q.n, ghn = q.ghn;
     const float g = dhn[i];
     const float dn = g * (1.f - z);
     const float dz = g * (h[i] - nn);
@@ -826,44 +790,46 @@ __global__ void rssm_sample_bwd_kernel(const float* __restrict__ mls, const floa
 
 // =============================================================================================== ABI
 #define ST ((hipStream_t)stream)
+// The launch step of the flat grid-stride kernels: ew_grid(n) workgroups of 256 threads on the stream, then the launch check
+// under `name`.  The arguments are converted to the kernel's parameter types (the int64_t sizes of the ABI to long).  Argument
+// checks and the behaviour at n == 0 stay with each entry point.
+template <typename... P, typename... A>
+static int launch_flat(const char* name, void (*kernel)(P...), long n, void* stream, A... args) {
+  hipLaunchKernelGGL(kernel, dim3(ew_grid(n)), dim3(256), 0, ST, static_cast<P>(args)...);
+  MUVO_CHECK_LAUNCH(name);
+  return MUVO_OK;
+}
+// the template instance of a checked max-pool window (3x3 / 2 / 1 or 2x2 / 2 / 0) resp. of a checked softmax row length
+#define MAXPOOL_INSTANCE(kernel, k) ((k) == 3 ? kernel<3, 2, 1> : kernel<2, 2, 0>)
+#define SOFTMAX_INSTANCE(kernel, cols) (softmax_dropout_maxv(cols) == 8 ? kernel<8> : kernel<SOFTMAX_MAXV>)
+
 extern "C" {
 
 int muvo_act_bwd(const float* y, const float* dy, float* dx, int64_t n, int act, float slope, void* stream) {
   MUVO_CHECK_ARG(y && dy && dx && n >= 0, "act_bwd: bad args");
   if (n == 0) return MUVO_OK;
-  hipLaunchKernelGGL(act_bwd_kernel, dim3(ew_grid(n)), dim3(256), 0, ST, y, dy, dx, (long)n, act, slope);
-  MUVO_CHECK_LAUNCH("act_bwd");
-  return MUVO_OK;
+  return launch_flat("act_bwd", act_bwd_kernel, n, stream, y, dy, dx, n, act, slope);
 }
 int muvo_act_fwd(const float* x, float* y, int64_t n, int act, float slope, void* stream) {
   MUVO_CHECK_ARG(x && y && n >= 0, "act_fwd: bad args");
   if (n == 0) return MUVO_OK;
-  hipLaunchKernelGGL(act_fwd_kernel, dim3(ew_grid(n)), dim3(256), 0, ST, x, y, (long)n, act, slope);
-  MUVO_CHECK_LAUNCH("act_fwd");
-  return MUVO_OK;
+  return launch_flat("act_fwd", act_fwd_kernel, n, stream, x, y, n, act, slope);
 }
 int muvo_dropout(const float* x, float* y, int64_t n, float p, uint64_t seed, void* stream) {
   MUVO_CHECK_ARG(x && y && n >= 0 && p >= 0.f && p < 1.f, "dropout: bad args");
   if (n == 0) return MUVO_OK;
-  hipLaunchKernelGGL(dropout_kernel, dim3(ew_grid(n)), dim3(256), 0, ST, x, y, (long)n, p, seed);
-  MUVO_CHECK_LAUNCH("dropout");
-  return MUVO_OK;
+  return launch_flat("dropout", dropout_kernel, n, stream, x, y, n, p, seed);
 }
 int muvo_axpby(const float* a, const float* b, float* out, int64_t n, float alpha, float beta, void* stream) {
   MUVO_CHECK_ARG(a && out && n >= 0, "axpby: bad args");
   if (n == 0) return MUVO_OK;
-  hipLaunchKernelGGL(axpby_kernel, dim3(ew_grid(n)), dim3(256), 0, ST, a, b, out, (long)n, alpha, beta);
-  MUVO_CHECK_LAUNCH("axpby");
-  return MUVO_OK;
+  return launch_flat("axpby", axpby_kernel, n, stream, a, b, out, n, alpha, beta);
 }
 int muvo_copy2d(const float* src, float* dst, int64_t rows, int64_t cols, int64_t ld_src, int64_t ld_dst, int accumulate,
                 void* stream) {
   MUVO_CHECK_ARG(src && dst && rows >= 0 && cols >= 0 && ld_src >= cols && ld_dst >= cols, "copy2d: bad args");
   if (rows * cols == 0) return MUVO_OK;
-  hipLaunchKernelGGL(copy2d_kernel, dim3(ew_grid(rows * cols)), dim3(256), 0, ST, src, dst, (long)rows, (long)cols,
-                     (long)ld_src, (long)ld_dst, accumulate);
-  MUVO_CHECK_LAUNCH("copy2d");
-  return MUVO_OK;
+  return launch_flat("copy2d", copy2d_kernel, rows * cols, stream, src, dst, rows, cols, ld_src, ld_dst, accumulate);
 }
 int muvo_colsum_acc(const float* x, float* out, int64_t rows, int64_t cols, int64_t ld, void* stream) {
   MUVO_CHECK_ARG(x && out && rows > 0 && cols > 0 && ld >= cols, "colsum: bad args");
@@ -876,9 +842,7 @@ int muvo_colsum_acc(const float* x, float* out, int64_t rows, int64_t cols, int6
 }
 int muvo_batchsum(const float* x, float* out, int N, int64_t inner, int accumulate, void* stream) {
   MUVO_CHECK_ARG(x && out && N > 0 && inner > 0, "batchsum: bad args");
-  hipLaunchKernelGGL(batchsum_kernel, dim3(ew_grid(inner)), dim3(256), 0, ST, x, out, N, (long)inner, accumulate);
-  MUVO_CHECK_LAUNCH("batchsum");
-  return MUVO_OK;
+  return launch_flat("batchsum", batchsum_kernel, inner, stream, x, out, N, inner, accumulate);
 }
 int muvo_nchw_to_tokens(const float* x, const float* pos, const float* temb, int temb_stride, float* tokens, int N, int C,
                         int L, int l0, void* stream) {
@@ -908,8 +872,7 @@ static void maxpool2d_route(bool backward, int64_t NC, int H, int W, int k, int 
     r->grid[0] = cdiv(OW, 256); r->grid[1] = cdiv(OH, 4);
     return;
   }
-  static const bool v8 = !getenv("MUVO_MAXPOOL_BWD_V8") || atoi(getenv("MUVO_MAXPOOL_BWD_V8")) != 0;   // A/B switch
-  if (k == 3 && v8 && W % 8 == 0 && OW % 4 == 0 && 2 * OW == W && 2 * OH == H && ((((uintptr_t)in) | ((uintptr_t)out)) & 15) == 0 &&
+  if (k == 3 && W % 8 == 0 && OW % 4 == 0 && 2 * OW == W && 2 * OH == H && ((((uintptr_t)in) | ((uintptr_t)out)) & 15) == 0 &&
       (((uintptr_t)idx) & 3) == 0) {
     r->v8 = 1;
     r->grid[0] = cdiv(W / 8, 64); r->grid[1] = cdiv(H / 2, 4);
@@ -917,10 +880,12 @@ static void maxpool2d_route(bool backward, int64_t NC, int H, int W, int k, int 
   }
   r->grid[0] = cdiv(W, 256); r->grid[1] = cdiv(H, 4);
 }
-static int maxpool2d_check(int64_t NC, int H, int W, int k, int s, int p) {
+// out: the (OH, OW) a launcher was given (the route query has none)
+static int maxpool2d_check(int64_t NC, int H, int W, int k, int s, int p, const int* out = nullptr) {
   MUVO_CHECK_ARG(NC > 0 && NC <= 2147483647L && H > 0 && W > 0, "maxpool2d: bad sizes");
   MUVO_CHECK_ARG((k == 3 && s == 2 && p == 1) || (k == 2 && s == 2 && p == 0), "maxpool2d: only 3x3 s2 p1 and 2x2 s2 p0 are on the path");
   MUVO_CHECK_ARG(H + 2 * p >= k && W + 2 * p >= k, "maxpool2d: window larger than the padded image");
+  MUVO_CHECK_ARG(!out || (out[0] == (H + 2 * p - k) / s + 1 && out[1] == (W + 2 * p - k) / s + 1), "maxpool2d: output size");
   return MUVO_OK;
 }
 int muvo_maxpool2d_route(int backward, int64_t NC, int H, int W, int k, int s, int p, const void* in, const void* idx,
@@ -934,81 +899,28 @@ int muvo_maxpool2d_route(int backward, int64_t NC, int H, int W, int k, int s, i
 int muvo_maxpool2d_fwd(const float* x, float* y, uint8_t* idx, int64_t NC, int H, int W, int OH, int OW, int k, int s, int p,
                        void* stream) {
   MUVO_CHECK_ARG(x && y && idx, "maxpool2d_fwd: bad args");
-  int rc = maxpool2d_check(NC, H, W, k, s, p);
+  const int out[2] = {OH, OW};
+  int rc = maxpool2d_check(NC, H, W, k, s, p, out);
   if (rc) return rc;
-  MUVO_CHECK_ARG(OH == (H + 2 * p - k) / s + 1 && OW == (W + 2 * p - k) / s + 1 && cdiv(OH, 4) <= 65535, "maxpool2d_fwd: output size");
+  MUVO_CHECK_ARG(cdiv(OH, 4) <= 65535, "maxpool2d_fwd: image too tall");
   muvo_maxpool2d_route_info r;
   maxpool2d_route(false, NC, H, W, k, s, p, x, idx, y, &r);
-  const dim3 grid(r.grid[0], r.grid[1], r.grid[2]), block(r.block[0], r.block[1]);
-  if (r.k == 3) hipLaunchKernelGGL((maxpool2d_fwd_t_kernel<3, 2, 1>), grid, block, 0, ST, x, y, idx, H, W, OH, OW, r.load16);
-  else hipLaunchKernelGGL((maxpool2d_fwd_t_kernel<2, 2, 0>), grid, block, 0, ST, x, y, idx, H, W, OH, OW, r.load16);
+  hipLaunchKernelGGL(MAXPOOL_INSTANCE(maxpool2d_fwd_t_kernel, r.k), dim3(r.grid[0], r.grid[1], r.grid[2]), dim3(r.block[0], r.block[1]), 0,
+                     ST, x, y, idx, H, W, OH, OW, r.load16);
   MUVO_CHECK_LAUNCH("maxpool2d_fwd");
   return MUVO_OK;
 }
-// 3x3 stride-2 pad-1 form for W % 8 == 0, OW % 4 == 0, H = 2 OH (the ResNet stems): a lane owns EIGHT consecutive input columns
-// of the ROW PAIR (2r, 2r+1).  They are touched by the five windows 4l .. 4l+4 of the window rows r (rows 2r-1 .. 2r+1) and r+1
-// (row 2r+1 only): per window row one 16-byte gradient load, one 4-byte winner load and one scalar pair for the fifth window -
-// instead of 2 x 3 scalar pairs per four columns of one row - and four 16-byte stores.  Standalone on 20 x 64 x 160 x 416:
-// 96 us against 134 us with one row per lane (tools/dev/maxpool_bwd_probe.hip; stores alone 54 us); it is the last memory-bound
-// pass on the main stream before the stem's weight gradient.
-__global__ void __launch_bounds__(256) maxpool3s2_bwd_v8_kernel(const float* __restrict__ dy, const uint8_t* __restrict__ idx,
-                                                                 float* __restrict__ dx, int H, int W, int OH, int OW) {
-  const int l = blockIdx.x * 64 + threadIdx.x, w0 = 8 * l, r = blockIdx.y * 4 + threadIdx.y;
-  if (w0 >= W || 2 * r >= H) return;
-  const long nc = blockIdx.z;
-  float g0[8], g1[8];
-#pragma unroll
-  for (int e = 0; e < 8; ++e) g0[e] = g1[e] = 0.f;
-  const int j4 = min(4 * l + 4, OW - 1);                              // fifth window (clamped; masked below)
-  const bool live4 = 4 * l + 4 <= OW - 1;
-#pragma unroll
-  for (int i = 0; i < 2; ++i) {
-    const int oh = min(r + i, OH - 1);
-    const bool live = r + i <= OH - 1;
-    const long ro = (nc * OH + oh) * (long)OW;
-    const float4 d4 = *(const float4*)(dy + ro + 4 * l);
-    const uchar4 i4 = *(const uchar4*)(idx + ro + 4 * l);
-    const float dd[5] = {d4.x, d4.y, d4.z, d4.w, dy[ro + j4]};
-    const int ww[5] = {i4.x, i4.y, i4.z, i4.w, idx[ro + j4]};
-#pragma unroll
-    for (int j = 0; j < 5; ++j) {
-      const bool lv = live && (j < 4 || live4);
-      const int a0 = ww[j] / 3, b0 = ww[j] - 3 * a0;                   // winner (row, column) inside the window
-#pragma unroll
-      for (int b = 0; b < 3; ++b) {
-        const int e = 2 * j - 1 + b;                                   // window 4l+j covers columns 2j-1 .. 2j+1 of this lane
-        if (e >= 0 && e < 8 && lv && b0 == b) {
-          // window row r: input rows 2r-1 (a = 0, another lane's pair), 2r (a = 1), 2r+1 (a = 2); window row r+1: row 2r+1 is a = 0
-          if (i == 0) {
-            if (a0 == 1) g0[e] += dd[j];
-            if (a0 == 2) g1[e] += dd[j];
-          } else if (a0 == 0) {
-            g1[e] += dd[j];
-          }
-        }
-      }
-    }
-  }
-  float* o = dx + (nc * H + 2 * r) * (long)W + w0;
-  *(float4*)o = make_float4(g0[0], g0[1], g0[2], g0[3]);
-  *(float4*)(o + 4) = make_float4(g0[4], g0[5], g0[6], g0[7]);
-  *(float4*)(o + W) = make_float4(g1[0], g1[1], g1[2], g1[3]);
-  *(float4*)(o + W + 4) = make_float4(g1[4], g1[5], g1[6], g1[7]);
-}
-
 int muvo_maxpool2d_bwd(const float* dy, const uint8_t* idx, float* dx, int64_t NC, int H, int W, int OH, int OW, int k,
                        int s, int p, void* stream) {
   MUVO_CHECK_ARG(dy && dx && idx, "maxpool2d_bwd: bad args");
-  int rc = maxpool2d_check(NC, H, W, k, s, p);
+  const int out[2] = {OH, OW};
+  int rc = maxpool2d_check(NC, H, W, k, s, p, out);
   if (rc) return rc;
-  MUVO_CHECK_ARG(OH == (H + 2 * p - k) / s + 1 && OW == (W + 2 * p - k) / s + 1, "maxpool2d_bwd: output size");
   MUVO_CHECK_ARG(cdiv(H, 4) <= 65535, "maxpool2d_bwd: image too tall");
   muvo_maxpool2d_route_info r;
   maxpool2d_route(true, NC, H, W, k, s, p, dy, idx, dx, &r);
-  const dim3 grid(r.grid[0], r.grid[1], r.grid[2]), block(r.block[0], r.block[1]);
-  if (r.v8) hipLaunchKernelGGL(maxpool3s2_bwd_v8_kernel, grid, block, 0, ST, dy, idx, dx, H, W, OH, OW);
-  else if (r.k == 3) hipLaunchKernelGGL((maxpool2d_bwd_t_kernel<3, 2, 1>), grid, block, 0, ST, dy, idx, dx, H, W, OH, OW);
-  else hipLaunchKernelGGL((maxpool2d_bwd_t_kernel<2, 2, 0>), grid, block, 0, ST, dy, idx, dx, H, W, OH, OW);
+  hipLaunchKernelGGL((r.v8 ? maxpool3s2_bwd_v8_kernel : MAXPOOL_INSTANCE(maxpool2d_bwd_t_kernel, r.k)), dim3(r.grid[0], r.grid[1], r.grid[2]),
+                     dim3(r.block[0], r.block[1]), 0, ST, dy, idx, dx, H, W, OH, OW);
   MUVO_CHECK_LAUNCH("maxpool2d_bwd");
   return MUVO_OK;
 }
@@ -1020,19 +932,16 @@ int muvo_avgpool_fwd(const float* x, float* y, int64_t G, int64_t S, void* strea
 }
 int muvo_avgpool_bwd(const float* dy, float* dx, int64_t G, int64_t S, void* stream) {
   MUVO_CHECK_ARG(dy && dx && G > 0 && S > 0, "avgpool_bwd: bad args");
-  hipLaunchKernelGGL(avgpool_bwd_kernel, dim3(ew_grid(G * S)), dim3(256), 0, ST, dy, dx, (long)G, (long)S);
-  MUVO_CHECK_LAUNCH("avgpool_bwd");
-  return MUVO_OK;
+  return launch_flat("avgpool_bwd", avgpool_bwd_kernel, G * S, stream, dy, dx, G, S);
 }
 // The host decision of muvo_upsample3d_x2_fwd / _bwd for checked sizes: kernel, grid, block and the d segments of the walking
-// kernels.  The pointers count only by their alignment: a kernel is chosen only if every pointer it accesses with 16-byte
+// backward kernel.  The pointers count only by their alignment: a kernel is chosen only if every pointer it accesses with 16-byte
 // instructions is 16-byte aligned (W % 4 == 0 resp. W % 2 == 0 keeps every row start as aligned as the base), anything else
 // goes to the next kernel down, ultimately the scalar ones.  The launchers launch from it, muvo_upsample3d_route reports it.
 static void upsample3d_route(bool backward, int64_t NC, int D, int H, int W, const void* in, const void* out,
                              muvo_upsample3d_route_info* r) {
   const bool in16 = (((uintptr_t)in) & 15) == 0, out16 = (((uintptr_t)out) & 15) == 0;
   const int oq = W / 2;                     // fine float4 per row
-  const int q8 = W / 4;
   const bool oq_ok = W % 4 == 0 && oq <= 64 && (oq & (oq - 1)) == 0;
   r->segs = 1; r->dseg = D;
   r->grid[1] = r->grid[2] = 1;
@@ -1041,9 +950,6 @@ static void upsample3d_route(bool backward, int64_t NC, int D, int H, int W, con
     if (oq_ok && D + 1 <= 65535 && NC <= 65535 && in16 && out16) {          // float4 loads of x, 16-byte stores of y
       r->kernel = MUVO_UPSAMPLE_ROW;
       r->grid[0] = cdiv((long)(H + 1) * oq, 256); r->grid[1] = D + 1; r->grid[2] = (int32_t)NC;
-    } else if (W % 4 == 0 && q8 <= 64 && (q8 & (q8 - 1)) == 0 && 2 * D <= 65535 && NC <= 65535 && in16 && out16) {   // the same
-      r->kernel = MUVO_UPSAMPLE_VEC8;
-      r->grid[0] = cdiv((long)2 * H * q8, 256); r->grid[1] = 2 * D; r->grid[2] = (int32_t)NC;
     } else if (W % 2 == 0 && 2 * D <= 65535 && NC <= 65535 && out16) {      // dword loads of x, float4 stores of y
       r->kernel = MUVO_UPSAMPLE_VEC;
       r->grid[0] = cdiv((long)2 * H * (2 * W / 4), 256); r->grid[1] = 2 * D; r->grid[2] = (int32_t)NC;
@@ -1053,8 +959,8 @@ static void upsample3d_route(bool backward, int64_t NC, int D, int H, int W, con
     }
     return;
   }
-  static const int walk = getenv("MUVO_UPSAMPLE_WALK") ? atoi(getenv("MUVO_UPSAMPLE_WALK")) : 2;
-  if (walk == 2 && oq_ok && NC <= 65535 && in16 && out16) {
+  if (oq_ok && NC <= 65535 && in16 && out16) {                              // float4 loads of dy, float2 stores of dx
+    // enough workgroups to fill the chip: split the d range (each segment recomputes its two lead-in planes)
     const int rgroups = cdiv(H, 256 / oq);
     int segs = 1;
     while ((long)NC * rgroups * segs < 4096 && segs * 16 <= D) segs *= 2;
@@ -1062,15 +968,6 @@ static void upsample3d_route(bool backward, int64_t NC, int D, int H, int W, con
     r->dseg = cdiv(D, segs);
     r->segs = cdiv(D, r->dseg);
     r->grid[0] = rgroups; r->grid[1] = r->segs; r->grid[2] = (int32_t)NC;
-  } else if (walk && W % 4 == 0 && (W / 4) * H <= 1024 && (W / 4) * H >= 128 && NC <= 65535 && in16 && out16) {
-    // enough workgroups to fill the chip: split the d range (each segment recomputes its two lead-in planes)
-    int segs = 1;
-    while ((long)NC * segs < 1024 && segs * 8 <= D) segs *= 2;
-    r->kernel = MUVO_UPSAMPLE_WALK;
-    r->dseg = cdiv(D, segs);
-    r->segs = cdiv(D, r->dseg);
-    r->grid[0] = r->segs; r->grid[1] = (int32_t)NC;
-    r->block[0] = W / 4; r->block[1] = H;
   } else if (W % 4 == 0 && D <= 65535 && NC <= 65535 && in16 && out16) {    // float4 loads of dy, float4 stores of dx
     r->kernel = MUVO_UPSAMPLE_VEC;
     r->grid[0] = cdiv((long)H * (W / 4), 256); r->grid[1] = D; r->grid[2] = (int32_t)NC;
@@ -1091,7 +988,6 @@ int muvo_upsample3d_x2_fwd(const float* x, float* y, int64_t NC, int D, int H, i
   upsample3d_route(false, NC, D, H, W, x, y, &r);
   const dim3 grid(r.grid[0], r.grid[1], r.grid[2]), block(r.block[0], r.block[1], r.block[2]);
   if (r.kernel == MUVO_UPSAMPLE_ROW) hipLaunchKernelGGL(upsample3d_x2_fwd_row_kernel, grid, block, 0, ST, x, y, D, H, W);
-  else if (r.kernel == MUVO_UPSAMPLE_VEC8) hipLaunchKernelGGL(upsample3d_x2_fwd_vec8_kernel, grid, block, 0, ST, x, y, D, H, W);
   else if (r.kernel == MUVO_UPSAMPLE_VEC) hipLaunchKernelGGL(upsample3d_x2_fwd_vec_kernel, grid, block, 0, ST, x, y, D, H, W);
   else hipLaunchKernelGGL(upsample3d_x2_fwd_kernel, grid, block, 0, ST, x, y, (long)NC, D, H, W);
   MUVO_CHECK_LAUNCH("upsample3d_fwd");
@@ -1103,7 +999,6 @@ int muvo_upsample3d_x2_bwd(const float* dy, float* dx, int64_t NC, int D, int H,
   upsample3d_route(true, NC, D, H, W, dy, dx, &r);
   const dim3 grid(r.grid[0], r.grid[1], r.grid[2]), block(r.block[0], r.block[1], r.block[2]);
   if (r.kernel == MUVO_UPSAMPLE_ROW) hipLaunchKernelGGL(upsample3d_x2_bwd_row_kernel, grid, block, 0, ST, dy, dx, D, H, W, r.dseg);
-  else if (r.kernel == MUVO_UPSAMPLE_WALK) hipLaunchKernelGGL(upsample3d_x2_bwd_walk_kernel, grid, block, 0, ST, dy, dx, D, H, W, r.dseg);
   else if (r.kernel == MUVO_UPSAMPLE_VEC) hipLaunchKernelGGL(upsample3d_x2_bwd_vec_kernel, grid, block, 0, ST, dy, dx, D, H, W);
   else hipLaunchKernelGGL(upsample3d_x2_bwd_kernel, grid, block, 0, ST, dy, dx, (long)NC, D, H, W);
   MUVO_CHECK_LAUNCH("upsample3d_bwd");
@@ -1113,47 +1008,42 @@ int muvo_preprocess_image(const uint8_t* img, float* label, float* norm, int64_t
                           int CH, int CW, const float* mean3, const float* std3, void* stream) {
   MUVO_CHECK_ARG(img && norm && mean3 && std3 && C == 3, "preprocess_image: bad args");
   MUVO_CHECK_ARG(top >= 0 && left >= 0 && top + CH <= H && left + CW <= W, "preprocess_image: crop outside the image");
-  hipLaunchKernelGGL(preprocess_image_kernel, dim3(ew_grid(NC * CH * CW)), dim3(256), 0, ST, img, label, norm, (long)NC, C, H,
-                     W, top, left, CH, CW, mean3[0], mean3[1], mean3[2], std3[0], std3[1], std3[2]);
-  MUVO_CHECK_LAUNCH("preprocess_image");
-  return MUVO_OK;
+  return launch_flat("preprocess_image", preprocess_image_kernel, NC * CH * CW, stream, img, label, norm, NC, C, H, W, top, left, CH,
+                     CW, norm3_of(mean3, std3));
 }
 int muvo_preprocess_route(const uint8_t* img, float* norm, int64_t NC, int C, int H, int W, int OH, int OW,
                           const float* mean3, const float* std3, void* stream) {
   MUVO_CHECK_ARG(img && norm && mean3 && std3 && C == 3, "preprocess_route: bad args");
-  hipLaunchKernelGGL(preprocess_route_kernel, dim3(ew_grid(NC * OH * OW)), dim3(256), 0, ST, img, norm, (long)NC, C, H, W, OH,
-                     OW, mean3[0], mean3[1], mean3[2], std3[0], std3[1], std3[2]);
-  MUVO_CHECK_LAUNCH("preprocess_route");
-  return MUVO_OK;
+  return launch_flat("preprocess_route", preprocess_route_kernel, NC * OH * OW, stream, img, norm, NC, C, H, W, OH, OW,
+                     norm3_of(mean3, std3));
 }
 int muvo_divide_scalar(const float* x, float* y, int64_t n, float divisor, void* stream) {
   MUVO_CHECK_ARG(x && y && n > 0 && divisor != 0.f, "divide_scalar: bad args");
-  hipLaunchKernelGGL(scale_kernel, dim3(ew_grid(n)), dim3(256), 0, ST, x, y, (long)n, divisor);
-  MUVO_CHECK_LAUNCH("divide_scalar");
-  return MUVO_OK;
+  return launch_flat("divide_scalar", scale_kernel, n, stream, x, y, n, divisor);
 }
 int muvo_resize_bilinear(const float* x, float* y, int64_t NC, int H, int W, int OH, int OW, void* stream) {
   MUVO_CHECK_ARG(x && y && NC > 0 && H > 0 && W > 0 && OH > 0 && OW > 0, "resize_bilinear: bad args");
-  hipLaunchKernelGGL(resize_bilinear_kernel, dim3(ew_grid(NC * OH * OW)), dim3(256), 0, ST, x, y, (long)NC, H, W, OH, OW);
-  MUVO_CHECK_LAUNCH("resize_bilinear");
-  return MUVO_OK;
+  return launch_flat("resize_bilinear", resize_bilinear_kernel, NC * OH * OW, stream, x, y, NC, H, W, OH, OW);
+}
+int muvo_resize_bilinear_aa(const float* x, float* y, float* ynorm, const float* mean, const float* std, int64_t NC, int C, int H,
+                            int W, int OH, int OW, void* stream) {
+  MUVO_CHECK_ARG(x && y && NC > 0 && C > 0 && H > 0 && W > 0 && OH > 0 && OW > 0, "resize_bilinear_aa: bad args");
+  MUVO_CHECK_ARG(ynorm == nullptr || (mean && std && C <= 3), "resize_bilinear_aa: the normalised copy needs mean / std of <= 3 channels");
+  float m[3] = {0.f, 0.f, 0.f}, s[3] = {1.f, 1.f, 1.f};
+  if (ynorm) for (int c = 0; c < C; ++c) { m[c] = mean[c]; s[c] = std[c]; }
+  return launch_flat("resize_bilinear_aa_kernel", resize_bilinear_aa_kernel, NC * OH * OW, stream, x, y, ynorm, norm3_of(m, s), NC, C, H, W,
+                     OH, OW);
 }
 int muvo_resize_nearest_f32(const float* x, float* y, int64_t NC, int D, int H, int W, int OD, int OH, int OW, void* stream) {
   MUVO_CHECK_ARG(x && y && NC > 0, "resize_nearest_f32: bad args");
-  hipLaunchKernelGGL((resize_nearest_kernel<float>), dim3(ew_grid(NC * OD * OH * OW)), dim3(256), 0, ST, x, y, (long)NC, D, H,
-                     W, OD, OH, OW);
-  MUVO_CHECK_LAUNCH("resize_nearest_f32");
-  return MUVO_OK;
+  return launch_flat("resize_nearest_f32", resize_nearest_kernel<float>, NC * OD * OH * OW, stream, x, y, NC, D, H, W, OD, OH, OW);
 }
 int muvo_resize_nearest_u8(const uint8_t* x, uint8_t* y, int64_t NC, int D, int H, int W, int OD, int OH, int OW,
                            void* stream) {
   MUVO_CHECK_ARG(x && y && NC > 0, "resize_nearest_u8: bad args");
-  hipLaunchKernelGGL((resize_nearest_kernel<uint8_t>), dim3(ew_grid(NC * OD * OH * OW)), dim3(256), 0, ST, x, y, (long)NC, D,
-                     H, W, OD, OH, OW);
-  MUVO_CHECK_LAUNCH("resize_nearest_u8");
-  return MUVO_OK;
+  return launch_flat("resize_nearest_u8", resize_nearest_kernel<uint8_t>, NC * OD * OH * OW, stream, x, y, NC, D, H, W, OD, OH, OW);
 }
-// the MAXV instance of the softmax kernels for a checked row length (the launchers and muvo_softmax_dropout_route)
+// the MAXV instance of the softmax kernels for a checked row length (SOFTMAX_INSTANCE and muvo_softmax_dropout_route)
 static int softmax_dropout_maxv(int cols) { return cols <= 512 ? 8 : SOFTMAX_MAXV; }
 int muvo_softmax_dropout_route(int cols) {
   MUVO_CHECK_ARG(cols > 0 && cols <= 64 * SOFTMAX_MAXV, "softmax_route: bad args (cols=%d, max %d)", cols, 64 * SOFTMAX_MAXV);
@@ -1162,56 +1052,44 @@ int muvo_softmax_dropout_route(int cols) {
 int muvo_softmax_dropout_fwd(const float* S, float* P, float* Pd, int64_t rows, int cols, float p, uint64_t seed,
                              void* stream) {
   MUVO_CHECK_ARG(S && P && rows > 0 && cols > 0 && cols <= 64 * SOFTMAX_MAXV, "softmax_fwd: bad args (cols=%d, max %d)", cols, 64 * SOFTMAX_MAXV);
-  if (softmax_dropout_maxv(cols) == 8)
-    hipLaunchKernelGGL((softmax_dropout_fwd_kernel<8>), dim3(cdiv(rows, 4)), dim3(256), 0, ST, S, P, Pd, (long)rows, cols, p, seed);
-  else
-    hipLaunchKernelGGL((softmax_dropout_fwd_kernel<SOFTMAX_MAXV>), dim3(cdiv(rows, 4)), dim3(256), 0, ST, S, P, Pd, (long)rows, cols, p, seed);
+  hipLaunchKernelGGL(SOFTMAX_INSTANCE(softmax_dropout_fwd_kernel, cols), dim3(cdiv(rows, 4)), dim3(256), 0, ST, S, P, Pd, (long)rows, cols,
+                     p, seed);
   MUVO_CHECK_LAUNCH("softmax_fwd");
   return MUVO_OK;
 }
 int muvo_softmax_dropout_bwd(const float* P, const float* dPd, float* dS, int64_t rows, int cols, float p, uint64_t seed,
                              void* stream) {
   MUVO_CHECK_ARG(P && dPd && dS && rows > 0 && cols > 0 && cols <= 64 * SOFTMAX_MAXV, "softmax_bwd: bad args");
-  if (softmax_dropout_maxv(cols) == 8)
-    hipLaunchKernelGGL((softmax_dropout_bwd_kernel<8>), dim3(cdiv(rows, 4)), dim3(256), 0, ST, P, dPd, dS, (long)rows, cols, p, seed);
-  else
-    hipLaunchKernelGGL((softmax_dropout_bwd_kernel<SOFTMAX_MAXV>), dim3(cdiv(rows, 4)), dim3(256), 0, ST, P, dPd, dS, (long)rows, cols, p, seed);
+  hipLaunchKernelGGL(SOFTMAX_INSTANCE(softmax_dropout_bwd_kernel, cols), dim3(cdiv(rows, 4)), dim3(256), 0, ST, P, dPd, dS, (long)rows, cols,
+                     p, seed);
   MUVO_CHECK_LAUNCH("softmax_bwd");
   return MUVO_OK;
 }
 int muvo_gru_fwd(const float* gi, const float* gh, const float* h, float* hnew, int B, int H, void* stream) {
   MUVO_CHECK_ARG(gi && gh && h && hnew && B > 0 && H > 0, "gru_fwd: bad args");
-  hipLaunchKernelGGL(gru_fwd_kernel, dim3(ew_grid((long)B * H)), dim3(256), 0, ST, gi, gh, h, hnew, B, H);
-  MUVO_CHECK_LAUNCH("gru_fwd");
-  return MUVO_OK;
+  return launch_flat("gru_fwd", gru_fwd_kernel, (long)B * H, stream, gi, gh, h, hnew, B, H);
 }
 int muvo_gru_bwd(const float* gi, const float* gh, const float* h, const float* dhnew, float* dgi, float* dgh, float* dh,
                  int B, int H, void* stream) {
   MUVO_CHECK_ARG(gi && gh && h && dhnew && dgi && dgh && dh && B > 0 && H > 0, "gru_bwd: bad args");
-  hipLaunchKernelGGL(gru_bwd_kernel, dim3(ew_grid((long)B * H)), dim3(256), 0, ST, gi, gh, h, dhnew, dgi, dgh, dh, B, H);
-  MUVO_CHECK_LAUNCH("gru_bwd");
-  return MUVO_OK;
+  return launch_flat("gru_bwd", gru_bwd_kernel, (long)B * H, stream, gi, gh, h, dhnew, dgi, dgh, dh, B, H);
 }
 int muvo_rssm_sample_fwd(const float* mu_logsigma, const float* eps, int64_t eps_ld, float* mu, float* sigma, float* sample,
                          int B, int S, float min_std, void* stream) {
   MUVO_CHECK_ARG(mu_logsigma && mu && sigma && sample && B > 0 && S > 0, "rssm_sample_fwd: bad args");
-  hipLaunchKernelGGL(rssm_sample_fwd_kernel, dim3(ew_grid((long)B * S)), dim3(256), 0, ST, mu_logsigma, eps, (long)eps_ld, mu,
-                     sigma, sample, B, S, min_std);
-  MUVO_CHECK_LAUNCH("rssm_sample_fwd");
-  return MUVO_OK;
+  return launch_flat("rssm_sample_fwd", rssm_sample_fwd_kernel, (long)B * S, stream, mu_logsigma, eps, eps_ld, mu, sigma, sample, B, S,
+                     min_std);
 }
 int muvo_rssm_sample_bwd(const float* mu_logsigma, const float* eps, int64_t eps_ld, const float* dmu, const float* dsigma,
                          const float* dsample, float* dmls, int B, int S, void* stream) {
   MUVO_CHECK_ARG(mu_logsigma && dmls && B > 0 && S > 0, "rssm_sample_bwd: bad args");
-  hipLaunchKernelGGL(rssm_sample_bwd_kernel, dim3(ew_grid((long)B * S)), dim3(256), 0, ST, mu_logsigma, eps, (long)eps_ld, dmu,
-                     dsigma, dsample, dmls, B, S);
-  MUVO_CHECK_LAUNCH("rssm_sample_bwd");
-  return MUVO_OK;
+  return launch_flat("rssm_sample_bwd", rssm_sample_bwd_kernel, (long)B * S, stream, mu_logsigma, eps, eps_ld, dmu, dsigma, dsample, dmls,
+                     B, S);
 }
 
 }  // extern "C"
 
-// ------------------------------------------------------------------------------------------------
+// ================================================================================== not an element-wise operation of the model
 // Stand-in for the local footprint of a ring all-reduce on a one-GPU box (include/muvo_hip.h: muvo_fake_allreduce)
 __global__ void __launch_bounds__(256) fake_allreduce_kernel(f32x4* __restrict__ buf, long n4, int sleep) {
   const long stride = (long)gridDim.x * 256;
@@ -1235,73 +1113,7 @@ __global__ void __launch_bounds__(256) fake_allreduce_kernel(f32x4* __restrict__
 extern "C" int muvo_fake_allreduce(float* buf, int64_t n, int workgroups, int sleep, void* stream) {
   MUVO_CHECK_ARG(buf && n > 0 && n % 4 == 0 && ((uintptr_t)buf & 15) == 0, "fake_allreduce: n %% 4 == 0 and a 16-byte aligned buffer");
   MUVO_CHECK_ARG(workgroups >= 1 && workgroups <= 256 && sleep >= 0 && sleep <= 100000, "fake_allreduce: bad launch parameters");
-  hipLaunchKernelGGL(fake_allreduce_kernel, dim3(workgroups), dim3(256), 0, (hipStream_t)stream, (f32x4*)buf, (long)(n / 4), sleep);
+  hipLaunchKernelGGL(fake_allreduce_kernel, dim3(workgroups), dim3(256), 0, ST, (f32x4*)buf, (long)(n / 4), sleep);
   MUVO_CHECK_LAUNCH("fake_allreduce_kernel");
-  return MUVO_OK;
-}
-
-// ------------------------------------------------------------------------------------------------
-// Antialiased linear resize of (NC, H, W) float planes (include/muvo_hip.h: muvo_resize_bilinear_aa): EVAL.RESOLUTION of
-// PreProcess.forward (preprocess.py:209-210,252-273: torchvision 0.15.2 resize(antialias=True) = ATen _upsample_bilinear2d_aa).
-// One thread per output pixel; per axis the taps [lo, hi) and triangle weights of ATen's _compute_indices_min_size_weights_aa in
-// float32, normalised; horizontal sums first, then the vertical combination (the order of the separable reference kernel).
-struct AaTaps { int lo, n; float center, inv, total; };
-__device__ __forceinline__ AaTaps aa_taps(int o, int in_size, float scale) {
-  const float support = scale >= 1.f ? scale : 1.f;
-  AaTaps t;
-  t.inv = scale >= 1.f ? 1.f / scale : 1.f;
-  t.center = scale * ((float)o + 0.5f);
-  int lo = (int)(t.center - support + 0.5f), hi = (int)(t.center + support + 0.5f);
-  lo = lo < 0 ? 0 : lo;
-  hi = hi > in_size ? in_size : hi;
-  t.lo = lo;
-  t.n = hi - lo;
-  float tot = 0.f;
-  for (int j = 0; j < t.n; ++j) {
-    const float w = 1.f - fabsf(((float)(j + lo) - t.center + 0.5f) * t.inv);
-    tot += w > 0.f ? w : 0.f;
-  }
-  t.total = tot;
-  return t;
-}
-__device__ __forceinline__ float aa_weight(const AaTaps& t, int j) {
-  const float w = 1.f - fabsf(((float)(j + t.lo) - t.center + 0.5f) * t.inv);
-  return (w > 0.f ? w : 0.f) / t.total;
-}
-__global__ void __launch_bounds__(256) resize_bilinear_aa_kernel(const float* __restrict__ x, float* __restrict__ y,
-                                                                 float* __restrict__ ynorm, float m0, float m1, float m2, float s0,
-                                                                 float s1, float s2, long NC, int C, int H, int W, int OH, int OW) {
-  const float sh = (float)H / (float)OH, sw = (float)W / (float)OW;
-  const long total = NC * OH * OW;
-  for (long i = blockIdx.x * 256L + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
-    const int ox = (int)(i % OW), oy = (int)((i / OW) % OH);
-    const long nc = i / ((long)OW * OH);
-    const AaTaps tx = aa_taps(ox, W, sw), ty = aa_taps(oy, H, sh);
-    const float* p = x + nc * (long)H * W;
-    float acc = 0.f;
-    for (int r = 0; r < ty.n; ++r) {
-      const float* row = p + (long)(ty.lo + r) * W + tx.lo;
-      float rs = 0.f;
-      for (int j = 0; j < tx.n; ++j) rs += row[j] * aa_weight(tx, j);
-      acc += rs * aa_weight(ty, r);
-    }
-    y[i] = acc;
-    if (ynorm) {
-      const int c = (int)(nc % C);
-      const float m = c == 0 ? m0 : (c == 1 ? m1 : m2), sd = c == 0 ? s0 : (c == 1 ? s1 : s2);
-      ynorm[i] = (acc - m) / sd;
-    }
-  }
-}
-extern "C" int muvo_resize_bilinear_aa(const float* x, float* y, float* ynorm, const float* mean, const float* std, int64_t NC, int C, int H,
-                                       int W, int OH, int OW, void* stream) {
-  MUVO_CHECK_ARG(x && y && NC > 0 && C > 0 && H > 0 && W > 0 && OH > 0 && OW > 0, "resize_bilinear_aa: bad args");
-  MUVO_CHECK_ARG(ynorm == nullptr || (mean && std && C <= 3), "resize_bilinear_aa: the normalised copy needs mean / std of <= 3 channels");
-  float m[3] = {0.f, 0.f, 0.f}, s[3] = {1.f, 1.f, 1.f};
-  if (ynorm) for (int c = 0; c < C; ++c) { m[c] = mean[c]; s[c] = std[c]; }
-  const long total = (long)NC * OH * OW;
-  hipLaunchKernelGGL(resize_bilinear_aa_kernel, dim3(ew_grid(total)), dim3(256), 0, (hipStream_t)stream, x, y, ynorm, m[0], m[1], m[2],
-                     s[0], s[1], s[2], (long)NC, C, H, W, OH, OW);
-  MUVO_CHECK_LAUNCH("resize_bilinear_aa_kernel");
   return MUVO_OK;
 }

@@ -2116,7 +2116,7 @@ def upsample3d_x2(x):
     return Upsample3dFn.apply(x)
 
 
-UPSAMPLE_KERNELS = ('scalar', 'vec', 'vec8', 'walk', 'row')
+UPSAMPLE_KERNELS = ('scalar', 'vec', 'row')
 
 
 def upsample3d_route(backward, nc, d, h, w, in_addr=0, out_addr=0):

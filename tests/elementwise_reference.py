@@ -15,12 +15,12 @@ muvo_dropout over ones with the same seed, whose element index is row * cols + c
 
 Emulations (float32 on the CPU, every product and every sum rounded once: the library is built with -ffp-contract=off).
   upsample forward  'scalar' the nested form a (b (c v + fw v) + fh (..)) + fd (..);  'vec' the same form over the four clamped
-                    column slots of a lane;  'vec8' the four rows blended first ((w00 r00 + w01 r01) + w10 r10) + w11 r11 with
-                    lin_src weights, then 0.25 / 0.75 across columns;  'row' the same blend with the weights wd * wh of the
-                    2 x 2 block form (0.75 / 0.25 on both clamped planes, also at the borders)
+                    column slots of a lane;  'row' the four rows blended first ((w00 r00 + w01 r01) + w10 r10) + w11 r11 with the
+                    weights wd * wh of the 2 x 2 block form (0.75 / 0.25 on both clamped planes, also at the borders), then
+                    0.25 / 0.75 across columns
   upsample backward 'scalar' the gather (row sums over c, then acc += (wa wb) row);  'vec' acc += (wa wb) (column form) over the
-                    16 (a, b);  'walk' / 'row' plane contributions sum_b wb (column form) first, then (wa0 P + wa1 P) + (wa2 P +
-                    wa3 P) (the two differ only in clamped, zero-weighted loads, which add an exact 0)
+                    16 (a, b);  'row' plane contributions sum_b wb (column form) first, then (wa0 P + wa1 P) + (wa2 P + wa3 P)
+                    (clamped, zero-weighted loads add an exact 0)
   average pool      64 strided lanes, then the xor butterfly of wave_sum, then / S
   softmax, GRU, RSSM sample, activations: the kernel's own sequence with the host's expf / tanhf / expm1f
   bilinear resize   the kernel's float32 coordinates and weights; forward the nested two-row form, adjoint the gather order
@@ -31,7 +31,7 @@ the margin of 2 is gemm_reference.OWN_WORST's: another rounding order of the sam
 CPU test recomputes both tables and fails when they are stale.  No bar comes from a GPU run.
 
 Dispatch mirror.  upsample_plan / maxpool_plan / softmax_plan restate muvo_upsample3d_route / muvo_maxpool2d_route /
-muvo_softmax_dropout_route for default settings (MUVO_UPSAMPLE_WALK 2, MUVO_MAXPOOL_BWD_V8 1, MUVO_EW_GRID_CAP 4096)."""
+muvo_softmax_dropout_route (MUVO_EW_GRID_CAP at its default of 4096)."""
 import functools
 import math
 import zlib
@@ -54,9 +54,9 @@ TINY = 1e-30                 # floor of the relative-error denominators: results
 # TRANS_WORST: worst (rms, max e) of the plain float32 CPU evaluation of each kernel with expf / tanhf; the bar is 4 x that.
 # tests/test_elementwise_reference.py::test_bar_tables_are_not_stale recomputes every entry (within 2 % / never above).
 OWN_WORST = {
-    'up_fwd_row': (6.384e-08, 3.257e-07), 'up_fwd_vec8': (5.485e-08, 2.704e-07), 'up_fwd_vec': (5.342e-08, 2.717e-07),
+    'up_fwd_row': (6.384e-08, 3.257e-07), 'up_fwd_vec': (5.342e-08, 2.954e-07),
     'up_fwd_scalar': (5.611e-08, 2.486e-07),
-    'up_bwd_row': (7.776e-08, 4.139e-07), 'up_bwd_walk': (7.868e-08, 4.213e-07), 'up_bwd_vec': (8.306e-08, 4.410e-07),
+    'up_bwd_row': (7.776e-08, 4.139e-07), 'up_bwd_vec': (8.972e-08, 6.221e-07),
     'up_bwd_scalar': (1.022e-07, 4.409e-07),
     'avgpool_fwd': (6.046e-07, 1.565e-07),           # (rms against the rms of the MEANS, which cancel: larger than max e)
     # the kernels form their source coordinates in float32: 96 / 42 * 40.5 = 92.6 is rounded at ulp(92.6) / 2 = 3.8e-6, which is
@@ -72,8 +72,9 @@ TRANS_WORST = {          # rms here: rms of the normalised error (norm_stats)
 }
 # Measured on an MI355X by tests/test_elementwise_kernels_gpu.py (ELEMSTAT lines: largest max e / rms over all cases of a kernel
 # and the largest share of its bar).  Not the source of any bar.
-#   upsample forward   row 3.26e-7 / 6.38e-8   vec8 2.70e-7 / 5.48e-8   vec 2.72e-7 / 5.34e-8   scalar 2.49e-7 / 5.61e-8   (0.50 each)
-#   upsample backward  row 4.14e-7 / 7.78e-8   walk 4.21e-7 / 7.87e-8   vec 4.41e-7 / 8.31e-8   scalar 4.41e-7 / 1.02e-7   (0.50 each)
+#   upsample forward   row 3.26e-7 / 6.38e-8   vec 2.95e-7 / 5.34e-8   scalar 2.49e-7 / 5.61e-8   (0.50 each)
+#   upsample backward  row 4.14e-7 / 7.78e-8   vec 6.22e-7 / 8.97e-8   scalar 4.41e-7 / 1.02e-7   (0.50 each)
+#   (vec: with the shapes that the retired eight-outputs forward and block-per-plane backward kernels used to take)
 #   avgpool_fwd 1.57e-7 / 6.04e-7 (0.50)   resize_bilinear 5.37e-5 / 5.09e-6 (0.50)   resize_bilinear_bwd 7.64e-5 / 5.09e-6 (0.50)
 #   (a share of 0.50 is the emulation's own worst case: the kernel rounds exactly as emulated)
 #   softmax P 2.05e-6 / 2.29e-7 (0.25)   Pd 2.13e-6 / 2.06e-7 (0.25)   dS 1.74e-6 / 2.61e-7 (0.26)
@@ -125,15 +126,13 @@ def _pow2(v):
 
 
 def upsample_plan(backward, NC, D, H, W, in16=True, out16=True):
-    """muvo_upsample3d_route at default settings: dict(kernel, grid, block, segs, dseg)"""
-    oq, q8 = W // 2, W // 4
+    """muvo_upsample3d_route: dict(kernel, grid, block, segs, dseg)"""
+    oq = W // 2
     oq_ok = W % 4 == 0 and oq <= 64 and _pow2(oq)
     r = {'segs': 1, 'dseg': D, 'block': (256, 1, 1)}
     if not backward:
         if oq_ok and D + 1 <= 65535 and NC <= 65535 and in16 and out16:
             r.update(kernel='row', grid=(_cdiv((H + 1) * oq, 256), D + 1, NC))
-        elif W % 4 == 0 and q8 <= 64 and _pow2(q8) and 2 * D <= 65535 and NC <= 65535 and in16 and out16:
-            r.update(kernel='vec8', grid=(_cdiv(2 * H * q8, 256), 2 * D, NC))
         elif W % 2 == 0 and 2 * D <= 65535 and NC <= 65535 and out16:
             r.update(kernel='vec', grid=(_cdiv(2 * H * (2 * W // 4), 256), 2 * D, NC))
         else:
@@ -145,12 +144,6 @@ def upsample_plan(backward, NC, D, H, W, in16=True, out16=True):
             segs *= 2
         dseg = _cdiv(D, segs)
         r.update(kernel='row', dseg=dseg, segs=_cdiv(D, dseg), grid=(rg, _cdiv(D, dseg), NC))
-    elif W % 4 == 0 and 128 <= (W // 4) * H <= 1024 and NC <= 65535 and in16 and out16:
-        segs = 1
-        while NC * segs < 1024 and segs * 8 <= D:
-            segs *= 2
-        dseg = _cdiv(D, segs)
-        r.update(kernel='walk', dseg=dseg, segs=_cdiv(D, dseg), grid=(_cdiv(D, dseg), NC, 1), block=(W // 4, H, 1))
     elif W % 4 == 0 and D <= 65535 and NC <= 65535 and in16 and out16:
         r.update(kernel='vec', grid=(_cdiv(H * (W // 4), 256), D, NC))
     else:
@@ -159,9 +152,9 @@ def upsample_plan(backward, NC, D, H, W, in16=True, out16=True):
 
 
 # pointers each upsample kernel accesses with 16-byte instructions: (in, out)
-UPSAMPLE_NEEDS16 = {(0, 'row'): (True, True), (0, 'vec8'): (True, True), (0, 'vec'): (False, True), (0, 'scalar'): (False, False),
-                    (1, 'row'): (True, True), (1, 'walk'): (True, True), (1, 'vec'): (True, True), (1, 'scalar'): (False, False)}
-# (the backward row kernel stores dx as float2; the route asks for 16 bytes like the walking kernel it replaced)
+UPSAMPLE_NEEDS16 = {(0, 'row'): (True, True), (0, 'vec'): (False, True), (0, 'scalar'): (False, False),
+                    (1, 'row'): (True, True), (1, 'vec'): (True, True), (1, 'scalar'): (False, False)}
+# (the backward row kernel stores dx as float2; the route asks for 16 bytes all the same)
 
 
 def pool_out(n, k, s, p):
@@ -169,7 +162,7 @@ def pool_out(n, k, s, p):
 
 
 def maxpool_plan(backward, NC, H, W, k, s, p, in16=True, idx4=True, out16=True):
-    """muvo_maxpool2d_route at default settings: dict(k, load16, v8, grid, block)"""
+    """muvo_maxpool2d_route: dict(k, load16, v8, grid, block)"""
     OH, OW = pool_out(H, k, s, p), pool_out(W, k, s, p)
     r = {'k': k, 'load16': False, 'v8': False, 'block': (64, 4, 1)}
     if not backward:
@@ -205,11 +198,11 @@ UP_FWD_CASES = [
     ucase('row', 3, 2, 3, 8),
     ucase('row', 1, 3, 5, 128),          # OQ = 64: 384 live lanes, a partial second workgroup
     ucase('row', 2, 2, 7, 32),
-    ucase('vec8', 2, 2, 3, 256),         # 384 live lanes
-    ucase('vec8', 1, 1, 1, 256),
+    ucase('vec', 2, 2, 3, 256),          # W / 2 = 128 is past the row kernel: 768 live lanes, three workgroups
+    ucase('vec', 1, 1, 1, 256),
     ucase('vec', 2, 2, 3, 2), ucase('vec', 1, 3, 2, 6), ucase('vec', 2, 1, 4, 12), ucase('vec', 1, 2, 3, 20),
     ucase('vec', 3, 2, 3, 8, in16=False),          # a row shape with a misaligned x
-    ucase('vec', 1, 1, 1, 256, in16=False),        # a vec8 shape with a misaligned x
+    ucase('vec', 1, 1, 1, 256, in16=False),        # the widest shape with a misaligned x
     ucase('scalar', 2, 2, 3, 5), ucase('scalar', 1, 3, 3, 1),
     ucase('scalar', 65536, 1, 1, 4),     # NC beyond the z extent of a grid
     ucase('scalar', 3, 2, 3, 8, out16=False), ucase('scalar', 1, 1, 1, 256, out16=False), ucase('scalar', 2, 2, 3, 2, out16=False),
@@ -221,13 +214,14 @@ UP_BWD_CASES = [
     ucase('row', 2, 17, 6, 32),          # two segments of 9 and 8
     ucase('row', 1, 33, 3, 8),           # four segments, the last of 6
     ucase('row', 1, 16, 2, 16),          # two segments of 8
-    ucase('walk', 1, 1, 43, 12),         # 129 threads
-    ucase('walk', 2, 9, 43, 12),         # segments of 5 and 4
-    ucase('walk', 1, 8, 22, 24),         # segments of 4 and 4
-    ucase('walk', 1, 2, 341, 12),        # 1023 threads
-    ucase('walk', 1, 1, 2, 256),         # (W / 4) H = 128 exactly (W / 2 = 128 is past the row kernel)
-    ucase('walk', 1, 2, 16, 256),        # (W / 4) H = 1024 exactly
-    ucase('vec', 1, 2, 3, 12), ucase('vec', 1, 1, 42, 12), ucase('vec', 1, 1, 342, 12),      # 126 / 1026: either side of the walk range
+    # W / 2 no power of two <= 64: the float4 gather, one lane per four coarse columns, H (W / 4) lanes per (d, nc)
+    ucase('vec', 1, 1, 43, 12),          # 129 lanes
+    ucase('vec', 2, 9, 43, 12),
+    ucase('vec', 1, 8, 22, 24),
+    ucase('vec', 1, 2, 341, 12),         # 1023 lanes: four workgroups, the last with 255 live lanes
+    ucase('vec', 1, 1, 2, 256),          # W / 2 = 128 is past the row kernel: 128 lanes
+    ucase('vec', 1, 2, 16, 256),         # 1024 lanes: exactly four workgroups
+    ucase('vec', 1, 2, 3, 12), ucase('vec', 1, 1, 42, 12), ucase('vec', 1, 1, 342, 12),      # 9 / 126 / 1026 lanes
     ucase('scalar', 2, 2, 3, 5), ucase('scalar', 1, 2, 2, 6), ucase('scalar', 1, 3, 3, 2),
     ucase('scalar', 65536, 1, 1, 4),
     ucase('scalar', 1, 16, 2, 16, in16=False), ucase('scalar', 1, 2, 3, 12, in16=False),
@@ -372,7 +366,7 @@ def _col_blend(c, fault=None):
 
 
 def emu_up_fwd(kind, x, fault=None):
-    """float32 emulation of the forward kernel `kind` ('scalar', 'vec', 'vec8', 'row') on x (NC, D, H, W)"""
+    """float32 emulation of the forward kernel `kind` ('scalar', 'vec', 'row') on x (NC, D, H, W)"""
     assert x.dtype == torch.float32
     NC, D, H, W = x.shape
 
@@ -396,14 +390,9 @@ def emu_up_fwd(kind, x, fault=None):
         def lerp_w(r):
             return c * r[..., w0] + fw * r[..., w1]
         return a * (b * lerp_w(r00) + fh * lerp_w(r01)) + fd * (b * lerp_w(r10) + fh * lerp_w(r11))
-    if kind == 'vec8':
-        d0, d1, fd = _lin_src(D)
-        h0, h1, fh = _lin_src(H)
-        wd0, wd1, wh0, wh1 = 1 - fd, fd, 1 - fh, fh
-    else:
-        assert kind == 'row'
-        d0, d1, wd0, wd1 = _block_src(D)
-        h0, h1, wh0, wh1 = _block_src(H)
+    assert kind == 'row'
+    d0, d1, wd0, wd1 = _block_src(D)
+    h0, h1, wh0, wh1 = _block_src(H)
     wd0, wd1 = wd0.view(1, -1, 1, 1), wd1.view(1, -1, 1, 1)
     wh0, wh1 = wh0.view(1, 1, -1, 1), wh1.view(1, 1, -1, 1)
     w00, w01, w10, w11 = wd0 * wh0, wd0 * wh1, wd1 * wh0, wd1 * wh1
@@ -444,9 +433,9 @@ def _take(G, dim, k, n):
 
 
 def emu_up_bwd(kind, g, dseg=None, fault=None):
-    """float32 emulation of the backward kernel `kind` ('scalar', 'vec', 'walk', 'row') on g (NC, 2D, 2H, 2W).
+    """float32 emulation of the backward kernel `kind` ('scalar', 'vec', 'row') on g (NC, 2D, 2H, 2W).
     faults: 'last_col' / 'last_row' / 'last_plane' (weight 0.75 instead of 1 at the last index), 'same_lane', and for the walking
-    kernels 'no_lead_in' (every d segment but the first starts with its two lead-in planes at zero)"""
+    row kernel 'no_lead_in' (every d segment but the first starts with its two lead-in planes at zero)"""
     assert g.dtype == torch.float32
     NC, D, H, W = g.shape[0], g.shape[1] // 2, g.shape[2] // 2, g.shape[3] // 2
     wa, wb = _bwd_w(D, fault == 'last_plane'), _bwd_w(H, fault == 'last_row')
@@ -471,7 +460,7 @@ def emu_up_bwd(kind, g, dseg=None, fault=None):
                 col = _col_reduce(_take(Ga, 2, ib, H), W, cf)
                 acc = acc + (wa[ia].view(1, -1, 1, 1) * wb[ib].view(1, 1, -1, 1)) * col
         return acc
-    assert kind in ('walk', 'row')
+    assert kind == 'row'
     P = torch.zeros(NC, 2 * D, H, W)                          # plane contributions: sum over the four fine rows, in row order
     for ib in range(4):
         P = P + wb[ib].view(1, 1, -1, 1) * _col_reduce(_take(g, 2, ib, H), W, cf)
@@ -496,21 +485,16 @@ def up_owner(kind, backward, c, index, plan):
     if not backward and kind == 'row':
         idx = ((h + 1) // 2) * (W // 2) + w // 4
         s += f': workgroup ({idx // 256}, {(d + 1) // 2}, {nc}) lane {idx % 256}'
-    elif not backward and kind == 'vec8':
-        idx = h * (W // 4) + w // 8
-        s += f': workgroup ({idx // 256}, {d}, {nc}) lane {idx % 256}'
     elif kind == 'vec':
         idx = h * (W // 4 if backward else W // 2) + w // 4
         s += f': workgroup ({idx // 256}, {d}, {nc}) lane {idx % 256}'
     elif backward and kind == 'row':
         per = 256 // (W // 2)
         s += f': workgroup ({h // per}, {d // plan["dseg"]}, {nc}) lane {(h % per) * (W // 2) + w // 2}'
-    elif backward and kind == 'walk':
-        s += f': workgroup ({d // plan["dseg"]}, {nc}) thread ({w // 4}, {h})'
     else:
         flat = ((nc * n[0] + d) * n[1] + h) * n[2] + w
         s += f': grid-stride element {flat}, first pass workgroup {(flat // 256) % plan["grid"][0]} lane {flat % 256}'
-    if backward and kind in ('row', 'walk') and plan['segs'] > 1:
+    if backward and kind == 'row' and plan['segs'] > 1:
         s += f'; d segment {d // plan["dseg"]} of {plan["segs"]}' + (' (first plane of its segment)' if d % plan['dseg'] == 0 and d else '')
     return s + ('; border in ' + ''.join(border) if border else '; interior')
 

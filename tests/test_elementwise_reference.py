@@ -57,6 +57,18 @@ def test_upsample_mirror_equals_route_and_respects_alignment():
     print(f'ELEMSTAT upsample route sweep: {n} queries')
 
 
+def test_upsample_route_reports_three_kernels_per_direction():
+    """the route query never names a kernel outside scalar / vec / row, whatever the width and the alignment of the pointers"""
+    ops = _ops()
+    assert ops.UPSAMPLE_KERNELS == ('scalar', 'vec', 'row')
+    seen = {0: set(), 1: set()}
+    for W in range(1, 261):
+        for backward, in16, out16 in itertools.product((0, 1), (True, False), (True, False)):
+            for NC, D, H in ((1, 2, 3), (2, 16, 43), (65536, 1, 1)):
+                seen[backward].add(ops.upsample3d_route(backward, NC, D, H, W, _addr(in16), _addr(out16))['kernel'])
+    assert seen == {0: {'scalar', 'vec', 'row'}, 1: {'scalar', 'vec', 'row'}}, seen
+
+
 def test_maxpool_mirror_equals_route_and_respects_alignment():
     ops = _ops()
     seen = set()
@@ -108,12 +120,15 @@ def test_every_kernel_is_named_and_every_case_takes_its_route():
     by = {c['name']: R.upsample_plan(1, c['NC'], c['D'], c['H'], c['W']) for c in R.UP_BWD_CASES if c['in16'] and c['out16']}
     assert (by['row-2x17x6x32']['segs'], by['row-2x17x6x32']['dseg']) == (2, 9)             # 9 + 8
     assert (by['row-1x33x3x8']['segs'], by['row-1x33x3x8']['dseg']) == (4, 9)               # 9 + 9 + 9 + 6
-    assert (by['walk-2x9x43x12']['segs'], by['walk-2x9x43x12']['dseg']) == (2, 5)           # 5 + 4
-    assert by['walk-1x1x43x12']['block'] == (3, 43, 1) and by['walk-1x2x341x12']['block'] == (3, 341, 1)
-    assert by['walk-1x1x2x256']['block'] == (64, 2, 1) and by['walk-1x2x16x256']['block'] == (64, 16, 1)
+    assert (by['row-1x16x2x16']['segs'], by['row-1x16x2x16']['dseg']) == (2, 8)             # 8 + 8
+    assert (by['vec-2x9x43x12']['segs'], by['vec-2x9x43x12']['dseg']) == (1, 9)             # only the row kernel walks in segments
+    assert by['vec-2x9x43x12']['grid'] == (1, 9, 2) and by['vec-1x1x43x12']['grid'] == (1, 1, 1)        # 129 lanes
+    assert by['vec-1x2x341x12']['grid'] == (4, 2, 1) and by['vec-1x2x16x256']['grid'] == (4, 2, 1)      # 1023 / 1024 lanes
+    assert by['vec-1x1x2x256']['grid'] == (1, 1, 1)
+    assert all(p['block'] == (256, 1, 1) for p in by.values())
     assert by['row-1x2x5x128']['grid'] == (2, 1, 1)
     fw = {c['name']: R.upsample_plan(0, c['NC'], c['D'], c['H'], c['W']) for c in R.UP_FWD_CASES if c['in16'] and c['out16']}
-    assert fw['row-1x3x5x128']['grid'] == (2, 4, 1) and fw['vec8-2x2x3x256']['grid'] == (2, 4, 2)
+    assert fw['row-1x3x5x128']['grid'] == (2, 4, 1) and fw['vec-2x2x3x256']['grid'] == (3, 4, 2)
     for backward, cases in ((0, R.MAXPOOL_FWD_CASES), (1, R.MAXPOOL_BWD_CASES)):
         for c in cases:
             plan = R.maxpool_plan(backward, c['NC'], c['H'], c['W'], c['k'], c['s'], c['p'], c['in16'], True, c['out16'])
@@ -226,10 +241,13 @@ def test_bar_tables_are_not_stale_and_emulations_stay_within():
         print(f'ELEMSTAT worst float32 evaluation {k}: rms {rms:.3e} max e {e:.3e} (tabulated {t[0]:.3e} {t[1]:.3e})')
         # the host's expf / tanhf differ between C libraries and vector widths: a factor of 2 either way, against a bar of 4 x
         assert rms <= 2 * t[0] and t[0] <= 2 * rms and e <= 2 * t[1] and t[1] <= 2 * e, (k, rms, e, t)
-    # no bar is so loose that a float32 kernel could lose a term: all upsample bars are a few u
+    # no bar is so loose that a float32 kernel could lose a term.  The smallest term of an output or gradient element carries
+    # the weight 0.25^3 among at most 64 terms of weight <= 1, so losing it moves e by about 0.25^3 / sqrt(64) = 2e-3 = 3e4 u; the
+    # bars stay three orders of magnitude below that.  The largest is the float4 gather's: its 16 serial additions per element
+    # reach 10.4 u once among the 74304 elements of its largest case, so its bar is 20.8 u (the other kernels' stay below 16 u).
     for k in R.OWN_WORST:
         if k.startswith('up_'):
-            assert R.kernel_bar(k)[1] < 16 * R.U32, k
+            assert R.kernel_bar(k)[1] < (32 if k == 'up_bwd_vec' else 16) * R.U32, k
 
 
 def test_exact_emulations_are_exact():
@@ -264,20 +282,20 @@ def _case(cases, name):
 
 
 def test_planted_upsample_faults_fail():
-    for name in ('row-2x17x6x32', 'walk-2x9x43x12', 'vec-1x2x3x12', 'scalar-2x2x3x5', 'row-1x33x3x8', 'walk-1x8x22x24'):
+    for name in ('row-2x17x6x32', 'vec-2x9x43x12', 'vec-1x2x3x12', 'scalar-2x2x3x5', 'row-1x33x3x8', 'vec-1x8x22x24', 'row-1x16x2x16'):
         c = _case(R.UP_BWD_CASES, name)
         g = R.up_inputs(c, 1)
         ref, bar = R.ref_up_bwd(g), R.kernel_bar(f'up_bwd_{c["kernel"]}')
         assert R.within(R.error_stats(R.emu_up_bwd(c['kernel'], g), *ref), bar)
         for fault in ('last_col', 'last_row', 'last_plane'):
             _clear(f'{name} {fault}', R.error_stats(R.emu_up_bwd(c['kernel'], g, fault=fault), *ref), bar)
-        if c['kernel'] in ('row', 'walk'):
+        if c['kernel'] == 'row':
             plan = R.upsample_plan(1, c['NC'], c['D'], c['H'], c['W'])
             assert plan['segs'] > 1
             _clear(f'{name} no_lead_in', R.error_stats(R.emu_up_bwd(c['kernel'], g, dseg=plan['dseg'], fault='no_lead_in'), *ref), bar)
         if c['kernel'] == 'row':
             _clear(f'{name} same_lane', R.error_stats(R.emu_up_bwd('row', g, fault='same_lane'), *ref), bar)
-    for name in ('row-3x2x3x8', 'row-1x3x5x128', 'vec8-2x2x3x256'):
+    for name in ('row-3x2x3x8', 'row-1x3x5x128', 'row-2x2x7x32'):
         c = _case(R.UP_FWD_CASES, name)
         x = R.up_inputs(c, 0)
         _clear(f'fwd {name} same_lane', R.error_stats(R.emu_up_fwd(c['kernel'], x, fault='same_lane'), *R.ref_up_fwd(x)),
