@@ -960,6 +960,50 @@ int muvo_render_class_fwd(const float* logits, const uint8_t* labels, int64_t F,
 int muvo_render_class_bwd(const float* logits, int64_t F, int C, int X, int Y, int Z, const float* rays, int64_t R, int64_t n_valid, const double* mass,
                           const int32_t* target, float weight, const float* gout, void* ws, int64_t ws_bytes, float* dlogits, void* stream);
 
+/* ---- Euclidean distance transform of voxel grids, boundary loss and voxel Chamfer counts (edt.hip; extensions)
+ * OUR DEFINITIONS; tests/edt_reference.py restates them.
+ * Grid: a class grid is (F, X, Y, Z) uint8, z fastest.  A cell is OCCUPIED iff 1 <= v <= 254; 0 is free, 255 is "unknown" and never
+ *   occupied.  The class grid of a prediction is what muvo_raycast_bricks_logits writes (the first maximum over C: a tie with
+ *   class 0 is free).
+ * Transform: edt2(grid, cap)[f, v] = min(cap, min over the occupied cells u of frame f of |v - u|^2), an int32; distances in cells,
+ *   cap >= 1.  A frame without an occupied cell is `cap` everywhere; cap >= X^2 + Y^2 + Z^2 is the untruncated transform.  Exact in
+ *   integers.  Sizes: F in 1..65535, every axis >= 1 with X^2 + Y^2 + Z^2 < 2^31, F X Y Z < 2^36; everything else is refused before
+ *   the device is touched.  Three separable min-plus passes d(i) = min_j (i - j)^2 + d(j), z, y, x, capped after each; with
+ *   r^2 < cap only offsets |o| <= r are visited.  ws: muvo_voxel_edt_ws_bytes(F, X, Y, Z) bytes (-1 for refused sizes), 4-byte
+ *   aligned, the intermediate of the y pass; out (F, X, Y, Z) int32. */
+int64_t muvo_voxel_edt_ws_bytes(int64_t F, int X, int Y, int Z);
+int muvo_voxel_edt(const uint8_t* grid, int64_t F, int X, int Y, int Z, int32_t cap, void* ws, int64_t ws_bytes, int32_t* out, void* stream);
+/* Boundary loss: logits (F, C, X, Y, Z) fp32, 2 <= C <= 16, labels (F, X, Y, Z) uint8, truncation T >= 1 cells; the sizes of the
+ *   rendered losses (every axis in 1..2048, V = X Y Z < 2^30).  Per frame f: g = label occupied, k = label is 255, P = the
+ *   prediction's class grid occupied (a constant of the backward pass); q = s_0 = e_0 / sum_c e_c (fp32, e_c = exp(z_c - max),
+ *   the sum in ascending c), p = 1 - q; edt_label = edt2(label, T^2), edt_pred = edt2(P, T^2), dG = sqrt(edt_label) / T and
+ *   dP = sqrt(edt_pred) / T in fp32, both in [0, 1]; n_G = the occupied label cells.
+ *   L_f = (sum_{v: !g, !k} p dG + sum_{v: g} q dP) / n_G, the terms fp32 products, the sums fp64.
+ *   loss[0] = weight x the mean of L_f over the frames with n_G > 0, 0 without such a frame.  Both sums are divided by n_G: at
+ *   n_P = n_G and hard predictions the term is the truncated Chamfer distance in units of T.
+ *   Forward: per-workgroup fp64 partials, then one workgroup adds them in a fixed order: the same bits on every call in both modes
+ *   of muvo_set_deterministic.  n_g (F + 1) int32: n_G per frame, then the number of frames with n_G > 0 - kept for the backward.
+ *   ws: muvo_voxel_boundary_ws_bytes(F, V) bytes (-1 for refused sizes), 16-byte aligned, written then read.
+ *   Backward: elementwise, no atomics, every element of dlogits (F, C, X, Y, Z) written: w dp/dz_c with dp/dz_0 = -q p,
+ *   dp/dz_c = q s_c and w = gout weight / (frames n_G) x (dG where !g and !k, -dP where g, 0 where k): exactly 0 on 255 cells and
+ *   on frames with n_G = 0.  gout = the upstream gradient of the scalar, on the device. */
+int64_t muvo_voxel_boundary_ws_bytes(int64_t F, int64_t V);
+int muvo_voxel_boundary_forward(const float* logits, const uint8_t* labels, const int32_t* edt_label, const int32_t* edt_pred, int64_t F, int C, int X, int Y, int Z,
+                                int truncate, float weight, void* ws, int64_t ws_bytes, int32_t* n_g, float* loss, void* stream);
+int muvo_voxel_boundary_backward(const float* logits, const uint8_t* labels, const int32_t* edt_label, const int32_t* edt_pred, const int32_t* n_g, int64_t F, int C,
+                                 int X, int Y, int Z, int truncate, float weight, const float* gout, float* dlogits, void* stream);
+/* Voxel Chamfer / F-score counts of label grids G and prediction grids P (both (F, X, Y, Z) uint8, the sizes of the boundary loss)
+ *   from their UNTRUNCATED transforms edt_label = edt2(G, cap) and edt_pred = edt2(P, cap), cap >= X^2 + Y^2 + Z^2.  A frame where
+ *   either set is empty (its transform reaches X^2 + Y^2 + Z^2 at cell 0) is skipped and counted.  Every other frame adds to the
+ *   device accumulators counts (10) int64: [0] frames, [1] skipped frames, [2] n_P, [3] n_G, [4..6] hits_P[i] = #{v in P :
+ *   edt_label(v) <= thresholds2[i]}, [7..9] hits_G[i] = #{v in G : edt_pred(v) <= thresholds2[i]}, and sums (2) fp64:
+ *   sum_PG = sum_{v in P} sqrt((double)edt_label(v)), sum_GP = sum_{v in G} sqrt((double)edt_pred(v)).  thresholds2: 3 squared
+ *   distances in cells, integers >= 0, on the host.  Integer counts by 64-bit atomics after a combine per wave and workgroup, the
+ *   fp64 sums by per-workgroup partials that one wave adds in a fixed order.  ws: muvo_voxel_cd_ws_bytes(F, V) bytes, 8-byte aligned. */
+int64_t muvo_voxel_cd_ws_bytes(int64_t F, int64_t V);
+int muvo_voxel_cd_counts(const uint8_t* label, const uint8_t* pred, const int32_t* edt_label, const int32_t* edt_pred, int64_t F, int X, int Y, int Z,
+                         const int32_t* thresholds2, uint64_t* counts, double* sums, void* ws, int64_t ws_bytes, void* stream);
+
 /* ---- sensor-visibility mask of the voxel labels (visibility.hip; an extension) ----------------------------
  * OUR DEFINITION (the reference has no visibility mask; its SemScal / GeoScal losses carry ignore_index = 255 and nothing writes
  * one); tests/visibility_reference.py restates it and the kernels equal that restatement bit for bit.

@@ -34,6 +34,11 @@ TOLERATED_EXTRA_KEYS = ('CML_DATASET_VERSION', 'MODEL.TRANSFORMER_TRANSITION', '
 #   1, 2, 4; absent = [1, 2, 4]) names the output scales that get a term `voxel_render_class_{f}` = WEIGHT / f x
 #   render_class(voxel_f, voxel_label_f), STRIDE (an integer >= 1; absent = 1) takes every STRIDE-th azimuth of the range view as
 #   a ray - the table LOSSES.VOXEL_RENDER uses at the same stride.  Needs VOXEL_SEG.ENABLED.
+#   LOSSES.VOXEL_BOUNDARY.{WEIGHT,FACTORS,TRUNCATE_M} - the distance-transform boundary loss of the voxel head (a wrong voxel costs
+#   its distance to the other set's surface; the reference has none).  WEIGHT (float; absent = 0 = off) multiplies, FACTORS (a
+#   list drawn from 1, 2, 4; absent = [1, 2, 4]) names the output scales that get a term `voxel_boundary_{f}` = WEIGHT / f x
+#   boundary(voxel_f, voxel_target_f, T_f), TRUNCATE_M (a number > 0; absent = 4.0, RayIoU's largest threshold) truncates both
+#   distance transforms: T_f = max(1, round(TRUNCATE_M / (VOXEL.RESOLUTION f))) cells.  Needs VOXEL_SEG.ENABLED.
 #   VOXEL_SEG.VISIBILITY.{ENABLED,LIDAR_STRIDE,CAMERA_STRIDE} - the sensor-visibility mask of the voxel labels (the reference has
 #   none: its labels call every unobserved cell "free").  ENABLED (bool; absent = off: no table, no launch, no new batch key)
 #   makes PreProcess add `voxel_visible_label_{1,2,4}`: voxel_label_f with every free cell that no ray of the lidar sweep or the
@@ -47,6 +52,7 @@ EXTENSION_KEYS = ('MODEL.CONSTANT_SIZE', 'MODEL.CONSTANT_SIZE.RGB', 'MODEL.CONST
                   'LOSSES.VOXEL_RENDER', 'LOSSES.VOXEL_RENDER.WEIGHT', 'LOSSES.VOXEL_RENDER.FACTORS', 'LOSSES.VOXEL_RENDER.STRIDE',
                   'LOSSES.VOXEL_RENDER_CLASS', 'LOSSES.VOXEL_RENDER_CLASS.WEIGHT', 'LOSSES.VOXEL_RENDER_CLASS.FACTORS',
                   'LOSSES.VOXEL_RENDER_CLASS.STRIDE',
+                  'LOSSES.VOXEL_BOUNDARY', 'LOSSES.VOXEL_BOUNDARY.WEIGHT', 'LOSSES.VOXEL_BOUNDARY.FACTORS', 'LOSSES.VOXEL_BOUNDARY.TRUNCATE_M',
                   'VOXEL_SEG.VISIBILITY', 'VOXEL_SEG.VISIBILITY.ENABLED', 'VOXEL_SEG.VISIBILITY.LIDAR_STRIDE', 'VOXEL_SEG.VISIBILITY.CAMERA_STRIDE')
 DEFAULT_CONSTANT_SIZE = {'RGB': (5, 13), 'LIDAR': (1, 16), 'VOXEL': (3, 3, 1)}
 
@@ -134,6 +140,26 @@ def voxel_render_class(cfg):
     """(weight, factors, stride) of the rendered first-hit class loss: LOSSES.VOXEL_RENDER_CLASS.* if given, else
     (0.0, (1, 2, 4), 1); weight 0 = no such term.  The rules and texts of voxel_render."""
     return _rendered_loss(cfg, 'VOXEL_RENDER_CLASS', DEFAULT_VOXEL_RENDER_CLASS_FACTORS, DEFAULT_VOXEL_RENDER_CLASS_STRIDE)
+
+
+DEFAULT_VOXEL_BOUNDARY_FACTORS = (1, 2, 4)
+DEFAULT_VOXEL_BOUNDARY_TRUNCATE_M = 4.0            # RayIoU's largest threshold
+
+
+def voxel_boundary(cfg):
+    """(weight, factors, truncate_m) of the distance-transform boundary loss: LOSSES.VOXEL_BOUNDARY.* if given, else
+    (0.0, (1, 2, 4), 4.0); weight 0 = no such term.  WEIGHT and FACTORS by the rules and texts of voxel_render; TRUNCATE_M is a
+    number > 0, the truncation of both distance transforms in metres (voxel_boundary_cells turns it into cells)."""
+    weight, factors, _ = _rendered_loss(cfg, 'VOXEL_BOUNDARY', DEFAULT_VOXEL_BOUNDARY_FACTORS, 1)
+    truncate = (cfg.LOSSES.get('VOXEL_BOUNDARY', None) or {}).get('TRUNCATE_M', DEFAULT_VOXEL_BOUNDARY_TRUNCATE_M)
+    if isinstance(truncate, bool) or not isinstance(truncate, (int, float)) or not truncate > 0:
+        raise ValueError(f'LOSSES.VOXEL_BOUNDARY.TRUNCATE_M must be a number > 0, got {truncate!r}')
+    return weight, factors, float(truncate)
+
+
+def voxel_boundary_cells(cfg, truncate_m, f):
+    """the truncation in cells of scale f: max(1, round(TRUNCATE_M / (VOXEL.RESOLUTION f))) - 20, 10, 5 at the defaults"""
+    return max(1, int(round(truncate_m / (cfg.VOXEL.RESOLUTION * f))))
 
 
 DEFAULT_VISIBILITY_LIDAR_STRIDE = 1

@@ -113,6 +113,25 @@ class LovaszSoftmaxLoss(nn.Module):
         return ops.voxel_lovasz_loss(prediction, target, 1.0)[0]
 
 
+class BoundaryLoss(nn.Module):
+    """Distance-transform boundary loss of voxel logits (b, s, c, x, y, z) against uint8 labels (b, s, 1, x, y, z): per frame the
+    occupancy probability of every free cell times its distance to the label's nearest occupied cell plus the free probability of
+    every occupied label cell times its distance to the prediction's nearest occupied cell, both truncated at `truncate_cells`
+    and in units of it, over the label's occupied cells; the mean over the frames with such cells (not in
+    the reference).  Label 255 takes no part."""
+
+    def __init__(self, truncate_cells):
+        super().__init__()
+        if isinstance(truncate_cells, bool) or not isinstance(truncate_cells, int) or truncate_cells < 1:
+            raise ValueError(f'truncate_cells must be an integer >= 1, got {truncate_cells!r}')
+        self.truncate_cells = truncate_cells
+
+    def forward(self, prediction, target):
+        if prediction.dim() != 6 or target.dim() != 6:
+            raise ValueError(f'Expected 6-D logits and labels, got {tuple(prediction.shape)} and {tuple(target.shape)}')
+        return ops.voxel_boundary_loss(prediction, target, self.truncate_cells, 1.0)[0]
+
+
 class RenderedDepthLoss(nn.Module):
     """Rendered first-hit depth loss of voxel logits (b, s, c, x, y, z) against uint8 labels (b, s, 1, x, y, z) along the rays of
     one table (R, 7) float32 in grid units, on the device of the logits: the mean over frames and valid rays of |D - t*|, D the

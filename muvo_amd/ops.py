@@ -110,6 +110,9 @@ EXPORTS = [
     'muvo_lovasz_ws_bytes', 'muvo_lovasz_fwd', 'muvo_lovasz_bwd',
     'muvo_render_ws_bytes', 'muvo_render_fwd', 'muvo_render_bwd',
     'muvo_render_class_ws_bytes', 'muvo_render_class_fwd', 'muvo_render_class_bwd',
+    'muvo_voxel_edt_ws_bytes', 'muvo_voxel_edt',
+    'muvo_voxel_boundary_ws_bytes', 'muvo_voxel_boundary_forward', 'muvo_voxel_boundary_backward',
+    'muvo_voxel_cd_ws_bytes', 'muvo_voxel_cd_counts',
     'muvo_visibility_mark', 'muvo_visibility_apply',
 ]
 
@@ -138,7 +141,7 @@ def lib():
                 L.muvo_icp_ws_doubles.restype = C.c_int64
                 for name in ('muvo_flow_max_pairs', 'muvo_flow_workspace_bytes', 'muvo_flow_colour_ws_bytes', 'muvo_flow_epe_ws_doubles',
                              'muvo_raycast_brick_words', 'muvo_ray_iou_ws_doubles', 'muvo_lovasz_ws_bytes', 'muvo_render_ws_bytes',
-                             'muvo_render_class_ws_bytes'):
+                             'muvo_render_class_ws_bytes', 'muvo_voxel_edt_ws_bytes', 'muvo_voxel_boundary_ws_bytes', 'muvo_voxel_cd_ws_bytes'):
                     getattr(L, name).restype = C.c_int64
                 for name in EXPORTS:
                     getattr(L, name)  # AttributeError if a declared symbol is missing
@@ -3078,6 +3081,108 @@ def voxel_render_class_parts(logits, labels, rays, n_valid, weight=1.0):
     the loss has the bits of voxel_render_class_loss."""
     _, loss, mass, target, t_last, cells, _ = _render_class_forward(logits.detach(), labels, rays, n_valid, weight, True)
     return loss, mass, target, t_last, cells
+
+
+# ---- distance transform of voxel grids, boundary loss, voxel Chamfer counts (csrc/edt.hip; include/muvo_hip.h: muvo_voxel_edt) ----
+def voxel_edt(grid, cap):
+    """edt2 (F, X, Y, Z) int32 of a class grid (F, X, Y, Z) uint8: per cell min(cap, the squared distance in cells to the nearest
+    occupied cell (1..254) of its frame); `cap` everywhere in a frame without one.  cap >= X^2 + Y^2 + Z^2: untruncated."""
+    if grid.dtype != torch.uint8 or grid.dim() != 4:
+        raise ValueError(f'voxel_edt: a class grid (F, X, Y, Z) uint8, got {tuple(grid.shape)} {grid.dtype}')
+    grid = grid.contiguous()
+    F, X, Y, Z = (int(v) for v in grid.shape)
+    cap = int(cap)
+    n = int(lib().muvo_voxel_edt_ws_bytes(_i64(F), X, Y, Z)) if min(X, Y, Z) >= 1 and max(X, Y, Z) < 2 ** 31 else -1
+    if n < 0 or not 1 <= cap < 2 ** 31:
+        raise ValueError(f'voxel_edt: {F} frames of {X} x {Y} x {Z} with cap {cap} (1..65535 frames, every axis >= 1, '
+                         'X^2 + Y^2 + Z^2 < 2^31, fewer than 2^36 cells, 1 <= cap < 2^31)')
+    ws = torch.empty(max(4, n), device=grid.device, dtype=torch.uint8)
+    out = torch.empty((F, X, Y, Z), device=grid.device, dtype=torch.int32)
+    _ck(lib().muvo_voxel_edt(_p(grid), _i64(F), X, Y, Z, C.c_int32(cap), _p(ws), _i64(n), _p(out), _st()))
+    return out
+
+
+def _boundary_forward(logits, labels, truncate_cells, weight):
+    logits, labels = logits.contiguous(), labels.contiguous()
+    assert logits.dim() == 6 and logits.dtype == torch.float32, 'logits must be float32 (B,S,C,X,Y,Z)'
+    f, c, v = _voxel_dims(logits, labels)
+    X, Y, Z = (int(n) for n in logits.shape[3:])
+    T = int(truncate_cells)
+    n = int(lib().muvo_voxel_boundary_ws_bytes(_i64(f), _i64(v)))
+    if n < 0 or not 2 <= c <= 16 or not 1 <= T <= 46340 or max(X, Y, Z) > 2048:
+        raise ValueError(f'voxel_boundary_loss: {f} frames of {c} classes on {X} x {Y} x {Z} with a truncation of {T} cells (1..65535 frames, '
+                         '2..16 classes, 1..2048 per axis, fewer than 2^30 voxels, 1..46340 cells)')
+    dev = logits.device
+    pred = raycast_bricks(logits.detach().view(f, c, X, Y, Z))[0]
+    edt_label = voxel_edt(labels.view(f, X, Y, Z), T * T)
+    edt_pred = voxel_edt(pred, T * T)
+    ws = torch.empty(max(16, n), device=dev, dtype=torch.uint8)
+    n_g = torch.empty(f + 1, device=dev, dtype=torch.int32)
+    loss = torch.empty(1, device=dev, dtype=torch.float32)
+    _ck(lib().muvo_voxel_boundary_forward(_f(logits), _p(labels), _p(edt_label), _p(edt_pred), _i64(f), c, X, Y, Z, T, _fl(weight), _p(ws), _i64(n),
+                                          _p(n_g), _f(loss), _st()))
+    return logits, labels, loss, edt_label, edt_pred, pred, n_g, (f, c, X, Y, Z, T)
+
+
+class VoxelBoundaryFn(torch.autograd.Function):
+    """weight * distance-transform boundary loss (include/muvo_hip.h: muvo_voxel_boundary_forward) for logits
+    (B,S,C,X,Y,Z), labels u8 (B,S,1,X,Y,Z) and a truncation in cells.  The prediction's class grid and its transform are constants
+    of the backward pass.  Kept for it: the logits (the probabilities are recomputed), the labels, both transforms and n_G."""
+
+    @staticmethod
+    def forward(ctx, logits, labels, truncate_cells, weight, terms=False, grad_enabled=True):
+        need = ctx.needs_input_grad[0] and grad_enabled
+        logits, labels, loss, edt_label, edt_pred, _, n_g, dims = _boundary_forward(logits, labels, truncate_cells, weight)
+        ctx.dims, ctx.weight = dims, weight
+        if need:
+            ctx.save_for_backward(logits, labels, edt_label, edt_pred, n_g)
+        return _as_terms(ctx, loss, terms)
+
+    @staticmethod
+    def backward(ctx, g):
+        logits, labels, edt_label, edt_pred, n_g = ctx.saved_tensors
+        f, c, X, Y, Z, T = ctx.dims
+        g = _grad_scalar(g, logits.device)
+        dl = torch.empty_like(logits)
+        _ck(lib().muvo_voxel_boundary_backward(_f(logits), _p(labels), _p(edt_label), _p(edt_pred), _p(n_g), _i64(f), c, X, Y, Z, T, _fl(ctx.weight),
+                                               _f(g.contiguous()), _f(dl), _st()))
+        return dl, None, None, None, None, None
+
+
+def voxel_boundary_loss(logits, labels, truncate_cells, weight, terms=False):
+    """terms=True: a 1-tuple holding the 0-d loss instead of the (1,) tensor (as the other loss entry points)"""
+    return VoxelBoundaryFn.apply(logits, labels, truncate_cells, weight, terms, torch.is_grad_enabled())
+
+
+def voxel_boundary_parts(logits, labels, truncate_cells):
+    """What the loss is made of, for tests and the benchmark: (edt2 of the label (F, X, Y, Z) int32, edt2 of the prediction, the
+    prediction's class grid (F, X, Y, Z) uint8, n_G (F,) int32), both transforms capped at truncate_cells^2."""
+    _, _, _, edt_label, edt_pred, pred, n_g, _ = _boundary_forward(logits.detach(), labels, truncate_cells, 1.0)
+    return edt_label, edt_pred, pred, n_g[:-1].clone()
+
+
+def voxel_cd_counts(label, pred_grid, thresholds2, counts, sums):
+    """counts (10,) int64 - frames, skipped frames, n_P, n_G, hits_P[3], hits_G[3] - and sums (2,) float64 - sum_PG, sum_GP - on the
+    device are added to, over the F frames of the class grids label and pred_grid (F, X, Y, Z) uint8, from their untruncated
+    distance transforms (include/muvo_hip.h: muvo_voxel_cd_counts); thresholds2: three squared distances in cells, integers.
+    Nothing is read back."""
+    for t in (label, pred_grid):
+        assert t.dtype == torch.uint8 and t.dim() == 4, 'voxel_cd_counts: class grids (F, X, Y, Z) uint8'
+    label, pred_grid = label.contiguous(), pred_grid.contiguous()
+    assert label.shape == pred_grid.shape and label.device == pred_grid.device, 'voxel_cd_counts: label and prediction of one shape'
+    F, X, Y, Z = (int(v) for v in label.shape)
+    assert counts.dtype == torch.int64 and tuple(counts.shape) == (10,) and counts.is_contiguous() and counts.device == label.device
+    assert sums.dtype == torch.float64 and tuple(sums.shape) == (2,) and sums.is_contiguous() and sums.device == label.device
+    thr = [int(v) for v in thresholds2]
+    assert len(thr) == 3, 'voxel_cd_counts: three squared thresholds'
+    n = int(lib().muvo_voxel_cd_ws_bytes(_i64(F), _i64(X * Y * Z)))
+    if n < 0 or max(X, Y, Z) > 2048:
+        raise ValueError(f'voxel_cd_counts: {F} frames of {X} x {Y} x {Z} (1..65535 frames, 1..2048 per axis, fewer than 2^30 voxels)')
+    cap = X * X + Y * Y + Z * Z
+    edt_label, edt_pred = voxel_edt(label, cap), voxel_edt(pred_grid, cap)
+    ws = torch.empty(max(1, n // 8), device=label.device, dtype=torch.float64)
+    _ck(lib().muvo_voxel_cd_counts(_p(label), _p(pred_grid), _p(edt_label), _p(edt_pred), _i64(F), X, Y, Z, (C.c_int32 * 3)(*thr), _p(counts), _p(sums),
+                                   _p(ws), _i64(n), _st()))
 
 
 # ================================================================================================ ICP between lidar frames

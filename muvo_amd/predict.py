@@ -86,6 +86,8 @@ def build_parser():
     parser.add_argument('--ray-iou', action='store_true',
                         help='test: ray-based IoU of the voxel head (first hits of lidar-like rays through label and prediction) -> OUT/ray_iou.json')
     parser.add_argument('--ray-stride', type=int, default=4, metavar='K', help='--ray-iou: every K-th azimuth of the range view is a ray (default 4)')
+    parser.add_argument('--voxel-cd', action='store_true',
+                        help='test: Chamfer distance and F-scores at 1 / 2 / 4 m between the occupied cells of voxel label and prediction -> OUT/voxel_cd.json')
     parser.add_argument('--ego-motion', action='store_true',
                         help='test: drift of the ego path implied by the predicted lidar from the one implied by the recorded lidar -> OUT/ego_motion.json')
     parser.add_argument('--ego-threshold', type=float, default=5.0, metavar='M', help='ICP inlier distance in metres of --ego-motion and --traj (default 5, the reference)')
@@ -112,6 +114,8 @@ def parse_args(argv=None):
         raise SystemExit('--flow goes with --panels N')
     if (args.voxel or args.ray_iou) and args.mode != 'test':
         raise SystemExit('--voxel and --ray-iou go with --mode test')
+    if args.voxel_cd and args.mode != 'test':
+        raise SystemExit('--voxel-cd goes with --mode test')
     if args.voxel and not args.panels:
         raise SystemExit('--voxel goes with --panels N')
     if args.voxel_size < 1 or args.ray_stride < 1:
@@ -226,7 +230,7 @@ def seed_batch(module, seed, loader_idx, i):
 
 def run(cfg, device, out_dir, mode, loaders=None, limit_batches=None, shard_size=500, seed=1234, hook=None, dataset_root=None,
         data=None, module=None, log=print, panels=0, traj=False, ego_motion=None, icp_options=None, flow=False, optical_flow=False,
-        voxel=False, voxel_size=256, ray_iou=None):
+        voxel=False, voxel_size=256, ray_iou=None, voxel_cd=None):
     """Runs one mode and returns what it wrote: {'files': [...], 'batches': {loader: n}, 'metrics': {...}, 'confusion': {...} (test)}.
     hook(i, batch, output, output_imagine): called per batch with the device tensors (test mode: output_imagine is the list
     of imagined samples).  data: a set-up DataModule to take the test loaders from (default: one over dataset_root /
@@ -237,7 +241,9 @@ def run(cfg, device, out_dir, mode, loaders=None, limit_batches=None, shard_size
     max_iteration) of the ICP behind the `_traj` panel (default: 5 m, 1, 2000).  flow (test, with panels): also the `_flow` panel;
     optical_flow (test): muvo_amd.flow.FlowMetric runs on every batch and writes out_dir/optical_flow.json; metrics.json does
     not change.  voxel (test, with panels): also the `_voxel` panel with tiles of voxel_size pixels; ray_iou (test): dict(stride) -
-    muvo_amd.voxel_view.RayIoUMetric runs on every batch and writes out_dir/ray_iou.json; metrics.json does not change."""
+    muvo_amd.voxel_view.RayIoUMetric runs on every batch and writes out_dir/ray_iou.json; metrics.json does not change.  voxel_cd
+    (test): a dict (empty: no options) - muvo_amd.voxel_view.VoxelDistanceMetric runs on every batch and writes
+    out_dir/voxel_cd.json; metrics.json does not change."""
     refuse_multi_process()
     if mode not in ('test', 'sim'):
         raise ValueError(f'mode {mode!r}: test or sim')
@@ -260,9 +266,11 @@ def run(cfg, device, out_dir, mode, loaders=None, limit_batches=None, shard_size
     if mode == 'sim':
         if panels or traj or ego_motion is not None or flow or optical_flow or voxel or ray_iou is not None:
             raise ValueError('panels, the ego-motion metric, the optical-flow metric and the ray IoU belong to mode test')
+        if voxel_cd is not None:
+            raise ValueError('the voxel Chamfer distance belongs to mode test')
         return _run_sim(cfg, module, chosen, out_dir, limit_batches, shard_size, seed, hook, log)
     return _run_test(cfg, module, chosen, out_dir, limit_batches, shard_size, seed, hook, log, panels, traj, ego_motion, icp_options, flow, optical_flow,
-                     voxel, voxel_size, ray_iou)
+                     voxel, voxel_size, ray_iou, voxel_cd)
 
 
 def _batches(loader, limit):
@@ -273,13 +281,19 @@ def _batches(loader, limit):
 
 
 def _run_test(cfg, module, loaders, out_dir, limit_batches, shard_size, seed, hook, log, panels=0, traj=False, ego_motion=None, icp_options=None,
-              flow=False, optical_flow=False, voxel=False, voxel_size=256, ray_iou=None):
+              flow=False, optical_flow=False, voxel=False, voxel_size=256, ray_iou=None, voxel_cd=None):
     counts = {}
     writer, was_writer, was_traj, was_opt = None, module.panel_writer, module.traj_panels, module.traj_options
     ego, flow_metric, was_flow = None, None, module.flow_panels
     ray_metric, was_voxel, was_vopt = None, module.voxel_panels, module.voxel_options
     if (voxel or ray_iou is not None) and not cfg.VOXEL_SEG.ENABLED:
         raise ValueError('the ray IoU and the `_voxel` panel need the voxel head (VOXEL_SEG.ENABLED)')
+    if voxel_cd is not None and not cfg.VOXEL_SEG.ENABLED:
+        raise ValueError('the voxel Chamfer distance needs the voxel head (VOXEL_SEG.ENABLED)')
+    cd_metric = None
+    if voxel_cd is not None:
+        from muvo_amd.voxel_view import VoxelDistanceMetric
+        cd_metric = VoxelDistanceMetric(cfg, **voxel_cd)
     if ray_iou is not None:
         from muvo_amd.voxel_view import RayIoUMetric
         ray_metric = RayIoUMetric(cfg, **ray_iou)
@@ -309,6 +323,8 @@ def _run_test(cfg, module, loaders, out_dir, limit_batches, shard_size, seed, ho
                 flow_metric.start_loader(idx)
             if ray_metric is not None:
                 ray_metric.start_loader(idx)
+            if cd_metric is not None:
+                cd_metric.start_loader(idx)
             for i, batch in _batches(loader, limit_batches):
                 seed_batch(module, seed, idx, i)
                 module.panel_writer = writer if i < panels else None
@@ -324,6 +340,8 @@ def _run_test(cfg, module, loaders, out_dir, limit_batches, shard_size, seed, ho
                     flow_metric.update(i, batch, output, output_imagines)
                 if ray_metric is not None:
                     ray_metric.update(i, batch, output, output_imagines)
+                if cd_metric is not None:
+                    cd_metric.update(i, batch, output, output_imagines)
                 counts[idx] += 1
     finally:
         module.panel_writer, module.traj_panels, module.traj_options, module.flow_panels = was_writer, was_traj, was_opt, was_flow
@@ -359,6 +377,10 @@ def _run_test(cfg, module, loaders, out_dir, limit_batches, shard_size, seed, ho
         files.append(ray_metric.write(out_dir))
         out['ray_iou'] = ray_metric.result()
         log(json.dumps({'ray_iou': out['ray_iou']}))
+    if cd_metric is not None:
+        files.append(cd_metric.write(out_dir))
+        out['voxel_cd'] = cd_metric.result()
+        log('voxel_cd ' + json.dumps(out['voxel_cd'], sort_keys=True))
     return out
 
 
@@ -419,7 +441,7 @@ def main(argv=None):
         ego_motion=dict(threshold=args.ego_threshold, stride=args.ego_stride, max_iteration=args.ego_max_iteration) if args.ego_motion else None,
         icp_options=dict(threshold=args.ego_threshold, source_stride=args.ego_stride, max_iteration=args.ego_max_iteration),
         flow=args.flow, optical_flow=args.optical_flow, voxel=args.voxel, voxel_size=args.voxel_size,
-        ray_iou=dict(stride=args.ray_stride) if args.ray_iou else None)
+        ray_iou=dict(stride=args.ray_stride) if args.ray_iou else None, voxel_cd={} if args.voxel_cd else None)
 
 
 if __name__ == '__main__':

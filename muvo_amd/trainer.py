@@ -14,7 +14,8 @@ import numpy as np
 import torch
 
 from muvo_amd import ops
-from muvo_amd.config import get_cfg, lidar_cd, voxel_lovasz, voxel_render, voxel_render_class, voxel_visibility
+from muvo_amd.config import (get_cfg, lidar_cd, voxel_boundary, voxel_boundary_cells, voxel_lovasz, voxel_render, voxel_render_class,
+                             voxel_visibility)
 from muvo_amd.models.mile import Mile
 from muvo_amd.models.preprocess import PreProcess
 from muvo_amd.optim import FusedAdamW
@@ -500,6 +501,14 @@ class WorldModelTrainer(_Base):
                 rays, n_valid = render_table(cfg, f, rc_stride, tuple(pred.shape[3:]), pred.device)
                 losses[f'voxel_render_class_{f}'] = ops.voxel_render_class_loss(pred, batch[f'voxel_label_{f}'], rays, n_valid, w_rc * (1 / f),
                                                                                 terms=True)[0]
+        # the distance-transform boundary loss of the voxel head (extension, config.py: LOSSES.VOXEL_BOUNDARY; absent = off: no
+        # term, no launch), last for the same reason; like the Lovasz term it reads the visible labels when the mask is on - 255
+        # cells are inert by its definition
+        w_bd, bd_factors, bd_truncate = voxel_boundary(cfg)
+        if w_bd > 0:
+            for f in bd_factors:
+                losses[f'voxel_boundary_{f}'] = ops.voxel_boundary_loss(output[f'voxel_{f}'], voxel_target(cfg, batch, f),
+                                                                        voxel_boundary_cells(cfg, bd_truncate, f), w_bd * (1 / f), terms=True)[0]
         return losses
 
     def _seg_loss(self, tag, c, is_bev=False):

@@ -295,3 +295,85 @@ class RayIoUMetric:
             json.dump(self.result(), fh, indent=1, sort_keys=True)
             fh.write('\n')
         return path
+
+
+def cd_thresholds2(resolution, thresholds=THRESHOLDS):
+    """RayIoU's thresholds in metres as squared distances in cells: floor((thr / resolution)^2 + 1e-9) - 25, 100, 400 at 0.2 m"""
+    return [int(math.floor((t / resolution) ** 2 + 1e-9)) for t in thresholds]
+
+
+class VoxelDistanceMetric:
+    """`predict --mode test --voxel-cd`: per loader the Chamfer distance and the F-scores at 1 / 2 / 4 m between the occupied cells
+    of `voxel_label_1` (unmasked) and of the prediction's class grid, from the untruncated distance transforms of both grids
+     - the reconstructed frames and, apart from them, the frames of the first imagined sample.  `update` is the
+    per-batch hook of predict.run and only queues kernels (integer counts and fp64 sums stay on the device); `result()` reads them
+    once per loader."""
+
+    def __init__(self, cfg, prefix='test'):
+        self.cfg, self.prefix = cfg, prefix
+        self.thresholds2 = cd_thresholds2(float(cfg.VOXEL.RESOLUTION))
+        self.loader = None
+        self.acc = {}
+
+    def start_loader(self, idx):
+        self.loader = str(idx)
+        self.acc[self.loader] = dict(counts=None, sums=None)
+
+    def _add(self, a, which, label, pred):
+        from muvo_amd import ops
+        if not pred.shape[0]:
+            return
+        if a['counts'] is None:
+            a['counts'] = torch.zeros((2, 10), dtype=torch.int64, device=pred.device)
+            a['sums'] = torch.zeros((2, 2), dtype=torch.float64, device=pred.device)
+        ops.voxel_cd_counts(label, ops.raycast_bricks(pred)[0], self.thresholds2, a['counts'][which], a['sums'][which])
+
+    def update(self, i, batch, output, output_imagines):
+        if self.loader is None:
+            self.start_loader(0)
+        a = self.acc[self.loader]
+        pred = output['voxel_1'].detach().float()
+        b, rf = pred.shape[:2]
+        label = batch['voxel_label_1']
+        label = (label[:, :, 0] if label.dim() == 6 else label).to(torch.uint8)
+        with torch.no_grad():
+            self._add(a, 0, _frames(label[:, :rf].contiguous()), _frames(pred))
+            if output_imagines:
+                im = output_imagines[0]['voxel_1'].detach().float()
+                self._add(a, 1, _frames(label[:, rf:rf + im.shape[1]].contiguous()), _frames(im))
+
+    @staticmethod
+    def summarise(counts, sums, resolution):
+        """counts (2, 10) - frames, skipped, n_P, n_G, hits_P[3], hits_G[3] - and sums (2, 2) - sum_PG, sum_GP - as nested lists ->
+        the figures of one loader without its prefix; a figure whose denominator is 0 is 0.0"""
+        def ratio(a, b):
+            return a / b if b else 0.0
+        out = {}
+        for which, tail in ((0, ''), (1, '_imagine')):
+            frames, skipped, n_p, n_g = (int(v) for v in counts[which][:4])
+            out[f'voxel_cd{tail}'] = float(resolution) * (ratio(sums[which][0], n_p) + ratio(sums[which][1], n_g))
+            for k, thr in enumerate(THRESHOLDS):
+                p, r = ratio(int(counts[which][4 + k]), n_p), ratio(int(counts[which][7 + k]), n_g)
+                out[f'voxel_precision_{int(thr)}m{tail}'] = p
+                out[f'voxel_recall_{int(thr)}m{tail}'] = r
+                out[f'voxel_fscore_{int(thr)}m{tail}'] = ratio(2 * p * r, p + r)
+            out[f'voxel_cd_frames{tail}'] = frames
+            out[f'voxel_cd_skipped{tail}'] = skipped
+        return out
+
+    def result(self):
+        out = {}
+        for idx, a in self.acc.items():
+            if a['counts'] is None:
+                counts, sums = [[0] * 10] * 2, [[0.0, 0.0]] * 2
+            else:
+                counts, sums = a['counts'].cpu().tolist(), a['sums'].cpu().tolist()
+            out.update({f'{self.prefix}{idx}_{k}': v for k, v in self.summarise(counts, sums, self.cfg.VOXEL.RESOLUTION).items()})
+        return out
+
+    def write(self, out_dir):
+        path = os.path.join(out_dir, 'voxel_cd.json')
+        with open(path, 'w') as fh:
+            json.dump(self.result(), fh, indent=1, sort_keys=True)
+            fh.write('\n')
+        return path
