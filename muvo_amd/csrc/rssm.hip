@@ -153,8 +153,8 @@ __global__ void __launch_bounds__(RSSM_THREADS) rssm_fwd_kernel(const RssmFwdArg
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int gw = blockIdx.x * RSSM_WPB + wave, NW = gridDim.x * RSSM_WPB;
   const long gtid = (long)blockIdx.x * RSSM_THREADS + tid, gthreads = (long)gridDim.x * RSSM_THREADS;
-  float* xa = lds;                 // stage inputs: [B][<= HQ]
-  float* xb = xa + B * HQ;         //               [B][<= HP]
+  float* xa = lds;                 // stage inputs: [B][<= max(HQ, S)] (stage 0 holds z_{t-1}: S floats per sequence)
+  float* xb = xa + B * (HQ > S ? HQ : S);   //      [B][<= HP]
   float* hs = xb + B * HP;         // h_{t-1}: [B][H], kept through stage 1
   float* as = hs + B * H;          // a_{t-1}: [B][AD]
   unsigned target = 0;
@@ -274,9 +274,10 @@ __global__ void __launch_bounds__(RSSM_THREADS) rssm_bwd_kernel(const RssmBwdArg
   const int HP = H + A, HQ = H + E + A;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int gw = blockIdx.x * RSSM_WPB + wave, NW = gridDim.x * RSSM_WPB;
-  float* xa = lds;                 // [B][<= max(HQ, 3H)]
-  float* xb = xa + B * (HQ > 3 * H ? HQ : 3 * H);   // [B][<= max(HP, 3H)]
-  float* dd = xb + B * (HP > 3 * H ? HP : 3 * H);   // direct dh_{t-1} path: [B][H]
+  const int M3 = 3 * H > 2 * S ? 3 * H : 2 * S;     // B2 holds dgi / dgh (3H), B0 holds dmls (2S) in both buffers
+  float* xa = lds;                 // [B][<= max(HQ, 3H, 2S)]
+  float* xb = xa + B * (HQ > M3 ? HQ : M3);         // [B][<= max(HP, 3H, 2S)]
+  float* dd = xb + B * (HP > M3 ? HP : M3);         // direct dh_{t-1} path: [B][H]
   unsigned target = 0;
   for (int t = T - 1; t >= 0; --t) {
     const bool up = (a.use_prior >> t) & 1ull;       // the carry dz of step t+1 belongs to the prior (else posterior) sample
@@ -453,11 +454,12 @@ static bool rssm_dims_ok(const RssmDims& d) {
   return d.B >= 1 && d.B <= 64 && d.T >= 1 && d.T <= 64 && d.H % 4 == 0 && d.S % 4 == 0 && d.E % 4 == 0 && d.A % 4 == 0 &&
          d.AD >= 1 && d.H > 0 && d.S > 0 && d.E > 0 && d.A > 0;
 }
-static size_t rssm_fwd_lds(int B, int H, int E, int A, int AD) {
-  return sizeof(float) * ((size_t)B * ((H + E + A) + (H + A) + H + AD) + 16);
+static size_t rssm_fwd_lds(int B, int H, int S, int E, int A, int AD) {
+  const int HQ = H + E + A;
+  return sizeof(float) * ((size_t)B * ((HQ > S ? HQ : S) + (H + A) + H + AD) + 16);
 }
-static size_t rssm_bwd_lds(int B, int H, int E, int A) {
-  const int HP = H + A, HQ = H + E + A, m1 = HQ > 3 * H ? HQ : 3 * H, m2 = HP > 3 * H ? HP : 3 * H;
+static size_t rssm_bwd_lds(int B, int H, int S, int E, int A) {
+  const int HP = H + A, HQ = H + E + A, m3 = 3 * H > 2 * S ? 3 * H : 2 * S, m1 = HQ > m3 ? HQ : m3, m2 = HP > m3 ? HP : m3;
   return sizeof(float) * ((size_t)B * (m1 + m2 + H) + 16);
 }
 
@@ -469,7 +471,7 @@ int muvo_rssm_supported(int B, int T, int H, int S, int E, int A, int AD) {
   const RssmDims d = {B, T, H, S, E, A, AD};
   if (!rssm_dims_ok(d) || !rssm_dev()) return 0;
   const int Bc = B < RSSM_BM ? B : RSSM_BM;
-  return rssm_fwd_lds(Bc, H, E, A, AD) <= RSSM_MAX_DYN_LDS && rssm_bwd_lds(Bc, H, E, A) <= RSSM_MAX_DYN_LDS ? 1 : 0;
+  return rssm_fwd_lds(Bc, H, S, E, A, AD) <= RSSM_MAX_DYN_LDS && rssm_bwd_lds(Bc, H, S, E, A) <= RSSM_MAX_DYN_LDS ? 1 : 0;
 }
 int64_t muvo_rssm_transposed_floats(int H, int S, int E, int A) {
   const int64_t HP = H + A, HQ = H + E + A;
@@ -489,7 +491,7 @@ int muvo_rssm_forward(int B, int T, int H, int S, int E, int A, int AD, const fl
   a.use_prior = use_prior_mask; a.bar = barrier_word; a.min_std = min_std;
   const int HP = H + A, HQ = H + E + A;
   const int Bmax = B < RSSM_BM ? B : RSSM_BM;
-  const size_t ldsb = rssm_fwd_lds(Bmax, H, E, A, AD);
+  const size_t ldsb = rssm_fwd_lds(Bmax, H, S, E, A, AD);
   MUVO_CHECK_ARG(ldsb <= RSSM_MAX_DYN_LDS, "rssm_forward: LDS");
   RssmDev* dv = rssm_dev();
   MUVO_CHECK_ARG(dv, "rssm_forward: cannot query the device");
@@ -543,7 +545,7 @@ int muvo_rssm_backward(int B, int T, int H, int S, int E, int A, int AD, const f
   for (int i = 0; i < 5; ++i) MUVO_CHECK_ARG(kept5[i], "rssm_backward: kept tensor %d is NULL", i);
   for (int i = 0; i < 10; ++i) MUVO_CHECK_ARG(grads10[i], "rssm_backward: gradient buffer %d is NULL", i);
   const int Bmax = B < RSSM_BM ? B : RSSM_BM;
-  const size_t ldsb = rssm_bwd_lds(Bmax, H, E, A);
+  const size_t ldsb = rssm_bwd_lds(Bmax, H, S, E, A);
   MUVO_CHECK_ARG(ldsb <= RSSM_MAX_DYN_LDS, "rssm_backward: LDS");
   RssmDev* dv = rssm_dev();
   MUVO_CHECK_ARG(dv, "rssm_backward: cannot query the device");
