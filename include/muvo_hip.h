@@ -378,8 +378,9 @@ int muvo_attention_stream_bwd(const float* qkv, const float* out, const float* d
  *   W_post2: dmls_post x y1_post; W_post0: dy1_post x x_post; W_prior2: dmls_prior x y1_prior; W_prior0: dy1_prior x x_prior;
  *   W_ih: dgi x u; W_hh: dgh x h_prev; W_pre: du x z_prev; action modules: dla x a_prev; biases: column sums of the dY.
  *   wt_scratch: muvo_rssm_transposed_floats() floats (the transposed weights are rebuilt by every call); scratch:
- *   muvo_rssm_scratch_floats() floats; barrier_word: 8 bytes of device memory, zero before the first call: [0] the
- *   barrier counter (reset by every launch), [1] the sticky time-out flag (the caller polls it: ops.rssm_check). */
+ *   muvo_rssm_scratch_floats() floats; barrier_word: four 32-bit words of device memory (ops.rssm_barrier_words), zero
+ *   before the first call: [0] the barrier counter (reset by every launch), [1] the sticky time-out flag (the caller polls
+ *   it: ops.rssm_check); the kernels touch no other word.  csrc/rssm.hip names the entries of every table in these orders. */
 int muvo_rssm_supported(int B, int T, int H, int S, int E, int A, int AD);
 int64_t muvo_rssm_transposed_floats(int H, int S, int E, int A);
 int64_t muvo_rssm_scratch_floats(int B, int H, int S, int E, int A);

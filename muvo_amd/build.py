@@ -92,7 +92,7 @@ def _stale(out, deps):
 
 def build(force=False, verbose=True):
     hipcc = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
-    hdrs = [os.path.join(CSRC, 'common.h'), os.path.join(CSRC, 'conv_vox.h'), os.path.join(CSRC, 'conv_pw.h'), os.path.join(CSRC, 'conv_plan.h'), os.path.join(CSRC, 'conv_bf3.h'), os.path.join(CSRC, 'input_dev.h'), os.path.join(CSRC, 'icp_fit.h'), os.path.join(CSRC, 'voxel_grid.h'), os.path.join(CSRC, 'resample.h'), os.path.join(HERE, '..', 'include', 'muvo_hip.h'),
+    hdrs = [os.path.join(CSRC, 'common.h'), os.path.join(CSRC, 'conv_vox.h'), os.path.join(CSRC, 'conv_pw.h'), os.path.join(CSRC, 'conv_plan.h'), os.path.join(CSRC, 'conv_bf3.h'), os.path.join(CSRC, 'input_dev.h'), os.path.join(CSRC, 'icp_fit.h'), os.path.join(CSRC, 'voxel_grid.h'), os.path.join(CSRC, 'resample.h'), os.path.join(CSRC, 'rssm_cell.h'), os.path.join(HERE, '..', 'include', 'muvo_hip.h'),
             os.path.abspath(__file__)]   # the flags are part of the recipe
     objdir = os.path.join(HERE, 'build')
     os.makedirs(objdir, exist_ok=True)

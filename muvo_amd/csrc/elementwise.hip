@@ -4,6 +4,7 @@
 // (common.py:169), PreProcess (preprocess.py:102-225), attention softmax(+dropout), GRU / RSSM pointwise
 // math (transition.py:18-24,160-181).  All coalesced, grid-stride.
 #include "resample.h"
+#include "rssm_cell.h"
 
 #define GRID_STRIDE(i, n) for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < (n); i += (long)gridDim.x * blockDim.x)
 
@@ -717,24 +718,14 @@ __global__ void __launch_bounds__(256) softmax_dropout_bwd_kernel(const float* _
 }
 
 // ---------------------------------------------------------------------------------------- RSSM
-// torch.nn.GRUCell: r = s(gi_r+gh_r), z = s(gi_z+gh_z), n = tanh(gi_n + r*gh_n), h' = (1-z)*n + z*h
-struct GruGates { float r, z, n, ghn; };
-// the gates of element j of a sequence whose rows of gi / gh (3 H floats: r | z | n) start at a / c
-__device__ __forceinline__ GruGates gru_gates(const float* __restrict__ a, const float* __restrict__ c, int H, long j) {
-  GruGates g;
-  g.r = sigmoidf_(a[j] + c[j]);
-  g.z = sigmoidf_(a[H + j] + c[H + j]);
-  g.ghn = c[2 * H + j];
-  g.n = tanhf(a[2 * H + j] + g.r * g.ghn);
-  return g;
-}
+// the per-op path of the GRU cell and the sample step (rssm_cell.h); rows of gi / gh are 3 H floats: r | z | n
 __global__ void gru_fwd_kernel(const float* __restrict__ gi, const float* __restrict__ gh, const float* __restrict__ h,
                                float* __restrict__ hn, int B, int H) {
   const long n = (long)B * H;
   GRID_STRIDE(i, n) {
     const long b = i / H, j = i - b * H;
-    const GruGates q = gru_gates(gi + b * 3 * H, gh + b * 3 * H, H, j);
-    hn[i] = (1.f - q.z) * q.n + q.z * h[i];
+    const float *a = gi + b * 3 * H, *c = gh + b * 3 * H;
+    hn[i] = gru_combine(gru_gates(a[j], a[H + j], a[2 * H + j], c[j], c[H + j], c[2 * H + j]), h[i]);
   }
 }
 __global__ void gru_bwd_kernel(const float* __restrict__ gi, const float* __restrict__ gh, const float* __restrict__ h,
@@ -743,24 +734,18 @@ __global__ void gru_bwd_kernel(const float* __restrict__ gi, const float* __rest
   const long n = (long)B * H;
   GRID_STRIDE(i, n) {
     const long b = i / H, j = i - b * H;
-    const GruGates q = gru_gates(gi + b * 3 * H, gh + b * 3 * H, H, j);
-    const float r = q.r, z = q.z, nn = q.n, ghn = q.ghn;
-    const float g = dhn[i];
-    const float dn = g * (1.f - z);
-    const float dz = g * (h[i] - nn);
-    const float dpre_n = dn * (1.f - nn * nn);
-    const float dr = dpre_n * ghn;
-    const float dpre_r = dr * r * (1.f - r);
-    const float dpre_z = dz * z * (1.f - z);
+    const float *a = gi + b * 3 * H, *c = gh + b * 3 * H;
+    const float ghn = c[2 * H + j];
+    const GruAdjoint d = gru_adjoint(gru_gates(a[j], a[H + j], a[2 * H + j], c[j], c[H + j], ghn), ghn, h[i], dhn[i]);
     float* da = dgi + b * 3 * H;
     float* dc = dgh + b * 3 * H;
-    da[j] = dpre_r; dc[j] = dpre_r;
-    da[H + j] = dpre_z; dc[H + j] = dpre_z;
-    da[2 * H + j] = dpre_n; dc[2 * H + j] = dpre_n * r;
-    dh[i] = g * z;
+    da[j] = d.dpre_r; dc[j] = d.dpre_r;
+    da[H + j] = d.dpre_z; dc[H + j] = d.dpre_z;
+    da[2 * H + j] = d.dpre_n; dc[2 * H + j] = d.dgh_n;
+    dh[i] = d.dh;
   }
 }
-// (mu | log_sigma) (B, 2S) -> mu, sigma = 2*sigmoid(ls/2)+min_std, sample = mu + sigma*eps   (transition.py:18-24,176-181)
+// (mu | log_sigma) (B, 2S) -> mu, sigma, sample; eps == nullptr: no noise
 __global__ void rssm_sample_fwd_kernel(const float* __restrict__ mls, const float* __restrict__ eps, long eps_ld,
                                        float* __restrict__ mu, float* __restrict__ sigma, float* __restrict__ sample,
                                        int B, int S, float min_std) {
@@ -768,10 +753,10 @@ __global__ void rssm_sample_fwd_kernel(const float* __restrict__ mls, const floa
   GRID_STRIDE(i, n) {
     const long b = i / S, j = i - b * S;
     const float m = mls[b * 2 * S + j];
-    const float sg = 2.f * sigmoidf_(mls[b * 2 * S + S + j] * 0.5f) + min_std;
+    const float sg = rssm_sigma(mls[b * 2 * S + S + j], min_std);
     mu[i] = m;
     sigma[i] = sg;
-    sample[i] = m + sg * (eps ? eps[b * eps_ld + j] : 0.f);
+    sample[i] = rssm_sample(m, sg, eps ? eps[b * eps_ld + j] : 0.f);
   }
 }
 __global__ void rssm_sample_bwd_kernel(const float* __restrict__ mls, const float* __restrict__ eps, long eps_ld,
@@ -780,11 +765,10 @@ __global__ void rssm_sample_bwd_kernel(const float* __restrict__ mls, const floa
   const long n = (long)B * S;
   GRID_STRIDE(i, n) {
     const long b = i / S, j = i - b * S;
-    const float s = sigmoidf_(mls[b * 2 * S + S + j] * 0.5f);
-    const float dsm = dsample ? dsample[i] : 0.f;
-    const float e = eps ? eps[b * eps_ld + j] : 0.f;
-    dmls[b * 2 * S + j] = (dmu ? dmu[i] : 0.f) + dsm;
-    dmls[b * 2 * S + S + j] = ((dsigma ? dsigma[i] : 0.f) + dsm * e) * s * (1.f - s);
+    const SampleAdjoint d = rssm_sample_adjoint(mls[b * 2 * S + S + j], eps ? eps[b * eps_ld + j] : 0.f, dmu ? dmu[i] : 0.f,
+                                                dsigma ? dsigma[i] : 0.f, dsample ? dsample[i] : 0.f);
+    dmls[b * 2 * S + j] = d.dmu;
+    dmls[b * 2 * S + S + j] = d.dls;
   }
 }
 

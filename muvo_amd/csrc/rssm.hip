@@ -16,40 +16,85 @@
 // NOT formed per step — every per-step input / output gradient is kept (b*T rows) and the caller forms dW = dY^T X with one
 // skinny GEMM per weight after the loop.
 #include "common.h"
+#include "rssm_cell.h"
 
 #define ST ((hipStream_t)stream)
 #define RSSM_THREADS 512
 #define RSSM_WPB (RSSM_THREADS / 64)
 #define RSSM_BM 4                 // batch rows held per wave accumulator set
 
+// The order of every pointer table of the C ABI (include/muvo_hip.h) is stated here and nowhere else in this unit: the kernels
+// and the host code name the entries, rssm_widths gives each (B, T, .) tensor's last-axis width under the same names.
+enum { W_PRE, B_PRE, W_IH, W_HH, B_IH, B_HH, W_PA, B_PA, W_QA, B_QA, W_P0, B_P0, W_P2, B_P2, W_Q0, B_Q0, W_Q2, B_Q2, W_N };   // weights[18]
+enum { O_H, O_MU_P, O_SG_P, O_Z_P, O_MU_Q, O_SG_Q, O_Z_Q, O_N };                       // out7, and upstream7: their gradients
+enum { K_HPREV, K_ZPREV, K_APREV, K_U, K_GI, K_GH, K_XP, K_XQ, K_Y1P, K_Y1Q, K_MLS_P, K_MLS_Q, K_N };                       // keep12
+enum { KP_HPREV, KP_GI, KP_GH, KP_MLS_P, KP_MLS_Q, KP_N };                             // kept5: what the backward reads of keep12
+static const int KEPT5[KP_N] = {K_HPREV, K_GI, K_GH, K_MLS_P, K_MLS_Q};
+enum { G_EMB, G_MLS_P, G_MLS_Q, G_Y1P, G_Y1Q, G_GI, G_GH, G_U, G_LA_P, G_LA_Q, G_N };  // grads10
+enum { WT_PRE, WT_IH, WT_HH, WT_P0, WT_P2, WT_Q0, WT_Q2, WT_N };                       // the big matrices the backward reads transposed
+
 struct RssmDims { int B, T, H, S, E, A, AD; };
-struct RssmW {                    // PyTorch layouts [out][in]; in backward the 7 big ones are the TRANSPOSES [in][out]
-  const float *w_pre, *b_pre, *w_ih, *w_hh, *b_ih, *b_hh, *w_pa, *b_pa, *w_qa, *b_qa, *w_p0, *b_p0, *w_p2, *b_p2, *w_q0,
-      *b_q0, *w_q2, *b_q2;
-};
+struct RssmWidths { long out[O_N], keep[K_N], kept[KP_N], grad[G_N]; };
+static RssmWidths rssm_widths(const RssmDims& d) {
+  const long H = d.H, S = d.S, HP = d.H + d.A, HQ = d.H + d.E + d.A;
+  RssmWidths w;
+  w.out[O_H] = H;
+  for (int i = O_MU_P; i < O_N; ++i) w.out[i] = S;
+  w.keep[K_HPREV] = w.keep[K_U] = H; w.keep[K_ZPREV] = S; w.keep[K_APREV] = d.AD; w.keep[K_GI] = w.keep[K_GH] = 3 * H;
+  w.keep[K_XP] = w.keep[K_Y1P] = HP; w.keep[K_XQ] = w.keep[K_Y1Q] = HQ; w.keep[K_MLS_P] = w.keep[K_MLS_Q] = 2 * S;
+  for (int i = 0; i < KP_N; ++i) w.kept[i] = w.keep[KEPT5[i]];
+  w.grad[G_EMB] = d.E; w.grad[G_MLS_P] = w.grad[G_MLS_Q] = 2 * S; w.grad[G_Y1P] = HP; w.grad[G_Y1Q] = HQ;
+  w.grad[G_GI] = w.grad[G_GH] = 3 * H; w.grad[G_U] = H; w.grad[G_LA_P] = w.grad[G_LA_Q] = d.A;
+  return w;
+}
+// The kernels index these arrays with constants only (a by-value argument array indexed at run time goes to scratch).
 struct RssmFwdArgs {
   RssmDims d;
-  RssmW w;
+  const float* w[W_N];                          // PyTorch layouts [out][in]
   const float *emb, *act, *noise;               // (B,T,E) (B,T,AD) (B,T,2,S)
   unsigned long long use_prior;                 // bit t: step t+1 continues from the PRIOR sample of step t
-  float *h, *mu_p, *sg_p, *z_p, *mu_q, *sg_q, *z_q;                                        // outputs (B,T,.)
-  float *hprev, *zprev, *aprev, *u, *gi, *gh, *xp, *xq, *y1p, *y1q, *mls_p, *mls_q;       // kept for backward (B,T,.)
+  float* out[O_N];                              // outputs (B,T,.)
+  float* keep[K_N];                             // kept for backward (B,T,.)
   unsigned* bar;
   float min_std;
 };
 struct RssmBwdArgs {
   RssmDims d;
-  RssmW wt;                                     // transposed big weights
-  const float *noise, *hprev, *gi, *gh, *mls_p, *mls_q;
+  const float* wt[WT_N];                        // the TRANSPOSES [in][out]
+  const float* noise;
+  const float* kept[KP_N];
   unsigned long long use_prior;
-  const float *g_h, *g_mu_p, *g_sg_p, *g_z_p, *g_mu_q, *g_sg_q, *g_z_q;                  // upstream (B,T,.), may be NULL
-  float *d_emb;                                                                            // (B,T,E)
-  float *dmls_p, *dmls_q, *dy1p, *dy1q, *dgi, *dgh, *du, *dla_p, *dla_q;                  // per-step gradients kept (B,T,.)
+  const float* up[O_N];                         // upstream (B,T,.), may be NULL
+  float* grad[G_N];                             // per-step gradients kept (B,T,.)
   float *dxp, *dxq, *dh_carry, *dz_carry;       // scratch: (B,HP) (B,HQ) 2 x (B,H) (B,S)
   unsigned* bar;
 };
 
-__device__ __forceinline__ float sigm(float x) { return 1.f / (1.f + expf(-x)); }
+// Dynamic LDS of a launch, in floats: the kernels carve their buffers from these offsets, the host sizes the launch and answers
+// muvo_rssm_supported from the totals (tests/rssm_reference.py restates them: fwd_lds, bwd_lds).  A launch holds one slab of at
+// most RSSM_BM of the d.B sequences.
+struct RssmFwdLds { long xa, xb, hs, as, total; };
+__host__ __device__ inline RssmFwdLds rssm_fwd_lds(const RssmDims& d) {
+  const long B = d.B < RSSM_BM ? d.B : RSSM_BM, H = d.H, S = d.S, HP = H + d.A, HQ = H + d.E + d.A;
+  RssmFwdLds l;
+  l.xa = 0;                                     // stage inputs: [B][<= max(HQ, S)] (stage 0 holds z_{t-1}: S floats per sequence)
+  l.xb = l.xa + B * (HQ > S ? HQ : S);          //               [B][<= HP]
+  l.hs = l.xb + B * HP;                         // h_{t-1}: [B][H], kept through stage 1
+  l.as = l.hs + B * H;                          // a_{t-1}: [B][AD]
+  l.total = l.as + B * d.AD + 16;
+  return l;
+}
+struct RssmBwdLds { long xa, xb, dd, total; };
+__host__ __device__ inline RssmBwdLds rssm_bwd_lds(const RssmDims& d) {
+  const long B = d.B < RSSM_BM ? d.B : RSSM_BM, H = d.H, S = d.S, HP = H + d.A, HQ = H + d.E + d.A;
+  const long M3 = 3 * H > 2 * S ? 3 * H : 2 * S;             // B2 holds dgi / dgh (3H), B0 holds dmls (2S) in both buffers
+  RssmBwdLds l;
+  l.xa = 0;                                     // [B][<= max(HQ, 3H, 2S)]
+  l.xb = l.xa + B * (HQ > M3 ? HQ : M3);        // [B][<= max(HP, 3H, 2S)]
+  l.dd = l.xb + B * (HP > M3 ? HP : M3);        // direct dh_{t-1} path: [B][H]
+  l.total = l.dd + B * H + 16;
+  return l;
+}
 
 // Data that one workgroup writes and another reads across a grid barrier moves through agent-scope relaxed atomics (32-bit
 // loads / stores that are coherent across the 8 XCDs by themselves), so the barrier needs NO L2 write-back / invalidate:
@@ -146,123 +191,131 @@ __device__ __forceinline__ void lds_load(float* dst, const float* __restrict__ s
   }
 }
 
+// What one output row of a layer needs.  The NR weight rows of K floats are dotted with the input vectors xs[r * K + k] in LDS
+// (xs == nullptr: no dot product, the epilogue does the row's whole work); `part` says which of the stage's concatenated row
+// ranges the row lies in (prior 0 | posterior 1 where a stage has the two branches) and j is its index inside that range.
+template <int NR> struct LayerRow { const float* w[NR]; const float* xs; int K, part, j; };
+// row o of a stage of n prior rows followed by the posterior rows: the weight rows j, n + j, ... of the branch's matrix
+template <int NR>
+__device__ __forceinline__ LayerRow<NR> pq_row(int o, int n, const float* wp, const float* wq, int Kp, int Kq, const float* xp,
+                                               const float* xq) {
+  LayerRow<NR> r;
+  r.part = o >= n; r.j = r.part ? o - n : o; r.K = r.part ? Kq : Kp; r.xs = r.part ? xq : xp;
+#pragma unroll
+  for (int q = 0; q < NR; ++q) r.w[q] = (r.part ? wq : wp) + (long)(q * n + r.j) * r.K;
+  return r;
+}
+// One layer.  The `rows` output rows are dealt to the waves of the whole grid, row o to wave o % NW; a wave forms the NR dot
+// products of its row for all B sequences, then lane b < B ends the row for sequence b: epi(row, v), v[q] the q-th dot product.
+template <int NR, class Row, class Epi>
+__device__ __forceinline__ void layer(int rows, int B, Row row, Epi epi) {
+  const int lane = threadIdx.x & 63;
+  const int gw = blockIdx.x * RSSM_WPB + (threadIdx.x >> 6), NW = gridDim.x * RSSM_WPB;
+  for (int o = gw; o < rows; o += NW) {
+    const LayerRow<NR> r = row(o);
+    float acc[NR][RSSM_BM] = {};
+    if (r.xs) wave_dots<NR>(r.w, r.xs, r.K, r.K, B, acc);
+    if (lane < B) {
+      float v[NR];
+#pragma unroll
+      for (int q = 0; q < NR; ++q) v[q] = pick(acc[q], lane);
+      epi(r, v);
+    }
+  }
+}
+
 __global__ void __launch_bounds__(RSSM_THREADS) rssm_fwd_kernel(const RssmFwdArgs a) {
   extern __shared__ float lds[];
   const int B = a.d.B, T = a.d.T, H = a.d.H, S = a.d.S, E = a.d.E, A = a.d.A, AD = a.d.AD;
   const int HP = H + A, HQ = H + E + A;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int gw = blockIdx.x * RSSM_WPB + wave, NW = gridDim.x * RSSM_WPB;
+  const int tid = threadIdx.x, lane = tid & 63;
   const long gtid = (long)blockIdx.x * RSSM_THREADS + tid, gthreads = (long)gridDim.x * RSSM_THREADS;
-  float* xa = lds;                 // stage inputs: [B][<= max(HQ, S)] (stage 0 holds z_{t-1}: S floats per sequence)
-  float* xb = xa + B * (HQ > S ? HQ : S);   //      [B][<= HP]
-  float* hs = xb + B * HP;         // h_{t-1}: [B][H], kept through stage 1
-  float* as = hs + B * H;          // a_{t-1}: [B][AD]
+  const RssmFwdLds l = rssm_fwd_lds(a.d);
+  float *xa = lds + l.xa, *xb = lds + l.xb, *hs = lds + l.hs, *as = lds + l.as;
   unsigned target = 0;
   for (int t = 0; t < T; ++t) {
+    const long lrow = (long)lane * T + t;        // row of sequence `lane` (< B: the epilogues) in the (B T, .) tensors
     // ------------------------------------------------------------------ stage 0: u = W_pre z, gh = W_hh h, action latents
-    const float* zsrc = t == 0 ? nullptr : (((a.use_prior >> (t - 1)) & 1ull) ? a.z_p : a.z_q) + (long)(t - 1) * S;
+    const float* zsrc = t == 0 ? nullptr : (((a.use_prior >> (t - 1)) & 1ull) ? a.out[O_Z_P] : a.out[O_Z_Q]) + (long)(t - 1) * S;
     lds_load(xa, zsrc, B, S, (long)T * S);
-    lds_load(hs, t == 0 ? nullptr : a.h + (long)(t - 1) * H, B, H, (long)T * H);
+    lds_load(hs, t == 0 ? nullptr : a.out[O_H] + (long)(t - 1) * H, B, H, (long)T * H);
     lds_load(as, t == 0 ? nullptr : a.act + (long)(t - 1) * AD, B, AD, (long)T * AD);
     __syncthreads();
     if (blockIdx.x == 0) {         // the step's inputs, kept for the weight gradients
-      for (int i = tid; i < B * S; i += RSSM_THREADS) a.zprev[((long)(i / S) * T + t) * S + i % S] = xa[i];
-      for (int i = tid; i < B * H; i += RSSM_THREADS) a.hprev[((long)(i / H) * T + t) * H + i % H] = hs[i];
-      for (int i = tid; i < B * AD; i += RSSM_THREADS) a.aprev[((long)(i / AD) * T + t) * AD + i % AD] = as[i];
+      for (int i = tid; i < B * S; i += RSSM_THREADS) a.keep[K_ZPREV][((long)(i / S) * T + t) * S + i % S] = xa[i];
+      for (int i = tid; i < B * H; i += RSSM_THREADS) a.keep[K_HPREV][((long)(i / H) * T + t) * H + i % H] = hs[i];
+      for (int i = tid; i < B * AD; i += RSSM_THREADS) a.keep[K_APREV][((long)(i / AD) * T + t) * AD + i % AD] = as[i];
     }
-    for (int o = gw; o < 4 * H + 2 * A; o += NW) {
-      if (o < H) {
-        const float* const wr[1] = {a.w.w_pre + (long)o * S};
-        float acc[1][RSSM_BM];
-        wave_dots<1>(wr, xa, S, S, B, acc);
-        if (lane < B) coh_store(&a.u[((long)lane * T + t) * H + o], pick(acc[0], lane) + a.w.b_pre[o]);
-      } else if (o < 4 * H) {
-        const int oo = o - H;
-        const float* const wr[1] = {a.w.w_hh + (long)oo * H};
-        float acc[1][RSSM_BM];
-        wave_dots<1>(wr, hs, H, H, B, acc);
-        if (lane < B) coh_store(&a.gh[((long)lane * T + t) * 3 * H + oo], pick(acc[0], lane) + a.w.b_hh[oo]);
-      } else if (lane < B) {
-        const int oo = o - 4 * H, post = oo >= A, j = post ? oo - A : oo;
-        const float* wj = (post ? a.w.w_qa : a.w.w_pa) + (long)j * AD;
-        float v = (post ? a.w.b_qa : a.w.b_pa)[j];
-        for (int k = 0; k < AD; ++k) v += wj[k] * as[lane * AD + k];
-        if (post) coh_store(&a.xq[((long)lane * T + t) * HQ + H + E + j], v);
-        else coh_store(&a.xp[((long)lane * T + t) * HP + H + j], v);
-      }
-    }
+    layer<1>(4 * H + 2 * A, B,
+             [&](int o) -> LayerRow<1> {         // H rows of u | 3H of gh | A prior, A posterior action latents
+               if (o < 4 * H) return pq_row<1>(o, H, a.w[W_PRE], a.w[W_HH], S, H, xa, hs);
+               const int post = o - 4 * H >= A;
+               return {{nullptr}, nullptr, 0, 2 + post, o - 4 * H - (post ? A : 0)};
+             },
+             [&](const LayerRow<1>& r, const float (&v)[1]) {
+               const int post = r.part == 3, j = r.j;
+               if (r.part == 0) coh_store(&a.keep[K_U][lrow * H + j], v[0] + a.w[B_PRE][j]);
+               else if (r.part == 1) coh_store(&a.keep[K_GH][lrow * 3 * H + j], v[0] + a.w[B_HH][j]);
+               else {                             // AD terms: the lane sums them serially, starting at the bias
+                 const float* wj = (post ? a.w[W_QA] : a.w[W_PA]) + (long)j * AD;
+                 float s = (post ? a.w[B_QA] : a.w[B_PA])[j];
+                 for (int k = 0; k < AD; ++k) s += wj[k] * as[lane * AD + k];
+                 if (post) coh_store(&a.keep[K_XQ][lrow * HQ + H + E + j], s);
+                 else coh_store(&a.keep[K_XP][lrow * HP + H + j], s);
+               }
+             });
     for (long i = gtid; i < (long)B * E; i += gthreads) {      // the embedding slice of the posterior input
       const int b = (int)(i / E), e = (int)(i - (long)b * E);
-      coh_store(&a.xq[((long)b * T + t) * HQ + H + e], a.emb[((long)b * T + t) * E + e]);
+      coh_store(&a.keep[K_XQ][((long)b * T + t) * HQ + H + e], a.emb[((long)b * T + t) * E + e]);
     }
     target += gridDim.x;
     GRID_BARRIER(a.bar, target);
     // ------------------------------------------------------------------ stage 1: gi = W_ih u, GRU cell -> h_t
-    lds_load(xa, a.u + (long)t * H, B, H, (long)T * H);
+    lds_load(xa, a.keep[K_U] + (long)t * H, B, H, (long)T * H);
     __syncthreads();
-    for (int j = gw; j < H; j += NW) {
-      const float* const wr[3] = {a.w.w_ih + (long)j * H, a.w.w_ih + (long)(H + j) * H, a.w.w_ih + (long)(2 * H + j) * H};
-      float acc[3][RSSM_BM];
-      wave_dots<3>(wr, xa, H, H, B, acc);
-      if (lane < B) {
-        const long base = ((long)lane * T + t) * 3 * H;
-        const float ir = pick(acc[0], lane) + a.w.b_ih[j], iz = pick(acc[1], lane) + a.w.b_ih[H + j], in_ = pick(acc[2], lane) + a.w.b_ih[2 * H + j];
-        a.gi[base + j] = ir; a.gi[base + H + j] = iz; a.gi[base + 2 * H + j] = in_;
-        const float r = sigm(ir + coh_load(&a.gh[base + j]));
-        const float z = sigm(iz + coh_load(&a.gh[base + H + j]));
-        const float nn = tanhf(in_ + r * coh_load(&a.gh[base + 2 * H + j]));
-        const float hn = (1.f - z) * nn + z * hs[lane * H + j];
-        coh_store(&a.h[((long)lane * T + t) * H + j], hn);
-        coh_store(&a.xp[((long)lane * T + t) * HP + j], hn);
-        coh_store(&a.xq[((long)lane * T + t) * HQ + j], hn);
-      }
-    }
+    layer<3>(H, B, [&](int o) { return pq_row<3>(o, H, a.w[W_IH], a.w[W_IH], H, H, xa, xa); },
+             [&](const LayerRow<3>& r, const float (&v)[3]) {
+               const int j = r.j;
+               const float* gh = a.keep[K_GH] + lrow * 3 * H;
+               float* gi = a.keep[K_GI] + lrow * 3 * H;
+               const float ir = v[0] + a.w[B_IH][j], iz = v[1] + a.w[B_IH][H + j], in_ = v[2] + a.w[B_IH][2 * H + j];
+               gi[j] = ir; gi[H + j] = iz; gi[2 * H + j] = in_;
+               const GruGates q = gru_gates(ir, iz, in_, coh_load(&gh[j]), coh_load(&gh[H + j]), coh_load(&gh[2 * H + j]));
+               const float hn = gru_combine(q, hs[lane * H + j]);
+               coh_store(&a.out[O_H][lrow * H + j], hn);
+               coh_store(&a.keep[K_XP][lrow * HP + j], hn);
+               coh_store(&a.keep[K_XQ][lrow * HQ + j], hn);
+             });
     target += gridDim.x;
     GRID_BARRIER(a.bar, target);
     // ------------------------------------------------------------------ stage 2: first MLP layers (no activation: slope 1)
-    lds_load(xa, a.xq + (long)t * HQ, B, HQ, (long)T * HQ);
-    lds_load(xb, a.xp + (long)t * HP, B, HP, (long)T * HP);
+    lds_load(xa, a.keep[K_XQ] + (long)t * HQ, B, HQ, (long)T * HQ);
+    lds_load(xb, a.keep[K_XP] + (long)t * HP, B, HP, (long)T * HP);
     __syncthreads();
-    for (int o = gw; o < HP + HQ; o += NW) {
-      float acc[1][RSSM_BM];
-      if (o < HP) {
-        const float* const wr[1] = {a.w.w_p0 + (long)o * HP};
-        wave_dots<1>(wr, xb, HP, HP, B, acc);
-        if (lane < B) coh_store(&a.y1p[((long)lane * T + t) * HP + o], pick(acc[0], lane) + a.w.b_p0[o]);
-      } else {
-        const int oo = o - HP;
-        const float* const wr[1] = {a.w.w_q0 + (long)oo * HQ};
-        wave_dots<1>(wr, xa, HQ, HQ, B, acc);
-        if (lane < B) coh_store(&a.y1q[((long)lane * T + t) * HQ + oo], pick(acc[0], lane) + a.w.b_q0[oo]);
-      }
-    }
+    layer<1>(HP + HQ, B, [&](int o) { return pq_row<1>(o, HP, a.w[W_P0], a.w[W_Q0], HP, HQ, xb, xa); },
+             [&](const LayerRow<1>& r, const float (&v)[1]) {
+               float* y1 = r.part ? a.keep[K_Y1Q] : a.keep[K_Y1P];
+               coh_store(&y1[lrow * r.K + r.j], v[0] + (r.part ? a.w[B_Q0] : a.w[B_P0])[r.j]);
+             });
     target += gridDim.x;
     GRID_BARRIER(a.bar, target);
     // ------------------------------------------------------------------ stage 3: (mu | log sigma), sample
-    lds_load(xa, a.y1q + (long)t * HQ, B, HQ, (long)T * HQ);
-    lds_load(xb, a.y1p + (long)t * HP, B, HP, (long)T * HP);
+    lds_load(xa, a.keep[K_Y1Q] + (long)t * HQ, B, HQ, (long)T * HQ);
+    lds_load(xb, a.keep[K_Y1P] + (long)t * HP, B, HP, (long)T * HP);
     __syncthreads();
-    for (int p = gw; p < 2 * S; p += NW) {
-      const int post = p >= S, j = post ? p - S : p;
-      const int K = post ? HQ : HP;
-      const float* W = post ? a.w.w_q2 : a.w.w_p2;
-      const float* bias = post ? a.w.b_q2 : a.w.b_p2;
-      const float* const wr[2] = {W + (long)j * K, W + (long)(S + j) * K};
-      float acc[2][RSSM_BM];
-      wave_dots<2>(wr, post ? xa : xb, K, K, B, acc);
-      if (lane < B) {
-        const long bt = (long)lane * T + t;
-        const float m = pick(acc[0], lane) + bias[j], ls = pick(acc[1], lane) + bias[S + j];
-        float* mls = post ? a.mls_q : a.mls_p;
-        mls[bt * 2 * S + j] = m;
-        mls[bt * 2 * S + S + j] = ls;
-        const float sg = 2.f * sigm(ls * 0.5f) + a.min_std;
-        const float e = a.noise[(bt * 2 + post) * S + j];
-        (post ? a.mu_q : a.mu_p)[bt * S + j] = m;
-        (post ? a.sg_q : a.sg_p)[bt * S + j] = sg;
-        coh_store(&(post ? a.z_q : a.z_p)[bt * S + j], m + sg * e);
-      }
-    }
+    layer<2>(2 * S, B, [&](int o) { return pq_row<2>(o, S, a.w[W_P2], a.w[W_Q2], HP, HQ, xb, xa); },
+             [&](const LayerRow<2>& r, const float (&v)[2]) {
+               const int post = r.part, j = r.j;
+               const float* bias = post ? a.w[B_Q2] : a.w[B_P2];
+               const float m = v[0] + bias[j], ls = v[1] + bias[S + j];
+               float* mls = post ? a.keep[K_MLS_Q] : a.keep[K_MLS_P];
+               mls[lrow * 2 * S + j] = m;
+               mls[lrow * 2 * S + S + j] = ls;
+               const float sg = rssm_sigma(ls, a.min_std);
+               (post ? a.out[O_MU_Q] : a.out[O_MU_P])[lrow * S + j] = m;
+               (post ? a.out[O_SG_Q] : a.out[O_SG_P])[lrow * S + j] = sg;
+               coh_store(&(post ? a.out[O_Z_Q] : a.out[O_Z_P])[lrow * S + j], rssm_sample(m, sg, a.noise[(lrow * 2 + post) * S + j]));
+             });
     target += gridDim.x;
     GRID_BARRIER(a.bar, target);
   }
@@ -272,80 +325,54 @@ __global__ void __launch_bounds__(RSSM_THREADS) rssm_bwd_kernel(const RssmBwdArg
   extern __shared__ float lds[];
   const int B = a.d.B, T = a.d.T, H = a.d.H, S = a.d.S, E = a.d.E, A = a.d.A;
   const int HP = H + A, HQ = H + E + A;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int gw = blockIdx.x * RSSM_WPB + wave, NW = gridDim.x * RSSM_WPB;
-  const int M3 = 3 * H > 2 * S ? 3 * H : 2 * S;     // B2 holds dgi / dgh (3H), B0 holds dmls (2S) in both buffers
-  float* xa = lds;                 // [B][<= max(HQ, 3H, 2S)]
-  float* xb = xa + B * (HQ > M3 ? HQ : M3);         // [B][<= max(HP, 3H, 2S)]
-  float* dd = xb + B * (HP > M3 ? HP : M3);         // direct dh_{t-1} path: [B][H]
+  const int tid = threadIdx.x, lane = tid & 63;
+  const RssmBwdLds l = rssm_bwd_lds(a.d);
+  float *xa = lds + l.xa, *xb = lds + l.xb, *dd = lds + l.dd;
   unsigned target = 0;
   for (int t = T - 1; t >= 0; --t) {
     const bool up = (a.use_prior >> t) & 1ull;       // the carry dz of step t+1 belongs to the prior (else posterior) sample
     const bool has_carry = t < T - 1;
+    const long lrow = (long)lane * T + t;        // row of sequence `lane` (< B: the epilogues) in the (B T, .) tensors
     // ------------------------------------------------------------------ B0: d(mu | log sigma), then dy1 = W2^T dmls
     for (int i = tid; i < B * S * 2; i += RSSM_THREADS) {
       const int post = i >= B * S, ii = post ? i - B * S : i;
       const int b = ii / S, j = ii - b * S;
       const long bt = (long)b * T + t;
-      const float* mls = post ? a.mls_q : a.mls_p;
-      const float* gmu = post ? a.g_mu_q : a.g_mu_p;
-      const float* gsg = post ? a.g_sg_q : a.g_sg_p;
-      const float* gz = post ? a.g_z_q : a.g_z_p;
+      const float* mls = post ? a.kept[KP_MLS_Q] : a.kept[KP_MLS_P];
+      const float* gmu = post ? a.up[O_MU_Q] : a.up[O_MU_P];
+      const float* gsg = post ? a.up[O_SG_Q] : a.up[O_SG_P];
+      const float* gz = post ? a.up[O_Z_Q] : a.up[O_Z_P];
       float dz = gz ? gz[bt * S + j] : 0.f;
       if (has_carry && (up != (bool)post)) dz += coh_load(&a.dz_carry[b * S + j]);
-      const float s = sigm(mls[bt * 2 * S + S + j] * 0.5f);
-      const float e = a.noise[(bt * 2 + post) * S + j];
-      const float dmu = (gmu ? gmu[bt * S + j] : 0.f) + dz;
-      const float dls = ((gsg ? gsg[bt * S + j] : 0.f) + dz * e) * s * (1.f - s);
+      const SampleAdjoint d = rssm_sample_adjoint(mls[bt * 2 * S + S + j], a.noise[(bt * 2 + post) * S + j],
+                                                  gmu ? gmu[bt * S + j] : 0.f, gsg ? gsg[bt * S + j] : 0.f, dz);
       float* x = post ? xa : xb;
-      x[b * 2 * S + j] = dmu;
-      x[b * 2 * S + S + j] = dls;
+      x[b * 2 * S + j] = d.dmu;
+      x[b * 2 * S + S + j] = d.dls;
       if (blockIdx.x == 0) {
-        float* o = post ? a.dmls_q : a.dmls_p;
-        o[bt * 2 * S + j] = dmu;
-        o[bt * 2 * S + S + j] = dls;
+        float* o = post ? a.grad[G_MLS_Q] : a.grad[G_MLS_P];
+        o[bt * 2 * S + j] = d.dmu;
+        o[bt * 2 * S + S + j] = d.dls;
       }
     }
     __syncthreads();
-    for (int o = gw; o < HP + HQ; o += NW) {
-      float acc[1][RSSM_BM];
-      if (o < HP) {
-        const float* const wr[1] = {a.wt.w_p2 + (long)o * 2 * S};
-        wave_dots<1>(wr, xb, 2 * S, 2 * S, B, acc);
-        if (lane < B) coh_store(&a.dy1p[((long)lane * T + t) * HP + o], pick(acc[0], lane));
-      } else {
-        const int oo = o - HP;
-        const float* const wr[1] = {a.wt.w_q2 + (long)oo * 2 * S};
-        wave_dots<1>(wr, xa, 2 * S, 2 * S, B, acc);
-        if (lane < B) coh_store(&a.dy1q[((long)lane * T + t) * HQ + oo], pick(acc[0], lane));
-      }
-    }
+    layer<1>(HP + HQ, B, [&](int o) { return pq_row<1>(o, HP, a.wt[WT_P2], a.wt[WT_Q2], 2 * S, 2 * S, xb, xa); },
+             [&](const LayerRow<1>& r, const float (&v)[1]) {
+               coh_store(&(r.part ? a.grad[G_Y1Q] : a.grad[G_Y1P])[lrow * (r.part ? HQ : HP) + r.j], v[0]);
+             });
     target += gridDim.x;
     GRID_BARRIER(a.bar, target);
     // ------------------------------------------------------------------ B1: dx = W0^T dy1
-    lds_load(xa, a.dy1q + (long)t * HQ, B, HQ, (long)T * HQ);
-    lds_load(xb, a.dy1p + (long)t * HP, B, HP, (long)T * HP);
+    lds_load(xa, a.grad[G_Y1Q] + (long)t * HQ, B, HQ, (long)T * HQ);
+    lds_load(xb, a.grad[G_Y1P] + (long)t * HP, B, HP, (long)T * HP);
     __syncthreads();
-    for (int o = gw; o < HP + HQ; o += NW) {
-      float acc[1][RSSM_BM];
-      if (o < HP) {
-        const float* const wr[1] = {a.wt.w_p0 + (long)o * HP};
-        wave_dots<1>(wr, xb, HP, HP, B, acc);
-        if (lane < B) {
-          coh_store(&a.dxp[lane * HP + o], pick(acc[0], lane));
-          if (o >= H) a.dla_p[((long)lane * T + t) * A + (o - H)] = pick(acc[0], lane);
-        }
-      } else {
-        const int oo = o - HP;
-        const float* const wr[1] = {a.wt.w_q0 + (long)oo * HQ};
-        wave_dots<1>(wr, xa, HQ, HQ, B, acc);
-        if (lane < B) {
-          coh_store(&a.dxq[lane * HQ + oo], pick(acc[0], lane));
-          if (oo >= H + E) a.dla_q[((long)lane * T + t) * A + (oo - H - E)] = pick(acc[0], lane);
-          else if (oo >= H) a.d_emb[((long)lane * T + t) * E + (oo - H)] = pick(acc[0], lane);
-        }
-      }
-    }
+    layer<1>(HP + HQ, B, [&](int o) { return pq_row<1>(o, HP, a.wt[WT_P0], a.wt[WT_Q0], HP, HQ, xb, xa); },
+             [&](const LayerRow<1>& r, const float (&v)[1]) {      // x = (h | action latent) resp. (h | embedding | action latent)
+               const int j = r.j, la = r.part ? H + E : H;
+               coh_store(&(r.part ? a.dxq : a.dxp)[lane * r.K + j], v[0]);
+               if (j >= la) (r.part ? a.grad[G_LA_Q] : a.grad[G_LA_P])[lrow * A + (j - la)] = v[0];
+               else if (j >= H) a.grad[G_EMB][lrow * E + (j - H)] = v[0];
+             });
     target += gridDim.x;
     GRID_BARRIER(a.bar, target);
     // ------------------------------------------------------------------ B2: GRU cell backward, du = W_ih^T dgi, dh_{t-1}
@@ -354,50 +381,34 @@ __global__ void __launch_bounds__(RSSM_THREADS) rssm_bwd_kernel(const RssmBwdArg
     for (int i = tid; i < B * H; i += RSSM_THREADS) {
       const int b = i / H, j = i - b * H;
       const long bt = (long)b * T + t, base = bt * 3 * H;
-      float g = (a.g_h ? a.g_h[bt * H + j] : 0.f) + coh_load(&a.dxp[b * HP + j]) + coh_load(&a.dxq[b * HQ + j]);
+      const float *gi = a.kept[KP_GI] + base, *gh = a.kept[KP_GH] + base;
+      float g = (a.up[O_H] ? a.up[O_H][bt * H + j] : 0.f) + coh_load(&a.dxp[b * HP + j]) + coh_load(&a.dxq[b * HQ + j]);
       if (has_carry) g += coh_load(&carry_in[i]);
-      const float ghn = a.gh[base + 2 * H + j];
-      const float r = sigm(a.gi[base + j] + a.gh[base + j]);
-      const float z = sigm(a.gi[base + H + j] + a.gh[base + H + j]);
-      const float nn = tanhf(a.gi[base + 2 * H + j] + r * ghn);
-      const float dn = g * (1.f - z);
-      const float dzg = g * (a.hprev[bt * H + j] - nn);
-      const float dpre_n = dn * (1.f - nn * nn);
-      const float dpre_r = dpre_n * ghn * r * (1.f - r);
-      const float dpre_z = dzg * z * (1.f - z);
-      xa[b * 3 * H + j] = dpre_r; xa[b * 3 * H + H + j] = dpre_z; xa[b * 3 * H + 2 * H + j] = dpre_n;          // dgi
-      xb[b * 3 * H + j] = dpre_r; xb[b * 3 * H + H + j] = dpre_z; xb[b * 3 * H + 2 * H + j] = dpre_n * r;      // dgh
-      dd[i] = g * z;
+      const float ghn = gh[2 * H + j];
+      const GruAdjoint d = gru_adjoint(gru_gates(gi[j], gi[H + j], gi[2 * H + j], gh[j], gh[H + j], ghn), ghn,
+                                       a.kept[KP_HPREV][bt * H + j], g);
+      xa[b * 3 * H + j] = d.dpre_r; xa[b * 3 * H + H + j] = d.dpre_z; xa[b * 3 * H + 2 * H + j] = d.dpre_n;      // dgi
+      xb[b * 3 * H + j] = d.dpre_r; xb[b * 3 * H + H + j] = d.dpre_z; xb[b * 3 * H + 2 * H + j] = d.dgh_n;       // dgh
+      dd[i] = d.dh;
       if (blockIdx.x == 0) {
-        a.dgi[base + j] = dpre_r; a.dgi[base + H + j] = dpre_z; a.dgi[base + 2 * H + j] = dpre_n;
-        a.dgh[base + j] = dpre_r; a.dgh[base + H + j] = dpre_z; a.dgh[base + 2 * H + j] = dpre_n * r;
+        float *dgi = a.grad[G_GI] + base, *dgh = a.grad[G_GH] + base;
+        dgi[j] = d.dpre_r; dgi[H + j] = d.dpre_z; dgi[2 * H + j] = d.dpre_n;
+        dgh[j] = d.dpre_r; dgh[H + j] = d.dpre_z; dgh[2 * H + j] = d.dgh_n;
       }
     }
     __syncthreads();
-    for (int o = gw; o < 2 * H; o += NW) {
-      float acc[1][RSSM_BM];
-      if (o < H) {
-        const float* const wr[1] = {a.wt.w_ih + (long)o * 3 * H};
-        wave_dots<1>(wr, xa, 3 * H, 3 * H, B, acc);
-        if (lane < B) coh_store(&a.du[((long)lane * T + t) * H + o], pick(acc[0], lane));
-      } else {
-        const int oo = o - H;
-        const float* const wr[1] = {a.wt.w_hh + (long)oo * 3 * H};
-        wave_dots<1>(wr, xb, 3 * H, 3 * H, B, acc);
-        if (lane < B) coh_store(&carry_out[lane * H + oo], pick(acc[0], lane) + dd[lane * H + oo]);
-      }
-    }
+    layer<1>(2 * H, B, [&](int o) { return pq_row<1>(o, H, a.wt[WT_IH], a.wt[WT_HH], 3 * H, 3 * H, xa, xb); },      // du | dh_{t-1}
+             [&](const LayerRow<1>& r, const float (&v)[1]) {
+               if (r.part) coh_store(&carry_out[lane * H + r.j], v[0] + dd[lane * H + r.j]);
+               else coh_store(&a.grad[G_U][lrow * H + r.j], v[0]);
+             });
     target += gridDim.x;
     GRID_BARRIER(a.bar, target);
     // ------------------------------------------------------------------ B3: dz_{t-1} = W_pre^T du
-    lds_load(xa, a.du + (long)t * H, B, H, (long)T * H);
+    lds_load(xa, a.grad[G_U] + (long)t * H, B, H, (long)T * H);
     __syncthreads();
-    for (int o = gw; o < S; o += NW) {
-      const float* const wr[1] = {a.wt.w_pre + (long)o * H};
-      float acc[1][RSSM_BM];
-      wave_dots<1>(wr, xa, H, H, B, acc);
-      if (lane < B) coh_store(&a.dz_carry[lane * S + o], pick(acc[0], lane));
-    }
+    layer<1>(S, B, [&](int o) { return pq_row<1>(o, S, a.wt[WT_PRE], a.wt[WT_PRE], H, H, xa, xa); },
+             [&](const LayerRow<1>& r, const float (&v)[1]) { coh_store(&a.dz_carry[lane * S + r.j], v[0]); });
     target += gridDim.x;
     GRID_BARRIER(a.bar, target);
   }
@@ -420,6 +431,27 @@ __global__ void __launch_bounds__(256) rssm_transpose_kernel(const TransTable tb
       if (c0 + k < it.cols && r0 + tx < it.rows) it.out[(long)(c0 + k) * it.rows + r0 + tx] = tile[tx][k];
     __syncthreads();
   }
+}
+
+// The seven transposed matrices, in the order of RssmBwdArgs::wt and of their places in wt_scratch: {weight, rows, cols} of the
+// original.  Returns their floats; with a table to fill, tb gets weights[.] as input and consecutive pieces of `out` as output.
+static int64_t rssm_transposes(int H, int S, int E, int A, const float* const* weights, float* out, TransTable* tb) {
+  const int HP = H + A, HQ = H + E + A;
+  const int m[WT_N][3] = {{W_PRE, H, S}, {W_IH, 3 * H, H}, {W_HH, 3 * H, H}, {W_P0, HP, HP}, {W_P2, 2 * S, HP}, {W_Q0, HQ, HQ},
+                          {W_Q2, 2 * S, HQ}};
+  int64_t n = 0;
+  for (int i = 0; i < WT_N; ++i) {
+    if (tb) tb->m[i] = {weights[m[i][0]], out + n, m[i][1], m[i][2]};
+    n += (int64_t)m[i][1] * m[i][2];
+  }
+  return n;
+}
+// The backward kernel's global scratch for a launch over B sequences: dxp (B,HP) | dxq (B,HQ) | dh_carry 2 x (B,H), the steps
+// alternate between the halves | dz_carry (B,S).  Returns its floats; with arguments to fill, `a` gets the pieces of `base`.
+static int64_t rssm_bwd_scratch(int64_t B, int H, int S, int E, int A, float* base, RssmBwdArgs* a) {
+  const int64_t n[4] = {B * (H + A), B * (H + E + A), 2 * B * H, B * S};
+  if (a) { a->dxp = base; a->dxq = a->dxp + n[0]; a->dh_carry = a->dxq + n[1]; a->dz_carry = a->dh_carry + n[2]; }
+  return n[0] + n[1] + n[2] + n[3];
 }
 
 // Per-device launch state: CU count, and per kernel the number of co-resident workgroups the occupancy calculator grants
@@ -454,29 +486,60 @@ static bool rssm_dims_ok(const RssmDims& d) {
   return d.B >= 1 && d.B <= 64 && d.T >= 1 && d.T <= 64 && d.H % 4 == 0 && d.S % 4 == 0 && d.E % 4 == 0 && d.A % 4 == 0 &&
          d.AD >= 1 && d.H > 0 && d.S > 0 && d.E > 0 && d.A > 0;
 }
-static size_t rssm_fwd_lds(int B, int H, int S, int E, int A, int AD) {
-  const int HQ = H + E + A;
-  return sizeof(float) * ((size_t)B * ((HQ > S ? HQ : S) + (H + A) + H + AD) + 16);
+
+// dst[i] = src[i] + rows * width[i]: a table of (B, T, .) tensors moved to a slab's first row (a NULL entry stays NULL)
+template <int N, class P>
+static void rssm_offset(P* (&dst)[N], P* const* src, const long (&width)[N], long rows) {
+  for (int i = 0; i < N; ++i) dst[i] = src[i] ? src[i] + rows * width[i] : nullptr;
 }
-static size_t rssm_bwd_lds(int B, int H, int S, int E, int A) {
-  const int HP = H + A, HQ = H + E + A, m3 = 3 * H > 2 * S ? 3 * H : 2 * S, m1 = HQ > m3 ? HQ : m3, m2 = HP > m3 ? HP : m3;
-  return sizeof(float) * ((size_t)B * (m1 + m2 + H) + 16);
+
+// The launch path of both kernels, entered after the argument checks: the LDS limit, the device, the dynamic-LDS attribute (raised
+// once per device), the grid, the transposes (backward: tb), then one launch per slab of <= RSSM_BM sequences: slab(a, rows, Bc)
+// points the arguments at the slab, which starts at row `rows` of the (B T, .) tensors, the barrier counter is zeroed, the
+// kernel launched.  `a` arrives with everything that does not depend on the slab filled in.
+template <class Args, class Slab>
+static int rssm_launch(const char* name, void (*kernel)(Args), int RssmDev::*attr, size_t ldsb, const TransTable* tb, Args a,
+                       uint32_t* barrier_word, Slab slab, void* stream) {
+  MUVO_CHECK_ARG(ldsb <= RSSM_MAX_DYN_LDS, "%s: LDS", name);
+  RssmDev* dv = rssm_dev();
+  MUVO_CHECK_ARG(dv, "%s: cannot query the device", name);
+  if (!(dv->*attr)) {        // (static LDS of the kernel: the barrier's 4-byte flag; static + dynamic <= 160 KB)
+    if (hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, RSSM_MAX_DYN_LDS) != hipSuccess) {
+      (void)hipGetLastError();
+      muvo_set_error("%s: cannot raise the dynamic LDS limit", name);
+      return MUVO_ERR_HIP;
+    }
+    dv->*attr = 1;
+  }
+  const int G = rssm_grid((const void*)kernel, ldsb);
+  MUVO_CHECK_ARG(G > 0, "%s: the occupancy calculator grants no resident workgroup (LDS %zu B)", name, ldsb);
+  if (tb) {
+    hipLaunchKernelGGL(rssm_transpose_kernel, dim3(512, 1, WT_N), dim3(256), 0, ST, *tb);
+    MUVO_CHECK_LAUNCH(name);
+  }
+  const int B = a.d.B;
+  a.bar = barrier_word;
+  for (int b0 = 0; b0 < B; b0 += RSSM_BM) {
+    a.d.B = B - b0 < RSSM_BM ? B - b0 : RSSM_BM;
+    slab(a, (long)b0 * a.d.T, a.d.B);
+    if (hipMemsetAsync(barrier_word, 0, 4, ST) != hipSuccess) { muvo_set_error("%s: memset failed", name); return MUVO_ERR_HIP; }
+    hipLaunchKernelGGL(kernel, dim3(G), dim3(RSSM_THREADS), ldsb, ST, a);
+    MUVO_CHECK_LAUNCH(name);
+  }
+  return MUVO_OK;
 }
 
 extern "C" {
-/* pointer tables (see include/muvo_hip.h): weights[18], fwd_io[22], bwd_io[27].  Sequences are independent (transition.py:
-   76-127 loops over t, never over b): more than RSSM_BM of them run as consecutive launches over slabs of <= RSSM_BM
-   sequences of the same (B, T, .) tensors. */
+/* pointer tables (see include/muvo_hip.h): weights[18], out7, keep12, kept5, upstream7, grads10.  Sequences are independent
+   (transition.py:76-127 loops over t, never over b): more than RSSM_BM of them run as consecutive launches over slabs of
+   <= RSSM_BM sequences of the same (B, T, .) tensors. */
 int muvo_rssm_supported(int B, int T, int H, int S, int E, int A, int AD) {
   const RssmDims d = {B, T, H, S, E, A, AD};
   if (!rssm_dims_ok(d) || !rssm_dev()) return 0;
-  const int Bc = B < RSSM_BM ? B : RSSM_BM;
-  return rssm_fwd_lds(Bc, H, S, E, A, AD) <= RSSM_MAX_DYN_LDS && rssm_bwd_lds(Bc, H, S, E, A) <= RSSM_MAX_DYN_LDS ? 1 : 0;
+  return sizeof(float) * rssm_fwd_lds(d).total <= RSSM_MAX_DYN_LDS && sizeof(float) * rssm_bwd_lds(d).total <= RSSM_MAX_DYN_LDS ? 1 : 0;
 }
-int64_t muvo_rssm_transposed_floats(int H, int S, int E, int A) {
-  const int64_t HP = H + A, HQ = H + E + A;
-  return (int64_t)H * S + 2 * (int64_t)3 * H * H + HP * HP + 2 * (int64_t)S * HP + HQ * HQ + 2 * (int64_t)S * HQ;
-}
+int64_t muvo_rssm_transposed_floats(int H, int S, int E, int A) { return rssm_transposes(H, S, E, A, nullptr, nullptr, nullptr); }
+int64_t muvo_rssm_scratch_floats(int B, int H, int S, int E, int A) { return rssm_bwd_scratch(B, H, S, E, A, nullptr, nullptr); }
 int muvo_rssm_forward(int B, int T, int H, int S, int E, int A, int AD, const float* const* weights, const float* emb,
                       const float* act, const float* noise, uint64_t use_prior_mask, float* const* out7, float* const* keep12,
                       uint32_t* barrier_word, float min_std, void* stream) {
@@ -484,42 +547,17 @@ int muvo_rssm_forward(int B, int T, int H, int S, int E, int A, int AD, const fl
   a.d = {B, T, H, S, E, A, AD};
   MUVO_CHECK_ARG(rssm_dims_ok(a.d), "rssm_forward: dims (B=%d <= 64, T=%d <= 64, sizes %% 4) outside the fused kernel's range", B, T);
   MUVO_CHECK_ARG(weights && emb && act && noise && out7 && keep12 && barrier_word, "rssm_forward: null pointer");
-  const float** wp = (const float**)&a.w;
-  for (int i = 0; i < 18; ++i) { MUVO_CHECK_ARG(weights[i], "rssm_forward: weight %d is NULL", i); wp[i] = weights[i]; }
-  for (int i = 0; i < 7; ++i) MUVO_CHECK_ARG(out7[i], "rssm_forward: output %d is NULL", i);
-  for (int i = 0; i < 12; ++i) MUVO_CHECK_ARG(keep12[i], "rssm_forward: workspace %d is NULL", i);
-  a.use_prior = use_prior_mask; a.bar = barrier_word; a.min_std = min_std;
-  const int HP = H + A, HQ = H + E + A;
-  const int Bmax = B < RSSM_BM ? B : RSSM_BM;
-  const size_t ldsb = rssm_fwd_lds(Bmax, H, S, E, A, AD);
-  MUVO_CHECK_ARG(ldsb <= RSSM_MAX_DYN_LDS, "rssm_forward: LDS");
-  RssmDev* dv = rssm_dev();
-  MUVO_CHECK_ARG(dv, "rssm_forward: cannot query the device");
-  if (!dv->attr_fwd) {       // (static LDS of the kernel: the barrier's 4-byte flag; static + dynamic <= 160 KB)
-    if (hipFuncSetAttribute((const void*)rssm_fwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, RSSM_MAX_DYN_LDS) != hipSuccess) {
-      (void)hipGetLastError();
-      muvo_set_error("rssm_forward: cannot raise the dynamic LDS limit");
-      return MUVO_ERR_HIP;
-    }
-    dv->attr_fwd = 1;
-  }
-  const int G = rssm_grid((const void*)rssm_fwd_kernel, ldsb);
-  MUVO_CHECK_ARG(G > 0, "rssm_forward: the occupancy calculator grants no resident workgroup (LDS %zu B)", ldsb);
-  const long odim[7] = {H, S, S, S, S, S, S};
-  const long kdim[12] = {H, S, AD, H, 3L * H, 3L * H, HP, HQ, HP, HQ, 2L * S, 2L * S};
-  for (int b0 = 0; b0 < B; b0 += RSSM_BM) {
-    a.d.B = B - b0 < RSSM_BM ? B - b0 : RSSM_BM;
-    const long r0 = (long)b0 * T;
-    a.emb = emb + r0 * E; a.act = act + r0 * AD; a.noise = noise + r0 * 2 * S;
-    float** op = &a.h;
-    for (int i = 0; i < 7; ++i) op[i] = out7[i] + r0 * odim[i];
-    float** kp = &a.hprev;
-    for (int i = 0; i < 12; ++i) kp[i] = keep12[i] + r0 * kdim[i];
-    if (hipMemsetAsync(barrier_word, 0, 4, ST) != hipSuccess) { muvo_set_error("rssm_forward: memset failed"); return MUVO_ERR_HIP; }
-    hipLaunchKernelGGL(rssm_fwd_kernel, dim3(G), dim3(RSSM_THREADS), ldsb, ST, a);
-    MUVO_CHECK_LAUNCH("rssm_forward");
-  }
-  return MUVO_OK;
+  for (int i = 0; i < W_N; ++i) { MUVO_CHECK_ARG(weights[i], "rssm_forward: weight %d is NULL", i); a.w[i] = weights[i]; }
+  for (int i = 0; i < O_N; ++i) MUVO_CHECK_ARG(out7[i], "rssm_forward: output %d is NULL", i);
+  for (int i = 0; i < K_N; ++i) MUVO_CHECK_ARG(keep12[i], "rssm_forward: workspace %d is NULL", i);
+  a.use_prior = use_prior_mask; a.min_std = min_std;
+  const RssmWidths wd = rssm_widths(a.d);
+  return rssm_launch("rssm_forward", rssm_fwd_kernel, &RssmDev::attr_fwd, sizeof(float) * rssm_fwd_lds(a.d).total, nullptr, a, barrier_word,
+                     [&](RssmFwdArgs& s, long rows, int) {
+                       s.emb = emb + rows * E; s.act = act + rows * AD; s.noise = noise + rows * 2 * S;
+                       rssm_offset(s.out, out7, wd.out, rows);
+                       rssm_offset(s.keep, keep12, wd.keep, rows);
+                     }, stream);
 }
 int muvo_rssm_backward(int B, int T, int H, int S, int E, int A, int AD, const float* const* weights, float* wt_scratch,
                        const float* noise, uint64_t use_prior_mask, const float* const* kept5, const float* const* upstream7,
@@ -528,61 +566,20 @@ int muvo_rssm_backward(int B, int T, int H, int S, int E, int A, int AD, const f
   a.d = {B, T, H, S, E, A, AD};
   MUVO_CHECK_ARG(rssm_dims_ok(a.d), "rssm_backward: dims outside the fused kernel's range");
   MUVO_CHECK_ARG(weights && wt_scratch && noise && kept5 && upstream7 && grads10 && scratch && barrier_word, "rssm_backward: null pointer");
-  const int HP = H + A, HQ = H + E + A;
-  // transposes of the seven big matrices, one launch
   TransTable tb;
-  float* o = wt_scratch;
-  const struct { int idx, rows, cols; } mats[7] = {{0, H, S}, {2, 3 * H, H}, {3, 3 * H, H}, {10, HP, HP}, {12, 2 * S, HP},
-                                                   {14, HQ, HQ}, {16, 2 * S, HQ}};
-  const float** wtp = (const float**)&a.wt;
-  for (int i = 0; i < 18; ++i) wtp[i] = weights[i];
-  for (int i = 0; i < 7; ++i) {
-    MUVO_CHECK_ARG(weights[mats[i].idx], "rssm_backward: weight is NULL");
-    tb.m[i] = {weights[mats[i].idx], o, mats[i].rows, mats[i].cols};
-    wtp[mats[i].idx] = o;
-    o += (size_t)mats[i].rows * mats[i].cols;
-  }
-  for (int i = 0; i < 5; ++i) MUVO_CHECK_ARG(kept5[i], "rssm_backward: kept tensor %d is NULL", i);
-  for (int i = 0; i < 10; ++i) MUVO_CHECK_ARG(grads10[i], "rssm_backward: gradient buffer %d is NULL", i);
-  const int Bmax = B < RSSM_BM ? B : RSSM_BM;
-  const size_t ldsb = rssm_bwd_lds(Bmax, H, S, E, A);
-  MUVO_CHECK_ARG(ldsb <= RSSM_MAX_DYN_LDS, "rssm_backward: LDS");
-  RssmDev* dv = rssm_dev();
-  MUVO_CHECK_ARG(dv, "rssm_backward: cannot query the device");
-  if (!dv->attr_bwd) {
-    if (hipFuncSetAttribute((const void*)rssm_bwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, RSSM_MAX_DYN_LDS) != hipSuccess) {
-      (void)hipGetLastError();
-      muvo_set_error("rssm_backward: cannot raise the dynamic LDS limit");
-      return MUVO_ERR_HIP;
-    }
-    dv->attr_bwd = 1;
-  }
-  const int G = rssm_grid((const void*)rssm_bwd_kernel, ldsb);
-  MUVO_CHECK_ARG(G > 0, "rssm_backward: the occupancy calculator grants no resident workgroup (LDS %zu B)", ldsb);
-  hipLaunchKernelGGL(rssm_transpose_kernel, dim3(512, 1, 7), dim3(256), 0, ST, tb);
-  a.use_prior = use_prior_mask; a.bar = barrier_word;
-  const long kdim[5] = {H, 3L * H, 3L * H, 2L * S, 2L * S};
-  const long udim[7] = {H, S, S, S, S, S, S};
-  const long gdim[10] = {E, 2L * S, 2L * S, HP, HQ, 3L * H, 3L * H, H, A, A};
-  for (int b0 = 0; b0 < B; b0 += RSSM_BM) {
-    const int Bc = B - b0 < RSSM_BM ? B - b0 : RSSM_BM;
-    a.d.B = Bc;
-    const long r0 = (long)b0 * T;
-    a.noise = noise + r0 * 2 * S;
-    const float** kp = &a.hprev;
-    for (int i = 0; i < 5; ++i) kp[i] = kept5[i] + r0 * kdim[i];
-    const float** up = &a.g_h;
-    for (int i = 0; i < 7; ++i) up[i] = upstream7[i] ? upstream7[i] + r0 * udim[i] : nullptr;
-    float** gp = &a.d_emb;
-    for (int i = 0; i < 10; ++i) gp[i] = grads10[i] + r0 * gdim[i];
-    a.dxp = scratch; a.dxq = a.dxp + (size_t)Bc * HP; a.dh_carry = a.dxq + (size_t)Bc * HQ; a.dz_carry = a.dh_carry + (size_t)2 * Bc * H;
-    if (hipMemsetAsync(barrier_word, 0, 4, ST) != hipSuccess) { muvo_set_error("rssm_backward: memset failed"); return MUVO_ERR_HIP; }
-    hipLaunchKernelGGL(rssm_bwd_kernel, dim3(G), dim3(RSSM_THREADS), ldsb, ST, a);
-    MUVO_CHECK_LAUNCH("rssm_backward");
-  }
-  return MUVO_OK;
-}
-int64_t muvo_rssm_scratch_floats(int B, int H, int S, int E, int A) {
-  return (int64_t)B * ((H + A) + (H + E + A) + 2 * H + S);
+  rssm_transposes(H, S, E, A, weights, wt_scratch, &tb);
+  for (int i = 0; i < WT_N; ++i) { MUVO_CHECK_ARG(tb.m[i].in, "rssm_backward: a weight is NULL"); a.wt[i] = tb.m[i].out; }
+  for (int i = 0; i < KP_N; ++i) MUVO_CHECK_ARG(kept5[i], "rssm_backward: kept tensor %d is NULL", i);
+  for (int i = 0; i < G_N; ++i) MUVO_CHECK_ARG(grads10[i], "rssm_backward: gradient buffer %d is NULL", i);
+  a.use_prior = use_prior_mask;
+  const RssmWidths wd = rssm_widths(a.d);
+  return rssm_launch("rssm_backward", rssm_bwd_kernel, &RssmDev::attr_bwd, sizeof(float) * rssm_bwd_lds(a.d).total, &tb, a, barrier_word,
+                     [&](RssmBwdArgs& s, long rows, int Bc) {
+                       s.noise = noise + rows * 2 * S;
+                       rssm_offset(s.kept, kept5, wd.kept, rows);
+                       rssm_offset(s.up, upstream7, wd.out, rows);
+                       rssm_offset(s.grad, grads10, wd.grad, rows);
+                       rssm_bwd_scratch(Bc, H, S, E, A, scratch, &s);
+                     }, stream);
 }
 }

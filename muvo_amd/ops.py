@@ -2368,14 +2368,40 @@ def _ptr_table(tensors):
     return arr
 
 
+# The pointer tables of muvo_rssm_forward / muvo_rssm_backward by name, in the order of include/muvo_hip.h: the weights with their
+# place in the module, the kept and gradient tensors (B, T, .) with the symbol of their last-axis width (_rssm_new).  Plain data:
+# tests/test_rssm_reference.py holds it against tests/rssm_reference.py.
+RSSM_WEIGHTS = dict(w_pre='pre_gru_net.0.weight', b_pre='pre_gru_net.0.bias', w_ih='recurrent_model.weight_ih',
+                    w_hh='recurrent_model.weight_hh', b_ih='recurrent_model.bias_ih', b_hh='recurrent_model.bias_hh',
+                    w_pa='prior_action_module.0.weight', b_pa='prior_action_module.0.bias', w_qa='posterior_action_module.0.weight',
+                    b_qa='posterior_action_module.0.bias', w_p0='prior.module.0.weight', b_p0='prior.module.0.bias',
+                    w_p2='prior.module.2.weight', b_p2='prior.module.2.bias', w_q0='posterior.module.0.weight',
+                    b_q0='posterior.module.0.bias', w_q2='posterior.module.2.weight', b_q2='posterior.module.2.bias')
+RSSM_KEEP12 = dict(hprev='H', zprev='S', aprev='AD', u='H', gi='3H', gh='3H', xp='HP', xq='HQ', y1p='HP', y1q='HQ', mls_p='2S', mls_q='2S')
+RSSM_GRAD10 = dict(d_emb='E', dmls_p='2S', dmls_q='2S', dy1p='HP', dy1q='HQ', dgi='3H', dgh='3H', du='H', dla_p='A', dla_q='A')
+# weight gradient = dY^T X over the B T rows, bias gradient = column sums of dY: (dY, X, weight, bias)
+RSSM_PARAM_PAIRS = (('du', 'zprev', 'w_pre', 'b_pre'), ('dgi', 'u', 'w_ih', 'b_ih'), ('dgh', 'hprev', 'w_hh', 'b_hh'),
+                    ('dla_p', 'aprev', 'w_pa', 'b_pa'), ('dla_q', 'aprev', 'w_qa', 'b_qa'), ('dy1p', 'xp', 'w_p0', 'b_p0'),
+                    ('dmls_p', 'y1p', 'w_p2', 'b_p2'), ('dy1q', 'xq', 'w_q0', 'b_q0'), ('dmls_q', 'y1q', 'w_q2', 'b_q2'))
+
+
 def rssm_weights(rssm):
-    """The 18 parameter tensors in the order of include/muvo_hip.h: muvo_rssm_forward."""
-    return [rssm.pre_gru_net[0].weight, rssm.pre_gru_net[0].bias, rssm.recurrent_model.weight_ih, rssm.recurrent_model.weight_hh,
-            rssm.recurrent_model.bias_ih, rssm.recurrent_model.bias_hh, rssm.prior_action_module[0].weight,
-            rssm.prior_action_module[0].bias, rssm.posterior_action_module[0].weight, rssm.posterior_action_module[0].bias,
-            rssm.prior.module[0].weight, rssm.prior.module[0].bias, rssm.prior.module[2].weight, rssm.prior.module[2].bias,
-            rssm.posterior.module[0].weight, rssm.posterior.module[0].bias, rssm.posterior.module[2].weight,
-            rssm.posterior.module[2].bias]
+    """The 18 parameter tensors in the order of RSSM_WEIGHTS."""
+    return [rssm.get_parameter(path) for path in RSSM_WEIGHTS.values()]
+
+
+def _rssm_new(table, dims, dev):
+    """{name: empty (B, T, width) tensor} in the order of a table {name: width symbol}"""
+    B, T, H, S, E, A, AD = dims
+    wd = {'H': H, 'S': S, 'E': E, 'A': A, 'AD': AD, '3H': 3 * H, '2S': 2 * S, 'HP': H + A, 'HQ': H + E + A}
+    return {n: torch.empty(B, T, wd[w], device=dev, dtype=torch.float32) for n, w in table.items()}
+
+
+def _rssm_grid_may_start(dev):
+    """deterministic mode runs single-workgroup weight-gradient kernels on the side streams that can hold a compute unit for a long
+    time: the persistent grid must not wait for them inside its bounded barrier spin"""
+    if get_deterministic():
+        join_side_streams(dev)
 
 
 class RSSMFusedFn(torch.autograd.Function):
@@ -2386,59 +2412,49 @@ class RSSMFusedFn(torch.autograd.Function):
     def forward(ctx, emb, act, noise, rssm, mask):
         emb, act, noise = emb.contiguous(), act.contiguous(), noise.contiguous()
         B, T, E = emb.shape
-        AD, H, S, A = act.shape[-1], rssm.hidden_state_dim, rssm.state_dim, rssm.action_latent_dim
+        dims = (B, T, rssm.hidden_state_dim, rssm.state_dim, E, rssm.action_latent_dim, act.shape[-1])
         dev = emb.device
-        new = lambda n: torch.empty(B, T, n, device=dev, dtype=torch.float32)
-        out = [new(H)] + [new(S) for _ in range(6)]
-        keep = [new(n) for n in (H, S, AD, H, 3 * H, 3 * H, H + A, H + E + A, H + A, H + E + A, 2 * S, 2 * S)]
+        out = _rssm_new(dict(h='H', mu_p='S', sg_p='S', z_p='S', mu_q='S', sg_q='S', z_q='S'), dims, dev)
+        keep = _rssm_new(RSSM_KEEP12, dims, dev)
         bar = rssm_barrier_words(dev)
         rssm_check(dev, post=False)
-        if get_deterministic():
-            # deterministic mode runs single-workgroup weight-gradient kernels on the side streams that can hold a compute unit for
-            # a long time: the persistent grid must not wait for them inside its bounded barrier spin
-            join_side_streams(dev)
-        w = rssm_weights(rssm)
-        _ck(lib().muvo_rssm_forward(B, T, H, S, E, A, AD, _ptr_table(w), _f(emb), _f(act), _f(noise), C.c_uint64(mask),
-                                    _ptr_table(out), _ptr_table(keep), _p(bar), _fl(rssm.prior.min_std), _st()))
+        _rssm_grid_may_start(dev)
+        _ck(lib().muvo_rssm_forward(*dims, _ptr_table(rssm_weights(rssm)), _f(emb), _f(act), _f(noise), C.c_uint64(mask),
+                                    _ptr_table(list(out.values())), _ptr_table(list(keep.values())), _p(bar),
+                                    _fl(rssm.prior.min_std), _st()))
         if not any(ctx.needs_input_grad):
             rssm_check(dev)        # no backward will follow (validation / imagination): post the error-word copy here
-        ctx.rssm, ctx.mask, ctx.dims = rssm, mask, (B, T, H, S, E, A, AD)
-        ctx.save_for_backward(noise, *keep)
-        return tuple(out)
+        ctx.rssm, ctx.mask, ctx.dims = rssm, mask, dims
+        ctx.save_for_backward(noise, *keep.values())
+        return tuple(out.values())
 
     @staticmethod
     def backward(ctx, *gout):
-        noise, hprev, zprev, aprev, u, gi, gh, xp, xq, y1p, y1q, mls_p, mls_q = ctx.saved_tensors
+        noise, *kept = ctx.saved_tensors
         B, T, H, S, E, A, AD = ctx.dims
-        rssm = ctx.rssm
         dev = noise.device
         L = lib()
         gout = [None if g is None else g.contiguous() for g in gout]
-        new = lambda n: torch.empty(B, T, n, device=dev, dtype=torch.float32)
-        d_emb = new(E)
-        dmls_p, dmls_q, dy1p, dy1q, dgi, dgh, du, dla_p, dla_q = (new(n) for n in (2 * S, 2 * S, H + A, H + E + A, 3 * H, 3 * H, H, A, A))
+        t = dict(zip(RSSM_KEEP12, kept), **_rssm_new(RSSM_GRAD10, ctx.dims, dev))
         wt = scratch('rssm_wt', L.muvo_rssm_transposed_floats(H, S, E, A), dev)
         sc = scratch('rssm_scratch', L.muvo_rssm_scratch_floats(B, H, S, E, A), dev)
         bar = rssm_barrier_words(dev)
-        if get_deterministic():
-            join_side_streams(dev)
-        w = rssm_weights(rssm)
-        _ck(L.muvo_rssm_backward(B, T, H, S, E, A, AD, _ptr_table(w), _f(wt), _f(noise), C.c_uint64(ctx.mask),
-                                 _ptr_table([hprev, gi, gh, mls_p, mls_q]), _ptr_table(gout),
-                                 _ptr_table([d_emb, dmls_p, dmls_q, dy1p, dy1q, dgi, dgh, du, dla_p, dla_q]), _f(sc), _p(bar), _st()))
+        _rssm_grid_may_start(dev)
+        w = dict(zip(RSSM_WEIGHTS, rssm_weights(ctx.rssm)))
+        _ck(L.muvo_rssm_backward(*ctx.dims, _ptr_table(list(w.values())), _f(wt), _f(noise), C.c_uint64(ctx.mask),
+                                 _ptr_table([t[n] for n in ('hprev', 'gi', 'gh', 'mls_p', 'mls_q')]), _ptr_table(gout),
+                                 _ptr_table([t[n] for n in RSSM_GRAD10]), _f(sc), _p(bar), _st()))
         rssm_check(dev)
         rows = B * T
-        for dz, x, wi in ((du, zprev, 0), (dgi, u, 2), (dgh, hprev, 3), (dla_p, aprev, 6), (dla_q, aprev, 8), (dy1p, xp, 10),
-                          (dmls_p, y1p, 12), (dy1q, xq, 14), (dmls_q, y1q, 16)):
-            weight = w[wi]
-            out_f, in_f = weight.shape
-            if weight.requires_grad:
-                gemm(dz, x, grad_of(weight), out_f, in_f, rows, 1, out_f, in_f, 1, in_f, mode=1)
-        for dz, bi in ((du, 1), (dgi, 4), (dgh, 5), (dla_p, 7), (dla_q, 9), (dy1p, 11), (dmls_p, 13), (dy1q, 15), (dmls_q, 17)):
-            if w[bi].requires_grad:
-                n = w[bi].numel()
-                _ck(L.muvo_colsum_acc(_f(dz), _f(grad_of(w[bi])), _i64(rows), _i64(n), _i64(n), _st()))
-        return d_emb, None, None, None, None
+        for dy, x, wn, _ in RSSM_PARAM_PAIRS:
+            out_f, in_f = w[wn].shape
+            if w[wn].requires_grad:
+                gemm(t[dy], t[x], grad_of(w[wn]), out_f, in_f, rows, 1, out_f, in_f, 1, in_f, mode=1)
+        for dy, _, _, bn in RSSM_PARAM_PAIRS:
+            if w[bn].requires_grad:
+                n = w[bn].numel()
+                _ck(L.muvo_colsum_acc(_f(t[dy]), _f(grad_of(w[bn])), _i64(rows), _i64(n), _i64(n), _st()))
+        return t['d_emb'], None, None, None, None
 
 
 FUSED_RSSM = os.environ.get('MUVO_FUSED_RSSM', '1') != '0'

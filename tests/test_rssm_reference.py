@@ -228,3 +228,16 @@ def test_support_mirror_sweep():
     assert R.supported(4, 1, 4, 4, 10196, 4, 1) == 1 and R.supported(4, 1, 4, 4, 10200, 4, 1) == 0
     for H in range(1400, 1500, 4):
         assert R.supported(4, 1, H, 4, 4, 4, 2) == int(H <= 1460)
+
+
+def test_ops_tables_are_the_reference_tables():
+    """ops.RSSMFusedFn addresses its tensors by the names and in the table orders stated here (plain data: no GPU, no library)"""
+    from muvo_amd import ops
+    assert ops.RSSM_PARAM_PAIRS == R.PARAM_PAIRS
+    assert tuple(ops.RSSM_WEIGHTS) == R.WNAMES and tuple(ops.RSSM_WEIGHTS.values()) == R.MODULE_NAMES
+    assert tuple(ops.RSSM_KEEP12) == R.KEEP12 and tuple(ops.RSSM_GRAD10) == R.GRAD10
+    for c in R.CASES:
+        wd = R.widths(c)
+        dims = (1, 1, *c['dims'], c['AD'])
+        made = dict(ops._rssm_new(ops.RSSM_KEEP12, dims, 'cpu'), **ops._rssm_new(ops.RSSM_GRAD10, dims, 'cpu'))
+        assert {n: t.shape[-1] for n, t in made.items()} == {n: wd[n] for n in R.KEEP12 + R.GRAD10}, c['name']
