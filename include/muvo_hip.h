@@ -1005,6 +1005,46 @@ int64_t muvo_voxel_cd_ws_bytes(int64_t F, int64_t V);
 int muvo_voxel_cd_counts(const uint8_t* label, const uint8_t* pred, const int32_t* edt_label, const int32_t* edt_pred, int64_t F, int X, int Y, int Z,
                          const int32_t* thresholds2, uint64_t* counts, double* sums, void* ws, int64_t ws_bytes, void* stream);
 
+/* ---- BEV instances from the centre / offset heads and their panoptic quality (bev_instance.hip; extensions)
+ * OUR DEFINITIONS (the post-processing of Panoptic-DeepLab / FIERY, which the reference does not carry);
+ * tests/bev_instance_reference.py restates them and the kernels equal that restatement exactly.
+ * Inputs per frame: a centre map c (H, W) fp32; offsets o (2, H, W) fp32, channel 0 = centre_y - y, channel 1 = centre_x - x (the
+ *   convention of muvo_instance_labels); and EITHER logits (C, H, W) fp32, 2 <= C <= 32, with a 32-bit set `things` (bit k: class k
+ *   is a thing) OR a foreground mask (H, W) uint8 (non-zero = foreground); the other pointer is null.  F in 1..65535 frames along a
+ *   grid dimension, H and W in 1..4096, H W <= 2^24; everything else is refused before the device is touched.
+ * Foreground: a pixel is foreground iff its argmax class is a thing.  The argmax starts at class 0, scans upward and replaces on
+ *   strictly greater: the first maximum wins, a NaN never replaces the running maximum (and a NaN at class 0 is never replaced).
+ * Peaks: p is a peak iff c[p] > threshold and no in-bounds q of the (2 radius + 1)^2 window has c[q] > c[p]; radius in 1..3.  Every
+ *   pixel of a plateau of equal maxima is a peak; a NaN is never a peak and never suppresses a neighbour.  threshold is not NaN.
+ * Selection: the K peaks with the highest score, 1 <= K <= 254, among equal scores (-0 = +0) the lower row-major index; the kept
+ *   centres are numbered 1..n in that order (score descending, then index ascending).  centres (F, K, 2) int32 holds (y, x) of centre
+ *   k at row k - 1 and (-1, -1) in the rows past n; n (F) int32; capped (F) int32 is 1 where the frame had more than K peaks, else 0.
+ * Grouping: for a foreground pixel (y, x), in fp32 and in this order (the library is built with -ffp-contract=off):
+ *     ty = (float)y + o0;  tx = (float)x + o1;  d_k = (ty - cy_k) * (ty - cy_k) + (tx - cx_k) * (tx - cx_k)
+ *   its id is the k (1-based) of the smallest d_k, the lowest k on equal d_k; a non-finite d_k never wins.  Background pixels, pixels
+ *   whose d_k are all non-finite and every pixel of a frame without a centre get id 0.  ids (F, H, W) uint8.
+ * ws: muvo_bev_instance_ws_bytes(F, H, W) bytes (-1 for refused sizes), 8-byte aligned: a counter and H W candidate keys per frame.
+ *   One memset and three launches whatever F; no host synchronisation, nothing is copied to the host.  The candidate list is filled
+ *   through an integer atomic; its order is arbitrary and no output depends on it. */
+int64_t muvo_bev_instance_ws_bytes(int64_t F, int H, int W);
+int muvo_bev_instance_decode(const float* center, const float* offset, const float* logits, int C, uint32_t things, const uint8_t* foreground, int64_t F,
+                             int H, int W, float threshold, int radius, int K, void* ws, int64_t ws_bytes, uint8_t* ids, int32_t* centres, int32_t* n,
+                             int32_t* capped, void* stream);
+/* Panoptic-quality counts of label ids g and predicted ids q, both (F, H, W) uint8 with 0 = none (sizes as above).  Per frame: the
+ *   areas a_i = #{g = i}, b_j = #{q = j} and the intersections n_ij; segments i, j > 0 MATCH iff 3 n_ij > a_i + b_j (IoU > 1/2 in
+ *   integers: a match is unique); TP = matches, FP = predicted segments (b_j > 0) without a match, FN = label segments (a_i > 0)
+ *   without one; the frame's IoU sum = sum over the matches of n_ij / (a_i + b_j - n_ij) in fp64.  ADDED TO the device accumulators
+ *   counts (7) int64 - [0] frames, [1] frames whose capped[f] != 0 (capped (F) int32 of the decode; may be null), [2] label
+ *   segments, [3] predicted segments, [4] tp, [5] fp, [6] fn - by integer atomics, and iou_sum (1) fp64: each frame's sum is added in
+ *   a fixed order into a slot of its own and one wave adds the slots in a fixed order (the same bits on every call).
+ *   ws: muvo_bev_pq_ws_bytes(F) bytes (-1 for refused F), 8-byte aligned: a 256 x 256 table of 32-bit counters per frame, filled by
+ *   integer atomics, and the slots: 256 KB a frame whatever the ids are, so the workspace, not the ABI's F <= 65535, bounds a call in
+ *   practice (1 GB at 4000 frames); a caller with more frames than its memory allows splits them over calls - the accumulators add up.
+ *   One memset and three launches whatever F; nothing is read back. */
+int64_t muvo_bev_pq_ws_bytes(int64_t F);
+int muvo_bev_pq_counts(const uint8_t* label, const uint8_t* pred, const int32_t* capped, int64_t F, int H, int W, uint64_t* counts, double* iou_sum, void* ws,
+                       int64_t ws_bytes, void* stream);
+
 /* ---- sensor-visibility mask of the voxel labels (visibility.hip; an extension) ----------------------------
  * OUR DEFINITION (the reference has no visibility mask; its SemScal / GeoScal losses carry ignore_index = 255 and nothing writes
  * one); tests/visibility_reference.py restates it and the kernels equal that restatement bit for bit.

@@ -113,6 +113,7 @@ EXPORTS = [
     'muvo_voxel_edt_ws_bytes', 'muvo_voxel_edt',
     'muvo_voxel_boundary_ws_bytes', 'muvo_voxel_boundary_forward', 'muvo_voxel_boundary_backward',
     'muvo_voxel_cd_ws_bytes', 'muvo_voxel_cd_counts',
+    'muvo_bev_instance_ws_bytes', 'muvo_bev_instance_decode', 'muvo_bev_pq_ws_bytes', 'muvo_bev_pq_counts',
     'muvo_visibility_mark', 'muvo_visibility_apply',
 ]
 
@@ -141,7 +142,8 @@ def lib():
                 L.muvo_icp_ws_doubles.restype = C.c_int64
                 for name in ('muvo_flow_max_pairs', 'muvo_flow_workspace_bytes', 'muvo_flow_colour_ws_bytes', 'muvo_flow_epe_ws_doubles',
                              'muvo_raycast_brick_words', 'muvo_ray_iou_ws_doubles', 'muvo_lovasz_ws_bytes', 'muvo_render_ws_bytes',
-                             'muvo_render_class_ws_bytes', 'muvo_voxel_edt_ws_bytes', 'muvo_voxel_boundary_ws_bytes', 'muvo_voxel_cd_ws_bytes'):
+                             'muvo_render_class_ws_bytes', 'muvo_voxel_edt_ws_bytes', 'muvo_voxel_boundary_ws_bytes', 'muvo_voxel_cd_ws_bytes',
+                             'muvo_bev_instance_ws_bytes', 'muvo_bev_pq_ws_bytes'):
                     getattr(L, name).restype = C.c_int64
                 for name in EXPORTS:
                     getattr(L, name)  # AttributeError if a declared symbol is missing
@@ -3199,6 +3201,76 @@ def voxel_cd_counts(label, pred_grid, thresholds2, counts, sums):
     ws = torch.empty(max(1, n // 8), device=label.device, dtype=torch.float64)
     _ck(lib().muvo_voxel_cd_counts(_p(label), _p(pred_grid), _p(edt_label), _p(edt_pred), _i64(F), X, Y, Z, (C.c_int32 * 3)(*thr), _p(counts), _p(sums),
                                    _p(ws), _i64(n), _st()))
+
+
+# ================================================================================================ BEV instances, panoptic quality
+def bev_instance_decode(center, offset, logits=None, foreground=None, threshold=0.1, radius=1, max_centres=100, thing_classes=(3, 4)):
+    """Instances from the centre / offset heads (include/muvo_hip.h: muvo_bev_instance_decode): center (F, H, W) fp32, offset
+    (F, 2, H, W) fp32 and either logits (F, C, H, W) fp32 with the thing classes or a foreground mask (F, H, W) uint8 ->
+    (ids (F, H, W) uint8, centres (F, K, 2) int32 (y, x), n (F,) int32, capped (F,) int32) on the device.  Nothing is read back."""
+    assert center.dtype == torch.float32 and center.dim() == 3, 'bev_instance_decode: centre maps (F, H, W) float32'
+    F, H, W = (int(v) for v in center.shape)
+    assert offset.dtype == torch.float32 and tuple(offset.shape) == (F, 2, H, W), 'bev_instance_decode: offsets (F, 2, H, W) float32'
+    assert (logits is None) != (foreground is None), 'bev_instance_decode: either logits or a foreground mask'
+    K, radius = int(max_centres), int(radius)
+    if not 1 <= K <= 254:
+        raise ValueError(f'bev_instance_decode: {K} centres outside 1..254')
+    if not 1 <= radius <= 3:
+        raise ValueError(f'bev_instance_decode: radius {radius} outside 1..3')
+    if math.isnan(float(threshold)):
+        raise ValueError('bev_instance_decode: the threshold is NaN')
+    Cn, things = 0, 0
+    if logits is not None:
+        assert logits.dtype == torch.float32 and logits.dim() == 4 and (logits.shape[0], *logits.shape[2:]) == (F, H, W), \
+            'bev_instance_decode: logits (F, C, H, W) float32'
+        Cn = int(logits.shape[1])
+        if not 2 <= Cn <= 32:
+            raise ValueError(f'bev_instance_decode: {Cn} classes outside 2..32')
+        for k in thing_classes:
+            if not 0 <= int(k) < 32:
+                raise ValueError(f'bev_instance_decode: thing class {k} outside 0..31')
+            things |= 1 << int(k)
+    else:
+        assert foreground.dtype == torch.uint8 and tuple(foreground.shape) == (F, H, W), 'bev_instance_decode: foreground mask (F, H, W) uint8'
+    src = logits if logits is not None else foreground
+    assert offset.device == center.device and src.device == center.device, 'bev_instance_decode: tensors of one device'
+    nbytes = int(lib().muvo_bev_instance_ws_bytes(_i64(F), H, W))
+    if nbytes < 0:
+        raise ValueError(f'bev_instance_decode: {F} frames of {H} x {W} (1..65535 frames, 1..4096 a side, at most 2^24 pixels)')
+    center, offset, src = center.contiguous(), offset.contiguous(), src.contiguous()
+    dev = center.device
+    ws = torch.empty(nbytes // 8, device=dev, dtype=torch.int64)
+    ids = torch.empty((F, H, W), device=dev, dtype=torch.uint8)
+    centres = torch.empty((F, K, 2), device=dev, dtype=torch.int32)
+    n = torch.empty((F,), device=dev, dtype=torch.int32)
+    capped = torch.empty((F,), device=dev, dtype=torch.int32)
+    _ck(lib().muvo_bev_instance_decode(_f(center), _f(offset), _f(src) if logits is not None else None, Cn, C.c_uint32(things),
+                                       _p(src) if logits is None else None, _i64(F), H, W, _fl(threshold), radius, K, _p(ws), _i64(nbytes), _p(ids),
+                                       _p(centres), _p(n), _p(capped), _st()))
+    return ids, centres, n, capped
+
+
+def bev_pq_counts(label, pred, counts, iou_sum, capped=None):
+    """counts (7,) int64 - frames, capped frames, label segments, predicted segments, tp, fp, fn - and iou_sum (1,) float64 on the
+    device are added to, over the F frames of the id maps label and pred (F, H, W) uint8, 0 = none (include/muvo_hip.h:
+    muvo_bev_pq_counts); capped: the (F,) int32 flags of bev_instance_decode, or None.  Nothing is read back."""
+    for t in (label, pred):
+        assert t.dtype == torch.uint8 and t.dim() == 3, 'bev_pq_counts: id maps (F, H, W) uint8'
+    assert label.shape == pred.shape and label.device == pred.device, 'bev_pq_counts: label and prediction of one shape'
+    F, H, W = (int(v) for v in label.shape)
+    assert counts.dtype == torch.int64 and tuple(counts.shape) == (7,) and counts.is_contiguous() and counts.device == label.device, \
+        'bev_pq_counts: counts (7,) int64'
+    assert iou_sum.dtype == torch.float64 and tuple(iou_sum.shape) == (1,) and iou_sum.is_contiguous() and iou_sum.device == label.device, \
+        'bev_pq_counts: iou_sum (1,) float64'
+    if capped is not None:
+        assert capped.dtype == torch.int32 and tuple(capped.shape) == (F,) and capped.device == label.device, 'bev_pq_counts: capped (F,) int32'
+        capped = capped.contiguous()
+    nbytes = int(lib().muvo_bev_pq_ws_bytes(_i64(F)))
+    if nbytes < 0 or not (1 <= H <= 4096 and 1 <= W <= 4096 and H * W <= 1 << 24):
+        raise ValueError(f'bev_pq_counts: {F} frames of {H} x {W} (1..65535 frames, 1..4096 a side, at most 2^24 pixels)')
+    label, pred = label.contiguous(), pred.contiguous()
+    ws = torch.empty(nbytes // 8, device=label.device, dtype=torch.int64)
+    _ck(lib().muvo_bev_pq_counts(_p(label), _p(pred), _p(capped), _i64(F), H, W, _p(counts), _p(iou_sum), _p(ws), _i64(nbytes), _st()))
 
 
 # ================================================================================================ ICP between lidar frames

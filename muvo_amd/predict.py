@@ -16,6 +16,9 @@ the TensorBoard writer, here they arrive with the rest) and `{set}_{bev,lidar,ca
 [label][prediction] as nested integer lists.  The reference's class-name table has two entries, so only two of the lidar and
 camera head's nine per-class scores carry a name; the matrix holds what the other seven are computed from.  The counts are
 taken on the device (csrc/metrics.hip: argmax + confusion matrix in one kernel per head and batch) and read once at the end.
+With that head on, `--bev-pq` also writes `bev_pq.json`, the panoptic quality of the instances decoded on the device from the
+head's centre / offset outputs, and `--panels N --inst` the `_inst` panels (muvo_amd/bev_instances.py); `metrics.json` is the same
+with and without them.
 
 `--mode sim` follows the loop of sim_run.py:49-116 (module in train() mode, the transformer's dropout modules off, no_grad;
 per batch `preprocess`, then `model.sim_forward(batch, is_dreaming=False)`) over one loader (default 2, sim_run.py:44) and
@@ -88,6 +91,11 @@ def build_parser():
     parser.add_argument('--ray-stride', type=int, default=4, metavar='K', help='--ray-iou: every K-th azimuth of the range view is a ray (default 4)')
     parser.add_argument('--voxel-cd', action='store_true',
                         help='test: Chamfer distance and F-scores at 1 / 2 / 4 m between the occupied cells of voxel label and prediction -> OUT/voxel_cd.json')
+    parser.add_argument('--bev-pq', action='store_true',
+                        help='test: panoptic quality of the instances decoded from the BEV centre / offset heads -> OUT/bev_pq.json')
+    parser.add_argument('--inst', action='store_true', help='with --panels: also the BEV instance panel `_inst` (label ids and decoded ids)')
+    parser.add_argument('--inst-threshold', type=float, default=0.1, metavar='T', help='--bev-pq / --inst: a centre is a peak above T (default 0.1)')
+    parser.add_argument('--inst-max-centres', type=int, default=100, metavar='K', help='--bev-pq / --inst: at most K centres per frame (default 100; 1..254)')
     parser.add_argument('--ego-motion', action='store_true',
                         help='test: drift of the ego path implied by the predicted lidar from the one implied by the recorded lidar -> OUT/ego_motion.json')
     parser.add_argument('--ego-threshold', type=float, default=5.0, metavar='M', help='ICP inlier distance in metres of --ego-motion and --traj (default 5, the reference)')
@@ -118,6 +126,12 @@ def parse_args(argv=None):
         raise SystemExit('--voxel-cd goes with --mode test')
     if args.voxel and not args.panels:
         raise SystemExit('--voxel goes with --panels N')
+    if (args.bev_pq or args.inst) and args.mode != 'test':
+        raise SystemExit('--bev-pq and --inst go with --mode test')
+    if args.inst and not args.panels:
+        raise SystemExit('--inst goes with --panels N')
+    if not 1 <= args.inst_max_centres <= 254 or args.inst_threshold != args.inst_threshold:
+        raise SystemExit('--inst-max-centres lies in 1..254 and --inst-threshold is a number')
     if args.voxel_size < 1 or args.ray_stride < 1:
         raise SystemExit('--voxel-size and --ray-stride must be positive')
     if args.ego_threshold <= 0 or args.ego_stride < 1 or args.ego_max_iteration < 0:
@@ -230,7 +244,7 @@ def seed_batch(module, seed, loader_idx, i):
 
 def run(cfg, device, out_dir, mode, loaders=None, limit_batches=None, shard_size=500, seed=1234, hook=None, dataset_root=None,
         data=None, module=None, log=print, panels=0, traj=False, ego_motion=None, icp_options=None, flow=False, optical_flow=False,
-        voxel=False, voxel_size=256, ray_iou=None, voxel_cd=None):
+        voxel=False, voxel_size=256, ray_iou=None, voxel_cd=None, bev_pq=None, inst=False):
     """Runs one mode and returns what it wrote: {'files': [...], 'batches': {loader: n}, 'metrics': {...}, 'confusion': {...} (test)}.
     hook(i, batch, output, output_imagine): called per batch with the device tensors (test mode: output_imagine is the list
     of imagined samples).  data: a set-up DataModule to take the test loaders from (default: one over dataset_root /
@@ -243,7 +257,10 @@ def run(cfg, device, out_dir, mode, loaders=None, limit_batches=None, shard_size
     not change.  voxel (test, with panels): also the `_voxel` panel with tiles of voxel_size pixels; ray_iou (test): dict(stride) -
     muvo_amd.voxel_view.RayIoUMetric runs on every batch and writes out_dir/ray_iou.json; metrics.json does not change.  voxel_cd
     (test): a dict (empty: no options) - muvo_amd.voxel_view.VoxelDistanceMetric runs on every batch and writes
-    out_dir/voxel_cd.json; metrics.json does not change."""
+    out_dir/voxel_cd.json; metrics.json does not change.  bev_pq (test): a dict of decode options (threshold, radius, max_centres,
+    thing_classes; empty: the defaults) - muvo_amd.bev_instances.PanopticQualityMetric runs on every batch and writes
+    out_dir/bev_pq.json; metrics.json does not change.  inst (test, with panels): also the `_inst` panel - True: decoded with the
+    options of bev_pq (the defaults without it); a dict: with decode options of its own."""
     refuse_multi_process()
     if mode not in ('test', 'sim'):
         raise ValueError(f'mode {mode!r}: test or sim')
@@ -268,9 +285,11 @@ def run(cfg, device, out_dir, mode, loaders=None, limit_batches=None, shard_size
             raise ValueError('panels, the ego-motion metric, the optical-flow metric and the ray IoU belong to mode test')
         if voxel_cd is not None:
             raise ValueError('the voxel Chamfer distance belongs to mode test')
+        if bev_pq is not None or isinstance(inst, dict) or inst:
+            raise ValueError('the BEV panoptic quality and the `_inst` panel belong to mode test')
         return _run_sim(cfg, module, chosen, out_dir, limit_batches, shard_size, seed, hook, log)
     return _run_test(cfg, module, chosen, out_dir, limit_batches, shard_size, seed, hook, log, panels, traj, ego_motion, icp_options, flow, optical_flow,
-                     voxel, voxel_size, ray_iou, voxel_cd)
+                     voxel, voxel_size, ray_iou, voxel_cd, bev_pq, inst)
 
 
 def _batches(loader, limit):
@@ -281,7 +300,7 @@ def _batches(loader, limit):
 
 
 def _run_test(cfg, module, loaders, out_dir, limit_batches, shard_size, seed, hook, log, panels=0, traj=False, ego_motion=None, icp_options=None,
-              flow=False, optical_flow=False, voxel=False, voxel_size=256, ray_iou=None, voxel_cd=None):
+              flow=False, optical_flow=False, voxel=False, voxel_size=256, ray_iou=None, voxel_cd=None, bev_pq=None, inst=False):
     counts = {}
     writer, was_writer, was_traj, was_opt = None, module.panel_writer, module.traj_panels, module.traj_options
     ego, flow_metric, was_flow = None, None, module.flow_panels
@@ -290,6 +309,15 @@ def _run_test(cfg, module, loaders, out_dir, limit_batches, shard_size, seed, ho
         raise ValueError('the ray IoU and the `_voxel` panel need the voxel head (VOXEL_SEG.ENABLED)')
     if voxel_cd is not None and not cfg.VOXEL_SEG.ENABLED:
         raise ValueError('the voxel Chamfer distance needs the voxel head (VOXEL_SEG.ENABLED)')
+    if (bev_pq is not None or isinstance(inst, dict) or inst) and not cfg.SEMANTIC_SEG.ENABLED:
+        raise ValueError('the BEV panoptic quality and the `_inst` panel need the bird\'s-eye-view head (SEMANTIC_SEG.ENABLED)')
+    inst_on = isinstance(inst, dict) or bool(inst)
+    pq_metric, was_inst, was_iopt = None, getattr(module, 'inst_panels', False), getattr(module, 'inst_options', {})
+    if bev_pq is not None:
+        from muvo_amd.bev_instances import PanopticQualityMetric
+        pq_metric = PanopticQualityMetric(cfg, **bev_pq)
+    if inst_on:                              # a dict: the panel's own decode options; True: those of the metric, else the defaults
+        module.inst_options = dict(inst) if isinstance(inst, dict) else dict(bev_pq or {})
     cd_metric = None
     if voxel_cd is not None:
         from muvo_amd.voxel_view import VoxelDistanceMetric
@@ -325,12 +353,16 @@ def _run_test(cfg, module, loaders, out_dir, limit_batches, shard_size, seed, ho
                 ray_metric.start_loader(idx)
             if cd_metric is not None:
                 cd_metric.start_loader(idx)
+            if pq_metric is not None:
+                pq_metric.start_loader(idx)
             for i, batch in _batches(loader, limit_batches):
                 seed_batch(module, seed, idx, i)
                 module.panel_writer = writer if i < panels else None
                 module.traj_panels = bool(traj)
                 module.flow_panels = bool(flow)
                 module.voxel_panels = bool(voxel)
+                if inst_on:
+                    module.inst_panels = True
                 output, output_imagines = module.test_step(batch, i, idx)
                 if hook is not None:
                     hook(i, batch, output, output_imagines)
@@ -342,10 +374,14 @@ def _run_test(cfg, module, loaders, out_dir, limit_batches, shard_size, seed, ho
                     ray_metric.update(i, batch, output, output_imagines)
                 if cd_metric is not None:
                     cd_metric.update(i, batch, output, output_imagines)
+                if pq_metric is not None:
+                    pq_metric.update(i, batch, output, output_imagines)
                 counts[idx] += 1
     finally:
         module.panel_writer, module.traj_panels, module.traj_options, module.flow_panels = was_writer, was_traj, was_opt, was_flow
         module.voxel_panels, module.voxel_options = was_voxel, was_vopt
+        if inst_on:
+            module.inst_panels, module.inst_options = was_inst, was_iopt
     logged, confusion = {}, {}
     was_fn, module.log_fn = module.log_fn, lambda name, value: logged.__setitem__(name, float(value))
     was_cm, module.on_confusion = module.on_confusion, lambda name, matrix: confusion.__setitem__(name, matrix.tolist())
@@ -381,6 +417,10 @@ def _run_test(cfg, module, loaders, out_dir, limit_batches, shard_size, seed, ho
         files.append(cd_metric.write(out_dir))
         out['voxel_cd'] = cd_metric.result()
         log('voxel_cd ' + json.dumps(out['voxel_cd'], sort_keys=True))
+    if pq_metric is not None:
+        files.append(pq_metric.write(out_dir))
+        out['bev_pq'] = pq_metric.result()
+        log('bev_pq ' + json.dumps(out['bev_pq'], sort_keys=True))
     return out
 
 
@@ -441,7 +481,9 @@ def main(argv=None):
         ego_motion=dict(threshold=args.ego_threshold, stride=args.ego_stride, max_iteration=args.ego_max_iteration) if args.ego_motion else None,
         icp_options=dict(threshold=args.ego_threshold, source_stride=args.ego_stride, max_iteration=args.ego_max_iteration),
         flow=args.flow, optical_flow=args.optical_flow, voxel=args.voxel, voxel_size=args.voxel_size,
-        ray_iou=dict(stride=args.ray_stride) if args.ray_iou else None, voxel_cd={} if args.voxel_cd else None)
+        ray_iou=dict(stride=args.ray_stride) if args.ray_iou else None, voxel_cd={} if args.voxel_cd else None,
+        bev_pq=dict(threshold=args.inst_threshold, max_centres=args.inst_max_centres) if args.bev_pq else None,
+        inst=dict(threshold=args.inst_threshold, max_centres=args.inst_max_centres) if args.inst else False)
 
 
 if __name__ == '__main__':

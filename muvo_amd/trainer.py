@@ -141,6 +141,8 @@ class WorldModelTrainer(_Base):
         self.flow_panels = False       # with a writer and EVAL.RGB_SUPERVISION: also `_flow` (muvo_amd/flow.py, dense optical flow)
         self.voxel_panels = False      # with a writer and VOXEL_SEG: also `_voxel` (muvo_amd/voxel_view.py, ray-cast 3-D view)
         self.voxel_options = {}        # size of that panel's tiles (default 256)
+        self.inst_panels = False       # with a writer and SEMANTIC_SEG: also `_inst` (muvo_amd/bev_instances.py, decoded BEV instances)
+        self.inst_options = {}         # decode options of that panel (threshold, radius, max_centres, thing_classes)
         # evaluation metrics per validation / test dataloader (trainer.py:51-55,100-129,191-197); created on first use
         # because they hold device accumulators
         self.metrics_vals = [{}, {}, {}]
@@ -597,6 +599,11 @@ class WorldModelTrainer(_Base):
             from muvo_amd.voxel_view import voxel_panel
             with torch.no_grad():
                 writer.add_images(f'{name}_voxel', voxel_panel(self.cfg, batch, output, output_imagines, **getattr(self, 'voxel_options', {})),
+                                  global_step=self._step_now())
+        if getattr(self, 'inst_panels', False) and self.cfg.SEMANTIC_SEG.ENABLED:
+            from muvo_amd.bev_instances import inst_panel
+            with torch.no_grad():
+                writer.add_images(f'{name}_inst', inst_panel(self.cfg, batch, output, output_imagines, **getattr(self, 'inst_options', {})),
                                   global_step=self._step_now())
         return panels
 
