@@ -334,26 +334,28 @@ int muvo_preprocess_image(const uint8_t* img, float* label, float* norm, int64_t
                           int CH, int CW, const float* mean3, const float* std3, void* stream);
 int muvo_preprocess_route(const uint8_t* img, float* norm, int64_t NC, int C, int H, int W, int OH, int OW,
                           const float* mean3, const float* std3, void* stream);
-/* Fused multi-head self-attention core of nn.TransformerEncoderLayer (muvo/models/mile.py:96-101,558), csrc/attention.hip:
+/* Fused multi-head self-attention core of nn.TransformerEncoderLayer (muvo/models/mile.py:96-101,558), csrc/attention.hip, one
+ * unit with two paths that share every tile step, the layouts, the exact-fp32 MFMA arithmetic and the dropout mask index, so one
+ * seed gives one mask on either:
  * qkv (L, N, 3*H*DH) packed in-projection (q | k | v along the last axis, heads contiguous inside each), out (L, N, H*DH) =
- * dropout(softmax(q k^T / sqrt(DH))) v per (n, head), lse (N*H, L) row log-sum-exp saved for the backward pass; K and V of a
- * head live in LDS, the L x L matrices never reach HBM.  p / seed: attention-probability dropout, mask index
- * ((n*H + h)*L + query)*L + key (same as muvo_softmax_dropout_*).  muvo_attention_supported: DH in {16,32,48,64}, L <= 384
- * and 2 * roundup(L,16) * (DH+4) * 4 bytes (+ 8 * roundup(L,16)) <= 160 KB of LDS; otherwise use the unfused entry points.
- * muvo_attention_bwd writes all of dqkv (dq, dk, dv) — no atomics, deterministic. */
+ * dropout(softmax(q k^T / sqrt(DH))) v per (n, head), lse (N*H, L) row log-sum-exp saved for the backward pass; the L x L
+ * matrices never reach HBM.  p / seed: attention-probability dropout, mask index ((n*H + h)*L + query)*L + key (same as
+ * muvo_softmax_dropout_*).  Both backward entry points write all of dqkv (dq, dk, dv) - no atomics, no communication between
+ * workgroups: bit-reproducible.
+ * Resident path, muvo_attention_*: K and V of a head live whole in LDS.  muvo_attention_supported: DH in {16,32,48,64}, L <= 384
+ * and 2 * roundup(L,16) * (DH+4) * 4 bytes (+ 8 * roundup(L,16)) <= 160 KB of LDS; otherwise use the streamed or the unfused
+ * entry points. */
 int muvo_attention_supported(int L, int DH);
 int muvo_attention_fwd(const float* qkv, float* out, float* lse, int L, int N, int H, int DH, float p, uint64_t seed,
                        void* stream);
 int muvo_attention_bwd(const float* qkv, const float* out, const float* dout, const float* lse, float* dqkv, int L, int N, int H,
                        int DH, float p, uint64_t seed, void* stream);
-/* The same attention core for any L >= 1 (csrc/attention.hip, streamed kernels): keys (forward, dQ) or queries (dK, dV) pass
- * through LDS in blocks of bk rows, the forward carries a running maximum and running sum per query (online softmax), a
- * workgroup owns bq rows; nothing of size L x L is written anywhere.  Same layouts, same exact-fp32 MFMA arithmetic, same
- * dropout mask index as above, so one seed gives one mask on every path.  muvo_attention_stream_supported: DH in {16,32,48,64}
+/* Streamed path, muvo_attention_stream_*, any L >= 1: the same kernels with the keys (forward, dQ) or the queries (dK, dV)
+ * passing through LDS in blocks of bk rows, the forward carries a running maximum and running sum per query (online softmax), a
+ * workgroup owns bq rows.  muvo_attention_stream_supported: DH in {16,32,48,64}
  * and L >= 1.  muvo_attention_stream_blocks reports the compiled (bq, bk).  muvo_attention_stream_bwd takes a caller-allocated
  * workspace dws of N*H*L floats: the dQ kernel stores D = dout . out per query there and the dK/dV kernel, queued after it on
- * the same stream, reads it; the contents afterwards are D (nothing to keep).  All of dqkv is written; no atomics, no
- * communication between workgroups: bit-reproducible. */
+ * the same stream, reads it; the contents afterwards are D (nothing to keep). */
 int muvo_attention_stream_supported(int L, int DH);
 int muvo_attention_stream_blocks(int* bq, int* bk);
 int muvo_attention_stream_fwd(const float* qkv, float* out, float* lse, int L, int N, int H, int DH, float p, uint64_t seed,

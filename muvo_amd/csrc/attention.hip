@@ -60,635 +60,489 @@ __device__ __forceinline__ float quad_group_sum(float v) {
   return v + __shfl_xor(v, 32, 64);
 }
 
-// out (L, N, E), lse (N*H, L)
+// ================================================================================================ two paths, one set of steps
+// Resident (L <= 16 ATTN_MAXT): K and V (forward, dQ) or Q and dO (dK, dV) of the head are staged whole, as ONE block of
+// roundup(L, 16) rows.  Streamed (any L): the same kernels with the keys (forward, dQ) or the queries (dK, dV) walked in LDS
+// blocks of ATTN_SBK rows instead of held whole: nothing is bounded by L but the loop count.  The streamed forward carries a
+// running maximum m and running sum l per query (online softmax): per block  m' = max(m, block max), O *= exp(m - m'), l = l exp(m - m') + sum exp(s - m'), O += P V, and
+// divides by l once at the end.  m starts at -inf, but m' is finite from the first block on (key k0 of every block is < L), so
+// exp(m - m') is exp(-inf) = 0 there and never inf - inf; keys >= L of the tail block get s = -inf, p = 0.  The rescale factor
+// lives on lane = query while the O accumulator rows are (g, r): four wave shuffles per block bring it over.  The rescale is
+// unconditional (no data-dependent branch).  The streamed dQ additionally writes D = dO . O per query into the caller's (N*H, L)
+// workspace; dK, dV (launched after it on the same stream) reads D from there instead of re-reading `out` once per key block.
+// One LDS buffer, two barriers per block, every wave takes part in every barrier: a wave whose 16 rows lie beyond L skips the
+// arithmetic between the barriers and its stores, never the barriers.  70 KB at DH = 64: two workgroups share a CU and one
+// computes while the other stages.  Workgroups are independent, loop bounds depend on L alone, no atomics: bit-reproducible.
+// Every tile step below takes the index of the block's first row (k0 / q0) and works on k0 + local; resident passes 0.
+#define ATTN_SBK 128                     // rows per streamed LDS block
+#define ATTN_SBQ (16 * ATTN_WAVES)       // rows a workgroup owns
+// Register budget: up to DH = 48 the streamed forward and dK/dV kernels fit 128 registers (4 waves per SIMD = two workgroups per
+// CU); at DH = 64 that cap spills to scratch, so those two run one workgroup per CU there.  0 = no hint (the resident dK/dV).
+#define ATTN_STREAM_WAVES(DH) ((DH) <= 48 ? 4 : 2)
+#define ATTN_DKV_WAVES(DH, STREAM) ((STREAM) ? ATTN_STREAM_WAVES(DH) : 0)
+
+// What a wave knows about its (frame, head) and its 16 rows: queries in forward and dQ, keys in dK/dV
+struct AttnCtx {
+  int tid, g, c;        // thread of the workgroup; lane = 16 g + c
+  int nh, n, h;         // blockIdx.y = n * H + h
+  int E;                // H * DH: a qkv row is q | k | v of E floats each
+  long rs, ro;          // floats from one token's row to the next in qkv / dqkv and in out / dout
+  long hq, ho;          // where the head starts in token 0's row of qkv / dqkv (its q part) and of out / dout
+  int r0, row;          // first of the wave's 16 rows; this lane's row r0 + c
+};
+template <int DH>
+__device__ __forceinline__ AttnCtx attn_ctx(int N, int H) {
+  AttnCtx x;
+  x.tid = threadIdx.x;
+  const int lane = x.tid & 63, wave = x.tid >> 6;
+  x.g = lane >> 4; x.c = lane & 15;
+  x.nh = blockIdx.y; x.n = x.nh / H; x.h = x.nh - x.n * H;
+  x.E = H * DH;
+  x.rs = (long)N * 3 * x.E; x.ro = (long)N * x.E;
+  x.hq = (long)x.n * 3 * x.E + x.h * DH; x.ho = (long)x.n * x.E + x.h * DH;
+  x.r0 = (blockIdx.x * ATTN_WAVES + wave) * 16; x.row = x.r0 + x.c;
+  return x;
+}
+// rows of one LDS block; the kernels carve their LDS by it and the host sizes it by it
+__host__ __device__ __forceinline__ int attn_block_rows(bool stream, int L) { return stream ? ATTN_SBK : (L + 15) & ~15; }
+// dropout mask index of (query, key 0): ((n*H + h)*L + query)*L
+__device__ __forceinline__ uint64_t attn_mask_row(int nh, int query, int L) { return ((uint64_t)nh * L + query) * (uint64_t)L; }
+template <int DT>
+__device__ __forceinline__ void attn_zero(f32x4* a) {
+#pragma unroll
+  for (int dt = 0; dt < DT; ++dt) a[dt] = (f32x4){0.f, 0.f, 0.f, 0.f};
+}
+
+// Score tile t of the staged keys: S^T = K Q^T (16 keys x the wave's 16 queries), scaled, keys >= L at -inf; mx takes its maximum
+template <int DH>
+__device__ __forceinline__ f32x4 attn_score_tile(const float* Ks, int t, const float* qf, int k0, int L, float scale,
+                                                 const AttnCtx& x, float& mx) {
+  constexpr int DQ = DH / 4, RS = DH + 4;
+  float kf[DQ];
+  attn_lds_frag<DH>(kf, Ks + (t * 16 + x.c) * RS, x.g);
+  f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int k = 0; k < DQ; ++k) acc = MFMA16(kf[k], qf[k], acc);      // S^T[key 4g+r][query c]
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    const int key = k0 + t * 16 + 4 * x.g + r;
+    acc[r] = key < L ? acc[r] * scale : -INFINITY;
+    mx = fmaxf(mx, acc[r]);
+  }
+  return acc;
+}
+// s -> exp(s - mx) in place, added to sum
+__device__ __forceinline__ void attn_exp_tile(f32x4& s, float mx, float& sum) {
+#pragma unroll
+  for (int r = 0; r < 4; ++r) { s[r] = expf(s[r] - mx); sum += s[r]; }
+}
+// O += P V for tile t of the staged values, p (laid out as the score tile) times the dropout factor
+template <int DH>
+__device__ __forceinline__ void attn_pv_tile(f32x4* o, const float* Vs, int t, f32x4 p, int k0, uint64_t maskrow, float pdrop,
+                                             uint64_t seed, const AttnCtx& x) {
+  constexpr int RS = DH + 4, DT = DH / 16;
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    const int kl = t * 16 + 4 * x.g + r;
+    float pr = p[r];
+    if (pdrop > 0.f) pr *= dropout_scale(seed, maskrow + (uint64_t)(k0 + kl), pdrop);
+    const float* vrow = Vs + kl * RS + x.c;
+#pragma unroll
+    for (int dt = 0; dt < DT; ++dt) o[dt] = MFMA16(pr, vrow[dt * 16], o[dt]);   // O[query 4g'+r'][d = 16 dt + c]
+  }
+}
+// The wave's accumulator rows r0 + 4g + r (< L), columns 16 dt + c, to dst + row * stride
+template <int DH>
+__device__ __forceinline__ void attn_store_rows(float* dst, long stride, const f32x4* acc, const AttnCtx& x, int L) {
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    const int row = x.r0 + 4 * x.g + r;
+    if (row < L) {
+      float* p = dst + (long)row * stride + x.c;
+#pragma unroll
+      for (int dt = 0; dt < DH / 16; ++dt) p[dt * 16] = acc[dt][r];
+    }
+  }
+}
+// accumulator row r times f (a float) or f[r] (an f32x4)
+template <int DT, class F>
+__device__ __forceinline__ void attn_scale_rows(f32x4* a, F f) {
+#pragma unroll
+  for (int dt = 0; dt < DT; ++dt) a[dt] = a[dt] * f;
+}
+// D[query] = dO . O = sum_j dP_j P_j of this lane's query, from the quad's fragments
+template <int DH>
+__device__ __forceinline__ float attn_d_frag(const float* dof, const float* __restrict__ out, const AttnCtx& x, int L) {
+  constexpr int DQ = DH / 4;
+  float of[DQ];
+  attn_frag<DH>(of, out + x.ho, x.ro, x.row, L, x.g);
+  float dsum = 0.f;
+#pragma unroll
+  for (int k = 0; k < DQ; ++k) dsum += dof[k] * of[k];
+  return quad_group_sum(dsum);
+}
+// dQ += dS K for tile t of the staged keys and values; the probabilities come back from the row log-sum-exp lq
+template <int DH>
+__device__ __forceinline__ void attn_dq_tile(f32x4* dq, const float* Ks, const float* Vs, int t, const float* qf, const float* dof,
+                                             float lq, float dsum, int k0, uint64_t maskrow, int L, float scale, float pdrop,
+                                             uint64_t seed, const AttnCtx& x) {
+  constexpr int DQ = DH / 4, RS = DH + 4, DT = DH / 16;
+  float kf[DQ], vf[DQ];
+  attn_lds_frag<DH>(kf, Ks + (t * 16 + x.c) * RS, x.g);
+  attn_lds_frag<DH>(vf, Vs + (t * 16 + x.c) * RS, x.g);
+  f32x4 st = {0.f, 0.f, 0.f, 0.f}, dp = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int k = 0; k < DQ; ++k) {
+    st = MFMA16(kf[k], qf[k], st);                // S^T[key][query]
+    dp = MFMA16(vf[k], dof[k], dp);               // dPd^T[key][query] = V[key] . dO[query]
+  }
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    const int kl = t * 16 + 4 * x.g + r, key = k0 + kl;
+    const float p = (key < L && x.row < L) ? expf(st[r] * scale - lq) : 0.f;
+    const float mk = pdrop > 0.f ? dropout_scale(seed, maskrow + (uint64_t)key, pdrop) : 1.f;
+    const float ds = p * (dp[r] * mk - dsum);
+    const float* krow = Ks + kl * RS + x.c;
+#pragma unroll
+    for (int dt = 0; dt < DT; ++dt) dq[dt] = MFMA16(ds, krow[dt * 16], dq[dt]);
+  }
+}
+// dV += Pd^T dO, dK += dS^T Q for tile t of the staged queries (Q, dO, lse and D per query in LDS); the keys are in registers
+template <int DH>
+__device__ __forceinline__ void attn_dkv_tile(f32x4* dk, f32x4* dv, const float* Qs, const float* Gs, const float* Ls,
+                                              const float* Ds, int t, const float* kf, const float* vf, int q0, int L, float scale,
+                                              float pdrop, uint64_t seed, const AttnCtx& x) {
+  constexpr int DQ = DH / 4, RS = DH + 4, DT = DH / 16;
+  float qv[DQ], gv[DQ];
+  attn_lds_frag<DH>(qv, Qs + (t * 16 + x.c) * RS, x.g);
+  attn_lds_frag<DH>(gv, Gs + (t * 16 + x.c) * RS, x.g);
+  f32x4 sv = {0.f, 0.f, 0.f, 0.f}, dp = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int k = 0; k < DQ; ++k) {
+    sv = MFMA16(qv[k], kf[k], sv);                // S[query 4g+r][key c]
+    dp = MFMA16(gv[k], vf[k], dp);                // dPd[query][key]
+  }
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    const int ql = t * 16 + 4 * x.g + r, q = q0 + ql;
+    const bool valid = q < L && x.row < L;
+    const float p = valid ? expf(sv[r] * scale - Ls[ql]) : 0.f;
+    const float mk = (pdrop > 0.f && valid) ? dropout_scale(seed, attn_mask_row(x.nh, q, L) + (uint64_t)x.row, pdrop) : 1.f;
+    const float pd = p * mk;
+    const float ds = p * (dp[r] * mk - Ds[ql]);
+    const float* grow = Gs + ql * RS + x.c;
+    const float* qrow = Qs + ql * RS + x.c;
+#pragma unroll
+    for (int dt = 0; dt < DT; ++dt) {
+      dv[dt] = MFMA16(pd, grow[dt * 16], dv[dt]);  // dV[key 4g'+r'][d]
+      dk[dt] = MFMA16(ds, qrow[dt * 16], dk[dt]);
+    }
+  }
+}
+
+// ================================================================================================ forward: out (L, N, E), lse (N*H, L)
+// Resident: two passes over the ATTN_MAXT register tiles of the whole score row (maximum, then exp and sum)
 template <int DH>
 __global__ void __launch_bounds__(64 * ATTN_WAVES)
 attn_fwd_kernel(const float* __restrict__ qkv, float* __restrict__ out, float* __restrict__ lse, int L, int N, int H,
                 float scale, float pdrop, uint64_t seed) {
   constexpr int DQ = DH / 4, RS = DH + 4, DT = DH / 16;
   extern __shared__ float smem[];
-  const int Lp = (L + 15) & ~15, NT = Lp >> 4;
+  const int Lp = attn_block_rows(false, L), NT = Lp >> 4;
   float* Ks = smem;
   float* Vs = smem + Lp * RS;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, g = lane >> 4, c = lane & 15;
-  const int nh = blockIdx.y, n = nh / H, h = nh - n * H;
-  const int E = H * DH, E3 = 3 * E;
-  const long rs = (long)N * E3;
-  const float* base = qkv + (long)n * E3 + h * DH;
-  attn_stage<DH>(Ks, base + E, rs, L, Lp, tid);
-  attn_stage<DH>(Vs, base + 2 * E, rs, L, Lp, tid);
-  const int q0 = (blockIdx.x * ATTN_WAVES + wave) * 16, qrow = q0 + c;
+  const AttnCtx x = attn_ctx<DH>(N, H);
+  const float* base = qkv + x.hq;
+  attn_stage<DH>(Ks, base + x.E, x.rs, L, Lp, x.tid);
+  attn_stage<DH>(Vs, base + 2 * x.E, x.rs, L, Lp, x.tid);
   float qf[DQ];
-  attn_frag<DH>(qf, base, rs, qrow, L, g);
+  attn_frag<DH>(qf, base, x.rs, x.row, L, x.g);
   __syncthreads();
-  if (q0 >= L) return;
+  if (x.r0 >= L) return;                                         // after the only barrier
   f32x4 s[ATTN_MAXT];
   float mx = -INFINITY;
 #pragma unroll
-  for (int t = 0; t < ATTN_MAXT; ++t) {
-    if (t < NT) {
-      float kf[DQ];
-      attn_lds_frag<DH>(kf, Ks + (t * 16 + c) * RS, g);
-      f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-      for (int k = 0; k < DQ; ++k) acc = MFMA16(kf[k], qf[k], acc);      // S^T[key 4g+r][query c]
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int key = t * 16 + 4 * g + r;
-        acc[r] = key < L ? acc[r] * scale : -INFINITY;
-        mx = fmaxf(mx, acc[r]);
-      }
-      s[t] = acc;
-    }
-  }
+  for (int t = 0; t < ATTN_MAXT; ++t)
+    if (t < NT) s[t] = attn_score_tile<DH>(Ks, t, qf, 0, L, scale, x, mx);
   mx = quad_group_max(mx);
   float sum = 0.f;
 #pragma unroll
   for (int t = 0; t < ATTN_MAXT; ++t)
-    if (t < NT) {
-#pragma unroll
-      for (int r = 0; r < 4; ++r) { s[t][r] = expf(s[t][r] - mx); sum += s[t][r]; }
-    }
+    if (t < NT) attn_exp_tile(s[t], mx, sum);
   sum = quad_group_sum(sum);
   const float inv = 1.f / sum;
-  if (g == 0 && qrow < L) lse[(long)nh * L + qrow] = mx + logf(sum);
+  if (x.g == 0 && x.row < L) lse[(long)x.nh * L + x.row] = mx + logf(sum);
   f32x4 o[DT];
+  attn_zero<DT>(o);
+  const uint64_t maskrow = attn_mask_row(x.nh, x.row < L ? x.row : 0, L);
 #pragma unroll
-  for (int dt = 0; dt < DT; ++dt) o[dt] = (f32x4){0.f, 0.f, 0.f, 0.f};
-  const uint64_t rowbase = ((uint64_t)nh * L + (qrow < L ? qrow : 0)) * (uint64_t)L;
-#pragma unroll
-  for (int t = 0; t < ATTN_MAXT; ++t)
-    if (t < NT) {
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int key = t * 16 + 4 * g + r;
-        float p = s[t][r] * inv;
-        if (pdrop > 0.f) p *= dropout_scale(seed, rowbase + (uint64_t)key, pdrop);
-        const float* vrow = Vs + key * RS + c;
-#pragma unroll
-        for (int dt = 0; dt < DT; ++dt) o[dt] = MFMA16(p, vrow[dt * 16], o[dt]);   // O[query 4g'+r'][d = 16 dt + c]
-      }
-    }
-#pragma unroll
-  for (int r = 0; r < 4; ++r) {
-    const int q = q0 + 4 * g + r;
-    if (q < L) {
-      float* op = out + ((long)q * N + n) * E + h * DH + c;
-#pragma unroll
-      for (int dt = 0; dt < DT; ++dt) op[dt * 16] = o[dt][r];
-    }
-  }
+  for (int t = 0; t < ATTN_MAXT; ++t)                            // p is normalised BEFORE P V here; streamed divides O by l at the end
+    if (t < NT) attn_pv_tile<DH>(o, Vs, t, s[t] * inv, 0, maskrow, pdrop, seed, x);
+  attn_store_rows<DH>(out + x.ho, x.ro, o, x, L);
 }
 
-// dQ: one wave per 16 queries, K and V of the head in LDS
+// Streamed: the online softmax over key blocks
 template <int DH>
-__global__ void __launch_bounds__(64 * ATTN_WAVES)
-attn_bwd_dq_kernel(const float* __restrict__ qkv, const float* __restrict__ out, const float* __restrict__ dout,
-                   const float* __restrict__ lse, float* __restrict__ dqkv, int L, int N, int H, float scale, float pdrop,
-                   uint64_t seed) {
-  constexpr int DQ = DH / 4, RS = DH + 4, DT = DH / 16;
-  extern __shared__ float smem[];
-  const int Lp = (L + 15) & ~15, NT = Lp >> 4;
-  float* Ks = smem;
-  float* Vs = smem + Lp * RS;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, g = lane >> 4, c = lane & 15;
-  const int nh = blockIdx.y, n = nh / H, h = nh - n * H;
-  const int E = H * DH, E3 = 3 * E;
-  const long rs = (long)N * E3, ro = (long)N * E;
-  const float* base = qkv + (long)n * E3 + h * DH;
-  attn_stage<DH>(Ks, base + E, rs, L, Lp, tid);
-  attn_stage<DH>(Vs, base + 2 * E, rs, L, Lp, tid);
-  const int q0 = (blockIdx.x * ATTN_WAVES + wave) * 16, qrow = q0 + c;
-  float qf[DQ], dof[DQ], of[DQ];
-  attn_frag<DH>(qf, base, rs, qrow, L, g);
-  attn_frag<DH>(dof, dout + (long)n * E + h * DH, ro, qrow, L, g);
-  attn_frag<DH>(of, out + (long)n * E + h * DH, ro, qrow, L, g);
-  float dsum = 0.f;
-#pragma unroll
-  for (int k = 0; k < DQ; ++k) dsum += dof[k] * of[k];
-  dsum = quad_group_sum(dsum);                      // D[query] = dO . O = sum_j dP_j P_j
-  const float lq = qrow < L ? lse[(long)nh * L + qrow] : 0.f;
-  __syncthreads();
-  if (q0 >= L) return;
-  f32x4 dq[DT];
-#pragma unroll
-  for (int dt = 0; dt < DT; ++dt) dq[dt] = (f32x4){0.f, 0.f, 0.f, 0.f};
-  const uint64_t rowbase = ((uint64_t)nh * L + (qrow < L ? qrow : 0)) * (uint64_t)L;
-  for (int t = 0; t < NT; ++t) {
-    float kf[DQ], vf[DQ];
-    attn_lds_frag<DH>(kf, Ks + (t * 16 + c) * RS, g);
-    attn_lds_frag<DH>(vf, Vs + (t * 16 + c) * RS, g);
-    f32x4 st = {0.f, 0.f, 0.f, 0.f}, dp = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int k = 0; k < DQ; ++k) {
-      st = MFMA16(kf[k], qf[k], st);                // S^T[key][query]
-      dp = MFMA16(vf[k], dof[k], dp);               // dPd^T[key][query] = V[key] . dO[query]
-    }
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int key = t * 16 + 4 * g + r;
-      const float p = (key < L && qrow < L) ? expf(st[r] * scale - lq) : 0.f;
-      const float m = pdrop > 0.f ? dropout_scale(seed, rowbase + (uint64_t)key, pdrop) : 1.f;
-      const float ds = p * (dp[r] * m - dsum);
-      const float* krow = Ks + key * RS + c;
-#pragma unroll
-      for (int dt = 0; dt < DT; ++dt) dq[dt] = MFMA16(ds, krow[dt * 16], dq[dt]);
-    }
-  }
-#pragma unroll
-  for (int r = 0; r < 4; ++r) {
-    const int q = q0 + 4 * g + r;
-    if (q < L) {
-      float* dp = dqkv + ((long)q * N + n) * E3 + h * DH + c;
-#pragma unroll
-      for (int dt = 0; dt < DT; ++dt) dp[dt * 16] = dq[dt][r] * scale;
-    }
-  }
-}
-
-// dK, dV: one wave per 16 keys, Q and dO of the head (+ lse, D per query) in LDS
-template <int DH>
-__global__ void __launch_bounds__(64 * ATTN_WAVES)
-attn_bwd_dkv_kernel(const float* __restrict__ qkv, const float* __restrict__ out, const float* __restrict__ dout,
-                    const float* __restrict__ lse, float* __restrict__ dqkv, int L, int N, int H, float scale, float pdrop,
-                    uint64_t seed) {
-  constexpr int DQ = DH / 4, RS = DH + 4, DT = DH / 16;
-  extern __shared__ float smem[];
-  const int Lp = (L + 15) & ~15, NT = Lp >> 4;
-  float* Qs = smem;
-  float* Gs = smem + Lp * RS;          // dO
-  float* Ls = Gs + Lp * RS;            // lse per query
-  float* Ds = Ls + Lp;                 // dO . O per query
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, g = lane >> 4, c = lane & 15;
-  const int nh = blockIdx.y, n = nh / H, h = nh - n * H;
-  const int E = H * DH, E3 = 3 * E;
-  const long rs = (long)N * E3, ro = (long)N * E;
-  const float* base = qkv + (long)n * E3 + h * DH;
-  const float* dob = dout + (long)n * E + h * DH;
-  const float* ob = out + (long)n * E + h * DH;
-  attn_stage<DH>(Qs, base, rs, L, Lp, tid);
-  attn_stage<DH>(Gs, dob, ro, L, Lp, tid);
-  for (int q = tid; q < Lp; q += 64 * ATTN_WAVES) {
-    float d = 0.f, l = 0.f;
-    if (q < L) {
-      l = lse[(long)nh * L + q];
-#pragma unroll
-      for (int k = 0; k < DH; k += 4) {
-        const f32x4 a = *(const f32x4*)(dob + (long)q * ro + k), b = *(const f32x4*)(ob + (long)q * ro + k);
-        d += a[0] * b[0] + a[1] * b[1] + a[2] * b[2] + a[3] * b[3];
-      }
-    }
-    Ls[q] = l;
-    Ds[q] = d;
-  }
-  const int k0 = (blockIdx.x * ATTN_WAVES + wave) * 16, krow = k0 + c;
-  float kf[DQ], vf[DQ];
-  attn_frag<DH>(kf, base + E, rs, krow, L, g);
-  attn_frag<DH>(vf, base + 2 * E, rs, krow, L, g);
-  __syncthreads();
-  if (k0 >= L) return;
-  f32x4 dk[DT], dv[DT];
-#pragma unroll
-  for (int dt = 0; dt < DT; ++dt) { dk[dt] = (f32x4){0.f, 0.f, 0.f, 0.f}; dv[dt] = (f32x4){0.f, 0.f, 0.f, 0.f}; }
-  for (int t = 0; t < NT; ++t) {
-    float qv[DQ], gv[DQ];
-    attn_lds_frag<DH>(qv, Qs + (t * 16 + c) * RS, g);
-    attn_lds_frag<DH>(gv, Gs + (t * 16 + c) * RS, g);
-    f32x4 sv = {0.f, 0.f, 0.f, 0.f}, dp = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int k = 0; k < DQ; ++k) {
-      sv = MFMA16(qv[k], kf[k], sv);                // S[query 4g+r][key c]
-      dp = MFMA16(gv[k], vf[k], dp);                // dPd[query][key]
-    }
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int q = t * 16 + 4 * g + r;
-      const bool valid = q < L && krow < L;
-      const float p = valid ? expf(sv[r] * scale - Ls[q]) : 0.f;
-      const float m = (pdrop > 0.f && valid) ? dropout_scale(seed, ((uint64_t)nh * L + q) * (uint64_t)L + (uint64_t)krow, pdrop) : 1.f;
-      const float pd = p * m;
-      const float ds = p * (dp[r] * m - Ds[q]);
-      const float* grow = Gs + q * RS + c;
-      const float* qrow_ = Qs + q * RS + c;
-#pragma unroll
-      for (int dt = 0; dt < DT; ++dt) {
-        dv[dt] = MFMA16(pd, grow[dt * 16], dv[dt]);  // dV[key 4g'+r'][d]
-        dk[dt] = MFMA16(ds, qrow_[dt * 16], dk[dt]);
-      }
-    }
-  }
-#pragma unroll
-  for (int r = 0; r < 4; ++r) {
-    const int key = k0 + 4 * g + r;
-    if (key < L) {
-      float* dp = dqkv + ((long)key * N + n) * E3 + h * DH + c;
-#pragma unroll
-      for (int dt = 0; dt < DT; ++dt) {
-        dp[E + dt * 16] = dk[dt][r] * scale;
-        dp[2 * E + dt * 16] = dv[dt][r];
-      }
-    }
-  }
-}
-
-// ================================================================================================ streamed kernels (any L)
-// The same three kernels with the keys (forward, dQ) or the queries (dK, dV) walked in LDS blocks of ATTN_SBK rows instead of
-// held whole: nothing is bounded by L but the loop count.  Forward carries a running maximum m and running sum l per query
-// (online softmax): per block  m' = max(m, block max), O *= exp(m - m'), l = l exp(m - m') + sum exp(s - m'), O += P V, and
-// divides by l once at the end.  m starts at -inf, but m' is finite from the first block on (key k0 of every block is < L), so
-// exp(m - m') is exp(-inf) = 0 there and never inf - inf; keys >= L of the tail block get s = -inf, p = 0.  The rescale factor
-// lives on lane = query while the O accumulator rows are (g, r): four wave shuffles per block bring it over.  The rescale is
-// unconditional (no data-dependent branch).  dQ additionally writes D = dO . O per query into the caller's (N*H, L) workspace;
-// dK, dV (launched after it on the same stream) reads D from there instead of re-reading `out` once per key block.
-// One LDS buffer, two barriers per block, every wave takes part in every barrier: a wave whose 16 rows lie beyond L skips the
-// arithmetic between the barriers and its stores, never the barriers.  70 KB at DH = 64: two workgroups share a CU and one
-// computes while the other stages.  Workgroups are independent, loop bounds depend on L alone, no atomics: bit-reproducible.
-#define ATTN_SBK 128                     // rows per streamed LDS block
-#define ATTN_SBQ (16 * ATTN_WAVES)       // rows a workgroup owns
-// Register budget: up to DH = 48 the forward and dK/dV kernels fit 128 registers (4 waves per SIMD = two workgroups per CU); at
-// DH = 64 that cap spills to scratch, so those two run one workgroup per CU there.
-#define ATTN_STREAM_WAVES(DH) ((DH) <= 48 ? 4 : 2)
-
-template <int DH>
-__global__ void __launch_bounds__(64 * ATTN_WAVES)
-__attribute__((amdgpu_waves_per_eu(ATTN_STREAM_WAVES(DH)))) attn_stream_fwd_kernel(const float* __restrict__ qkv, float* __restrict__ out, float* __restrict__ lse, int L, int N, int H,
+__global__ void __launch_bounds__(64 * ATTN_WAVES) __attribute__((amdgpu_waves_per_eu(ATTN_STREAM_WAVES(DH))))
+attn_stream_fwd_kernel(const float* __restrict__ qkv, float* __restrict__ out, float* __restrict__ lse, int L, int N, int H,
                        float scale, float pdrop, uint64_t seed) {
   constexpr int DQ = DH / 4, RS = DH + 4, DT = DH / 16, KT = ATTN_SBK / 16;
   extern __shared__ float smem[];
   float* Ks = smem;
   float* Vs = smem + ATTN_SBK * RS;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, g = lane >> 4, c = lane & 15;
-  const int nh = blockIdx.y, n = nh / H, h = nh - n * H;
-  const int E = H * DH, E3 = 3 * E;
-  const long rs = (long)N * E3;
-  const float* base = qkv + (long)n * E3 + h * DH;
-  const int q0 = (blockIdx.x * ATTN_WAVES + wave) * 16, qrow = q0 + c;
+  const AttnCtx x = attn_ctx<DH>(N, H);
+  const float* base = qkv + x.hq;
   float qf[DQ];
-  attn_frag<DH>(qf, base, rs, qrow, L, g);
+  attn_frag<DH>(qf, base, x.rs, x.row, L, x.g);
   f32x4 o[DT];
-#pragma unroll
-  for (int dt = 0; dt < DT; ++dt) o[dt] = (f32x4){0.f, 0.f, 0.f, 0.f};
+  attn_zero<DT>(o);
   float m = -INFINITY, l = 0.f;
-  const uint64_t rowbase = ((uint64_t)nh * L + (qrow < L ? qrow : 0)) * (uint64_t)L;
+  const uint64_t maskrow = attn_mask_row(x.nh, x.row < L ? x.row : 0, L);
   for (int k0 = 0; k0 < L; k0 += ATTN_SBK) {
     if (k0) __syncthreads();                                   // every wave has read the previous block
-    attn_stage<DH>(Ks, base + E + (long)k0 * rs, rs, L - k0, ATTN_SBK, tid);
-    attn_stage<DH>(Vs, base + 2 * E + (long)k0 * rs, rs, L - k0, ATTN_SBK, tid);
+    attn_stage<DH>(Ks, base + x.E + (long)k0 * x.rs, x.rs, L - k0, ATTN_SBK, x.tid);
+    attn_stage<DH>(Vs, base + 2 * x.E + (long)k0 * x.rs, x.rs, L - k0, ATTN_SBK, x.tid);
     __syncthreads();
-    if (q0 < L) {                                              // wave-uniform; no barrier inside
+    if (x.r0 < L) {                                            // wave-uniform; no barrier inside
       f32x4 s[KT];
       float bm = -INFINITY;
 #pragma unroll
-      for (int t = 0; t < KT; ++t) {
-        float kf[DQ];
-        attn_lds_frag<DH>(kf, Ks + (t * 16 + c) * RS, g);
-        f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int k = 0; k < DQ; ++k) acc = MFMA16(kf[k], qf[k], acc);      // S^T[key 4g+r][query c]
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const int key = k0 + t * 16 + 4 * g + r;
-          acc[r] = key < L ? acc[r] * scale : -INFINITY;
-          bm = fmaxf(bm, acc[r]);
-        }
-        s[t] = acc;
-      }
+      for (int t = 0; t < KT; ++t) s[t] = attn_score_tile<DH>(Ks, t, qf, k0, L, scale, x, bm);
       const float mn = fmaxf(m, quad_group_max(bm));           // finite: key k0 < L is in this block
       const float alpha = expf(m - mn);                        // first block: exp(-inf) = 0
       float bs = 0.f;
 #pragma unroll
-      for (int t = 0; t < KT; ++t) {
-#pragma unroll
-        for (int r = 0; r < 4; ++r) { s[t][r] = expf(s[t][r] - mn); bs += s[t][r]; }
-      }
+      for (int t = 0; t < KT; ++t) attn_exp_tile(s[t], mn, bs);
       l = l * alpha + quad_group_sum(bs);
       m = mn;
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
-        const float a = __shfl(alpha, 4 * g + r, 64);          // factor of query 4g+r, from the lane that holds that query
+        const float a = __shfl(alpha, 4 * x.g + r, 64);        // factor of query 4g+r, from the lane that holds that query
 #pragma unroll
         for (int dt = 0; dt < DT; ++dt) o[dt][r] *= a;
       }
 #pragma unroll
-      for (int t = 0; t < KT; ++t) {
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const int kl = t * 16 + 4 * g + r;
-          float p = s[t][r];
-          if (pdrop > 0.f) p *= dropout_scale(seed, rowbase + (uint64_t)(k0 + kl), pdrop);
-          const float* vrow = Vs + kl * RS + c;
-#pragma unroll
-          for (int dt = 0; dt < DT; ++dt) o[dt] = MFMA16(p, vrow[dt * 16], o[dt]);   // O[query 4g'+r'][d = 16 dt + c]
-        }
-      }
+      for (int t = 0; t < KT; ++t) attn_pv_tile<DH>(o, Vs, t, s[t], k0, maskrow, pdrop, seed, x);
     }
   }
-  if (g == 0 && qrow < L) lse[(long)nh * L + qrow] = m + logf(l);
+  if (x.g == 0 && x.row < L) lse[(long)x.nh * L + x.row] = m + logf(l);
   const float inv = 1.f / l;
+  f32x4 iv;
 #pragma unroll
-  for (int r = 0; r < 4; ++r) {
-    const int q = q0 + 4 * g + r;
-    const float iv = __shfl(inv, 4 * g + r, 64);
-    if (q < L) {
-      float* op = out + ((long)q * N + n) * E + h * DH + c;
-#pragma unroll
-      for (int dt = 0; dt < DT; ++dt) op[dt * 16] = o[dt][r] * iv;
-    }
-  }
+  for (int r = 0; r < 4; ++r) iv[r] = __shfl(inv, 4 * x.g + r, 64);
+  attn_scale_rows<DT>(o, iv);
+  attn_store_rows<DH>(out + x.ho, x.ro, o, x, L);
 }
 
-// dQ per query block, keys streamed; also D[query] = dO . O -> dws (N*H, L)
-template <int DH>
+// ================================================================================================ backward, both paths
+// Two kernels, no atomics: dQ per 16-query wave over the staged K / V blocks, dK and dV per 16-key wave over the staged
+// Q / dO blocks.  STREAM = false: one block of roundup(L, 16) rows, the loop runs once.  The first block is staged before the
+// wave's own rows are fetched, so those loads overlap; every wave takes part in every barrier.
+// dqkv rows like qkv; the streamed dQ also writes D[query] = dO . O -> dws (N*H, L)
+template <int DH, bool STREAM>
 __global__ void __launch_bounds__(64 * ATTN_WAVES)
-attn_stream_bwd_dq_kernel(const float* __restrict__ qkv, const float* __restrict__ out, const float* __restrict__ dout,
-                          const float* __restrict__ lse, float* __restrict__ dqkv, float* __restrict__ dws, int L, int N, int H,
-                          float scale, float pdrop, uint64_t seed) {
-  constexpr int DQ = DH / 4, RS = DH + 4, DT = DH / 16, KT = ATTN_SBK / 16;
+attn_bwd_dq_kernel(const float* __restrict__ qkv, const float* __restrict__ out, const float* __restrict__ dout,
+                   const float* __restrict__ lse, float* __restrict__ dqkv, float* __restrict__ dws, int L, int N, int H, float scale,
+                   float pdrop, uint64_t seed) {
+  constexpr int DQ = DH / 4, RS = DH + 4, DT = DH / 16;
   extern __shared__ float smem[];
+  const int BR = attn_block_rows(STREAM, L), NT = BR >> 4;
   float* Ks = smem;
-  float* Vs = smem + ATTN_SBK * RS;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, g = lane >> 4, c = lane & 15;
-  const int nh = blockIdx.y, n = nh / H, h = nh - n * H;
-  const int E = H * DH, E3 = 3 * E;
-  const long rs = (long)N * E3, ro = (long)N * E;
-  const float* base = qkv + (long)n * E3 + h * DH;
-  const int q0 = (blockIdx.x * ATTN_WAVES + wave) * 16, qrow = q0 + c;
+  float* Vs = smem + BR * RS;
+  const AttnCtx x = attn_ctx<DH>(N, H);
+  const float* base = qkv + x.hq;
+  auto stage = [&](int k0) {
+    attn_stage<DH>(Ks, base + x.E + (long)k0 * x.rs, x.rs, L - k0, BR, x.tid);
+    attn_stage<DH>(Vs, base + 2 * x.E + (long)k0 * x.rs, x.rs, L - k0, BR, x.tid);
+  };
+  int k0 = 0;
+  stage(k0);
   float qf[DQ], dof[DQ];
-  float dsum = 0.f;
-  {
-    float of[DQ];
-    attn_frag<DH>(qf, base, rs, qrow, L, g);
-    attn_frag<DH>(dof, dout + (long)n * E + h * DH, ro, qrow, L, g);
-    attn_frag<DH>(of, out + (long)n * E + h * DH, ro, qrow, L, g);
-#pragma unroll
-    for (int k = 0; k < DQ; ++k) dsum += dof[k] * of[k];
-  }
-  dsum = quad_group_sum(dsum);                      // D[query] = dO . O = sum_j dP_j P_j
-  const float lq = qrow < L ? lse[(long)nh * L + qrow] : 0.f;
-  if (g == 0 && qrow < L) dws[(long)nh * L + qrow] = dsum;
+  attn_frag<DH>(qf, base, x.rs, x.row, L, x.g);
+  attn_frag<DH>(dof, dout + x.ho, x.ro, x.row, L, x.g);
+  const float dsum = attn_d_frag<DH>(dof, out, x, L);
+  const float lq = x.row < L ? lse[(long)x.nh * L + x.row] : 0.f;
+  if constexpr (STREAM)                                          // the resident dK/dV sums D itself (see there)
+    if (x.g == 0 && x.row < L) dws[(long)x.nh * L + x.row] = dsum;
   f32x4 dq[DT];
+  attn_zero<DT>(dq);
+  const uint64_t maskrow = attn_mask_row(x.nh, x.row < L ? x.row : 0, L);
+  for (;;) {
+    __syncthreads();                                             // the block is staged
+    if (x.r0 < L) {                                              // wave-uniform; no barrier inside
+      if constexpr (STREAM) {                                    // blocked summation: a block's sum is added to the total once
+        f32x4 dqb[DT];
+        attn_zero<DT>(dqb);
+        for (int t = 0; t < NT; ++t) attn_dq_tile<DH>(dqb, Ks, Vs, t, qf, dof, lq, dsum, k0, maskrow, L, scale, pdrop, seed, x);
 #pragma unroll
-  for (int dt = 0; dt < DT; ++dt) dq[dt] = (f32x4){0.f, 0.f, 0.f, 0.f};
-  const uint64_t rowbase = ((uint64_t)nh * L + (qrow < L ? qrow : 0)) * (uint64_t)L;
-  for (int k0 = 0; k0 < L; k0 += ATTN_SBK) {
-    if (k0) __syncthreads();
-    attn_stage<DH>(Ks, base + E + (long)k0 * rs, rs, L - k0, ATTN_SBK, tid);
-    attn_stage<DH>(Vs, base + 2 * E + (long)k0 * rs, rs, L - k0, ATTN_SBK, tid);
-    __syncthreads();
-    if (q0 < L) {
-      f32x4 dqb[DT];                                    // this block's sum, added to the total once: blocked summation
-#pragma unroll
-      for (int dt = 0; dt < DT; ++dt) dqb[dt] = (f32x4){0.f, 0.f, 0.f, 0.f};
-      for (int t = 0; t < KT; ++t) {
-        float kf[DQ], vf[DQ];
-        attn_lds_frag<DH>(kf, Ks + (t * 16 + c) * RS, g);
-        attn_lds_frag<DH>(vf, Vs + (t * 16 + c) * RS, g);
-        f32x4 st = {0.f, 0.f, 0.f, 0.f}, dp = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int k = 0; k < DQ; ++k) {
-          st = MFMA16(kf[k], qf[k], st);                // S^T[key][query]
-          dp = MFMA16(vf[k], dof[k], dp);               // dPd^T[key][query] = V[key] . dO[query]
-        }
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const int kl = t * 16 + 4 * g + r, key = k0 + kl;
-          const float p = (key < L && qrow < L) ? expf(st[r] * scale - lq) : 0.f;
-          const float mk = pdrop > 0.f ? dropout_scale(seed, rowbase + (uint64_t)key, pdrop) : 1.f;
-          const float ds = p * (dp[r] * mk - dsum);
-          const float* krow = Ks + kl * RS + c;
-#pragma unroll
-          for (int dt = 0; dt < DT; ++dt) dqb[dt] = MFMA16(ds, krow[dt * 16], dqb[dt]);
-        }
+        for (int dt = 0; dt < DT; ++dt) dq[dt] += dqb[dt];
+      } else {                                                   // one block: straight into dq (0 + x would turn a -0 into +0)
+        for (int t = 0; t < NT; ++t) attn_dq_tile<DH>(dq, Ks, Vs, t, qf, dof, lq, dsum, k0, maskrow, L, scale, pdrop, seed, x);
       }
-#pragma unroll
-      for (int dt = 0; dt < DT; ++dt) dq[dt] += dqb[dt];
     }
+    if (!STREAM || (k0 += BR) >= L) break;                       // the same for every wave; resident: the one block was all
+    __syncthreads();                                             // every wave has read the previous block
+    stage(k0);
   }
-#pragma unroll
-  for (int r = 0; r < 4; ++r) {
-    const int q = q0 + 4 * g + r;
-    if (q < L) {
-      float* dp = dqkv + ((long)q * N + n) * E3 + h * DH + c;
-#pragma unroll
-      for (int dt = 0; dt < DT; ++dt) dp[dt * 16] = dq[dt][r] * scale;
-    }
-  }
+  attn_scale_rows<DT>(dq, scale);
+  attn_store_rows<DH>(dqkv + x.hq, x.rs, dq, x, L);
 }
 
-// dK, dV per key block (keys in registers), queries streamed: Q, dO, lse and D (from dws) of one block in LDS
-template <int DH>
-__global__ void __launch_bounds__(64 * ATTN_WAVES)
-__attribute__((amdgpu_waves_per_eu(ATTN_STREAM_WAVES(DH)))) attn_stream_bwd_dkv_kernel(const float* __restrict__ qkv, const float* __restrict__ dout, const float* __restrict__ lse,
-                           const float* __restrict__ dws, float* __restrict__ dqkv, int L, int N, int H, float scale,
-                           float pdrop, uint64_t seed) {
-  constexpr int DQ = DH / 4, RS = DH + 4, DT = DH / 16, QT = ATTN_SBK / 16;
+// dK, dV: the wave's 16 keys in registers; Q, dO, lse and D per query of a block in LDS
+template <int DH, bool STREAM>
+__global__ void __launch_bounds__(64 * ATTN_WAVES) __attribute__((amdgpu_waves_per_eu(ATTN_DKV_WAVES(DH, STREAM))))
+attn_bwd_dkv_kernel(const float* __restrict__ qkv, const float* __restrict__ out, const float* __restrict__ dout,
+                    const float* __restrict__ lse, float* __restrict__ dqkv, float* __restrict__ dws, int L, int N, int H, float scale,
+                    float pdrop, uint64_t seed) {
+  constexpr int DQ = DH / 4, RS = DH + 4, DT = DH / 16;
   extern __shared__ float smem[];
+  const int BR = attn_block_rows(STREAM, L), NT = BR >> 4;
   float* Qs = smem;
-  float* Gs = smem + ATTN_SBK * RS;    // dO
-  float* Ls = Gs + ATTN_SBK * RS;      // lse per query
-  float* Ds = Ls + ATTN_SBK;           // dO . O per query
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, g = lane >> 4, c = lane & 15;
-  const int nh = blockIdx.y, n = nh / H, h = nh - n * H;
-  const int E = H * DH, E3 = 3 * E;
-  const long rs = (long)N * E3, ro = (long)N * E;
-  const float* base = qkv + (long)n * E3 + h * DH;
-  const float* dob = dout + (long)n * E + h * DH;
-  const int k0 = (blockIdx.x * ATTN_WAVES + wave) * 16, krow = k0 + c;
-  float kf[DQ], vf[DQ];
-  attn_frag<DH>(kf, base + E, rs, krow, L, g);
-  attn_frag<DH>(vf, base + 2 * E, rs, krow, L, g);
-  f32x4 dk[DT], dv[DT];
+  float* Gs = smem + BR * RS;          // dO
+  float* Ls = Gs + BR * RS;            // lse per query
+  float* Ds = Ls + BR;                 // dO . O per query
+  const AttnCtx x = attn_ctx<DH>(N, H);
+  const float* base = qkv + x.hq;
+  const float* dob = dout + x.ho;
+  auto stage = [&](int q0) {
+    attn_stage<DH>(Qs, base + (long)q0 * x.rs, x.rs, L - q0, BR, x.tid);
+    attn_stage<DH>(Gs, dob + (long)q0 * x.ro, x.ro, L - q0, BR, x.tid);
+    for (int ql = x.tid; ql < BR; ql += 64 * ATTN_WAVES) {
+      const int q = q0 + ql;
+      float d = 0.f, l = 0.f;
+      if (q < L) {
+        l = lse[(long)x.nh * L + q];
+        if constexpr (STREAM) {                                  // what the dQ kernel stored: a quad-partial sum plus two shuffles
+          d = dws[(long)x.nh * L + q];
+        } else {                                                 // summed here, serially over DH: another last bit than dQ's D
+          const float* ob = out + x.ho;
 #pragma unroll
-  for (int dt = 0; dt < DT; ++dt) { dk[dt] = (f32x4){0.f, 0.f, 0.f, 0.f}; dv[dt] = (f32x4){0.f, 0.f, 0.f, 0.f}; }
-  for (int qb = 0; qb < L; qb += ATTN_SBK) {
-    if (qb) __syncthreads();
-    attn_stage<DH>(Qs, base + (long)qb * rs, rs, L - qb, ATTN_SBK, tid);
-    attn_stage<DH>(Gs, dob + (long)qb * ro, ro, L - qb, ATTN_SBK, tid);
-    if (tid < ATTN_SBK) {
-      const int q = qb + tid;
-      Ls[tid] = q < L ? lse[(long)nh * L + q] : 0.f;
-      Ds[tid] = q < L ? dws[(long)nh * L + q] : 0.f;
-    }
-    __syncthreads();
-    if (k0 < L) {
-      for (int t = 0; t < QT; ++t) {
-        float qv[DQ], gv[DQ];
-        attn_lds_frag<DH>(qv, Qs + (t * 16 + c) * RS, g);
-        attn_lds_frag<DH>(gv, Gs + (t * 16 + c) * RS, g);
-        f32x4 sv = {0.f, 0.f, 0.f, 0.f}, dp = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int k = 0; k < DQ; ++k) {
-          sv = MFMA16(qv[k], kf[k], sv);                // S[query 4g+r][key c]
-          dp = MFMA16(gv[k], vf[k], dp);                // dPd[query][key]
-        }
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const int ql = t * 16 + 4 * g + r, q = qb + ql;
-          const bool valid = q < L && krow < L;
-          const float p = valid ? expf(sv[r] * scale - Ls[ql]) : 0.f;
-          const float mk = (pdrop > 0.f && valid) ? dropout_scale(seed, ((uint64_t)nh * L + q) * (uint64_t)L + (uint64_t)krow, pdrop) : 1.f;
-          const float pd = p * mk;
-          const float ds = p * (dp[r] * mk - Ds[ql]);
-          const float* grow = Gs + ql * RS + c;
-          const float* qrow_ = Qs + ql * RS + c;
-#pragma unroll
-          for (int dt = 0; dt < DT; ++dt) {
-            dv[dt] = MFMA16(pd, grow[dt * 16], dv[dt]);  // dV[key 4g'+r'][d]
-            dk[dt] = MFMA16(ds, qrow_[dt * 16], dk[dt]);
+          for (int k = 0; k < DH; k += 4) {
+            const f32x4 a = *(const f32x4*)(dob + (long)q * x.ro + k), b = *(const f32x4*)(ob + (long)q * x.ro + k);
+            d += a[0] * b[0] + a[1] * b[1] + a[2] * b[2] + a[3] * b[3];
           }
         }
       }
+      Ls[ql] = l;
+      Ds[ql] = d;
     }
+  };
+  int q0 = 0;
+  stage(q0);
+  float kf[DQ], vf[DQ];
+  attn_frag<DH>(kf, base + x.E, x.rs, x.row, L, x.g);
+  attn_frag<DH>(vf, base + 2 * x.E, x.rs, x.row, L, x.g);
+  f32x4 dk[DT], dv[DT];
+  attn_zero<DT>(dk);
+  attn_zero<DT>(dv);
+  for (;;) {
+    __syncthreads();                                             // the block is staged
+    if (x.r0 < L)                                                // wave-uniform; no barrier inside
+      for (int t = 0; t < NT; ++t) attn_dkv_tile<DH>(dk, dv, Qs, Gs, Ls, Ds, t, kf, vf, q0, L, scale, pdrop, seed, x);
+    if (!STREAM || (q0 += BR) >= L) break;                       // the same for every wave; resident: the one block was all
+    __syncthreads();                                             // every wave has read the previous block
+    stage(q0);
   }
-#pragma unroll
-  for (int r = 0; r < 4; ++r) {
-    const int key = k0 + 4 * g + r;
-    if (key < L) {
-      float* dp = dqkv + ((long)key * N + n) * E3 + h * DH + c;
-#pragma unroll
-      for (int dt = 0; dt < DT; ++dt) {
-        dp[E + dt * 16] = dk[dt][r] * scale;
-        dp[2 * E + dt * 16] = dv[dt][r];
-      }
-    }
-  }
+  attn_scale_rows<DT>(dk, scale);
+  attn_store_rows<DH>(dqkv + x.hq + x.E, x.rs, dk, x, L);
+  attn_store_rows<DH>(dqkv + x.hq + 2 * x.E, x.rs, dv, x, L);
 }
 
-template <int DH>
-static int attn_stream_launch(int which, const float* qkv, const float* out, const float* dout, float* lse, float* dst, float* dws,
-                              int L, int N, int H, float p, uint64_t seed, hipStream_t st) {
-  const float scale = 1.0f / sqrtf((float)DH);
-  const dim3 grid(cdiv(L, ATTN_SBQ), N * H), block(64 * ATTN_WAVES);
-  static bool attr[3] = {false, false, false};
-  const size_t lds = (size_t)2 * ATTN_SBK * (DH + 4) * 4 + (which == 2 ? (size_t)2 * ATTN_SBK * 4 : 0);
-  const void* fn = which == 0 ? (const void*)attn_stream_fwd_kernel<DH>
-                              : (which == 1 ? (const void*)attn_stream_bwd_dq_kernel<DH> : (const void*)attn_stream_bwd_dkv_kernel<DH>);
-  if (!attr[which]) {
-    if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) {
-      muvo_set_error("attention_stream: cannot raise the dynamic LDS limit");
-      return MUVO_ERR_HIP;
-    }
-    attr[which] = true;
-  }
-  if (which == 0)
-    hipLaunchKernelGGL(attn_stream_fwd_kernel<DH>, grid, block, lds, st, qkv, dst, lse, L, N, H, scale, p, seed);
-  else if (which == 1)
-    hipLaunchKernelGGL(attn_stream_bwd_dq_kernel<DH>, grid, block, lds, st, qkv, out, dout, (const float*)lse, dst, dws, L, N, H, scale, p, seed);
-  else
-    hipLaunchKernelGGL(attn_stream_bwd_dkv_kernel<DH>, grid, block, lds, st, qkv, dout, (const float*)lse, (const float*)dws, dst, L, N, H, scale, p, seed);
-  return MUVO_OK;
+// ================================================================================================ host
+static bool attn_dh_ok(int DH) { return DH == 16 || DH == 32 || DH == 48 || DH == 64; }
+// dynamic LDS of kernel `which` (0 forward, 1 dQ, 2 dK/dV): two matrices of one block's rows, dK/dV also lse and D per row
+static size_t attn_lds_bytes(int L, int DH, int which, bool stream) {
+  const int rows = attn_block_rows(stream, L);
+  return (size_t)2 * rows * (DH + 4) * 4 + (which == 2 ? (size_t)2 * rows * 4 : 0);
 }
 
-static int attn_stream_dispatch(int which, const float* qkv, const float* out, const float* dout, float* lse, float* dst,
-                                float* dws, int L, int N, int H, int DH, float p, uint64_t seed, hipStream_t st) {
-  switch (DH) {
-    case 16: return attn_stream_launch<16>(which, qkv, out, dout, lse, dst, dws, L, N, H, p, seed, st);
-    case 32: return attn_stream_launch<32>(which, qkv, out, dout, lse, dst, dws, L, N, H, p, seed, st);
-    case 48: return attn_stream_launch<48>(which, qkv, out, dout, lse, dst, dws, L, N, H, p, seed, st);
-    case 64: return attn_stream_launch<64>(which, qkv, out, dout, lse, dst, dws, L, N, H, p, seed, st);
-  }
-  muvo_set_error("attention_stream: head dimension %d not supported", DH);
-  return MUVO_ERR_INVALID_ARG;
-}
-
-static size_t attn_lds_bytes(int L, int DH, bool bwd_kv) {
-  const int Lp = (L + 15) & ~15;
-  return (size_t)2 * Lp * (DH + 4) * 4 + (bwd_kv ? (size_t)2 * Lp * 4 : 0);
-}
-
-template <int DH>
-static int attn_launch(int which, const float* qkv, const float* out, const float* dout, float* lse, float* dst, int L, int N,
-                       int H, float p, uint64_t seed, hipStream_t st) {
+template <int DH, bool STREAM>
+static int attn_launch(int which, const float* qkv, const float* out, const float* dout, float* lse, float* dst,
+                       float* dws, int L, int N, int H, float p, uint64_t seed, hipStream_t st) {
   const float scale = 1.0f / sqrtf((float)DH);
   const dim3 grid(cdiv(L, 16 * ATTN_WAVES), N * H), block(64 * ATTN_WAVES);
   static bool attr[3] = {false, false, false};
-  const size_t lds = attn_lds_bytes(L, DH, which == 2);
-  const void* fn = which == 0 ? (const void*)attn_fwd_kernel<DH> : (which == 1 ? (const void*)attn_bwd_dq_kernel<DH>
-                                                                               : (const void*)attn_bwd_dkv_kernel<DH>);
+  const size_t lds = attn_lds_bytes(L, DH, which, STREAM);
+  const auto fwd = STREAM ? attn_stream_fwd_kernel<DH> : attn_fwd_kernel<DH>;
+  const auto bwd = which == 1 ? attn_bwd_dq_kernel<DH, STREAM> : attn_bwd_dkv_kernel<DH, STREAM>;
   if (!attr[which]) {
-    if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) {
-      muvo_set_error("attention: cannot raise the dynamic LDS limit");
+    if (hipFuncSetAttribute(which == 0 ? (const void*)fwd : (const void*)bwd, hipFuncAttributeMaxDynamicSharedMemorySize,
+                            160 * 1024) != hipSuccess) {
+      muvo_set_error("%s: cannot raise the dynamic LDS limit", STREAM ? "attention_stream" : "attention");
       return MUVO_ERR_HIP;
     }
     attr[which] = true;
   }
   if (which == 0)
-    hipLaunchKernelGGL(attn_fwd_kernel<DH>, grid, block, lds, st, qkv, dst, lse, L, N, H, scale, p, seed);
-  else if (which == 1)
-    hipLaunchKernelGGL(attn_bwd_dq_kernel<DH>, grid, block, lds, st, qkv, out, dout, (const float*)lse, dst, L, N, H, scale, p, seed);
+    hipLaunchKernelGGL(fwd, grid, block, lds, st, qkv, dst, lse, L, N, H, scale, p, seed);
   else
-    hipLaunchKernelGGL(attn_bwd_dkv_kernel<DH>, grid, block, lds, st, qkv, out, dout, (const float*)lse, dst, L, N, H, scale, p, seed);
+    hipLaunchKernelGGL(bwd, grid, block, lds, st, qkv, out, dout, (const float*)lse, dst, dws, L, N, H, scale, p, seed);
   return MUVO_OK;
 }
 
-static int attn_dispatch(int which, const float* qkv, const float* out, const float* dout, float* lse, float* dst, int L, int N,
-                         int H, int DH, float p, uint64_t seed, hipStream_t st) {
+template <bool STREAM>
+static int attn_dispatch(int which, const float* qkv, const float* out, const float* dout, float* lse, float* dst,
+                         float* dws, int L, int N, int H, int DH, float p, uint64_t seed, hipStream_t st) {
   switch (DH) {
-    case 16: return attn_launch<16>(which, qkv, out, dout, lse, dst, L, N, H, p, seed, st);
-    case 32: return attn_launch<32>(which, qkv, out, dout, lse, dst, L, N, H, p, seed, st);
-    case 48: return attn_launch<48>(which, qkv, out, dout, lse, dst, L, N, H, p, seed, st);
-    case 64: return attn_launch<64>(which, qkv, out, dout, lse, dst, L, N, H, p, seed, st);
+    case 16: return attn_launch<16, STREAM>(which, qkv, out, dout, lse, dst, dws, L, N, H, p, seed, st);
+    case 32: return attn_launch<32, STREAM>(which, qkv, out, dout, lse, dst, dws, L, N, H, p, seed, st);
+    case 48: return attn_launch<48, STREAM>(which, qkv, out, dout, lse, dst, dws, L, N, H, p, seed, st);
+    case 64: return attn_launch<64, STREAM>(which, qkv, out, dout, lse, dst, dws, L, N, H, p, seed, st);
   }
-  muvo_set_error("attention: head dimension %d not supported", DH);
+  muvo_set_error("%s: head dimension %d not supported", STREAM ? "attention_stream" : "attention", DH);
   return MUVO_ERR_INVALID_ARG;
+}
+
+// One entry point: the argument check, then kernels first .. last (0 forward, 1 dQ, 2 dK/dV) of the path, queued on st.
+// ptrs: the entry point's own pointers are all there
+static int attn_run(const char* name, bool stream, int first, int last, bool ptrs, const float* qkv, const float* out,
+                    const float* dout, float* lse, float* dst, float* dws, int L, int N, int H, int DH, float p, uint64_t seed,
+                    hipStream_t st) {
+  MUVO_CHECK_ARG(ptrs && N > 0 && H > 0 && (long)N * H <= 65535, "%s: bad args", name);
+  if (stream)
+    MUVO_CHECK_ARG(muvo_attention_stream_supported(L, DH), "%s: L = %d, head dim = %d not supported", name, L, DH);
+  else
+    MUVO_CHECK_ARG(muvo_attention_supported(L, DH), "%s: L = %d, head dim = %d outside the fused kernel's range", name, L, DH);
+  MUVO_CHECK_ARG(p >= 0.f && p < 1.f, "%s: dropout probability", name);
+  for (int which = first; which <= last; ++which) {
+    const int rc = stream ? attn_dispatch<true>(which, qkv, out, dout, lse, dst, dws, L, N, H, DH, p, seed, st)
+                          : attn_dispatch<false>(which, qkv, out, dout, lse, dst, dws, L, N, H, DH, p, seed, st);
+    if (rc) return rc;
+  }
+  MUVO_CHECK_LAUNCH(name);
+  return MUVO_OK;
 }
 
 extern "C" {
 int muvo_attention_supported(int L, int DH) {
-  if (!(DH == 16 || DH == 32 || DH == 48 || DH == 64)) return 0;
+  if (!attn_dh_ok(DH)) return 0;
   if (L < 1 || L > 16 * ATTN_MAXT) return 0;
-  return attn_lds_bytes(L, DH, true) <= (size_t)160 * 1024 ? 1 : 0;
+  return attn_lds_bytes(L, DH, 2, false) <= (size_t)160 * 1024 ? 1 : 0;
 }
-int muvo_attention_fwd(const float* qkv, float* out, float* lse, int L, int N, int H, int DH, float p, uint64_t seed,
-                       void* stream) {
-  MUVO_CHECK_ARG(qkv && out && lse && N > 0 && H > 0 && (long)N * H <= 65535, "attention_fwd: bad args");
-  MUVO_CHECK_ARG(muvo_attention_supported(L, DH), "attention_fwd: L = %d, head dim = %d outside the fused kernel's range", L, DH);
-  MUVO_CHECK_ARG(p >= 0.f && p < 1.f, "attention_fwd: dropout probability");
-  const int rc = attn_dispatch(0, qkv, nullptr, nullptr, lse, out, L, N, H, DH, p, seed, ST);
-  if (rc) return rc;
-  MUVO_CHECK_LAUNCH("attention_fwd");
-  return MUVO_OK;
-}
-int muvo_attention_bwd(const float* qkv, const float* out, const float* dout, const float* lse, float* dqkv, int L, int N, int H,
-                       int DH, float p, uint64_t seed, void* stream) {
-  MUVO_CHECK_ARG(qkv && out && dout && lse && dqkv && N > 0 && H > 0 && (long)N * H <= 65535, "attention_bwd: bad args");
-  MUVO_CHECK_ARG(muvo_attention_supported(L, DH), "attention_bwd: L = %d, head dim = %d outside the fused kernel's range", L, DH);
-  int rc = attn_dispatch(1, qkv, out, dout, (float*)lse, dqkv, L, N, H, DH, p, seed, ST);
-  if (rc) return rc;
-  rc = attn_dispatch(2, qkv, out, dout, (float*)lse, dqkv, L, N, H, DH, p, seed, ST);
-  if (rc) return rc;
-  MUVO_CHECK_LAUNCH("attention_bwd");
-  return MUVO_OK;
-}
-int muvo_attention_stream_supported(int L, int DH) {
-  return (DH == 16 || DH == 32 || DH == 48 || DH == 64) && L >= 1 ? 1 : 0;
-}
+int muvo_attention_stream_supported(int L, int DH) { return attn_dh_ok(DH) && L >= 1 ? 1 : 0; }
 int muvo_attention_stream_blocks(int* bq, int* bk) {
   MUVO_CHECK_ARG(bq && bk, "attention_stream_blocks: null pointer");
   *bq = ATTN_SBQ;
   *bk = ATTN_SBK;
   return MUVO_OK;
 }
+int muvo_attention_fwd(const float* qkv, float* out, float* lse, int L, int N, int H, int DH, float p, uint64_t seed,
+                       void* stream) {
+  return attn_run("attention_fwd", false, 0, 0, qkv && out && lse, qkv, nullptr, nullptr, lse, out, nullptr, L, N, H, DH, p, seed, ST);
+}
+int muvo_attention_bwd(const float* qkv, const float* out, const float* dout, const float* lse, float* dqkv, int L, int N, int H,
+                       int DH, float p, uint64_t seed, void* stream) {
+  return attn_run("attention_bwd", false, 1, 2, qkv && out && dout && lse && dqkv, qkv, out, dout, (float*)lse, dqkv, nullptr, L, N,
+                  H, DH, p, seed, ST);
+}
 int muvo_attention_stream_fwd(const float* qkv, float* out, float* lse, int L, int N, int H, int DH, float p, uint64_t seed,
                               void* stream) {
-  MUVO_CHECK_ARG(qkv && out && lse && N > 0 && H > 0 && (long)N * H <= 65535, "attention_stream_fwd: bad args");
-  MUVO_CHECK_ARG(muvo_attention_stream_supported(L, DH), "attention_stream_fwd: L = %d, head dim = %d not supported", L, DH);
-  MUVO_CHECK_ARG(p >= 0.f && p < 1.f, "attention_stream_fwd: dropout probability");
-  const int rc = attn_stream_dispatch(0, qkv, nullptr, nullptr, lse, out, nullptr, L, N, H, DH, p, seed, ST);
-  if (rc) return rc;
-  MUVO_CHECK_LAUNCH("attention_stream_fwd");
-  return MUVO_OK;
+  return attn_run("attention_stream_fwd", true, 0, 0, qkv && out && lse, qkv, nullptr, nullptr, lse, out, nullptr, L, N, H, DH, p,
+                  seed, ST);
 }
 int muvo_attention_stream_bwd(const float* qkv, const float* out, const float* dout, const float* lse, float* dqkv, float* dws,
                               int L, int N, int H, int DH, float p, uint64_t seed, void* stream) {
-  MUVO_CHECK_ARG(qkv && out && dout && lse && dqkv && dws && N > 0 && H > 0 && (long)N * H <= 65535, "attention_stream_bwd: bad args");
-  MUVO_CHECK_ARG(muvo_attention_stream_supported(L, DH), "attention_stream_bwd: L = %d, head dim = %d not supported", L, DH);
-  MUVO_CHECK_ARG(p >= 0.f && p < 1.f, "attention_stream_bwd: dropout probability");
-  int rc = attn_stream_dispatch(1, qkv, out, dout, (float*)lse, dqkv, dws, L, N, H, DH, p, seed, ST);
-  if (rc) return rc;
-  rc = attn_stream_dispatch(2, qkv, out, dout, (float*)lse, dqkv, dws, L, N, H, DH, p, seed, ST);
-  if (rc) return rc;
-  MUVO_CHECK_LAUNCH("attention_stream_bwd");
-  return MUVO_OK;
+  return attn_run("attention_stream_bwd", true, 1, 2, qkv && out && dout && lse && dqkv && dws, qkv, out, dout, (float*)lse, dqkv,
+                  dws, L, N, H, DH, p, seed, ST);
 }
 }

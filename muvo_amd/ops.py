@@ -2215,58 +2215,46 @@ class AttentionFn(torch.autograd.Function):
         return dqkv, None, None, None
 
 
-class FlashAttentionFn(torch.autograd.Function):
-    """The same attention core as ONE kernel forward and two backward (csrc/attention.hip): K / V of a head staged in LDS,
-    softmax over register-resident score tiles with wave shuffles, no L x L tensor in HBM; saves only the row log-sum-exp."""
+class _FusedAttentionFn(torch.autograd.Function):
+    """The same attention core as ONE kernel forward and two backward (csrc/attention.hip), no L x L tensor in HBM; saves qkv, o
+    and the row log-sum-exp only, backward recomputes the probabilities from it.  The two paths of the unit subclass this with
+    their entry points (FWD, BWD) and whether backward takes the D = do . o workspace, (N * heads, L) floats (DWS)."""
+    FWD = BWD = None
+    DWS = False
 
-    @staticmethod
-    def forward(ctx, qkv, nheads, p, seed):
+    @classmethod
+    def forward(cls, ctx, qkv, nheads, p, seed):
         qkv = qkv.contiguous()
         l, n, e3 = qkv.shape
         e = e3 // 3
         o = torch.empty(l, n, e, device=qkv.device, dtype=torch.float32)
         lse = torch.empty(n * nheads, l, device=qkv.device, dtype=torch.float32)
-        _ck(lib().muvo_attention_fwd(_f(qkv), _f(o), _f(lse), l, n, nheads, e // nheads, _fl(p), C.c_uint64(seed), _st()))
+        _ck(getattr(lib(), cls.FWD)(_f(qkv), _f(o), _f(lse), l, n, nheads, e // nheads, _fl(p), C.c_uint64(seed), _st()))
         ctx.dims = (l, n, nheads, e // nheads, p, seed)
         ctx.save_for_backward(qkv, o, lse)
         return o
 
-    @staticmethod
-    def backward(ctx, do):
+    @classmethod
+    def backward(cls, ctx, do):
         qkv, o, lse = ctx.saved_tensors
         l, n, nheads, dh, p, seed = ctx.dims
         dqkv = torch.empty_like(qkv)
-        _ck(lib().muvo_attention_bwd(_f(qkv), _f(o), _f(do.contiguous()), _f(lse), _f(dqkv), l, n, nheads, dh, _fl(p),
-                                     C.c_uint64(seed), _st()))
+        dws = torch.empty_like(lse) if cls.DWS else None
+        _ck(getattr(lib(), cls.BWD)(_f(qkv), _f(o), _f(do.contiguous()), _f(lse), _f(dqkv), *((_f(dws),) if cls.DWS else ()), l, n,
+                                    nheads, dh, _fl(p), C.c_uint64(seed), _st()))
         return dqkv, None, None, None
 
 
-class StreamAttentionFn(torch.autograd.Function):
-    """The attention core for any sequence length (csrc/attention.hip, streamed kernels): K / V pass through LDS block by block
-    under an online softmax, backward recomputes the probabilities from the row log-sum-exp.  Saves qkv, o and lse only; the one
-    extra buffer of backward is D = do . o, (N * heads, L) floats."""
+class FlashAttentionFn(_FusedAttentionFn):
+    """Resident path (L <= 384): K / V of a head staged whole in LDS, softmax over register-resident score tiles with wave
+    shuffles."""
+    FWD, BWD = 'muvo_attention_fwd', 'muvo_attention_bwd'
 
-    @staticmethod
-    def forward(ctx, qkv, nheads, p, seed):
-        qkv = qkv.contiguous()
-        l, n, e3 = qkv.shape
-        e = e3 // 3
-        o = torch.empty(l, n, e, device=qkv.device, dtype=torch.float32)
-        lse = torch.empty(n * nheads, l, device=qkv.device, dtype=torch.float32)
-        _ck(lib().muvo_attention_stream_fwd(_f(qkv), _f(o), _f(lse), l, n, nheads, e // nheads, _fl(p), C.c_uint64(seed), _st()))
-        ctx.dims = (l, n, nheads, e // nheads, p, seed)
-        ctx.save_for_backward(qkv, o, lse)
-        return o
 
-    @staticmethod
-    def backward(ctx, do):
-        qkv, o, lse = ctx.saved_tensors
-        l, n, nheads, dh, p, seed = ctx.dims
-        dqkv = torch.empty_like(qkv)
-        dws = torch.empty_like(lse)
-        _ck(lib().muvo_attention_stream_bwd(_f(qkv), _f(o), _f(do.contiguous()), _f(lse), _f(dqkv), _f(dws), l, n, nheads, dh,
-                                            _fl(p), C.c_uint64(seed), _st()))
-        return dqkv, None, None, None
+class StreamAttentionFn(_FusedAttentionFn):
+    """Streamed path, any sequence length: K / V pass through LDS block by block under an online softmax; the one extra buffer of
+    backward is D."""
+    FWD, BWD, DWS = 'muvo_attention_stream_fwd', 'muvo_attention_stream_bwd', True
 
 
 FLASH_ATTENTION = os.environ.get('MUVO_FLASH_ATTN', '1') != '0'

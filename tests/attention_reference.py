@@ -1,5 +1,7 @@
-"""Float64 reference, float32 restatement of the online-softmax recurrence, case lists, spiked inputs and the comparison for the
-streamed attention kernels (muvo_amd/csrc/attention.hip: attn_stream_*).  Helpers only: no fixtures, no tests.
+"""Float64 reference, float32 restatement of the softmax recurrence, case lists, spiked inputs and the comparison for the fused
+attention kernels (muvo_amd/csrc/attention.hip), one unit with two paths: streamed (K / V blocks of BK rows under an online
+softmax, any L) and resident (K / V of a head whole in LDS, L <= 384: the same recurrence with ONE block, which is the two-pass
+softmax and the unblocked dQ sum).  Helpers only: no fixtures, no tests.
 tests/test_attention_reference.py (CPU) and tests/test_attention_stream_gpu.py (GPU) share everything here, so the bars the GPU
 test applies are the ones the CPU test proves to reject planted errors.  The metric (error_stats) and the seeded generator are
 those of tests/loss_reference.py.
@@ -10,7 +12,8 @@ The metric.  e = max |got - ref64| / max |ref64|, per tensor: o, lse, dqkv.
 
 The bar.  One for every float64 comparison: 4 x the e of blocked_float32() - the recurrence the forward kernel runs (running
 maximum m, running sum l, O rescaled by exp(m_old - m_new) per block of BK keys, divided by l at the end; backward from the row
-log-sum-exp, key block by key block), evaluated in float32 torch on the CPU - on the same inputs, tabulated per case in MEASURED
+log-sum-exp, key block by key block), evaluated in float32 torch on the CPU with the block of the case's path (float32_block:
+BK for a streamed case, the whole row for a resident one, id suffix -res) - on the same inputs, tabulated per case in MEASURED
 (`python tests/attention_reference.py` prints the table).  The factor 4 is what tests/norm_reference.py allows for another
 summation order.  Never the kernels' own error.  The dropout cases are tabulated with a CPU Bernoulli keep-mask of the same p
 (the GPU test takes the mask the library generates: same statistics, other bits).
@@ -32,12 +35,13 @@ NAMES = ('o', 'lse', 'dqkv')
 
 
 # ================================================================================================ cases
-def case(L, N, H, DH, spiked=False, p=0.0):
-    return dict(L=L, N=N, H=H, DH=DH, spiked=spiked, p=p)
+def case(L, N, H, DH, spiked=False, p=0.0, res=False):
+    return dict(L=L, N=N, H=H, DH=DH, spiked=spiked, p=p, res=res)
 
 
 def case_id(c):
-    return f'L{c["L"]}-N{c["N"]}H{c["H"]}D{c["DH"]}' + ('-spiked' if c['spiked'] else '') + (f'-p{c["p"]}' if c['p'] else '')
+    return f'L{c["L"]}-N{c["N"]}H{c["H"]}D{c["DH"]}' + ('-spiked' if c['spiked'] else '') + (f'-p{c["p"]}' if c['p'] else '') + \
+        ('-res' if c['res'] else '')
 
 
 PARITY_CASES = [case(L, 2, 2, 48) for L in (1, 15, BK - 1, BK, BK + 1, 385, 2 * BK + 23, 1037)] + \
@@ -46,10 +50,18 @@ BIG_CASE = case(5184, 1, 1, 48)                                           # 41 k
 SPIKED_CASES = [case(2 * BK + 23, 2, 2, 48, spiked=True), case(1037, 2, 2, 48, spiked=True)] + \
                [case(1037, 1, 2, DH, spiked=True) for DH in (16, 64)]
 DROPOUT_CASES = [case(517, 2, 4, 48, p=p) for p in (0.1, 0.5)]
-ALL_CASES = PARITY_CASES + [BIG_CASE] + SPIKED_CASES + DROPOUT_CASES
+STREAM_CASES = PARITY_CASES + [BIG_CASE] + SPIKED_CASES + DROPOUT_CASES
+# The resident path (res=True: its own ids, the same (L, N, H, DH) has another float32 evaluation there).  DH = 48: one key, one
+# key tile and its edges, 128 queries per workgroup (the last wave's rows; a second workgroup with seven idle waves), the model's
+# L, all RES_MAXT register tiles; the other head sizes on an odd head count; the largest L whose dK / dV LDS fits at DH = 64.
+RES_WG, RES_MAXL, RES_MAXL_D64 = 128, 384, 288
+RESIDENT_CASES = [case(L, 2, 2, 48, res=True) for L in (1, 15, 16, 17, RES_WG - 1, RES_WG, RES_WG + 1, 324, RES_MAXL - 1, RES_MAXL)] + \
+                 [case(279, 1, 3, DH, res=True) for DH in (16, 32, 64)] + [case(RES_MAXL_D64, 2, 2, 64, res=True)]
+RESIDENT_DROPOUT_CASES = [case(324, 2, 4, 48, p=p, res=True) for p in (0.1, 0.5)]
+ALL_CASES = STREAM_CASES + RESIDENT_CASES + RESIDENT_DROPOUT_CASES
 DROPOUT_SEEDS = {0.1: 77, 0.5: 123456789}
 
-# e of blocked_float32(bk = 128) against reference64 (this file run as a script; 16 CPU threads)
+# e of blocked_float32(bk = float32_block(case)) against reference64 (this file run as a script; 16 CPU threads)
 MEASURED = {
     'L1-N2H2D48': {'o': 0.00e+00, 'lse': 3.96e-08, 'dqkv': 4.76e-07},       # one key: p = 1, o = v exactly
     'L15-N2H2D48': {'o': 2.47e-07, 'lse': 8.84e-08, 'dqkv': 2.81e-07},
@@ -69,6 +81,23 @@ MEASURED = {
     'L1037-N1H2D64-spiked': {'o': 2.89e-06, 'lse': 2.53e-07, 'dqkv': 2.62e-06},
     'L517-N2H4D48-p0.1': {'o': 1.34e-06, 'lse': 9.66e-08, 'dqkv': 8.45e-07},
     'L517-N2H4D48-p0.5': {'o': 1.59e-06, 'lse': 9.66e-08, 'dqkv': 1.00e-06},
+    # resident path: blocked_float32 with one block (bk = L), the two-pass softmax and the unblocked dQ sum
+    'L1-N2H2D48-res': {'o': 0.00e+00, 'lse': 3.96e-08, 'dqkv': 4.76e-07},
+    'L15-N2H2D48-res': {'o': 2.47e-07, 'lse': 8.84e-08, 'dqkv': 2.81e-07},
+    'L16-N2H2D48-res': {'o': 2.95e-07, 'lse': 8.08e-08, 'dqkv': 2.95e-07},
+    'L17-N2H2D48-res': {'o': 3.77e-07, 'lse': 9.07e-08, 'dqkv': 3.76e-07},
+    'L127-N2H2D48-res': {'o': 6.01e-07, 'lse': 8.08e-08, 'dqkv': 7.74e-07},
+    'L128-N2H2D48-res': {'o': 6.14e-07, 'lse': 8.41e-08, 'dqkv': 6.77e-07},
+    'L129-N2H2D48-res': {'o': 5.62e-07, 'lse': 8.09e-08, 'dqkv': 3.62e-07},
+    'L324-N2H2D48-res': {'o': 5.18e-07, 'lse': 6.97e-08, 'dqkv': 6.37e-07},
+    'L383-N2H2D48-res': {'o': 7.19e-07, 'lse': 7.03e-08, 'dqkv': 9.93e-07},
+    'L384-N2H2D48-res': {'o': 8.41e-07, 'lse': 7.93e-08, 'dqkv': 9.16e-07},
+    'L279-N1H3D16-res': {'o': 5.61e-07, 'lse': 6.85e-08, 'dqkv': 5.65e-07},
+    'L279-N1H3D32-res': {'o': 7.63e-07, 'lse': 7.08e-08, 'dqkv': 5.88e-07},
+    'L279-N1H3D64-res': {'o': 6.55e-07, 'lse': 7.72e-08, 'dqkv': 1.07e-06},
+    'L288-N2H2D64-res': {'o': 6.91e-07, 'lse': 8.17e-08, 'dqkv': 1.02e-06},
+    'L324-N2H4D48-p0.1-res': {'o': 7.26e-07, 'lse': 7.28e-08, 'dqkv': 1.12e-06},
+    'L324-N2H4D48-p0.5-res': {'o': 8.61e-07, 'lse': 7.28e-08, 'dqkv': 7.19e-07},
 }
 BARS = {k: {n: 4 * e for n, e in v.items()} for k, v in MEASURED.items()}
 
@@ -245,10 +274,15 @@ def reference(c):
     return _reference_cached(case_id(c))
 
 
+def float32_block(c):
+    """key rows per block of the float32 evaluation: BK on the streamed path, the whole head (one block) on the resident one"""
+    return c['L'] if c['res'] else BK
+
+
 def float32_errors(c):
-    """{name: e} of blocked_float32 with BK on the case's inputs"""
+    """{name: e} of blocked_float32 on the case's inputs, with the block of the case's path"""
     inp, ref = reference(c)
-    sub = blocked_float32(inp['qkv'], c['H'], BK, inp['dout'], inp.get('cpu_keep'))
+    sub = blocked_float32(inp['qkv'], c['H'], float32_block(c), inp['dout'], inp.get('cpu_keep'))
     return {n: error_stats(sub[n], ref[n], scale_of(ref[n]))['max_e'] for n in NAMES}
 
 

@@ -42,6 +42,19 @@ def test_case_list():
     assert -(-R.BIG_CASE['L'] // bk) == 41
 
 
+def test_resident_case_list():
+    from muvo_amd import ops
+    cases = R.RESIDENT_CASES + R.RESIDENT_DROPOUT_CASES
+    assert all(R.case_id(c).endswith('-res') and R.float32_block(c) == c['L'] for c in cases)
+    assert not any(c['res'] for c in R.STREAM_CASES) and {R.float32_block(c) for c in R.STREAM_CASES} == {R.BK}
+    assert all(ops.lib().muvo_attention_supported(c['L'], c['DH']) == 1 for c in cases)
+    wg, top = R.RES_WG, R.RES_MAXL
+    assert [c['L'] for c in R.RESIDENT_CASES[:10]] == [1, 15, 16, 17, wg - 1, wg, wg + 1, 324, top - 1, top]
+    assert [(c['L'], c['H'], c['DH']) for c in R.RESIDENT_CASES[10:]] == [(279, 3, 16), (279, 3, 32), (279, 3, 64), (R.RES_MAXL_D64, 2, 64)]
+    assert [(c['L'], c['p']) for c in R.RESIDENT_DROPOUT_CASES] == [(324, 0.1), (324, 0.5)]
+    assert ops.lib().muvo_attention_supported(R.RES_MAXL_D64 + 1, 64) == 0 and ops.lib().muvo_attention_supported(top + 1, 48) == 0
+
+
 @pytest.mark.parametrize('c', R.ALL_CASES, ids=R.case_id)
 def test_measured_table_is_the_float32_evaluation(c):
     e = R.float32_errors(c)

@@ -1,8 +1,10 @@
-"""GPU: the streamed attention kernels (muvo_amd/csrc/attention.hip: attn_stream_*) through ops.StreamAttentionFn, against the
-float64 reference of tests/attention_reference.py under its bar (4 x the float32 CPU evaluation of the same recurrence on the same
-inputs; tests/test_attention_reference.py shows that bar rejects planted errors), on lengths at every edge of the block sizes
-the library reports, on spiked inputs that force the rescale, with dropout against the unfused path and against float64 with the
-library's own mask, for reproducibility, for memory (nothing L x L), and inside the transformer encoder."""
+"""GPU: the fused attention kernels (muvo_amd/csrc/attention.hip), streamed through ops.StreamAttentionFn and resident (K / V of a
+head whole in LDS, L <= 384) through ops.FlashAttentionFn, against the float64 reference of tests/attention_reference.py under its
+bar (4 x the float32 CPU evaluation of the same recurrence on the same inputs; tests/test_attention_reference.py shows that bar
+rejects planted errors).  Streamed: lengths at every edge of the block sizes the library reports, spiked inputs that force the
+rescale, dropout against the unfused path and against float64 with the library's own mask, reproducibility, memory (nothing
+L x L), and inside the transformer encoder.  Resident: one key, the edges of a key tile, of a workgroup's 128 queries and of the
+register tiles, the model's L, every head size, the largest L of DH = 64, and dropout the same two ways."""
 import ctypes as C
 
 import pytest
@@ -28,16 +30,26 @@ def _run(fn, qkv, dout, heads, p=0.0, seed=0):
     return o.detach(), x.grad
 
 
-def _stream(c, inp, dev, p=0.0, seed=0):
-    """{o, lse, dqkv} of the streamed kernels on a case's inputs (lse from the library call itself)"""
+def _kernels(path, c, inp, dev, p=0.0, seed=0):
+    """{o, lse, dqkv} of one path's kernels ('stream' | 'fused') on a case's inputs (lse from the library call itself)"""
     from muvo_amd import ops
+    fwd = {'stream': ops.lib().muvo_attention_stream_fwd, 'fused': ops.lib().muvo_attention_fwd}[path]
     qkv, dout = inp['qkv'].to(dev), inp['dout'].to(dev)
-    o, dqkv = _run(ops.StreamAttentionFn.apply, qkv, dout, c['H'], p, seed)
+    o, dqkv = _run(ops._ATTENTION_FNS[path].apply, qkv, dout, c['H'], p, seed)
     o2, lse = torch.empty_like(o), torch.empty(c['N'] * c['H'], c['L'], device=dev)
-    ops._ck(ops.lib().muvo_attention_stream_fwd(ops._f(qkv), ops._f(o2), ops._f(lse), c['L'], c['N'], c['H'], c['DH'], ops._fl(p),
-                                                C.c_uint64(seed), ops._st()))
+    ops._ck(fwd(ops._f(qkv), ops._f(o2), ops._f(lse), c['L'], c['N'], c['H'], c['DH'], ops._fl(p), C.c_uint64(seed), ops._st()))
     assert torch.equal(o, o2)
     return {'o': o, 'lse': lse, 'dqkv': dqkv}
+
+
+def _stream(c, inp, dev, p=0.0, seed=0):
+    return _kernels('stream', c, inp, dev, p, seed)
+
+
+def _resident(c, inp, dev, p=0.0, seed=0):
+    from muvo_amd import ops
+    assert c['res'] and ops.lib().muvo_attention_supported(c['L'], c['DH']) == 1
+    return _kernels('fused', c, inp, dev, p, seed)
 
 
 def _check(c, got, ref, tag=''):
@@ -185,3 +197,36 @@ def test_encoder_stream_vs_unfused(dev, monkeypatch):
     _close(dxs, dxu, rtol=1e-3, name='encoder dx')
     for k in gs:
         _close(gs[k], gu[k], rtol=1e-3, atol=1e-4, name=f'encoder grad {k}')
+
+
+# ------------------------------------------------------------------------------------------------ resident kernels (L <= 384)
+def test_resident_range(dev):
+    from muvo_amd import ops
+    L = ops.lib()
+    assert L.muvo_attention_supported(R.RES_MAXL_D64, 64) == 1 and L.muvo_attention_supported(R.RES_MAXL_D64 + 1, 64) == 0
+    assert L.muvo_attention_supported(R.RES_MAXL, 48) == 1 and L.muvo_attention_supported(R.RES_MAXL + 1, 48) == 0
+
+
+@pytest.mark.parametrize('c', R.RESIDENT_CASES, ids=R.case_id)
+def test_resident_float64_parity(dev, c):
+    inp, ref = R.reference(c)
+    _check(c, _resident(c, inp, dev), ref)
+
+
+@pytest.mark.parametrize('c', R.RESIDENT_DROPOUT_CASES, ids=R.case_id)
+def test_resident_dropout(dev, c):
+    """test_dropout on the resident path"""
+    from muvo_amd import ops
+    p, seed = c['p'], R.DROPOUT_SEEDS[c['p']]
+    inp = R.inputs(c)
+    qkv, dout = inp['qkv'].to(dev), inp['dout'].to(dev)
+    got = _resident(c, inp, dev, p, seed)
+    ou, du = _run(ops.AttentionFn.apply, qkv, dout, c['H'], p, seed)
+    _close(got['o'], ou, rtol=2e-5, name=f'resident vs unfused fwd p={p}')
+    _close(got['dqkv'], du, rtol=1e-4, name=f'resident vs unfused dqkv p={p}')
+    keep = ops.dropout(torch.ones(c['N'], c['H'], c['L'], c['L'], device=dev), p, seed).cpu()
+    assert abs(float((keep > 0).float().mean()) - (1 - p)) < 5e-3
+    ref = R.reference64(inp['qkv'], c['H'], inp['dout'], keep)
+    _check(c, got, ref, ' library mask')
+    o0, _ = _run(ops.FlashAttentionFn.apply, qkv, dout, c['H'])
+    assert not torch.allclose(got['o'], o0)                 # the mask does something
