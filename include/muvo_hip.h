@@ -1071,6 +1071,50 @@ int muvo_visibility_mark(const uint8_t* grid, const uint64_t* bricks, int F, int
                          int64_t words, void* stream);
 int muvo_visibility_apply(const uint8_t* label, const uint64_t* seen, int F, int X, int Y, int Z, uint8_t* out, uint64_t* counts, void* stream);
 
+/* ---- calibration and uncertainty of a sample ensemble (calibration.hip; an extension) ----------------------
+ * OUR DEFINITION (the reference scores every imagined sample's argmax on its own and has none of this);
+ * tests/calibration_reference.py restates it in float64.
+ * Inputs: logits = a HOST array of K device pointers, K in 1..8, each a contiguous (F, C, X, Y, Z) fp32 tensor (one sample each;
+ *   K = 1: a reconstruction or a single sample), C in 2..16; label (F, X, Y, Z) uint8, 255 = ignore; F * X * Y * Z <= 2^40.  The
+ *   entry only needs columns of Z contiguous cells: a 2-D head (F, C, H, W) goes in as X = H, Y = W, Z = 1.
+ * Per voxel, in fp32, classes in ascending order (the library is built with -ffp-contract=off):
+ *   p_k   = softmax(z_k): e_c = exp(z_c - max_c z_c), p_c = e_c * (1 / sum_c e_c); a logit of -inf is an ordinary input, p_c = 0
+ *   pbar  = (sum_k p_k) / K
+ *   yhat  = the first maximum of pbar over the classes (strict >: the lowest index wins a tie, the rule of muvo_voxel_rows_logits);
+ *           at K = 1 the first maximum of the logits themselves - exp is monotone, so that class is a maximum of pbar too, and the
+ *           prediction is the one of muvo_ssc_counts even where rounding made two probabilities equal
+ *   conf  = pbar[yhat];  correct = (yhat == y);  bin = min(B - 1, floor(conf * B))
+ *   A decision fp32 rounding could turn - the two largest pbar closer than 1e-5, or conf * B within 1e-5 B of an integer - is taken
+ *   again with pbar in fp64 (a rare branch that re-reads the voxel's logits): yhat, correct and bin, hence every integer output, equal
+ *   a float64 evaluation of these formulae unless that evaluation itself is within its own rounding of a tie.  Values stay fp32.
+ *   H     = -sum_c pbar_c ln pbar_c (0 ln 0 = 0);  Ebar = (sum_k H(p_k)) / K;  MI = max(0, H - Ebar)   (MI is exactly 0 at K = 1)
+ *   brier = sum_c (pbar_c - [y == c])^2;  nll = -ln max(pbar_y, 1e-12)
+ * Which voxels count.  label == 255: counted in `ignored`, nothing else (its logits are not even read unless a map is asked for).
+ *   Otherwise NON-FINITE - in any sample the maximum logit is +inf or -inf (every logit -inf: the softmax is undefined) or any logit
+ *   is NaN: counted in `skipped_nonfinite`, nothing else.  Otherwise scored: voxels + ignored + skipped_nonfinite = F X Y Z.
+ *   A scored voxel whose label is >= C goes the way of muvo_ssc_counts: it is never correct, it counts in the completion counts as
+ *   occupied, its prediction gets a false positive and no class gets the false negative; here also [y == c] is 0 for every c
+ *   (brier = sum pbar_c^2) and pbar_y = 0 (nll = -ln 1e-12).
+ * Accumulators: caller-owned, caller-zeroed device buffers that are ADDED TO (two calls into the same buffers add up), all
+ *   integers, all by 64-bit integer atomics - order-free, the same bits on every call and in both modes of muvo_set_deterministic:
+ *   table (B, 3) int64, B in 1..32 equal-width confidence bins, bin = min(B - 1, floor(conf * B)): n, n_correct, FIX(conf)
+ *   counts (4) int64: voxels (scored), ignored, skipped_nonfinite, correct
+ *   ssc (3 + 3 C) uint64: layout and counting rule of muvo_ssc_counts, taken on yhat; at K = 1 and finite logits equal to it
+ *   sums (6) int64: FIX(brier), FIX(nll), FIX(H) over correct voxels, FIX(H) over wrong, FIX(MI) over correct, FIX(MI) over wrong
+ *   FIX(v) = round-to-nearest-even(v * 2^24), an integer: the real sum is word / 2^24.  Rounding a voxel's value to 2^-24 costs at
+ *   most 2^-25 a voxel, below the fp32 error of the value itself.  OVERFLOW: a value is < 2^5 (nll <= 27.7, H and MI <= ln 16,
+ *   brier <= 2, conf <= 1), its FIX < 2^29, so a word cannot overflow before 2^34 scored voxels (1.7e10: 364 calls of 20 frames of
+ *   192 x 192 x 64) even if every voxel had the worst nll; the conf, brier, H and MI words hold 2^38 voxels.
+ * Optional outputs (NULL = not written; written, not added to):
+ *   ens (F, X, Y, Z) uint8: yhat; 255 where the label is 255 or the voxel is non-finite
+ *   top_entropy, top_mi (F, X, Y) uint8: the maximum over z of q(H), q(MI), q(v) = round-to-nearest-even(255 * min(1, v * (1 / ln C)))
+ *   with ln C in fp32, over ALL finite voxels of the column, labelled or ignored (they describe the forecast, not the score); a
+ *   non-finite voxel contributes 0.
+ * One launch, no workspace, no host synchronisation, nothing is copied to the host. */
+int muvo_voxel_calibration(const float* const* logits, int K, const uint8_t* label, int64_t F, int C, int X, int Y, int Z, int B,
+                           int64_t* table, int64_t* counts, uint64_t* ssc, int64_t* sums, uint8_t* ens, uint8_t* top_entropy, uint8_t* top_mi,
+                           void* stream);
+
 #ifdef __cplusplus
 }
 #endif

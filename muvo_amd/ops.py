@@ -115,6 +115,7 @@ EXPORTS = [
     'muvo_voxel_cd_ws_bytes', 'muvo_voxel_cd_counts',
     'muvo_bev_instance_ws_bytes', 'muvo_bev_instance_decode', 'muvo_bev_pq_ws_bytes', 'muvo_bev_pq_counts',
     'muvo_visibility_mark', 'muvo_visibility_apply',
+    'muvo_voxel_calibration',
 ]
 
 
@@ -3259,6 +3260,47 @@ def bev_pq_counts(label, pred, counts, iou_sum, capped=None):
     label, pred = label.contiguous(), pred.contiguous()
     ws = torch.empty(nbytes // 8, device=label.device, dtype=torch.int64)
     _ck(lib().muvo_bev_pq_counts(_p(label), _p(pred), _p(capped), _i64(F), H, W, _p(counts), _p(iou_sum), _p(ws), _i64(nbytes), _st()))
+
+
+# ---- calibration and uncertainty of a sample ensemble (csrc/calibration.hip; include/muvo_hip.h: muvo_voxel_calibration) -----------
+CALIBRATION_MAX_SAMPLES, CALIBRATION_MAX_CLASSES, CALIBRATION_MAX_BINS = 8, 16, 32
+CALIBRATION_FIX = float(1 << 24)          # the unit of the fixed-point words: real sum = word / CALIBRATION_FIX
+
+
+def voxel_calibration(logits_list, label, table, counts, ssc, sums, ens=None, top_entropy=None, top_mi=None):
+    """The K tensors of logits_list, (F, C, X, Y, Z) float32 each, against label (F, X, Y, Z) uint8 (255 = ignore): table (B, 3) int64,
+    counts (4,) int64, ssc (3 + 3 C,) int64 and sums (6,) int64 on the device are added to; ens (F, X, Y, Z) uint8 and top_entropy,
+    top_mi (F, X, Y) uint8 are written when given (include/muvo_hip.h: muvo_voxel_calibration).  Nothing is read back."""
+    logits_list = list(logits_list)
+    K = len(logits_list)
+    if not 1 <= K <= CALIBRATION_MAX_SAMPLES:
+        raise ValueError(f'voxel_calibration: {K} samples (1..{CALIBRATION_MAX_SAMPLES})')
+    first = logits_list[0]
+    assert first.dim() == 5 and first.dtype == torch.float32, 'voxel_calibration: logits (F, C, X, Y, Z) float32'
+    F, Cn, X, Y, Z = (int(v) for v in first.shape)
+    dev = first.device
+    for t in logits_list:
+        assert t.dtype == torch.float32 and t.shape == first.shape and t.device == dev, 'voxel_calibration: samples of one shape, dtype and device'
+    assert label.dtype == torch.uint8 and tuple(label.shape) == (F, X, Y, Z) and label.device == dev, 'voxel_calibration: label (F, X, Y, Z) uint8'
+    if not 2 <= Cn <= CALIBRATION_MAX_CLASSES:
+        raise ValueError(f'voxel_calibration: {Cn} classes (2..{CALIBRATION_MAX_CLASSES})')
+    assert table.dim() == 2 and table.shape[1] == 3, 'voxel_calibration: table (B, 3) int64'
+    B = int(table.shape[0])
+    if not 1 <= B <= CALIBRATION_MAX_BINS:
+        raise ValueError(f'voxel_calibration: {B} bins (1..{CALIBRATION_MAX_BINS})')
+    if F < 1 or min(X, Y, Z) < 1 or F * X * Y * Z > 1 << 40:
+        raise ValueError(f'voxel_calibration: {F} frames of {X} x {Y} x {Z} (at least one voxel, at most 2^40)')
+    for t, shape, what in ((table, (B, 3), 'table (B, 3)'), (counts, (4,), 'counts (4,)'), (ssc, (3 + 3 * Cn,), 'ssc (3 + 3 C,)'), (sums, (6,), 'sums (6,)')):
+        assert t.dtype == torch.int64 and tuple(t.shape) == shape and t.is_contiguous() and t.device == dev, f'voxel_calibration: {what} int64'
+    for t, shape, what in ((ens, (F, X, Y, Z), 'ens (F, X, Y, Z)'), (top_entropy, (F, X, Y), 'top_entropy (F, X, Y)'), (top_mi, (F, X, Y), 'top_mi (F, X, Y)')):
+        assert t is None or (t.dtype == torch.uint8 and tuple(t.shape) == shape and t.is_contiguous() and t.device == dev), f'voxel_calibration: {what} uint8'
+    logits_list = [t.contiguous() for t in logits_list]
+    label = label.contiguous()
+    ptrs = (C.c_void_p * K)(*[t.data_ptr() for t in logits_list])
+    for t in logits_list:
+        _f(t)
+    _ck(lib().muvo_voxel_calibration(ptrs, K, _p(label), _i64(F), Cn, X, Y, Z, B, _p(table), _p(counts), _p(ssc), _p(sums), _p(ens), _p(top_entropy),
+                                     _p(top_mi), _st()))
 
 
 # ================================================================================================ ICP between lidar frames

@@ -18,7 +18,9 @@ camera head's nine per-class scores carry a name; the matrix holds what the othe
 taken on the device (csrc/metrics.hip: argmax + confusion matrix in one kernel per head and batch) and read once at the end.
 With that head on, `--bev-pq` also writes `bev_pq.json`, the panoptic quality of the instances decoded on the device from the
 head's centre / offset outputs, and `--panels N --inst` the `_inst` panels (muvo_amd/bev_instances.py); `metrics.json` is the same
-with and without them.
+with and without them.  With the voxel head on, `--voxel-calibration` writes `voxel_calibration.json` - calibration, ensemble IoU and
+uncertainty of that head over all imagined samples jointly - and `--panels N --uncert` the `_uncert` panels (muvo_amd/calibration.py);
+`metrics.json` is again the same with and without them.
 
 `--mode sim` follows the loop of sim_run.py:49-116 (module in train() mode, the transformer's dropout modules off, no_grad;
 per batch `preprocess`, then `model.sim_forward(batch, is_dreaming=False)`) over one loader (default 2, sim_run.py:44) and
@@ -96,6 +98,11 @@ def build_parser():
     parser.add_argument('--inst', action='store_true', help='with --panels: also the BEV instance panel `_inst` (label ids and decoded ids)')
     parser.add_argument('--inst-threshold', type=float, default=0.1, metavar='T', help='--bev-pq / --inst: a centre is a peak above T (default 0.1)')
     parser.add_argument('--inst-max-centres', type=int, default=100, metavar='K', help='--bev-pq / --inst: at most K centres per frame (default 100; 1..254)')
+    parser.add_argument('--voxel-calibration', action='store_true',
+                        help='test: calibration (ECE, reliability, Brier, NLL), ensemble IoU and uncertainty of the voxel head over all imagined samples -> OUT/voxel_calibration.json')
+    parser.add_argument('--calibration-bins', type=int, default=15, metavar='B', help='--voxel-calibration: equal-width confidence bins (default 15; 1..32)')
+    parser.add_argument('--uncert', action='store_true',
+                        help='with --panels: also the uncertainty panel `_uncert` (top views of the predictive entropy and the mutual information)')
     parser.add_argument('--ego-motion', action='store_true',
                         help='test: drift of the ego path implied by the predicted lidar from the one implied by the recorded lidar -> OUT/ego_motion.json')
     parser.add_argument('--ego-threshold', type=float, default=5.0, metavar='M', help='ICP inlier distance in metres of --ego-motion and --traj (default 5, the reference)')
@@ -132,6 +139,12 @@ def parse_args(argv=None):
         raise SystemExit('--inst goes with --panels N')
     if not 1 <= args.inst_max_centres <= 254 or args.inst_threshold != args.inst_threshold:
         raise SystemExit('--inst-max-centres lies in 1..254 and --inst-threshold is a number')
+    if (args.voxel_calibration or args.uncert) and args.mode != 'test':
+        raise SystemExit('--voxel-calibration and --uncert go with --mode test')
+    if args.uncert and not args.panels:
+        raise SystemExit('--uncert goes with --panels N')
+    if not 1 <= args.calibration_bins <= 32:
+        raise SystemExit('--calibration-bins lies in 1..32')
     if args.voxel_size < 1 or args.ray_stride < 1:
         raise SystemExit('--voxel-size and --ray-stride must be positive')
     if args.ego_threshold <= 0 or args.ego_stride < 1 or args.ego_max_iteration < 0:
@@ -244,7 +257,7 @@ def seed_batch(module, seed, loader_idx, i):
 
 def run(cfg, device, out_dir, mode, loaders=None, limit_batches=None, shard_size=500, seed=1234, hook=None, dataset_root=None,
         data=None, module=None, log=print, panels=0, traj=False, ego_motion=None, icp_options=None, flow=False, optical_flow=False,
-        voxel=False, voxel_size=256, ray_iou=None, voxel_cd=None, bev_pq=None, inst=False):
+        voxel=False, voxel_size=256, ray_iou=None, voxel_cd=None, bev_pq=None, inst=False, voxel_calibration=None, uncert=False):
     """Runs one mode and returns what it wrote: {'files': [...], 'batches': {loader: n}, 'metrics': {...}, 'confusion': {...} (test)}.
     hook(i, batch, output, output_imagine): called per batch with the device tensors (test mode: output_imagine is the list
     of imagined samples).  data: a set-up DataModule to take the test loaders from (default: one over dataset_root /
@@ -260,7 +273,9 @@ def run(cfg, device, out_dir, mode, loaders=None, limit_batches=None, shard_size
     out_dir/voxel_cd.json; metrics.json does not change.  bev_pq (test): a dict of decode options (threshold, radius, max_centres,
     thing_classes; empty: the defaults) - muvo_amd.bev_instances.PanopticQualityMetric runs on every batch and writes
     out_dir/bev_pq.json; metrics.json does not change.  inst (test, with panels): also the `_inst` panel - True: decoded with the
-    options of bev_pq (the defaults without it); a dict: with decode options of its own."""
+    options of bev_pq (the defaults without it); a dict: with decode options of its own.  voxel_calibration (test): a dict of options
+    (bins; empty: 15) - muvo_amd.calibration.VoxelCalibrationMetric runs on every batch and writes out_dir/voxel_calibration.json;
+    metrics.json does not change.  uncert (test, with panels): also the `_uncert` panel."""
     refuse_multi_process()
     if mode not in ('test', 'sim'):
         raise ValueError(f'mode {mode!r}: test or sim')
@@ -287,9 +302,11 @@ def run(cfg, device, out_dir, mode, loaders=None, limit_batches=None, shard_size
             raise ValueError('the voxel Chamfer distance belongs to mode test')
         if bev_pq is not None or isinstance(inst, dict) or inst:
             raise ValueError('the BEV panoptic quality and the `_inst` panel belong to mode test')
+        if voxel_calibration is not None or uncert:
+            raise ValueError('the voxel calibration and the `_uncert` panel belong to mode test')
         return _run_sim(cfg, module, chosen, out_dir, limit_batches, shard_size, seed, hook, log)
     return _run_test(cfg, module, chosen, out_dir, limit_batches, shard_size, seed, hook, log, panels, traj, ego_motion, icp_options, flow, optical_flow,
-                     voxel, voxel_size, ray_iou, voxel_cd, bev_pq, inst)
+                     voxel, voxel_size, ray_iou, voxel_cd, bev_pq, inst, voxel_calibration, uncert)
 
 
 def _batches(loader, limit):
@@ -300,7 +317,7 @@ def _batches(loader, limit):
 
 
 def _run_test(cfg, module, loaders, out_dir, limit_batches, shard_size, seed, hook, log, panels=0, traj=False, ego_motion=None, icp_options=None,
-              flow=False, optical_flow=False, voxel=False, voxel_size=256, ray_iou=None, voxel_cd=None, bev_pq=None, inst=False):
+              flow=False, optical_flow=False, voxel=False, voxel_size=256, ray_iou=None, voxel_cd=None, bev_pq=None, inst=False, voxel_calibration=None, uncert=False):
     counts = {}
     writer, was_writer, was_traj, was_opt = None, module.panel_writer, module.traj_panels, module.traj_options
     ego, flow_metric, was_flow = None, None, module.flow_panels
@@ -311,6 +328,12 @@ def _run_test(cfg, module, loaders, out_dir, limit_batches, shard_size, seed, ho
         raise ValueError('the voxel Chamfer distance needs the voxel head (VOXEL_SEG.ENABLED)')
     if (bev_pq is not None or isinstance(inst, dict) or inst) and not cfg.SEMANTIC_SEG.ENABLED:
         raise ValueError('the BEV panoptic quality and the `_inst` panel need the bird\'s-eye-view head (SEMANTIC_SEG.ENABLED)')
+    if (voxel_calibration is not None or uncert) and not cfg.VOXEL_SEG.ENABLED:
+        raise ValueError('the voxel calibration and the `_uncert` panel need the voxel head (VOXEL_SEG.ENABLED)')
+    cal_metric, was_uncert = None, getattr(module, 'uncert_panels', False)
+    if voxel_calibration is not None:
+        from muvo_amd.calibration import VoxelCalibrationMetric
+        cal_metric = VoxelCalibrationMetric(cfg, **voxel_calibration)
     inst_on = isinstance(inst, dict) or bool(inst)
     pq_metric, was_inst, was_iopt = None, getattr(module, 'inst_panels', False), getattr(module, 'inst_options', {})
     if bev_pq is not None:
@@ -355,6 +378,8 @@ def _run_test(cfg, module, loaders, out_dir, limit_batches, shard_size, seed, ho
                 cd_metric.start_loader(idx)
             if pq_metric is not None:
                 pq_metric.start_loader(idx)
+            if cal_metric is not None:
+                cal_metric.start_loader(idx)
             for i, batch in _batches(loader, limit_batches):
                 seed_batch(module, seed, idx, i)
                 module.panel_writer = writer if i < panels else None
@@ -363,6 +388,8 @@ def _run_test(cfg, module, loaders, out_dir, limit_batches, shard_size, seed, ho
                 module.voxel_panels = bool(voxel)
                 if inst_on:
                     module.inst_panels = True
+                if uncert:
+                    module.uncert_panels = True
                 output, output_imagines = module.test_step(batch, i, idx)
                 if hook is not None:
                     hook(i, batch, output, output_imagines)
@@ -376,12 +403,16 @@ def _run_test(cfg, module, loaders, out_dir, limit_batches, shard_size, seed, ho
                     cd_metric.update(i, batch, output, output_imagines)
                 if pq_metric is not None:
                     pq_metric.update(i, batch, output, output_imagines)
+                if cal_metric is not None:
+                    cal_metric.update(i, batch, output, output_imagines)
                 counts[idx] += 1
     finally:
         module.panel_writer, module.traj_panels, module.traj_options, module.flow_panels = was_writer, was_traj, was_opt, was_flow
         module.voxel_panels, module.voxel_options = was_voxel, was_vopt
         if inst_on:
             module.inst_panels, module.inst_options = was_inst, was_iopt
+        if uncert:
+            module.uncert_panels = was_uncert
     logged, confusion = {}, {}
     was_fn, module.log_fn = module.log_fn, lambda name, value: logged.__setitem__(name, float(value))
     was_cm, module.on_confusion = module.on_confusion, lambda name, matrix: confusion.__setitem__(name, matrix.tolist())
@@ -421,6 +452,10 @@ def _run_test(cfg, module, loaders, out_dir, limit_batches, shard_size, seed, ho
         files.append(pq_metric.write(out_dir))
         out['bev_pq'] = pq_metric.result()
         log('bev_pq ' + json.dumps(out['bev_pq'], sort_keys=True))
+    if cal_metric is not None:
+        files.append(cal_metric.write(out_dir))
+        out['voxel_calibration'] = cal_metric.result()
+        log('voxel_calibration ' + json.dumps(out['voxel_calibration'], sort_keys=True))
     return out
 
 
@@ -483,7 +518,8 @@ def main(argv=None):
         flow=args.flow, optical_flow=args.optical_flow, voxel=args.voxel, voxel_size=args.voxel_size,
         ray_iou=dict(stride=args.ray_stride) if args.ray_iou else None, voxel_cd={} if args.voxel_cd else None,
         bev_pq=dict(threshold=args.inst_threshold, max_centres=args.inst_max_centres) if args.bev_pq else None,
-        inst=dict(threshold=args.inst_threshold, max_centres=args.inst_max_centres) if args.inst else False)
+        inst=dict(threshold=args.inst_threshold, max_centres=args.inst_max_centres) if args.inst else False,
+        voxel_calibration=dict(bins=args.calibration_bins) if args.voxel_calibration else None, uncert=args.uncert)
 
 
 if __name__ == '__main__':

@@ -54,7 +54,7 @@ def load_checkpoint(module, optimizer, scheduler, path):
 
 def fit(cfg, device, steps=None, resume=None, log=None, seed=1234, batch_fn=None, setup=None, dataset_root=None, input_stream=False,
         panel_dir=None, traj=False, traj_options=None, validate=False, limit_val_batches=3, sanity_val_steps=2, val_batch_fn=None, metrics_log=None,
-        flow=False, voxel=False, voxel_size=256, inst=False):
+        flow=False, voxel=False, voxel_size=256, inst=False, uncert=False):
     """The training loop; returns (module, list of per-step loss dicts as floats).  batch_fn(micro_index) / setup(module):
     hooks for tests (own batches, e.g. switching dropout off).  dataset_root (default: cfg.DATASET.DATAROOT): batches from the
     recordings below it instead of synthetic ones; input_stream=True prepares them on a side stream instead of the main one.
@@ -65,6 +65,8 @@ def fit(cfg, device, steps=None, resume=None, log=None, seed=1234, batch_fn=None
     flow: also the `_flow` panel (muvo_amd/flow.py: dense optical flow between consecutive camera frames, on the device).
     voxel: also the `_voxel` panel (muvo_amd/voxel_view.py: the voxel grids ray-cast in 3-D on the device), tiles of voxel_size pixels.
     inst: also the `_inst` panel (muvo_amd/bev_instances.py: the instances decoded from the BEV centre / offset heads, on the device).
+    uncert: also the `_uncert` panel (muvo_amd/calibration.py: top views of the voxel head's predictive entropy and mutual information);
+    it needs the voxel head (VOXEL_SEG.ENABLED), a ValueError otherwise.
 
     validate=True (train.py:104-110 under Lightning): before the first step a sanity pass of `sanity_val_steps` batches per
     validation loader whose results are dropped (not in a resumed run); after every optimizer step that is a multiple of
@@ -77,6 +79,8 @@ def fit(cfg, device, steps=None, resume=None, log=None, seed=1234, batch_fn=None
     record and {"step", "split": "val", ...} for every pass."""
     import torch.distributed as dist
     rank = dist.get_rank() if dist.is_initialized() else 0
+    if uncert and not cfg.VOXEL_SEG.ENABLED:
+        raise ValueError('the `_uncert` panel needs the voxel head (VOXEL_SEG.ENABLED)')
     torch.manual_seed(seed)
     module = WorldModelTrainer(cfg.convert_to_dict(), device=device)
     module.train()
@@ -89,6 +93,7 @@ def fit(cfg, device, steps=None, resume=None, log=None, seed=1234, batch_fn=None
         module.voxel_panels = bool(voxel)
         module.voxel_options = dict(size=int(voxel_size))
         module.inst_panels = bool(inst)
+        module.uncert_panels = bool(uncert)
     if setup is not None:
         setup(module)
     opts, scheds = module.configure_optimizers()
@@ -181,6 +186,7 @@ def build_parser():
     parser.add_argument('--flow', action='store_true', help='with --panel-dir: also the optical-flow panel `_flow` (dense Farneback flow between camera frames)')
     parser.add_argument('--voxel', action='store_true', help='with --panel-dir: also the 3-D voxel panel `_voxel` (the grids ray-cast on the device)')
     parser.add_argument('--inst', action='store_true', help='with --panel-dir: also the BEV instance panel `_inst` (label ids and the ids decoded from the centre / offset heads)')
+    parser.add_argument('--uncert', action='store_true', help='with --panel-dir: also the uncertainty panel `_uncert` (top views of the voxel head\'s predictive entropy and mutual information)')
     parser.add_argument('--voxel-size', type=int, default=256, metavar='R', help='--voxel: pixels a side of one tile (default 256)')
     parser.add_argument('--traj-stride', type=int, default=4, metavar='K', help='--traj: every K-th source point is an ICP query (default 4; 1 = exact)')
     parser.add_argument('--traj-max-iteration', type=int, default=200, metavar='N', help='--traj: ICP iteration cap (default 200; the reference: 2000)')
@@ -205,7 +211,7 @@ def main(argv=None):
     fit(cfg, device, resume=args.resume or None, dataset_root=args.dataset_root or None, panel_dir=args.panel_dir or None, traj=args.traj,
         traj_options=dict(source_stride=args.traj_stride, max_iteration=args.traj_max_iteration),
         validate=args.validate, limit_val_batches=args.limit_val_batches, sanity_val_steps=args.sanity_val_steps,
-        metrics_log=args.metrics_log or None, flow=args.flow, voxel=args.voxel, voxel_size=args.voxel_size, inst=args.inst)
+        metrics_log=args.metrics_log or None, flow=args.flow, voxel=args.voxel, voxel_size=args.voxel_size, inst=args.inst, uncert=args.uncert)
     if world > 1:
         dist.destroy_process_group()
 

@@ -143,6 +143,7 @@ class WorldModelTrainer(_Base):
         self.voxel_options = {}        # size of that panel's tiles (default 256)
         self.inst_panels = False       # with a writer and SEMANTIC_SEG: also `_inst` (muvo_amd/bev_instances.py, decoded BEV instances)
         self.inst_options = {}         # decode options of that panel (threshold, radius, max_centres, thing_classes)
+        self.uncert_panels = False     # with a writer and VOXEL_SEG: also `_uncert` (muvo_amd/calibration.py, entropy and mutual information)
         # evaluation metrics per validation / test dataloader (trainer.py:51-55,100-129,191-197); created on first use
         # because they hold device accumulators
         self.metrics_vals = [{}, {}, {}]
@@ -605,6 +606,10 @@ class WorldModelTrainer(_Base):
             with torch.no_grad():
                 writer.add_images(f'{name}_inst', inst_panel(self.cfg, batch, output, output_imagines, **getattr(self, 'inst_options', {})),
                                   global_step=self._step_now())
+        if getattr(self, 'uncert_panels', False) and self.cfg.VOXEL_SEG.ENABLED:
+            from muvo_amd.calibration import uncert_panel
+            with torch.no_grad():
+                writer.add_images(f'{name}_uncert', uncert_panel(self.cfg, batch, output, output_imagines), global_step=self._step_now())
         return panels
 
     if pl is None:
