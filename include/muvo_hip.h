@@ -1115,6 +1115,45 @@ int muvo_voxel_calibration(const float* const* logits, int K, const uint8_t* lab
                            int64_t* table, int64_t* counts, uint64_t* ssc, int64_t* sums, uint8_t* ens, uint8_t* top_entropy, uint8_t* top_mi,
                            void* stream);
 
+/* ---- voxel labels filled from neighbouring frames (voxel_aggregate.hip; an extension) -----------------------
+ * OUR DEFINITION (the reference has neither the visibility mask nor this); tests/voxel_aggregate_reference.py restates it in
+ * numpy float64 and muvo_voxel_aggregate equals that restatement byte for byte.
+ * Frames: F = B * S, frame f = i S + t is time t of sequence i.  State of cell c of frame f (the masked label of
+ *   muvo_visibility_apply): S(f, c) = the class v >= 1 if the cell is occupied (its occupancy bit is set; v = grid byte), 0 if it is
+ *   free and SEEN, UNK if it is free and not SEEN.
+ * Poses: link t (1 <= t < S) of sequence i is row i (S - 1) + t - 1 of T (B (S - 1), 4, 4) fp64, the rigid motion with
+ *   p_{t-1} ~ T_t p_t in RANGE-VIEW coordinates r = the x, y, z planes of range_view_label_1 times LIDAR_RE.SCALE (what
+ *   muvo_icp_* returns for the pair t -> t - 1): metres in the ego frame, x forward, y mirrored as convert_coor_lidar leaves it,
+ *   z up, origin at the ego vehicle's reference point (the lidar's offset is already added: input_dev.h range_point stores
+ *   raw + POINTS.LIDAR_POSITION).  A link is VALID iff its status is none of MUVO_ICP_FEW_INLIERS / _EMPTY / _BAD_FRAME, its
+ *   fitness >= min_fitness (a NaN fitness is invalid) and the 12 entries of its top three rows are finite.  fitness and status
+ *   (fp64, int64: the tensors of the ICP result) may both be NULL: then only finiteness decides.
+ * Frame map: a point r lies in grid coordinates g_a = map[a] r_a + map[3 + a] (a = x, y, z; cell j = floor(g)).  For the labels of
+ *   scale k in {1, 2, 4}: map = (1 / (VOXEL.RESOLUTION k)) for all three axes - the grid axes ARE the ego axes, no sign flips - and
+ *   (VOXEL.EV_POSITION) / k: voxelize.hip bins the ego-frame point e into cell (e + off) / res with off = VOXEL.EV_POSITION res,
+ *   and voxel_view.lidar_rays puts the lidar at EV_POSITION + (px, -py, pz) / res, the ego-frame position of raw point 0.
+ * Chain (muvo_voxel_pose_chain): M(t' <- t) for t' = t - d: M_d = T_{t-d+1} M_{d-1}; for t' = t + d: M_d = inv(T_{t+d}) M_{d-1},
+ *   M_0 = I, inv([R, tau]) = [R^T, -R^T tau] (the rigid inverse; -R^T tau as -((R_0a tau_0 + R_1a tau_1) + R_2a tau_2)), products
+ *   as ((a_0 b_0 + a_1 b_1) + a_2 b_2) [+ tau].  The pair is USABLE iff t' is in [0, S) and every link between t and t' is valid.
+ *   Conjugated into cells: R'_ab = (map[a] R_ab) / map[b], tau'_a = (map[a] tau_a + map[3+a]) - ((R'_a0 o_0 + R'_a1 o_1) + R'_a2 o_2)
+ *   with o = map[3..5].  Slot 2 (d - 1) holds t' = t - d, slot 2 (d - 1) + 1 holds t' = t + d, d = 1 .. window: the walk order.
+ *   mats (F, 2 window, 12) fp64 row-major 3 x 4, usable (F, 2 window) uint8; a slot that is not usable holds zeros.  All fp64, one
+ *   workgroup, nothing read back.  window in 1..64, S in 1..65535, map[0..2] non-zero and finite.
+ * Fill (muvo_voxel_aggregate): A(f, c) = S(f, c) where that is not UNK - own observations are never overridden and come out as
+ *   muvo_visibility_apply writes them.  Otherwise the slots are walked in order (nearest in time first, past before future); a
+ *   slot that is not usable is skipped; q = M (c + 1/2) in fp64, every row ((m0 cx + m1 cy) + m2 cz) + m3 in that order without
+ *   contraction; j = floor(q) per axis; if j is inside the grid (a NaN is outside) and S(f', j) != UNK for the slot's frame
+ *   f' = f -+ d then A = S(f', j) and the walk stops.  No value at the end: A = 255.
+ *   grid (F, X, Y, Z) uint8, bricks / seen: the words of muvo_raycast_bricks_grid / muvo_visibility_mark for it; out may not alias
+ *   grid.  counts (3,) int64 on the device, ADDED TO by integer atomics (one per workgroup and counter): [0] cells filled
+ *   occupied, [1] cells filled free, [2] cells still unknown; [0] + [1] + [2] = the unknown count of muvo_visibility_apply.
+ *   A pure gather: the same bytes on every call and in both modes of muvo_set_deterministic.  F a multiple of S, sizes as
+ *   muvo_visibility_apply. */
+int muvo_voxel_pose_chain(const double* T, const double* fitness, const int64_t* status, int B, int S, double min_fitness, int window,
+                          const double* map, double* mats, uint8_t* usable, void* stream);
+int muvo_voxel_aggregate(const uint8_t* grid, const uint64_t* bricks, const uint64_t* seen, int F, int S, int X, int Y, int Z, int window,
+                         const double* mats, const uint8_t* usable, uint8_t* out, int64_t* counts, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -46,6 +46,16 @@ TOLERATED_EXTRA_KEYS = ('CML_DATASET_VERSION', 'MODEL.TRANSFORMER_TRANSITION', '
 #   Lovasz) and the SSC metrics ignore; evaluation then also logs `{prefix}_Voxel_Unknown_Share`.  LIDAR_STRIDE (an integer >= 1;
 #   absent = 1) takes every STRIDE-th azimuth of the range view, CAMERA_STRIDE (an integer >= 1; absent = 2) every STRIDE-th
 #   pixel of the full camera frame in both directions.  Needs VOXEL_SEG.ENABLED, refuses VOXEL_SEG.USE_TOP_K.
+#   VOXEL_SEG.AGGREGATE.{ENABLED,WINDOW,MIN_FITNESS,ICP_ITERATIONS,ICP_STRIDE} - fills the cells the visibility mask calls unknown
+#   from the neighbouring frames of the same sequence (the reference has none).  ENABLED (bool; absent = off: no launch, no new
+#   batch key, no new metric name) makes PreProcess write into `voxel_visible_label_{1,2,4}` the aggregated labels: a cell the
+#   frame observed itself stays, every other cell takes what the nearest frame in time (past before future, at most WINDOW frames
+#   away - an integer >= 1, absent = 4, a definition and no measured optimum) saw at the place the ego motion carries it to, 255 if
+#   none did; evaluation then also logs `{prefix}_Voxel_Filled_Share` and `{prefix}_Voxel_Unknown_Share_Aggregated`.  The ego
+#   motion is `batch['voxel_ego_poses']` (b, s - 1, 4, 4) when given, else ICP between consecutive label range views with
+#   ICP_ITERATIONS (an integer >= 1; absent = 30) fits on every ICP_STRIDE-th point (an integer >= 1; absent = 4); a link whose
+#   fitness is below MIN_FITNESS (a number in [0, 1]; absent = 0.3) or whose registration failed carries nothing
+#   (DESIGN.md section 18).  Needs VOXEL_SEG.VISIBILITY.ENABLED, hence VOXEL_SEG.ENABLED and no VOXEL_SEG.USE_TOP_K.
 EXTENSION_KEYS = ('MODEL.CONSTANT_SIZE', 'MODEL.CONSTANT_SIZE.RGB', 'MODEL.CONSTANT_SIZE.LIDAR', 'MODEL.CONSTANT_SIZE.VOXEL',
                   'LOSSES.LIDAR_CD', 'LOSSES.LIDAR_CD.WEIGHT', 'LOSSES.LIDAR_CD.FACTORS',
                   'LOSSES.VOXEL_LOVASZ', 'LOSSES.VOXEL_LOVASZ.WEIGHT', 'LOSSES.VOXEL_LOVASZ.FACTORS',
@@ -53,7 +63,9 @@ EXTENSION_KEYS = ('MODEL.CONSTANT_SIZE', 'MODEL.CONSTANT_SIZE.RGB', 'MODEL.CONST
                   'LOSSES.VOXEL_RENDER_CLASS', 'LOSSES.VOXEL_RENDER_CLASS.WEIGHT', 'LOSSES.VOXEL_RENDER_CLASS.FACTORS',
                   'LOSSES.VOXEL_RENDER_CLASS.STRIDE',
                   'LOSSES.VOXEL_BOUNDARY', 'LOSSES.VOXEL_BOUNDARY.WEIGHT', 'LOSSES.VOXEL_BOUNDARY.FACTORS', 'LOSSES.VOXEL_BOUNDARY.TRUNCATE_M',
-                  'VOXEL_SEG.VISIBILITY', 'VOXEL_SEG.VISIBILITY.ENABLED', 'VOXEL_SEG.VISIBILITY.LIDAR_STRIDE', 'VOXEL_SEG.VISIBILITY.CAMERA_STRIDE')
+                  'VOXEL_SEG.VISIBILITY', 'VOXEL_SEG.VISIBILITY.ENABLED', 'VOXEL_SEG.VISIBILITY.LIDAR_STRIDE', 'VOXEL_SEG.VISIBILITY.CAMERA_STRIDE',
+                  'VOXEL_SEG.AGGREGATE', 'VOXEL_SEG.AGGREGATE.ENABLED', 'VOXEL_SEG.AGGREGATE.WINDOW', 'VOXEL_SEG.AGGREGATE.MIN_FITNESS',
+                  'VOXEL_SEG.AGGREGATE.ICP_ITERATIONS', 'VOXEL_SEG.AGGREGATE.ICP_STRIDE')
 DEFAULT_CONSTANT_SIZE = {'RGB': (5, 13), 'LIDAR': (1, 16), 'VOXEL': (3, 3, 1)}
 
 
@@ -185,6 +197,37 @@ def voxel_visibility(cfg):
         raise ValueError('VOXEL_SEG.VISIBILITY.ENABLED together with VOXEL_SEG.USE_TOP_K: the top-k cross-entropy runs through a '
                          'different kernel whose treatment of label 255 is not defined')
     return enabled, strides[0], strides[1]
+
+
+DEFAULT_AGGREGATE_WINDOW = 4                       # frames on each side: a definition, not a measured optimum
+DEFAULT_AGGREGATE_MIN_FITNESS = 0.3
+DEFAULT_AGGREGATE_ICP_ITERATIONS = 30
+DEFAULT_AGGREGATE_ICP_STRIDE = 4
+MAX_AGGREGATE_WINDOW = 64                          # the bound of muvo_voxel_pose_chain
+
+
+def voxel_aggregate(cfg):
+    """(enabled, window, min fitness, icp iterations, icp stride) of the fill of unobserved label cells from neighbouring frames:
+    VOXEL_SEG.AGGREGATE.* if given, else (False, 4, 0.3, 30, 4); off = no launch, no new batch key, no new metric name."""
+    node = cfg.VOXEL_SEG.get('AGGREGATE', None) or {}
+    enabled = node.get('ENABLED', False)
+    if not isinstance(enabled, bool):
+        raise ValueError(f'VOXEL_SEG.AGGREGATE.ENABLED must be true or false, got {enabled!r}')
+    window = node.get('WINDOW', DEFAULT_AGGREGATE_WINDOW)
+    if isinstance(window, bool) or not isinstance(window, int) or not 1 <= window <= MAX_AGGREGATE_WINDOW:
+        raise ValueError(f'VOXEL_SEG.AGGREGATE.WINDOW must be an integer in 1..{MAX_AGGREGATE_WINDOW}, got {window!r}')
+    fitness = node.get('MIN_FITNESS', DEFAULT_AGGREGATE_MIN_FITNESS)
+    if isinstance(fitness, bool) or not isinstance(fitness, (int, float)) or not 0 <= fitness <= 1:
+        raise ValueError(f'VOXEL_SEG.AGGREGATE.MIN_FITNESS must be a number in [0, 1], got {fitness!r}')
+    ints = []
+    for key, default in (('ICP_ITERATIONS', DEFAULT_AGGREGATE_ICP_ITERATIONS), ('ICP_STRIDE', DEFAULT_AGGREGATE_ICP_STRIDE)):
+        v = node.get(key, default)
+        if isinstance(v, bool) or not isinstance(v, int) or v < 1:
+            raise ValueError(f'VOXEL_SEG.AGGREGATE.{key} must be an integer >= 1, got {v!r}')
+        ints.append(int(v))
+    if enabled and not voxel_visibility(cfg)[0]:         # its refusals (VOXEL_SEG.ENABLED, USE_TOP_K) are raised by that call
+        raise ValueError('VOXEL_SEG.AGGREGATE.ENABLED needs VOXEL_SEG.VISIBILITY.ENABLED: aggregation fills the cells that mask calls unknown')
+    return enabled, int(window), float(fitness), ints[0], ints[1]
 
 
 class CfgNode(dict):

@@ -35,9 +35,9 @@ __device__ __forceinline__ RcHit rc_march(const RcGrid& g, const float* __restri
   uint64_t word = 0;
   const int bound = g.X + g.Y + g.Z + 3;
   for (int it = 0; it < bound; ++it) {
-    const int b = ((s.cx >> 2) * g.BY + (s.cy >> 2)) * g.BZ + (s.cz >> 2);
+    const int b = vg_brick_word(s.cx, s.cy, s.cz, g.BY, g.BZ);
     if (b != held) { word = g.bricks[b]; held = b; }
-    const bool occupied = (word >> (((s.cx & 3) << 4) | ((s.cy & 3) << 2) | (s.cz & 3))) & 1ull;
+    const bool occupied = (word >> vg_brick_shift(s.cx, s.cy, s.cz)) & 1ull;
     if (occupied) return RcHit{(s.cx * g.Y + s.cy) * g.Z + s.cz, s.t, face};
     face = vg_step(s, g.X, g.Y, g.Z);
     if (face < 0) return miss;

@@ -17,8 +17,6 @@
 #define VS_VOX (VS_THREADS * 4)          // voxels per workgroup and round of the apply pass (4 consecutive per lane)
 #define VS_APPLY_GROUPS 1024             // workgroups of the apply pass, all frames together: 4 per compute unit
 
-__device__ __forceinline__ int vs_shift(int x, int y, int z) { return ((x & 3) << 4) | ((y & 3) << 2) | (z & 3); }
-
 // One OR for the bits a ray collected in brick `b`.  PROBE: read the word first and skip the atomic when it already holds the bits.
 // Bits are only ever set during a call, so a stale read can only show too few of them and costs an atomic that was not needed;
 // the result is the same.  All rays of a table leave one origin: without the probe every one of them sends its first atomic to the
@@ -54,14 +52,14 @@ vis_mark_kernel(const uint64_t* __restrict__ bricks, const float* __restrict__ r
   uint64_t word = 0, bits = 0;
   const int bound = X + Y + Z + 3;
   for (int it = 0; it < bound; ++it) {
-    const int b = ((s.cx >> 2) * BY + (s.cy >> 2)) * BZ + (s.cz >> 2);
+    const int b = vg_brick_word(s.cx, s.cy, s.cz, BY, BZ);
     if (b != held || it == 0) {
       vs_flush<PROBE>(sf, held, bits);
       bits = 0;
       word = bf[b];
       held = b;
     }
-    const uint64_t bit = 1ull << vs_shift(s.cx, s.cy, s.cz);
+    const uint64_t bit = 1ull << vg_brick_shift(s.cx, s.cy, s.cz);
     bits |= bit;
     if (word & bit) break;
     if (vg_step(s, X, Y, Z) < 0) break;
@@ -88,14 +86,14 @@ vis_apply_kernel(const uint8_t* __restrict__ label, const uint64_t* __restrict__
     unsigned sn[4];
     if (vec) {
       const int z = (int)(h0 % Z), y = (int)((h0 / Z) % Y), x = (int)(h0 / ((long)Z * Y));
-      const uint64_t w = sf[((x >> 2) * BY + (y >> 2)) * BZ + (z >> 2)] >> vs_shift(x, y, 0);
+      const uint64_t w = sf[vg_brick_word(x, y, z, BY, BZ)] >> vg_brick_shift(x, y, 0);
       sn[0] = (unsigned)(w & 1ull); sn[1] = (unsigned)((w >> 1) & 1ull); sn[2] = (unsigned)((w >> 2) & 1ull); sn[3] = (unsigned)((w >> 3) & 1ull);
     } else {
 #pragma unroll
       for (int k = 0; k < 4; ++k) {
         const long h = h0 + k < V ? h0 + k : V - 1;
         const int z = (int)(h % Z), y = (int)((h / Z) % Y), x = (int)(h / ((long)Z * Y));
-        sn[k] = (unsigned)((sf[((x >> 2) * BY + (y >> 2)) * BZ + (z >> 2)] >> vs_shift(x, y, z)) & 1ull);
+        sn[k] = (unsigned)((sf[vg_brick_word(x, y, z, BY, BZ)] >> vg_brick_shift(x, y, z)) & 1ull);
       }
     }
     unsigned o[4];

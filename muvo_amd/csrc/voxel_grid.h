@@ -119,6 +119,11 @@ __device__ __forceinline__ int vg_step(VgRay& s, int X, int Y, int Z) {
 #undef VG_SLAB
 #undef VG_NEXT
 
+// ---- the 4 x 4 x 4 bricks (occupancy: raycast.hip; SEEN: visibility.hip; both: voxel_aggregate.hip): one uint64 per brick, word
+// ((x>>2) BY + (y>>2)) BZ + (z>>2) of the frame, bit (x&3) 16 + (y&3) 4 + (z&3)
+__device__ __forceinline__ int vg_brick_word(int x, int y, int z, int BY, int BZ) { return ((x >> 2) * BY + (y >> 2)) * BZ + (z >> 2); }
+__device__ __forceinline__ int vg_brick_shift(int x, int y, int z) { return ((x & 3) << 4) | ((y & 3) << 2) | (z & 3); }
+
 // ---- 4 consecutive voxels per lane: one 16-byte access (4 bytes for labels) when `vec` - aligned bases, V % 4 == 0, so that
 // h0 + 3 < V - guarded scalars otherwise
 __device__ __forceinline__ f32x4 vg_ld4(const float* __restrict__ p, long h0, long V, bool vec) {

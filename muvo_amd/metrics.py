@@ -298,6 +298,29 @@ class VoxelUnknownShare:
         self.counts, self.cells = None, 0
 
 
+class VoxelFilledShare:
+    """`{prefix}_Voxel_Filled_Share` and `{prefix}_Voxel_Unknown_Share_Aggregated` (extension, config.py: VOXEL_SEG.AGGREGATE): of
+    the label cells at scale 1, the share that was unknown to its own frame and filled from a neighbouring one (occupied or free),
+    and the share that stays 255 after that.  add_batch adds the batch's (3,) counts of muvo_voxel_aggregate - whole batches: a
+    frame is filled from frames on both sides of any slice - on the device; get_stat reads them."""
+
+    def __init__(self):
+        self.reset()
+
+    def add_batch(self, counts, cells):
+        self.counts = counts.clone() if self.counts is None else self.counts + counts
+        self.cells += int(cells)
+
+    def get_stat(self):
+        if not self.cells:
+            return 0.0, 0.0
+        occupied, free, unknown = (int(v) for v in self.counts.tolist())
+        return (occupied + free) / self.cells, unknown / self.cells
+
+    def reset(self):
+        self.counts, self.cells = None, 0
+
+
 class EvalMetrics:
     """The metric set of one validation dataloader on base_1d (trainer.py:426-490): ssim, psnr, cd, ssc."""
 

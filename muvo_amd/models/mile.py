@@ -227,7 +227,7 @@ class Mile(nn.Module):
     def _advance_latent(self, batch, action_prev, is_dreaming, frame):
         """encode frame `frame` of the (past-free) batch and advance (last_h, last_sample) one step with `action_prev`"""
         b = batch['image'].shape[0]
-        embedding_t = self.encode({k: v[:, frame:frame + 1].contiguous() if frame is not None else v for k, v in batch.items()})[:, -1]
+        embedding_t = self.encode({k: v[:, frame:frame + 1].contiguous() if frame is not None and v.dim() >= 2 else v for k, v in batch.items()})[:, -1]
         m = self.cfg.MODEL.TRANSITION
         if self.last_h is None:
             h_t = action_prev.new_zeros(b, m.HIDDEN_STATE_DIM)
@@ -258,7 +258,7 @@ class Mile(nn.Module):
         if self.count == 0:
             s = batch['image'].shape[1]
             action_t = batch['action'][:, -2]
-            cut = {k: v[:, s - 1:].contiguous() for k, v in batch.items()}       # remove_past(batch, s)
+            cut = {k: v[:, s - 1:].contiguous() if v.dim() >= 2 else v for k, v in batch.items()}       # remove_past(batch, s)
             self._advance_latent(cut, action_t, is_dreaming, None)
         else:
             self.count -= 1
@@ -275,7 +275,7 @@ class Mile(nn.Module):
         b = batch['image'].shape[0]
         if self.count == 0:
             s = self.receptive_field
-            batch = {k: v[:, s - 1:].contiguous() for k, v in batch.items()}     # remove_past(batch, receptive_field)
+            batch = {k: v[:, s - 1:].contiguous() if v.dim() >= 2 else v for k, v in batch.items()}     # remove_past(batch, receptive_field)
             action_t = ops.cat_last([batch['throttle_brake'][:, 0].contiguous(), batch['steering'][:, 0].contiguous()])
             action_last = torch.zeros_like(action_t) if self.last_action is None else self.last_action
             self._advance_latent(batch, action_last, is_dreaming, 0)

@@ -11,7 +11,7 @@ import torch
 import torch.nn as nn
 
 from muvo_amd import ops
-from muvo_amd.config import voxel_visibility
+from muvo_amd.config import voxel_aggregate, voxel_visibility
 
 
 def bev_out_of_view_mask(fov, image_width, resolution, crop_left, crop_right, bev_w, bev_h, offset_forward, camera_forward):
@@ -49,6 +49,7 @@ class PreProcess(nn.Module):
                              'full-size image while rgb_label_1 is the down-scaled one (the reference fails in its loss, trainer.py:296-302)')
         self._pins = {}
         voxel_visibility(cfg)           # raises here, not in the first step, on a bad VOXEL_SEG.VISIBILITY
+        voxel_aggregate(cfg)            # likewise VOXEL_SEG.AGGREGATE
         self.bev_out_of_view_mask = None
         if cfg.EVAL.MASK_VIEW:        # preprocess.py:20-21
             self.bev_out_of_view_mask = torch.from_numpy(bev_out_of_view_mask(
@@ -78,6 +79,27 @@ class PreProcess(nn.Module):
             ring['ev'][i] = torch.cuda.Event()
             ring['ev'][i].record(torch.cuda.current_stream(out.device))
         return out
+
+    def _ego_links(self, batch, b, s, icp_iterations, icp_stride):
+        """(T (b (s - 1), 4, 4) float64, fitness, status) of VOXEL_SEG.AGGREGATE: p_{t-1} ~ T_t p_t in metres of the ego frame.
+        `batch['voxel_ego_poses']` (b, s - 1, 4, 4) when given - all links valid, fitness and status None -, else ICP between the
+        consecutive frames of range_view_label_1 with a fixed budget, queued without a host read of the device."""
+        cfg = self.cfg
+        dev = batch['voxel'].device
+        if 'voxel_ego_poses' in batch:
+            T = torch.as_tensor(batch['voxel_ego_poses'])
+            if tuple(T.shape) != (b, s - 1, 4, 4):
+                raise ValueError(f"VOXEL_SEG.AGGREGATE: batch['voxel_ego_poses'] must be ({b}, {s - 1}, 4, 4), got {tuple(T.shape)}")
+            return T.to(device=dev, dtype=torch.float64).reshape(b * (s - 1), 4, 4).contiguous(), None, None
+        if s < 2:
+            return torch.zeros((0, 4, 4), dtype=torch.float64, device=dev), None, None
+        if 'range_view_label_1' not in batch:
+            raise ValueError("VOXEL_SEG.AGGREGATE.ENABLED needs the ego motion: batch['voxel_ego_poses'] (b, s - 1, 4, 4), or the lidar range "
+                             "view in the batch (LIDAR_RE.ENABLED and 'range_view_pcd_xyzd') to register consecutive frames")
+        from muvo_amd.odometry import register_consecutive
+        res = register_consecutive(batch['range_view_label_1'], float(cfg.LIDAR_RE.SCALE), queued=True, max_iteration=icp_iterations,
+                                   source_stride=icp_stride)
+        return res.T, res.fitness, res.status
 
     def forward(self, batch):
         cfg = self.cfg
@@ -189,9 +211,18 @@ class PreProcess(nn.Module):
                 batch[f'voxel_label_{f}'] = ops.resize_nearest(batch[f'voxel_label_{f // 2}'], (x // f, y // f, z // f))
             if voxel_visibility(cfg)[0]:     # extension (config.py: VOXEL_SEG.VISIBILITY; absent = off: no table, no launch, no key)
                 from muvo_amd.voxel_view import visibility_table
+                aggregate, window, min_fitness, icp_iterations, icp_stride = voxel_aggregate(cfg)
+                if aggregate:                   # extension (config.py: VOXEL_SEG.AGGREGATE; absent = off: nothing below runs)
+                    links, fitness, status = self._ego_links(batch, b, s, icp_iterations, icp_stride)
                 for f in (1, 2, 4):             # free cells no sensor ray passes become 255; voxel_label_f itself stays
                     label = batch[f'voxel_label_{f}']
                     grid = label.to(torch.uint8).reshape(-1, *label.shape[-3:])
                     rays = visibility_table(cfg, f, tuple(grid.shape[1:]), grid.device)
+                    if aggregate:               # ... unless a neighbouring frame of the sequence saw the place
+                        out, counts = ops.aggregated_labels(grid, rays, s, links, window, ops.voxel_cell_map(cfg, f), fitness, status, min_fitness)
+                        batch[f'voxel_visible_label_{f}'] = out.view(label.shape)
+                        if f == 1:
+                            batch['voxel_aggregate_counts'] = counts
+                        continue
                     batch[f'voxel_visible_label_{f}'] = ops.visible_labels(grid, rays)[0].view(label.shape)
         return batch

@@ -17,14 +17,16 @@ TILE, CANVAS, PAD_VALUE = 196, 192, 50
 LINE_COLOUR, DISC_COLOUR = (20, 150, 20), (150, 20, 20)
 
 
-def register_consecutive(range_view, scale, threshold=5.0, **kw):
+def register_consecutive(range_view, scale, threshold=5.0, queued=False, **kw):
     """range_view (b, s, C, H, W) -> ops.IcpResult over the b (s - 1) pairs (bs, t), t = 1 .. s - 1, in that order: frame t is
-    moved onto frame t - 1 of the same tensor, from the identity."""
+    moved onto frame t - 1 of the same tensor, from the identity.  queued: ops.icp_register_queued - the whole budget
+    `max_iteration` is queued and the host never waits for the device (the training loop's way); the same result."""
     from muvo_amd import ops
     b, s, C, H, W = range_view.shape
     frames = range_view.detach().float().contiguous().view(b * s, C, H * W)
     src = [i * s + t for i in range(b) for t in range(1, s)]
-    return ops.icp_register(frames, frames, src, [f - 1 for f in src], scale, threshold, **kw)
+    register = ops.icp_register_queued if queued else ops.icp_register
+    return register(frames, frames, src, [f - 1 for f in src], scale, threshold, **kw)
 
 
 def chain(T):

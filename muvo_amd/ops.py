@@ -116,6 +116,7 @@ EXPORTS = [
     'muvo_bev_instance_ws_bytes', 'muvo_bev_instance_decode', 'muvo_bev_pq_ws_bytes', 'muvo_bev_pq_counts',
     'muvo_visibility_mark', 'muvo_visibility_apply',
     'muvo_voxel_calibration',
+    'muvo_voxel_pose_chain', 'muvo_voxel_aggregate',
 ]
 
 
@@ -3362,7 +3363,15 @@ def icp_register(src, tgt, src_frames, tgt_frames, scale, threshold, max_iterati
     return _icp_run(src, tgt, src_frames, tgt_frames, scale, threshold, max_iteration, init, source_stride)
 
 
-def _icp_run(src, tgt, src_frames, tgt_frames, scale, threshold, max_iteration=2000, init=None, source_stride=1, on_chunk=None):
+def icp_register_queued(src, tgt, src_frames, tgt_frames, scale, threshold, max_iteration, init=None, source_stride=1):
+    """icp_register for a caller that must not wait for the device: all max_iteration + 1 evaluations are queued and the `done`
+    words are never read (a pair that has stopped costs workgroups that return at once).  The same IcpResult, bit for bit: what a
+    pair computes does not depend on when the host looks.  For small budgets - the cost is max_iteration + 1 launches whatever
+    the clouds are."""
+    return _icp_run(src, tgt, src_frames, tgt_frames, scale, threshold, max_iteration, init, source_stride, read_done=False)
+
+
+def _icp_run(src, tgt, src_frames, tgt_frames, scale, threshold, max_iteration=2000, init=None, source_stride=1, on_chunk=None, read_done=True):
     """icp_register; on_chunk(state, done) is called after every chunk (tests look at the state between chunks)"""
     if int(max_iteration) < 0:
         raise ValueError(f'icp: max_iteration {max_iteration} is negative')
@@ -3375,7 +3384,7 @@ def _icp_run(src, tgt, src_frames, tgt_frames, scale, threshold, max_iteration=2
         queued += count
         if on_chunk is not None:
             on_chunk(state, done)
-        if bool(done.cpu().all()):
+        if read_done and bool(done.cpu().all()):
             break
     return _icp_result(state)
 
@@ -3846,6 +3855,76 @@ def visible_labels(label, rays, counts=None):
     """bricks + mark + apply for a label grid (F, X, Y, Z) uint8: (masked label, counts)."""
     grid, bricks = raycast_bricks(label)
     return visibility_apply(grid, visibility_mark(grid, bricks, rays), counts)
+
+
+# ---- voxel labels filled from neighbouring frames (csrc/voxel_aggregate.hip; include/muvo_hip.h: muvo_voxel_aggregate, our definition)
+def voxel_cell_map(cfg, factor):
+    """The affine map (6,) float64 - scale per axis, then offset per axis - from range-view coordinates (the x, y, z planes of
+    range_view_label_1 times LIDAR_RE.SCALE: metres in the ego frame) to the grid coordinates of the voxel labels at scale
+    `factor`: g = r / (VOXEL.RESOLUTION factor) + VOXEL.EV_POSITION / factor (include/muvo_hip.h: muvo_voxel_pose_chain)."""
+    a = 1.0 / (float(cfg.VOXEL.RESOLUTION) * int(factor))
+    return [a, a, a] + [float(v) / int(factor) for v in cfg.VOXEL.EV_POSITION]
+
+
+def voxel_pose_chain(T, b, s, window, cell_map, fitness=None, status=None, min_fitness=0.0):
+    """(mats (b s, 2 window, 12) float64, usable (b s, 2 window) uint8) of the b (s - 1) link matrices T (b (s - 1), 4, 4) float64 on
+    the device, p_{t-1} ~ T_t p_t, in the walk order of muvo_voxel_aggregate and in the cell coordinates of `cell_map` (6 numbers:
+    voxel_cell_map).  fitness (float64) and status (int64), (b (s - 1),) device tensors as IcpResult holds them, decide with
+    min_fitness which links are valid; both None: every finite link is."""
+    b, s, window = int(b), int(s), int(window)
+    assert T.dtype == torch.float64 and T.is_cuda, 'voxel_pose_chain: float64 link matrices on the device'
+    T = T.reshape(-1, 4, 4).contiguous()
+    if b < 1 or s < 1 or T.shape[0] != b * (s - 1):
+        raise ValueError(f'voxel_pose_chain: {T.shape[0]} link matrices for {b} sequences of {s} frames')
+    if (fitness is None) != (status is None):
+        raise ValueError('voxel_pose_chain: fitness and status come together or not at all')
+    if fitness is not None:
+        assert fitness.dtype == torch.float64 and status.dtype == torch.int64 and fitness.device == T.device and status.device == T.device
+        assert tuple(fitness.shape) == (T.shape[0],) and tuple(status.shape) == (T.shape[0],), 'voxel_pose_chain: one fitness and one status per link'
+        fitness, status = fitness.contiguous(), status.contiguous()
+    if window < 1 or window > 64:
+        raise ValueError(f'voxel_pose_chain: window {window} outside 1..64')
+    cm = [float(v) for v in cell_map]
+    if len(cm) != 6:
+        raise ValueError('voxel_pose_chain: cell_map is 3 scales and 3 offsets')
+    mats = torch.empty((b * s, 2 * window, 12), dtype=torch.float64, device=T.device)
+    usable = torch.empty((b * s, 2 * window), dtype=torch.uint8, device=T.device)
+    _ck(lib().muvo_voxel_pose_chain(_p(T) if T.numel() else C.c_void_p(0), _p(fitness), _p(status), b, s, C.c_double(float(min_fitness)), window,
+                                    (C.c_double * 6)(*cm), _p(mats), _p(usable), _st()))
+    return mats, usable
+
+
+def voxel_aggregate(label, bricks, seen, s, mats, usable, counts=None):
+    """The aggregated masked label (F, X, Y, Z) uint8 of `label` (F = b s frames, sequences of s): what visibility_apply writes
+    where the frame observed the cell itself; every other cell takes the state of the cell it falls into in the nearest usable
+    frame of its sequence that observed it (mats, usable: voxel_pose_chain), 255 if none did.  counts (3,) int64 on the device
+    (filled occupied, filled free, still unknown) is added to; None: a fresh one.  Returns (label, counts)."""
+    assert label.dtype == torch.uint8 and label.dim() == 4 and label.is_contiguous()
+    F, X, Y, Z = (int(v) for v in label.shape)
+    words = ((X + 3) // 4) * ((Y + 3) // 4) * ((Z + 3) // 4)
+    for t, what in ((bricks, 'raycast_bricks'), (seen, 'visibility_mark')):
+        assert t.dtype == torch.int64 and t.is_contiguous() and t.device == label.device
+        assert tuple(t.shape) == (F, words), f'voxel_aggregate: the words of {what} for this grid'
+    s = int(s)
+    if s < 1 or F % s:
+        raise ValueError(f'voxel_aggregate: {F} frames are not sequences of {s}')
+    assert mats.dtype == torch.float64 and mats.dim() == 3 and mats.shape[0] == F and mats.shape[2] == 12 and mats.shape[1] % 2 == 0 and mats.is_contiguous() \
+        and mats.device == label.device, 'voxel_aggregate: mats (F, 2 window, 12) float64 of voxel_pose_chain'
+    assert usable.dtype == torch.uint8 and tuple(usable.shape) == tuple(mats.shape[:2]) and usable.is_contiguous() and usable.device == label.device
+    if counts is None:
+        counts = torch.zeros(3, dtype=torch.int64, device=label.device)
+    assert counts.dtype == torch.int64 and tuple(counts.shape) == (3,) and counts.is_contiguous() and counts.device == label.device
+    out = torch.empty_like(label)
+    _ck(lib().muvo_voxel_aggregate(_p(label), _p(bricks), _p(seen), F, s, X, Y, Z, int(mats.shape[1]) // 2, _p(mats), _p(usable), _p(out), _p(counts), _st()))
+    return out, counts
+
+
+def aggregated_labels(label, rays, s, T, window, cell_map, fitness=None, status=None, min_fitness=0.0, counts=None):
+    """bricks + mark + chain + aggregate for a label grid (b s, X, Y, Z) uint8: (aggregated masked label, counts)."""
+    grid, bricks = raycast_bricks(label)
+    seen = visibility_mark(grid, bricks, rays)
+    mats, usable = voxel_pose_chain(T, grid.shape[0] // int(s), s, window, cell_map, fitness, status, min_fitness)
+    return voxel_aggregate(grid, bricks, seen, s, mats, usable, counts)
 
 
 def _ray_args(grid, bricks, rays):

@@ -15,7 +15,7 @@ import torch
 
 from muvo_amd import ops
 from muvo_amd.config import (get_cfg, lidar_cd, voxel_boundary, voxel_boundary_cells, voxel_lovasz, voxel_render, voxel_render_class,
-                             voxel_visibility)
+                             voxel_aggregate, voxel_visibility)
 from muvo_amd.models.mile import Mile
 from muvo_amd.models.preprocess import PreProcess
 from muvo_amd.optim import FusedAdamW
@@ -72,6 +72,8 @@ def metric_names(cfg, prefix):
         names += [f'{prefix}_Voxel_mIoU', f'{prefix}_Voxel_IoU', f'{prefix}_Voxel_Precision', f'{prefix}_Voxel_Recall']
         if voxel_visibility(cfg)[0]:       # extension (config.py: VOXEL_SEG.VISIBILITY), absent = off: no such name
             names.append(f'{prefix}_Voxel_Unknown_Share')
+        if voxel_aggregate(cfg)[0]:        # extension (config.py: VOXEL_SEG.AGGREGATE), absent = off: no such names
+            names += [f'{prefix}_Voxel_Filled_Share', f'{prefix}_Voxel_Unknown_Share_Aggregated']
     return names
 
 
@@ -87,6 +89,8 @@ def metric_log_names(cfg, prefix):
         names += [f'{prefix}_Voxel_mIoU', f'{prefix}_Voxel_IoU', f'{prefix}_Voxel_Precision', f'{prefix}_Voxel_Recall']
         if voxel_visibility(cfg)[0]:       # extension (config.py: VOXEL_SEG.VISIBILITY), absent = off: no such name
             names.append(f'{prefix}_Voxel_Unknown_Share')
+        if voxel_aggregate(cfg)[0]:        # extension (config.py: VOXEL_SEG.AGGREGATE), absent = off: no such names
+            names += [f'{prefix}_Voxel_Filled_Share', f'{prefix}_Voxel_Unknown_Share_Aggregated']
     return names
 
 
@@ -191,8 +195,9 @@ class WorldModelTrainer(_Base):
             return losses, output, [], []
         rf, fh = self.rf, self.fh
         batch = self.preprocess(batch)
-        batch_rf = {k: v[:, :rf].contiguous() for k, v in batch.items()}
-        batch_fh = {k: v[:, rf:].contiguous() for k, v in batch.items()}
+        # (b, s, ...) tensors are cut in time; `voxel_aggregate_counts` (3,) has no time axis and stays whole
+        batch_rf = {k: v[:, :rf].contiguous() if v.dim() >= 2 else v for k, v in batch.items()}
+        batch_fh = {k: v[:, rf:].contiguous() if v.dim() >= 2 else v for k, v in batch.items()}
         output, state_dict = self.model.forward(batch_rf, deployment=False, noise=None if noise is None else noise[:, :rf],
                                                 use_prior=None if use_prior is None else list(use_prior[:rf]))
         losses = self.compute_loss(batch_rf, output)
@@ -225,6 +230,9 @@ class WorldModelTrainer(_Base):
                 if voxel_visibility(self.cfg)[0]:
                     from .metrics import VoxelUnknownShare
                     metrics['unknown'] = VoxelUnknownShare()
+                if voxel_aggregate(self.cfg)[0]:
+                    from .metrics import VoxelFilledShare
+                    metrics['filled'] = VoxelFilledShare()
         return metrics
 
     def add_metrics(self, metrics, batch, output, cd_index=None):
@@ -257,6 +265,8 @@ class WorldModelTrainer(_Base):
                 label = batch['voxel_label_1']
                 grid = label.to(torch.uint8).reshape(-1, *label.shape[-3:])
                 metrics['unknown'].add_batch(grid, visibility_table(self.cfg, 1, tuple(grid.shape[1:]), grid.device))
+            if 'filled' in metrics:          # the counts of the WHOLE batch (a frame is filled from both sides of the rf / fh split)
+                metrics['filled'].add_batch(batch['voxel_aggregate_counts'], batch.get('voxel_aggregate_cells', batch['voxel_label_1'].numel()))
 
     def compute_ssc_metrics(self, batch, output, metric):
         """trainer.py:482-490; the argmax over the class logits happens inside the counting kernel."""
@@ -281,8 +291,10 @@ class WorldModelTrainer(_Base):
         finally:
             for layer, v in zip(layers, saved):
                 layer.module_dropout_off = v
-        batch_rf = {key: value[:, :self.rf] for key, value in batch.items() if torch.is_tensor(value)}
-        batch_fh = {key: value[:, self.rf:] for key, value in batch.items() if torch.is_tensor(value)}
+        batch_rf = {key: value[:, :self.rf] if value.dim() >= 2 else value for key, value in batch.items() if torch.is_tensor(value)}
+        batch_fh = {key: value[:, self.rf:] if value.dim() >= 2 else value for key, value in batch.items() if torch.is_tensor(value)}
+        if 'voxel_aggregate_counts' in batch:       # (3,): no time axis to cut; both sets count the whole batch and its cells
+            batch_rf['voxel_aggregate_cells'] = batch_fh['voxel_aggregate_cells'] = batch['voxel_label_1'].numel()
         self.add_metrics(metrics, batch_rf, output, cd_index)
         for output_imagine in output_imagines:
             self.add_metrics(metrics_imagine, batch_fh, output_imagine, cd_index)
@@ -340,6 +352,11 @@ class WorldModelTrainer(_Base):
             if 'unknown' in metrics:
                 self.log(f'{prefix}_Voxel_Unknown_Share', metrics['unknown'].get_stat())
                 metrics['unknown'].reset()
+            if 'filled' in metrics:
+                filled, unknown = metrics['filled'].get_stat()
+                self.log(f'{prefix}_Voxel_Filled_Share', filled)
+                self.log(f'{prefix}_Voxel_Unknown_Share_Aggregated', unknown)
+                metrics['filled'].reset()
 
     def _log_iou(self, metrics, prefix, head):
         """trainer.py:525-530,542-554 for one head: per-class scores zipped with the class names, the mean over ALL classes."""
