@@ -768,7 +768,8 @@ int muvo_panel_voxel_top_grid(const uint8_t* grid, int F, int X, int Y, int Z, c
  *   fitness / rmse, then stops the pair - fewer than 3 inliers (MUVO_ICP_FEW_INLIERS), not the first evaluation and
  *   |d fitness| < 1e-6 and |d rmse| < 1e-6 (MUVO_ICP_CONVERGED), iterations == max_iteration (MUVO_ICP_MAX_ITERATION) - with T
  *   unchanged, or sets T <- U T with U the least-squares rigid motion of the inlier pairs (Horn's quaternion form in fp64: a
- *   proper rotation always).  No atomics anywhere: results do not depend on scheduling.
+ *   proper rotation always).  Atomics only in the grid build (below), where only the order inside a
+ *   cell depends on them: results do not depend on scheduling.
  *   corr (P,n) int32 or NULL: the target index of every query of the LAST correspond that ran for the pair, -1 = invalid or
  *   gated out (entries of non-query points are left alone); sums (P,17) or NULL: count, sum d^2, sum s (3), sum q (3),
  *   sum s q^T (9, row = component of s) of that evaluation, s = the moved query, q = its target point.
@@ -786,6 +787,25 @@ int muvo_icp_init(const float* src, const float* tgt, int64_t Fs, int64_t Ft, in
 int muvo_icp_iterate(const float* src, const float* tgt, int Cs, int Ct, int64_t n, const int32_t* src_frames, const int32_t* tgt_frames,
                      int64_t P, float scale, float threshold, int64_t stride, int max_iteration, int count, double* ws, double* state,
                      int32_t* done, int32_t* corr, double* sums, void* stream);
+/* The same registration with a grid-accelerated search: every output bit - corr, sums, state, done - equals muvo_icp_iterate's.
+ * Definition: per query the exhaustive search contributes the lexicographic minimum of (fp32 d^2, target index) over the valid
+ * target points, and only where that d^2 <= threshold^2 (fp32); the grid search finds exactly that minimum among the target
+ * points that can lie within the threshold, with the same d = fmaf(dz, dz, fmaf(dy, dy, dx dx)) on the same fp32 operands, the
+ * same gate and the same reduction (same queries per workgroup and lane, same order, same update kernel).
+ * muvo_icp_grid_build (after muvo_icp_init, once per registration: the pose moves only the sources): per pair that is not done,
+ *   the valid target points whose three scaled coordinates are finite (any other can never win) are binned into cubic cells
+ *   (edge threshold / 8, doubled until the bounding box has at most 2^17 cells) - bounding box, histogram and scatter with
+ *   integer atomics, exclusive scan.  Atomics only here, where only the order of the points inside a cell depends on them;
+ *   the winner rule is lexicographic, so results do not depend on scheduling.  grid: muvo_icp_grid_bytes(P, n) bytes, 16-byte
+ *   aligned, written here and read by muvo_icp_iterate_grid (same tgt, Ct, n, tgt_frames, P, scale; the threshold may differ).
+ * muvo_icp_iterate_grid: muvo_icp_iterate with the search over the grid; a query whose moved coordinates are not finite has no
+ *   candidate (corr -1), as in the exhaustive search where all its distances are NaN or inf. */
+int64_t muvo_icp_grid_bytes(int64_t P, int64_t n);
+int muvo_icp_grid_build(const float* tgt, int Ct, int64_t n, const int32_t* tgt_frames, int64_t P, float scale, float threshold,
+                        const int32_t* done, void* grid, int64_t grid_bytes, void* stream);
+int muvo_icp_iterate_grid(const float* src, const float* tgt, int Cs, int Ct, int64_t n, const int32_t* src_frames, const int32_t* tgt_frames,
+                          int64_t P, float scale, float threshold, int64_t stride, int max_iteration, int count, double* ws, double* state,
+                          int32_t* done, int32_t* corr, double* sums, const void* grid, int64_t grid_bytes, void* stream);
 
 /* ---- dense optical flow between camera frames (flow.hip): the flow behind the reference's `_flow` panel ------------------------
  * The reference calls cv2.calcOpticalFlowFarneback(img1, img2, None, 0.5, 3, 15, 3, 5, 1.2, 0) (trainer.py:1009-1020).  This is

@@ -46,14 +46,15 @@ TOLERATED_EXTRA_KEYS = ('CML_DATASET_VERSION', 'MODEL.TRANSFORMER_TRANSITION', '
 #   Lovasz) and the SSC metrics ignore; evaluation then also logs `{prefix}_Voxel_Unknown_Share`.  LIDAR_STRIDE (an integer >= 1;
 #   absent = 1) takes every STRIDE-th azimuth of the range view, CAMERA_STRIDE (an integer >= 1; absent = 2) every STRIDE-th
 #   pixel of the full camera frame in both directions.  Needs VOXEL_SEG.ENABLED, refuses VOXEL_SEG.USE_TOP_K.
-#   VOXEL_SEG.AGGREGATE.{ENABLED,WINDOW,MIN_FITNESS,ICP_ITERATIONS,ICP_STRIDE} - fills the cells the visibility mask calls unknown
+#   VOXEL_SEG.AGGREGATE.{ENABLED,WINDOW,MIN_FITNESS,ICP_ITERATIONS,ICP_STRIDE,ICP_SEARCH} - fills the cells the visibility mask calls unknown
 #   from the neighbouring frames of the same sequence (the reference has none).  ENABLED (bool; absent = off: no launch, no new
 #   batch key, no new metric name) makes PreProcess write into `voxel_visible_label_{1,2,4}` the aggregated labels: a cell the
 #   frame observed itself stays, every other cell takes what the nearest frame in time (past before future, at most WINDOW frames
 #   away - an integer >= 1, absent = 4, a definition and no measured optimum) saw at the place the ego motion carries it to, 255 if
 #   none did; evaluation then also logs `{prefix}_Voxel_Filled_Share` and `{prefix}_Voxel_Unknown_Share_Aggregated`.  The ego
 #   motion is `batch['voxel_ego_poses']` (b, s - 1, 4, 4) when given, else ICP between consecutive label range views with
-#   ICP_ITERATIONS (an integer >= 1; absent = 30) fits on every ICP_STRIDE-th point (an integer >= 1; absent = 4); a link whose
+#   ICP_ITERATIONS (an integer >= 1; absent = 30) fits on every ICP_STRIDE-th point (an integer >= 1; absent = 4) and the
+#   neighbour search ICP_SEARCH (the string brute or grid; absent = brute; grid gives the same poses bit for bit); a link whose
 #   fitness is below MIN_FITNESS (a number in [0, 1]; absent = 0.3) or whose registration failed carries nothing
 #   (DESIGN.md section 18).  Needs VOXEL_SEG.VISIBILITY.ENABLED, hence VOXEL_SEG.ENABLED and no VOXEL_SEG.USE_TOP_K.
 EXTENSION_KEYS = ('MODEL.CONSTANT_SIZE', 'MODEL.CONSTANT_SIZE.RGB', 'MODEL.CONSTANT_SIZE.LIDAR', 'MODEL.CONSTANT_SIZE.VOXEL',
@@ -65,7 +66,7 @@ EXTENSION_KEYS = ('MODEL.CONSTANT_SIZE', 'MODEL.CONSTANT_SIZE.RGB', 'MODEL.CONST
                   'LOSSES.VOXEL_BOUNDARY', 'LOSSES.VOXEL_BOUNDARY.WEIGHT', 'LOSSES.VOXEL_BOUNDARY.FACTORS', 'LOSSES.VOXEL_BOUNDARY.TRUNCATE_M',
                   'VOXEL_SEG.VISIBILITY', 'VOXEL_SEG.VISIBILITY.ENABLED', 'VOXEL_SEG.VISIBILITY.LIDAR_STRIDE', 'VOXEL_SEG.VISIBILITY.CAMERA_STRIDE',
                   'VOXEL_SEG.AGGREGATE', 'VOXEL_SEG.AGGREGATE.ENABLED', 'VOXEL_SEG.AGGREGATE.WINDOW', 'VOXEL_SEG.AGGREGATE.MIN_FITNESS',
-                  'VOXEL_SEG.AGGREGATE.ICP_ITERATIONS', 'VOXEL_SEG.AGGREGATE.ICP_STRIDE')
+                  'VOXEL_SEG.AGGREGATE.ICP_ITERATIONS', 'VOXEL_SEG.AGGREGATE.ICP_STRIDE', 'VOXEL_SEG.AGGREGATE.ICP_SEARCH')
 DEFAULT_CONSTANT_SIZE = {'RGB': (5, 13), 'LIDAR': (1, 16), 'VOXEL': (3, 3, 1)}
 
 
@@ -228,6 +229,18 @@ def voxel_aggregate(cfg):
     if enabled and not voxel_visibility(cfg)[0]:         # its refusals (VOXEL_SEG.ENABLED, USE_TOP_K) are raised by that call
         raise ValueError('VOXEL_SEG.AGGREGATE.ENABLED needs VOXEL_SEG.VISIBILITY.ENABLED: aggregation fills the cells that mask calls unknown')
     return enabled, int(window), float(fitness), ints[0], ints[1]
+
+
+AGGREGATE_ICP_SEARCHES = ('brute', 'grid')
+
+
+def voxel_aggregate_icp_search(cfg):
+    """the neighbour search of the aggregation's ICP: VOXEL_SEG.AGGREGATE.ICP_SEARCH, 'brute' or 'grid'; absent = 'brute'"""
+    node = cfg.VOXEL_SEG.get('AGGREGATE', None) or {}
+    search = node.get('ICP_SEARCH', 'brute')
+    if not isinstance(search, str) or search not in AGGREGATE_ICP_SEARCHES:
+        raise ValueError(f"VOXEL_SEG.AGGREGATE.ICP_SEARCH must be the string 'brute' or 'grid', got {search!r}")
+    return search
 
 
 class CfgNode(dict):

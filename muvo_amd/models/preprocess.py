@@ -11,7 +11,7 @@ import torch
 import torch.nn as nn
 
 from muvo_amd import ops
-from muvo_amd.config import voxel_aggregate, voxel_visibility
+from muvo_amd.config import voxel_aggregate, voxel_aggregate_icp_search, voxel_visibility
 
 
 def bev_out_of_view_mask(fov, image_width, resolution, crop_left, crop_right, bev_w, bev_h, offset_forward, camera_forward):
@@ -50,6 +50,7 @@ class PreProcess(nn.Module):
         self._pins = {}
         voxel_visibility(cfg)           # raises here, not in the first step, on a bad VOXEL_SEG.VISIBILITY
         voxel_aggregate(cfg)            # likewise VOXEL_SEG.AGGREGATE
+        voxel_aggregate_icp_search(cfg)
         self.bev_out_of_view_mask = None
         if cfg.EVAL.MASK_VIEW:        # preprocess.py:20-21
             self.bev_out_of_view_mask = torch.from_numpy(bev_out_of_view_mask(
@@ -80,10 +81,11 @@ class PreProcess(nn.Module):
             ring['ev'][i].record(torch.cuda.current_stream(out.device))
         return out
 
-    def _ego_links(self, batch, b, s, icp_iterations, icp_stride):
+    def _ego_links(self, batch, b, s, icp_iterations, icp_stride, icp_search='brute'):
         """(T (b (s - 1), 4, 4) float64, fitness, status) of VOXEL_SEG.AGGREGATE: p_{t-1} ~ T_t p_t in metres of the ego frame.
         `batch['voxel_ego_poses']` (b, s - 1, 4, 4) when given - all links valid, fitness and status None -, else ICP between the
-        consecutive frames of range_view_label_1 with a fixed budget, queued without a host read of the device."""
+        consecutive frames of range_view_label_1 with a fixed budget, queued without a host read of the device; icp_search =
+        VOXEL_SEG.AGGREGATE.ICP_SEARCH."""
         cfg = self.cfg
         dev = batch['voxel'].device
         if 'voxel_ego_poses' in batch:
@@ -98,7 +100,7 @@ class PreProcess(nn.Module):
                              "view in the batch (LIDAR_RE.ENABLED and 'range_view_pcd_xyzd') to register consecutive frames")
         from muvo_amd.odometry import register_consecutive
         res = register_consecutive(batch['range_view_label_1'], float(cfg.LIDAR_RE.SCALE), queued=True, max_iteration=icp_iterations,
-                                   source_stride=icp_stride)
+                                   source_stride=icp_stride, search=icp_search)
         return res.T, res.fitness, res.status
 
     def forward(self, batch):
@@ -213,7 +215,7 @@ class PreProcess(nn.Module):
                 from muvo_amd.voxel_view import visibility_table
                 aggregate, window, min_fitness, icp_iterations, icp_stride = voxel_aggregate(cfg)
                 if aggregate:                   # extension (config.py: VOXEL_SEG.AGGREGATE; absent = off: nothing below runs)
-                    links, fitness, status = self._ego_links(batch, b, s, icp_iterations, icp_stride)
+                    links, fitness, status = self._ego_links(batch, b, s, icp_iterations, icp_stride, voxel_aggregate_icp_search(cfg))
                 for f in (1, 2, 4):             # free cells no sensor ray passes become 255; voxel_label_f itself stays
                     label = batch[f'voxel_label_{f}']
                     grid = label.to(torch.uint8).reshape(-1, *label.shape[-3:])

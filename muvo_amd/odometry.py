@@ -20,7 +20,8 @@ LINE_COLOUR, DISC_COLOUR = (20, 150, 20), (150, 20, 20)
 def register_consecutive(range_view, scale, threshold=5.0, queued=False, **kw):
     """range_view (b, s, C, H, W) -> ops.IcpResult over the b (s - 1) pairs (bs, t), t = 1 .. s - 1, in that order: frame t is
     moved onto frame t - 1 of the same tensor, from the identity.  queued: ops.icp_register_queued - the whole budget
-    `max_iteration` is queued and the host never waits for the device (the training loop's way); the same result."""
+    `max_iteration` is queued and the host never waits for the device (the training loop's way); the same result.  Further
+    keywords go to the registration: max_iteration, source_stride, search ('brute' or 'grid', ops.icp_register)."""
     from muvo_amd import ops
     b, s, C, H, W = range_view.shape
     frames = range_view.detach().float().contiguous().view(b * s, C, H * W)
@@ -172,8 +173,8 @@ class EgoMotionMetric:
     KEYS = ('pos_error_reconstructed', 'pos_error_imagined', 'pos_error_last', 'yaw_error', 'fitness', 'pairs', 'pairs_at_max_iteration',
             'samples')
 
-    def __init__(self, cfg, threshold=5.0, stride=1, max_iteration=2000):
-        self.cfg, self.kw = cfg, dict(threshold=threshold, source_stride=stride, max_iteration=max_iteration)
+    def __init__(self, cfg, threshold=5.0, stride=1, max_iteration=2000, search='brute'):
+        self.cfg, self.kw = cfg, dict(threshold=threshold, source_stride=stride, max_iteration=max_iteration, search=search)
         self.loader = None
         self.acc = {}
 

@@ -11,6 +11,7 @@ return None for parameters and only propagate activation gradients.
 """
 import collections
 import contextlib
+import functools
 import ctypes as C
 import math
 import os
@@ -103,6 +104,7 @@ EXPORTS = [
     'muvo_panel_image', 'muvo_panel_logits', 'muvo_panel_labels', 'muvo_panel_fill', 'muvo_panel_bars', 'muvo_panel_scatter',
     'muvo_panel_voxel_top_logits', 'muvo_panel_voxel_top_grid',
     'muvo_icp_state_doubles', 'muvo_icp_ws_doubles', 'muvo_icp_init', 'muvo_icp_iterate',
+    'muvo_icp_grid_bytes', 'muvo_icp_grid_build', 'muvo_icp_iterate_grid',
     'muvo_flow_max_pairs', 'muvo_flow_workspace_bytes', 'muvo_flow_farneback', 'muvo_flow_colour_ws_bytes', 'muvo_flow_colour',
     'muvo_flow_epe_ws_doubles', 'muvo_flow_epe',
     'muvo_raycast_brick_words', 'muvo_raycast_bricks_grid', 'muvo_raycast_bricks_logits', 'muvo_raycast', 'muvo_panel_voxel_view',
@@ -142,6 +144,7 @@ def lib():
                 L.muvo_chamfer_loss_ws_doubles.restype = C.c_int64
                 L.muvo_icp_state_doubles.restype = C.c_int64
                 L.muvo_icp_ws_doubles.restype = C.c_int64
+                L.muvo_icp_grid_bytes.restype = C.c_int64
                 for name in ('muvo_flow_max_pairs', 'muvo_flow_workspace_bytes', 'muvo_flow_colour_ws_bytes', 'muvo_flow_epe_ws_doubles',
                              'muvo_raycast_brick_words', 'muvo_ray_iou_ws_doubles', 'muvo_lovasz_ws_bytes', 'muvo_render_ws_bytes',
                              'muvo_render_class_ws_bytes', 'muvo_voxel_edt_ws_bytes', 'muvo_voxel_boundary_ws_bytes', 'muvo_voxel_cd_ws_bytes',
@@ -3339,7 +3342,32 @@ def _icp_setup(src, tgt, src_frames, tgt_frames, scale, threshold, init, source_
     return frames, state, done, ws, P, n
 
 
-def _icp_iterate(src, tgt, frames, P, n, scale, threshold, stride, max_iteration, count, ws, state, done, corr=None, sums=None):
+ICP_SEARCHES = ('brute', 'grid')
+
+
+def _icp_search(search):
+    """refuses an unknown search before the library is loaded or a device is touched"""
+    if search not in ICP_SEARCHES:
+        raise ValueError(f"icp: search must be 'brute' or 'grid', got {search!r}")
+    return search
+
+
+def _icp_grid(tgt, frames, P, n, scale, threshold, done):
+    """search='grid': the cell grid of every pair's target points (muvo_icp_grid_build), built once per call after
+    muvo_icp_init on the current stream, no host read; a byte tensor owned by the call"""
+    L = lib()
+    grid = torch.empty(max(16, int(L.muvo_icp_grid_bytes(_i64(P), _i64(n)))), device=tgt.device, dtype=torch.uint8)
+    _ck(L.muvo_icp_grid_build(_f(tgt), int(tgt.shape[1]), _i64(n), _p(frames[1]), _i64(P), _fl(scale), _fl(threshold), _p(done), _p(grid),
+                              _i64(grid.numel()), _st()))
+    return grid
+
+
+def _icp_iterate(src, tgt, frames, P, n, scale, threshold, stride, max_iteration, count, ws, state, done, corr=None, sums=None, grid=None):
+    if grid is not None:
+        _ck(lib().muvo_icp_iterate_grid(_f(src), _f(tgt), int(src.shape[1]), int(tgt.shape[1]), _i64(n), _p(frames[0]), _p(frames[1]),
+                                        _i64(P), _fl(scale), _fl(threshold), _i64(stride), int(max_iteration), int(count), _p(ws),
+                                        _p(state), _p(done), _p(corr), _p(sums), _p(grid), _i64(grid.numel()), _st()))
+        return
     _ck(lib().muvo_icp_iterate(_f(src), _f(tgt), int(src.shape[1]), int(tgt.shape[1]), _i64(n), _p(frames[0]), _p(frames[1]), _i64(P),
                                _fl(scale), _fl(threshold), _i64(stride), int(max_iteration), int(count), _p(ws), _p(state), _p(done),
                                _p(corr), _p(sums), _st()))
@@ -3353,34 +3381,52 @@ def _icp_result(state):
     return IcpResult(T, state[:, 12].clone(), state[:, 13].clone(), state[:, 17].long(), status == ICP_CONVERGED, status)
 
 
+def _search_keyword(fn):
+    """icp_register keeps the parameter list its callers pin by introspection and takes one more keyword, `search`: 'brute' runs
+    the function as it always was, 'grid' the same registration over the cell grid; anything else is refused before the library is
+    loaded or a device is touched."""
+    @functools.wraps(fn)
+    def call(*args, search='brute', **kw):
+        if _icp_search(search) == 'brute':
+            return fn(*args, **kw)
+        return _icp_run(*args, search=search, **kw)
+    return call
+
+
+@_search_keyword
 def icp_register(src, tgt, src_frames, tgt_frames, scale, threshold, max_iteration=2000, init=None, source_stride=1):
     """Point-to-point ICP (include/muvo_hip.h: muvo_icp_*) of P frame pairs: pair p moves frame src_frames[p] of src (F, C, n)
     onto frame tgt_frames[p] of tgt (the same tensor twice is fine: no copy).  Planes 0..2 = x, y, z (times `scale`), plane 3 =
     range, valid iff range > 0.  Returns IcpResult of device tensors: T (P, 4, 4) float64 (target ~ T [source; 1]), fitness,
     inlier_rmse (P,) float64, iterations (P,) int64, converged (P,) bool (stopped by the 1e-6 deltas) and status (ICP_*).
     The host queues ICP_CHUNK iterations at a time and then reads the P done words: no sync per iteration.  init: (P, 4, 4)
-    start poses (default identity); source_stride k: only source points 0, k, 2k ... are queries (cost knob, 1 = exact)."""
+    start poses (default identity); source_stride k: only source points 0, k, 2k ... are queries (cost knob, 1 = exact).
+    Keyword search='brute' (every query scans every target point) or 'grid' (a cell grid of the target points, built once per
+    call; the same result bit for bit, see muvo_icp_iterate_grid)."""
     return _icp_run(src, tgt, src_frames, tgt_frames, scale, threshold, max_iteration, init, source_stride)
 
 
-def icp_register_queued(src, tgt, src_frames, tgt_frames, scale, threshold, max_iteration, init=None, source_stride=1):
+def icp_register_queued(src, tgt, src_frames, tgt_frames, scale, threshold, max_iteration, init=None, source_stride=1, search='brute'):
     """icp_register for a caller that must not wait for the device: all max_iteration + 1 evaluations are queued and the `done`
     words are never read (a pair that has stopped costs workgroups that return at once).  The same IcpResult, bit for bit: what a
     pair computes does not depend on when the host looks.  For small budgets - the cost is max_iteration + 1 launches whatever
     the clouds are."""
-    return _icp_run(src, tgt, src_frames, tgt_frames, scale, threshold, max_iteration, init, source_stride, read_done=False)
+    return _icp_run(src, tgt, src_frames, tgt_frames, scale, threshold, max_iteration, init, source_stride, read_done=False, search=search)
 
 
-def _icp_run(src, tgt, src_frames, tgt_frames, scale, threshold, max_iteration=2000, init=None, source_stride=1, on_chunk=None, read_done=True):
+def _icp_run(src, tgt, src_frames, tgt_frames, scale, threshold, max_iteration=2000, init=None, source_stride=1, on_chunk=None, read_done=True,
+             search='brute'):
     """icp_register; on_chunk(state, done) is called after every chunk (tests look at the state between chunks)"""
+    _icp_search(search)
     if int(max_iteration) < 0:
         raise ValueError(f'icp: max_iteration {max_iteration} is negative')
     src, tgt = src.contiguous(), tgt.contiguous()
     frames, state, done, ws, P, n = _icp_setup(src, tgt, src_frames, tgt_frames, scale, threshold, init, source_stride)
+    grid = _icp_grid(tgt, frames, P, n, scale, threshold, done) if search == 'grid' else None
     queued = 0
     while queued < max_iteration + 1:             # max_iteration fits need max_iteration + 1 evaluations
         count = min(ICP_CHUNK, max_iteration + 1 - queued)
-        _icp_iterate(src, tgt, frames, P, n, scale, threshold, source_stride, max_iteration, count, ws, state, done)
+        _icp_iterate(src, tgt, frames, P, n, scale, threshold, source_stride, max_iteration, count, ws, state, done, grid=grid)
         queued += count
         if on_chunk is not None:
             on_chunk(state, done)
@@ -3389,11 +3435,12 @@ def _icp_run(src, tgt, src_frames, tgt_frames, scale, threshold, max_iteration=2
     return _icp_result(state)
 
 
-def icp_step(src, tgt, src_frames, tgt_frames, scale, threshold, init=None, source_stride=1, out=None):
+def icp_step(src, tgt, src_frames, tgt_frames, scale, threshold, init=None, source_stride=1, out=None, search='brute'):
     """One evaluation at `init` (default identity) and the fit that follows it: (corr (P, n) int32 - the target index of every
     source point, -1 = invalid, gated out or no query -, sums (P, 17) float64 over the inliers - count, sum d^2, sum s, sum q,
     sum s q^T -, IcpResult after the step).  Pairs that are empty report zeros and -1.  out = (corr, sums): contiguous device
-    tensors of those shapes and types to write into (they are initialised here)."""
+    tensors of those shapes and types to write into (they are initialised here).  search: as icp_register."""
+    _icp_search(search)
     src, tgt = src.contiguous(), tgt.contiguous()
     frames, state, done, ws, P, n = _icp_setup(src, tgt, src_frames, tgt_frames, scale, threshold, init, source_stride)
     if out is None:
@@ -3403,7 +3450,8 @@ def icp_step(src, tgt, src_frames, tgt_frames, scale, threshold, init=None, sour
         raise ValueError(f'icp_step: out must be ({P}, {n}) int32 and ({P}, 17) float64')
     corr.fill_(-1)
     sums.zero_()
-    _icp_iterate(src, tgt, frames, P, n, scale, threshold, source_stride, 2000, 1, ws, state, done, corr, sums)
+    grid = _icp_grid(tgt, frames, P, n, scale, threshold, done) if search == 'grid' else None
+    _icp_iterate(src, tgt, frames, P, n, scale, threshold, source_stride, 2000, 1, ws, state, done, corr, sums, grid=grid)
     return corr, sums, _icp_result(state)
 
 

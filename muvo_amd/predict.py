@@ -107,6 +107,8 @@ def build_parser():
                         help='test: drift of the ego path implied by the predicted lidar from the one implied by the recorded lidar -> OUT/ego_motion.json')
     parser.add_argument('--ego-threshold', type=float, default=5.0, metavar='M', help='ICP inlier distance in metres of --ego-motion and --traj (default 5, the reference)')
     parser.add_argument('--ego-stride', type=int, default=1, metavar='K', help='every K-th source point is an ICP query (default 1: exact)')
+    parser.add_argument('--ego-search', choices=('brute', 'grid'), default='brute',
+                        help='neighbour search of the ICP of --ego-motion and --traj (default brute; grid: a cell grid of the target points, the same result bit for bit)')
     parser.add_argument('--ego-max-iteration', type=int, default=2000, metavar='N', help='ICP iteration cap (default 2000, the reference)')
     return parser
 
@@ -263,7 +265,7 @@ def run(cfg, device, out_dir, mode, loaders=None, limit_batches=None, shard_size
     of imagined samples).  data: a set-up DataModule to take the test loaders from (default: one over dataset_root /
     cfg.DATASET.DATAROOT); module: a WorldModelTrainer to use instead of building one from cfg.  panels (test): the picture grids
     of the first `panels` batches of every loader go to PNG files below out_dir/panels (muvo_amd/visualise.py), with traj also
-    `_traj`.  ego_motion (test): dict(threshold, stride, max_iteration) - muvo_amd.odometry.EgoMotionMetric runs behind `hook` on every
+    `_traj`.  ego_motion (test): dict(threshold, stride, max_iteration, search) - muvo_amd.odometry.EgoMotionMetric runs behind `hook` on every
     batch and writes out_dir/ego_motion.json; metrics.json does not change.  icp_options: dict(threshold, source_stride,
     max_iteration) of the ICP behind the `_traj` panel (default: 5 m, 1, 2000).  flow (test, with panels): also the `_flow` panel;
     optical_flow (test): muvo_amd.flow.FlowMetric runs on every batch and writes out_dir/optical_flow.json; metrics.json does
@@ -513,8 +515,8 @@ def main(argv=None):
     device = torch.device('cuda', 0)
     run(cfg, device, args.out, args.mode, loaders=chosen_loaders(args.mode, args.loader), limit_batches=args.limit_batches,
         shard_size=args.shard_size, seed=args.seed, dataset_root=args.dataset_root or None, panels=args.panels, traj=args.traj,
-        ego_motion=dict(threshold=args.ego_threshold, stride=args.ego_stride, max_iteration=args.ego_max_iteration) if args.ego_motion else None,
-        icp_options=dict(threshold=args.ego_threshold, source_stride=args.ego_stride, max_iteration=args.ego_max_iteration),
+        ego_motion=dict(threshold=args.ego_threshold, stride=args.ego_stride, max_iteration=args.ego_max_iteration, search=args.ego_search) if args.ego_motion else None,
+        icp_options=dict(threshold=args.ego_threshold, source_stride=args.ego_stride, max_iteration=args.ego_max_iteration, search=args.ego_search),
         flow=args.flow, optical_flow=args.optical_flow, voxel=args.voxel, voxel_size=args.voxel_size,
         ray_iou=dict(stride=args.ray_stride) if args.ray_iou else None, voxel_cd={} if args.voxel_cd else None,
         bev_pq=dict(threshold=args.inst_threshold, max_centres=args.inst_max_centres) if args.bev_pq else None,

@@ -60,7 +60,7 @@ def fit(cfg, device, steps=None, resume=None, log=None, seed=1234, batch_fn=None
     recordings below it instead of synthetic ones; input_stream=True prepares them on a side stream instead of the main one.
     panel_dir: rank 0 writes the picture grids (muvo_amd/visualise.py) of every LOG_VIDEO_INTERVAL-th step there as PNG files;
     traj: also the `_traj` panel (muvo_amd/odometry.py: the ego path from on-device ICP between consecutive lidar frames);
-    traj_options: dict(threshold, source_stride, max_iteration) of that ICP.  An untrained head is its worst case (tens of
+    traj_options: dict(threshold, source_stride, max_iteration, search) of that ICP.  An untrained head is its worst case (tens of
     iterations per pair at every 64 x 1024 frame): the command line defaults to every 4th point and 200 iterations.
     flow: also the `_flow` panel (muvo_amd/flow.py: dense optical flow between consecutive camera frames, on the device).
     voxel: also the `_voxel` panel (muvo_amd/voxel_view.py: the voxel grids ray-cast in 3-D on the device), tiles of voxel_size pixels.
@@ -190,6 +190,8 @@ def build_parser():
     parser.add_argument('--voxel-size', type=int, default=256, metavar='R', help='--voxel: pixels a side of one tile (default 256)')
     parser.add_argument('--traj-stride', type=int, default=4, metavar='K', help='--traj: every K-th source point is an ICP query (default 4; 1 = exact)')
     parser.add_argument('--traj-max-iteration', type=int, default=200, metavar='N', help='--traj: ICP iteration cap (default 200; the reference: 2000)')
+    parser.add_argument('--traj-search', choices=('brute', 'grid'), default='brute',
+                        help='--traj: neighbour search of the ICP (default brute; grid: a cell grid of the target points, the same result bit for bit)')
     parser.add_argument('--validate', action='store_true',
                         help='validate every VAL_CHECK_INTERVAL steps (after that step\'s checkpoint), with a sanity pass before the first step')
     parser.add_argument('--limit-val-batches', type=int, default=3, metavar='N', help='batches per validation loader and pass (default 3)')
@@ -209,7 +211,7 @@ def main(argv=None):
     if world > 1:
         dist.init_process_group('nccl', device_id=device)
     fit(cfg, device, resume=args.resume or None, dataset_root=args.dataset_root or None, panel_dir=args.panel_dir or None, traj=args.traj,
-        traj_options=dict(source_stride=args.traj_stride, max_iteration=args.traj_max_iteration),
+        traj_options=dict(source_stride=args.traj_stride, max_iteration=args.traj_max_iteration, search=args.traj_search),
         validate=args.validate, limit_val_batches=args.limit_val_batches, sanity_val_steps=args.sanity_val_steps,
         metrics_log=args.metrics_log or None, flow=args.flow, voxel=args.voxel, voxel_size=args.voxel_size, inst=args.inst, uncert=args.uncert)
     if world > 1:

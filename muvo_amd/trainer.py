@@ -141,7 +141,7 @@ class WorldModelTrainer(_Base):
         self.accumulate_now = False    # plain loop: True while a non-final micro-batch of gradient accumulation runs
         self.panel_writer = None       # object with add_images / add_video (muvo_amd.visualise.PanelWriter): None = no panels
         self.traj_panels = False       # with a writer and LIDAR_RE: also `_traj` (muvo_amd/odometry.py, ICP between lidar frames)
-        self.traj_options = {}         # threshold / source_stride / max_iteration of that ICP (default: 5 m, 1, 2000)
+        self.traj_options = {}         # threshold / source_stride / max_iteration / search of that ICP (default: 5 m, 1, 2000, brute)
         self.flow_panels = False       # with a writer and EVAL.RGB_SUPERVISION: also `_flow` (muvo_amd/flow.py, dense optical flow)
         self.voxel_panels = False      # with a writer and VOXEL_SEG: also `_voxel` (muvo_amd/voxel_view.py, ray-cast 3-D view)
         self.voxel_options = {}        # size of that panel's tiles (default 256)
