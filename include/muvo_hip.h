@@ -362,6 +362,28 @@ int muvo_attention_stream_fwd(const float* qkv, float* out, float* lse, int L, i
                               void* stream);
 int muvo_attention_stream_bwd(const float* qkv, const float* out, const float* dout, const float* lse, float* dqkv, float* dws,
                               int L, int N, int H, int DH, float p, uint64_t seed, void* stream);
+/* Key-padding mask: the four entry points above with a mask at the end of the argument list; same kernels, same constraints per
+ * path (resident: muvo_attention_supported; streamed: any L >= 1), same LDS.  key_mask (N, L) bytes, N the frame axis of qkv,
+ * one row for all heads of a frame, mask_stride bytes from one row to the next; a non-zero byte means the key is ignored
+ * (torch's src_key_padding_mask).  The kernels read it from global memory, a lane's four keys as one dword: key_mask and
+ * mask_stride must be multiples of 4 and mask_stride >= roundup(L, 4) (bytes of a row beyond L are never looked at).
+ * key_mask == NULL: no mask, the unmasked kernels run.
+ *  - A masked key gets the score -inf BEFORE the row maximum is taken: it adds nothing to the sum, to lse, to out, to dq, and
+ *    its own dk and dv rows are exactly 0.  Queries are never masked: a masked token still attends and gets its out row.
+ *  - The dropout mask index stays ((n*H + h)*L + query)*L + key with L the full length: with p > 0 the live (query, key) pairs
+ *    draw the bits they draw without a mask.
+ *  - A frame (or a row) with NO live key is defined as out = 0, lse = -inf, dqkv = 0 and nothing non-finite but that lse
+ *    (torch returns NaN there, which ends a training step); the backward never forms exp(s - lse) for a masked pair.
+ *  - An all-zero mask gives the bits of the unmasked entry point; like those, every call is bit-reproducible. */
+int muvo_attention_mask_fwd(const float* qkv, float* out, float* lse, int L, int N, int H, int DH, float p, uint64_t seed,
+                            void* stream, const uint8_t* key_mask, int64_t mask_stride);
+int muvo_attention_mask_bwd(const float* qkv, const float* out, const float* dout, const float* lse, float* dqkv, int L, int N,
+                            int H, int DH, float p, uint64_t seed, void* stream, const uint8_t* key_mask, int64_t mask_stride);
+int muvo_attention_stream_mask_fwd(const float* qkv, float* out, float* lse, int L, int N, int H, int DH, float p, uint64_t seed,
+                                   void* stream, const uint8_t* key_mask, int64_t mask_stride);
+int muvo_attention_stream_mask_bwd(const float* qkv, const float* out, const float* dout, const float* lse, float* dqkv,
+                                   float* dws, int L, int N, int H, int DH, float p, uint64_t seed, void* stream,
+                                   const uint8_t* key_mask, int64_t mask_stride);
 /* The whole recurrent state-space model (muvo/models/transition.py:76-173) as two persistent kernels (csrc/rssm.hip): one
  * workgroup per CU walks the T time steps, 4 grid barriers per step; T <= 64, H/S/E/A multiples of 4; B <= 64 sequences, run as
  * consecutive launches over slabs of 4 (sequences are independent).  The grid is clamped to what the occupancy calculator says

@@ -57,7 +57,13 @@ TOLERATED_EXTRA_KEYS = ('CML_DATASET_VERSION', 'MODEL.TRANSFORMER_TRANSITION', '
 #   neighbour search ICP_SEARCH (the string brute or grid; absent = brute; grid gives the same poses bit for bit); a link whose
 #   fitness is below MIN_FITNESS (a number in [0, 1]; absent = 0.3) or whose registration failed carries nothing
 #   (DESIGN.md section 18).  Needs VOXEL_SEG.VISIBILITY.ENABLED, hence VOXEL_SEG.ENABLED and no VOXEL_SEG.USE_TOP_K.
-EXTENSION_KEYS = ('MODEL.CONSTANT_SIZE', 'MODEL.CONSTANT_SIZE.RGB', 'MODEL.CONSTANT_SIZE.LIDAR', 'MODEL.CONSTANT_SIZE.VOXEL',
+#   MODEL.TRANSFORMER.SENSOR_DROPOUT.{CAMERA,LIDAR} - sensor (modality) dropout of the fusion transformer (the reference has none).
+#   Two probabilities (numbers in [0, 1]; absent = 0 = off: no draw, no mask, no new code on the step), CAMERA + LIDAR <= 1: in
+#   training mode each SEQUENCE of a batch loses its camera with probability CAMERA, its lidar with probability LIDAR, never
+#   both; the dropped sensor's feature map is replaced by zeros and its tokens are hidden as attention keys in all layers
+#   (`batch['sensor_drop']`, (b,) with 0 none / 1 camera / 2 lidar, says the same explicitly and in any mode).  DESIGN.md section 19.
+EXTENSION_KEYS = ('MODEL.TRANSFORMER.SENSOR_DROPOUT', 'MODEL.TRANSFORMER.SENSOR_DROPOUT.CAMERA', 'MODEL.TRANSFORMER.SENSOR_DROPOUT.LIDAR',
+                  'MODEL.CONSTANT_SIZE', 'MODEL.CONSTANT_SIZE.RGB', 'MODEL.CONSTANT_SIZE.LIDAR', 'MODEL.CONSTANT_SIZE.VOXEL',
                   'LOSSES.LIDAR_CD', 'LOSSES.LIDAR_CD.WEIGHT', 'LOSSES.LIDAR_CD.FACTORS',
                   'LOSSES.VOXEL_LOVASZ', 'LOSSES.VOXEL_LOVASZ.WEIGHT', 'LOSSES.VOXEL_LOVASZ.FACTORS',
                   'LOSSES.VOXEL_RENDER', 'LOSSES.VOXEL_RENDER.WEIGHT', 'LOSSES.VOXEL_RENDER.FACTORS', 'LOSSES.VOXEL_RENDER.STRIDE',
@@ -80,6 +86,23 @@ def constant_sizes(cfg):
             raise ValueError(f'MODEL.CONSTANT_SIZE.{k} must be {len(DEFAULT_CONSTANT_SIZE[k])} positive integers, got {v}')
         out.append(v)
     return tuple(out)
+
+
+def sensor_dropout(cfg):
+    """(camera, lidar) probabilities of sensor dropout: MODEL.TRANSFORMER.SENSOR_DROPOUT.* if given, else (0.0, 0.0) = off"""
+    node = cfg.MODEL.TRANSFORMER.get('SENSOR_DROPOUT', None) or {}
+    out = []
+    for key in ('CAMERA', 'LIDAR'):
+        v = node.get(key, 0.0)
+        if isinstance(v, bool) or not isinstance(v, (int, float)) or not 0 <= v <= 1:
+            raise ValueError(f'MODEL.TRANSFORMER.SENSOR_DROPOUT.{key} must be a number in [0, 1], got {v!r}')
+        out.append(float(v))
+    if out[0] + out[1] > 1:
+        raise ValueError(f'MODEL.TRANSFORMER.SENSOR_DROPOUT: CAMERA + LIDAR must be <= 1 (at most one sensor is dropped per '
+                         f'sequence), got {out[0]} + {out[1]}')
+    if max(out) > 0 and not cfg.MODEL.TRANSFORMER.ENABLED:
+        raise ValueError('MODEL.TRANSFORMER.SENSOR_DROPOUT needs MODEL.TRANSFORMER.ENABLED: the mask is in the fusion transformer')
+    return out[0], out[1]
 
 
 DEFAULT_LIDAR_CD_FACTORS = (2, 4)

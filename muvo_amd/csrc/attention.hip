@@ -107,16 +107,35 @@ __device__ __forceinline__ AttnCtx attn_ctx(int N, int H) {
 __host__ __device__ __forceinline__ int attn_block_rows(bool stream, int L) { return stream ? ATTN_SBK : (L + 15) & ~15; }
 // dropout mask index of (query, key 0): ((n*H + h)*L + query)*L
 __device__ __forceinline__ uint64_t attn_mask_row(int nh, int query, int L) { return ((uint64_t)nh * L + query) * (uint64_t)L; }
+// Key mask (MASK instantiations only; the others are the kernels as they were): key_mask (N, L) bytes, row stride mstride, shared by
+// the heads of a frame, non-zero = the key is ignored.  It is read from global memory - a frame's row is a few hundred bytes
+// that every workgroup of the frame re-reads from cache - so the LDS carving is the unmasked one.  A lane's four keys of a tile are
+// four consecutive bytes at a multiple of 4: one aligned dword (the host checks the alignment of base and stride), byte r = key
+// key4 + r; 0 beyond L, where the `key < L` test already decides.  A masked key is dead exactly like a key >= L: score -inf before
+// the maximum, p = 0 selected (never computed from exp(s - lse)) in backward.  New with a mask: a block, or a whole row, may have
+// no live key, so the maximum may stay -inf; attn_finite_max() keeps exp(-inf - (-inf)) out of the recurrence and the final 1 / l
+// and lse are selected for l = 0 (o = 0, lse = -inf).
+__device__ __forceinline__ uint32_t attn_mask_word(const uint8_t* __restrict__ mrow, int key4, int L) {
+  return key4 < L ? *(const uint32_t*)(mrow + key4) : 0u;
+}
+__device__ __forceinline__ bool attn_mask_bit(uint32_t mw, int r) { return ((mw >> (8 * r)) & 0xffu) != 0u; }
+// the maximum to subtract: 0 instead of -inf when nothing is live yet, so every exp(-inf - 0) is 0 and none is NaN
+template <bool MASK>
+__device__ __forceinline__ float attn_finite_max(float m) {
+  if constexpr (MASK) return m == -INFINITY ? 0.f : m;
+  return m;
+}
 template <int DT>
 __device__ __forceinline__ void attn_zero(f32x4* a) {
 #pragma unroll
   for (int dt = 0; dt < DT; ++dt) a[dt] = (f32x4){0.f, 0.f, 0.f, 0.f};
 }
 
-// Score tile t of the staged keys: S^T = K Q^T (16 keys x the wave's 16 queries), scaled, keys >= L at -inf; mx takes its maximum
-template <int DH>
+// Score tile t of the staged keys: S^T = K Q^T (16 keys x the wave's 16 queries), scaled, keys >= L (and masked keys, mw = their
+// mask word) at -inf; mx takes its maximum
+template <int DH, bool MASK>
 __device__ __forceinline__ f32x4 attn_score_tile(const float* Ks, int t, const float* qf, int k0, int L, float scale,
-                                                 const AttnCtx& x, float& mx) {
+                                                 const AttnCtx& x, float& mx, uint32_t mw) {
   constexpr int DQ = DH / 4, RS = DH + 4;
   float kf[DQ];
   attn_lds_frag<DH>(kf, Ks + (t * 16 + x.c) * RS, x.g);
@@ -126,7 +145,9 @@ __device__ __forceinline__ f32x4 attn_score_tile(const float* Ks, int t, const f
 #pragma unroll
   for (int r = 0; r < 4; ++r) {
     const int key = k0 + t * 16 + 4 * x.g + r;
-    acc[r] = key < L ? acc[r] * scale : -INFINITY;
+    bool live = key < L;
+    if constexpr (MASK) live = live && !attn_mask_bit(mw, r);
+    acc[r] = live ? acc[r] * scale : -INFINITY;
     mx = fmaxf(mx, acc[r]);
   }
   return acc;
@@ -182,10 +203,10 @@ __device__ __forceinline__ float attn_d_frag(const float* dof, const float* __re
   return quad_group_sum(dsum);
 }
 // dQ += dS K for tile t of the staged keys and values; the probabilities come back from the row log-sum-exp lq
-template <int DH>
+template <int DH, bool MASK>
 __device__ __forceinline__ void attn_dq_tile(f32x4* dq, const float* Ks, const float* Vs, int t, const float* qf, const float* dof,
                                              float lq, float dsum, int k0, uint64_t maskrow, int L, float scale, float pdrop,
-                                             uint64_t seed, const AttnCtx& x) {
+                                             uint64_t seed, const AttnCtx& x, uint32_t mw) {
   constexpr int DQ = DH / 4, RS = DH + 4, DT = DH / 16;
   float kf[DQ], vf[DQ];
   attn_lds_frag<DH>(kf, Ks + (t * 16 + x.c) * RS, x.g);
@@ -199,7 +220,9 @@ __device__ __forceinline__ void attn_dq_tile(f32x4* dq, const float* Ks, const f
 #pragma unroll
   for (int r = 0; r < 4; ++r) {
     const int kl = t * 16 + 4 * x.g + r, key = k0 + kl;
-    const float p = (key < L && x.row < L) ? expf(st[r] * scale - lq) : 0.f;
+    bool live = key < L && x.row < L;
+    if constexpr (MASK) live = live && !attn_mask_bit(mw, r);
+    const float p = live ? expf(st[r] * scale - lq) : 0.f;
     const float mk = pdrop > 0.f ? dropout_scale(seed, maskrow + (uint64_t)key, pdrop) : 1.f;
     const float ds = p * (dp[r] * mk - dsum);
     const float* krow = Ks + kl * RS + x.c;
@@ -208,10 +231,11 @@ __device__ __forceinline__ void attn_dq_tile(f32x4* dq, const float* Ks, const f
   }
 }
 // dV += Pd^T dO, dK += dS^T Q for tile t of the staged queries (Q, dO, lse and D per query in LDS); the keys are in registers
-template <int DH>
+// (MASK: keylive = this lane's key x.row is not masked)
+template <int DH, bool MASK>
 __device__ __forceinline__ void attn_dkv_tile(f32x4* dk, f32x4* dv, const float* Qs, const float* Gs, const float* Ls,
                                               const float* Ds, int t, const float* kf, const float* vf, int q0, int L, float scale,
-                                              float pdrop, uint64_t seed, const AttnCtx& x) {
+                                              float pdrop, uint64_t seed, const AttnCtx& x, bool keylive) {
   constexpr int DQ = DH / 4, RS = DH + 4, DT = DH / 16;
   float qv[DQ], gv[DQ];
   attn_lds_frag<DH>(qv, Qs + (t * 16 + x.c) * RS, x.g);
@@ -225,7 +249,8 @@ __device__ __forceinline__ void attn_dkv_tile(f32x4* dk, f32x4* dv, const float*
 #pragma unroll
   for (int r = 0; r < 4; ++r) {
     const int ql = t * 16 + 4 * x.g + r, q = q0 + ql;
-    const bool valid = q < L && x.row < L;
+    bool valid = q < L && x.row < L;
+    if constexpr (MASK) valid = valid && keylive;
     const float p = valid ? expf(sv[r] * scale - Ls[ql]) : 0.f;
     const float mk = (pdrop > 0.f && valid) ? dropout_scale(seed, attn_mask_row(x.nh, q, L) + (uint64_t)x.row, pdrop) : 1.f;
     const float pd = p * mk;
@@ -242,10 +267,10 @@ __device__ __forceinline__ void attn_dkv_tile(f32x4* dk, f32x4* dv, const float*
 
 // ================================================================================================ forward: out (L, N, E), lse (N*H, L)
 // Resident: two passes over the ATTN_MAXT register tiles of the whole score row (maximum, then exp and sum)
-template <int DH>
+template <int DH, bool MASK>
 __global__ void __launch_bounds__(64 * ATTN_WAVES)
 attn_fwd_kernel(const float* __restrict__ qkv, float* __restrict__ out, float* __restrict__ lse, int L, int N, int H,
-                float scale, float pdrop, uint64_t seed) {
+                float scale, float pdrop, uint64_t seed, const uint8_t* __restrict__ key_mask, long mstride) {
   constexpr int DQ = DH / 4, RS = DH + 4, DT = DH / 16;
   extern __shared__ float smem[];
   const int Lp = attn_block_rows(false, L), NT = Lp >> 4;
@@ -261,17 +286,19 @@ attn_fwd_kernel(const float* __restrict__ qkv, float* __restrict__ out, float* _
   if (x.r0 >= L) return;                                         // after the only barrier
   f32x4 s[ATTN_MAXT];
   float mx = -INFINITY;
+  const uint8_t* mrow = MASK ? key_mask + (long)x.n * mstride : nullptr;
 #pragma unroll
   for (int t = 0; t < ATTN_MAXT; ++t)
-    if (t < NT) s[t] = attn_score_tile<DH>(Ks, t, qf, 0, L, scale, x, mx);
-  mx = quad_group_max(mx);
+    if (t < NT) s[t] = attn_score_tile<DH, MASK>(Ks, t, qf, 0, L, scale, x, mx, MASK ? attn_mask_word(mrow, t * 16 + 4 * x.g, L) : 0u);
+  mx = attn_finite_max<MASK>(quad_group_max(mx));                // no live key: 0, every exp below is exp(-inf) = 0
   float sum = 0.f;
 #pragma unroll
   for (int t = 0; t < ATTN_MAXT; ++t)
     if (t < NT) attn_exp_tile(s[t], mx, sum);
   sum = quad_group_sum(sum);
-  const float inv = 1.f / sum;
-  if (x.g == 0 && x.row < L) lse[(long)x.nh * L + x.row] = mx + logf(sum);
+  const bool dead = MASK && !(sum > 0.f);                        // no live key: o = 0, lse = -inf
+  const float inv = dead ? 0.f : 1.f / sum;
+  if (x.g == 0 && x.row < L) lse[(long)x.nh * L + x.row] = dead ? -INFINITY : mx + logf(sum);
   f32x4 o[DT];
   attn_zero<DT>(o);
   const uint64_t maskrow = attn_mask_row(x.nh, x.row < L ? x.row : 0, L);
@@ -282,10 +309,13 @@ attn_fwd_kernel(const float* __restrict__ qkv, float* __restrict__ out, float* _
 }
 
 // Streamed: the online softmax over key blocks
-template <int DH>
+// With a mask a block may hold no live key: m' = max(m, -inf) is then m; while nothing has been live yet, m' = -inf and the
+// exponentials subtract attn_finite_max(m') = 0 instead: a = exp(-inf - 0) = 0 on l = 0 and O = 0, p = exp(-inf - 0) = 0.  A
+// later live block finds m = -inf, a = 0, as the first block of the unmasked kernel does.  l = 0 at the end: no live key at all.
+template <int DH, bool MASK>
 __global__ void __launch_bounds__(64 * ATTN_WAVES) __attribute__((amdgpu_waves_per_eu(ATTN_STREAM_WAVES(DH))))
 attn_stream_fwd_kernel(const float* __restrict__ qkv, float* __restrict__ out, float* __restrict__ lse, int L, int N, int H,
-                       float scale, float pdrop, uint64_t seed) {
+                       float scale, float pdrop, uint64_t seed, const uint8_t* __restrict__ key_mask, long mstride) {
   constexpr int DQ = DH / 4, RS = DH + 4, DT = DH / 16, KT = ATTN_SBK / 16;
   extern __shared__ float smem[];
   float* Ks = smem;
@@ -298,6 +328,7 @@ attn_stream_fwd_kernel(const float* __restrict__ qkv, float* __restrict__ out, f
   attn_zero<DT>(o);
   float m = -INFINITY, l = 0.f;
   const uint64_t maskrow = attn_mask_row(x.nh, x.row < L ? x.row : 0, L);
+  const uint8_t* mrow = MASK ? key_mask + (long)x.n * mstride : nullptr;
   for (int k0 = 0; k0 < L; k0 += ATTN_SBK) {
     if (k0) __syncthreads();                                   // every wave has read the previous block
     attn_stage<DH>(Ks, base + x.E + (long)k0 * x.rs, x.rs, L - k0, ATTN_SBK, x.tid);
@@ -307,12 +338,14 @@ attn_stream_fwd_kernel(const float* __restrict__ qkv, float* __restrict__ out, f
       f32x4 s[KT];
       float bm = -INFINITY;
 #pragma unroll
-      for (int t = 0; t < KT; ++t) s[t] = attn_score_tile<DH>(Ks, t, qf, k0, L, scale, x, bm);
-      const float mn = fmaxf(m, quad_group_max(bm));           // finite: key k0 < L is in this block
-      const float alpha = expf(m - mn);                        // first block: exp(-inf) = 0
+      for (int t = 0; t < KT; ++t)
+        s[t] = attn_score_tile<DH, MASK>(Ks, t, qf, k0, L, scale, x, bm, MASK ? attn_mask_word(mrow, k0 + t * 16 + 4 * x.g, L) : 0u);
+      const float mn = fmaxf(m, quad_group_max(bm));           // finite without a mask: key k0 < L is in this block
+      const float ms = attn_finite_max<MASK>(mn);              // what the exponentials subtract
+      const float alpha = expf(m - ms);                        // first live block: exp(-inf) = 0
       float bs = 0.f;
 #pragma unroll
-      for (int t = 0; t < KT; ++t) attn_exp_tile(s[t], mn, bs);
+      for (int t = 0; t < KT; ++t) attn_exp_tile(s[t], ms, bs);
       l = l * alpha + quad_group_sum(bs);
       m = mn;
 #pragma unroll
@@ -325,8 +358,9 @@ attn_stream_fwd_kernel(const float* __restrict__ qkv, float* __restrict__ out, f
       for (int t = 0; t < KT; ++t) attn_pv_tile<DH>(o, Vs, t, s[t], k0, maskrow, pdrop, seed, x);
     }
   }
-  if (x.g == 0 && x.row < L) lse[(long)x.nh * L + x.row] = m + logf(l);
-  const float inv = 1.f / l;
+  const bool dead = MASK && !(l > 0.f);                          // no live key: o = 0, lse = -inf
+  if (x.g == 0 && x.row < L) lse[(long)x.nh * L + x.row] = dead ? -INFINITY : m + logf(l);
+  const float inv = dead ? 0.f : 1.f / l;
   f32x4 iv;
 #pragma unroll
   for (int r = 0; r < 4; ++r) iv[r] = __shfl(inv, 4 * x.g + r, 64);
@@ -339,11 +373,11 @@ attn_stream_fwd_kernel(const float* __restrict__ qkv, float* __restrict__ out, f
 // Q / dO blocks.  STREAM = false: one block of roundup(L, 16) rows, the loop runs once.  The first block is staged before the
 // wave's own rows are fetched, so those loads overlap; every wave takes part in every barrier.
 // dqkv rows like qkv; the streamed dQ also writes D[query] = dO . O -> dws (N*H, L)
-template <int DH, bool STREAM>
+template <int DH, bool STREAM, bool MASK>
 __global__ void __launch_bounds__(64 * ATTN_WAVES)
 attn_bwd_dq_kernel(const float* __restrict__ qkv, const float* __restrict__ out, const float* __restrict__ dout,
                    const float* __restrict__ lse, float* __restrict__ dqkv, float* __restrict__ dws, int L, int N, int H, float scale,
-                   float pdrop, uint64_t seed) {
+                   float pdrop, uint64_t seed, const uint8_t* __restrict__ key_mask, long mstride) {
   constexpr int DQ = DH / 4, RS = DH + 4, DT = DH / 16;
   extern __shared__ float smem[];
   const int BR = attn_block_rows(STREAM, L), NT = BR >> 4;
@@ -367,17 +401,25 @@ attn_bwd_dq_kernel(const float* __restrict__ qkv, const float* __restrict__ out,
   f32x4 dq[DT];
   attn_zero<DT>(dq);
   const uint64_t maskrow = attn_mask_row(x.nh, x.row < L ? x.row : 0, L);
+  const uint8_t* mrow = MASK ? key_mask + (long)x.n * mstride : nullptr;
+  // the mask word of tile t is fetched one tile ahead (the tile loops are not unrolled): mnext is tile t + 1's while t runs
+  uint32_t mnext = MASK ? attn_mask_word(mrow, 4 * x.g, L) : 0u;
+  auto mword = [&](int t) {
+    const uint32_t mw = mnext;
+    if constexpr (MASK) mnext = attn_mask_word(mrow, k0 + (t + 1) * 16 + 4 * x.g, L);   // t + 1 = NT: tile 0 of the next block
+    return mw;
+  };
   for (;;) {
     __syncthreads();                                             // the block is staged
     if (x.r0 < L) {                                              // wave-uniform; no barrier inside
       if constexpr (STREAM) {                                    // blocked summation: a block's sum is added to the total once
         f32x4 dqb[DT];
         attn_zero<DT>(dqb);
-        for (int t = 0; t < NT; ++t) attn_dq_tile<DH>(dqb, Ks, Vs, t, qf, dof, lq, dsum, k0, maskrow, L, scale, pdrop, seed, x);
+        for (int t = 0; t < NT; ++t) attn_dq_tile<DH, MASK>(dqb, Ks, Vs, t, qf, dof, lq, dsum, k0, maskrow, L, scale, pdrop, seed, x, mword(t));
 #pragma unroll
         for (int dt = 0; dt < DT; ++dt) dq[dt] += dqb[dt];
       } else {                                                   // one block: straight into dq (0 + x would turn a -0 into +0)
-        for (int t = 0; t < NT; ++t) attn_dq_tile<DH>(dq, Ks, Vs, t, qf, dof, lq, dsum, k0, maskrow, L, scale, pdrop, seed, x);
+        for (int t = 0; t < NT; ++t) attn_dq_tile<DH, MASK>(dq, Ks, Vs, t, qf, dof, lq, dsum, k0, maskrow, L, scale, pdrop, seed, x, mword(t));
       }
     }
     if (!STREAM || (k0 += BR) >= L) break;                       // the same for every wave; resident: the one block was all
@@ -388,12 +430,13 @@ attn_bwd_dq_kernel(const float* __restrict__ qkv, const float* __restrict__ out,
   attn_store_rows<DH>(dqkv + x.hq, x.rs, dq, x, L);
 }
 
-// dK, dV: the wave's 16 keys in registers; Q, dO, lse and D per query of a block in LDS
-template <int DH, bool STREAM>
+// dK, dV: the wave's 16 keys in registers; Q, dO, lse and D per query of a block in LDS.  MASK: the lane's own key is masked or
+// not, one byte read once; a masked key's p is selected 0 for every query, so its dK and dV rows are exactly 0
+template <int DH, bool STREAM, bool MASK>
 __global__ void __launch_bounds__(64 * ATTN_WAVES) __attribute__((amdgpu_waves_per_eu(ATTN_DKV_WAVES(DH, STREAM))))
 attn_bwd_dkv_kernel(const float* __restrict__ qkv, const float* __restrict__ out, const float* __restrict__ dout,
                     const float* __restrict__ lse, float* __restrict__ dqkv, float* __restrict__ dws, int L, int N, int H, float scale,
-                    float pdrop, uint64_t seed) {
+                    float pdrop, uint64_t seed, const uint8_t* __restrict__ key_mask, long mstride) {
   constexpr int DQ = DH / 4, RS = DH + 4, DT = DH / 16;
   extern __shared__ float smem[];
   const int BR = attn_block_rows(STREAM, L), NT = BR >> 4;
@@ -435,10 +478,13 @@ attn_bwd_dkv_kernel(const float* __restrict__ qkv, const float* __restrict__ out
   f32x4 dk[DT], dv[DT];
   attn_zero<DT>(dk);
   attn_zero<DT>(dv);
+  bool keylive = true;
+  if constexpr (MASK)
+    if (x.row < L) keylive = key_mask[(long)x.n * mstride + x.row] == 0;
   for (;;) {
     __syncthreads();                                             // the block is staged
     if (x.r0 < L)                                                // wave-uniform; no barrier inside
-      for (int t = 0; t < NT; ++t) attn_dkv_tile<DH>(dk, dv, Qs, Gs, Ls, Ds, t, kf, vf, q0, L, scale, pdrop, seed, x);
+      for (int t = 0; t < NT; ++t) attn_dkv_tile<DH, MASK>(dk, dv, Qs, Gs, Ls, Ds, t, kf, vf, q0, L, scale, pdrop, seed, x, keylive);
     if (!STREAM || (q0 += BR) >= L) break;                       // the same for every wave; resident: the one block was all
     __syncthreads();                                             // every wave has read the previous block
     stage(q0);
@@ -456,15 +502,21 @@ static size_t attn_lds_bytes(int L, int DH, int which, bool stream) {
   return (size_t)2 * rows * (DH + 4) * 4 + (which == 2 ? (size_t)2 * rows * 4 : 0);
 }
 
-template <int DH, bool STREAM>
+// the key mask of a call: key (N, L) bytes, `stride` bytes from one frame's row to the next; key == nullptr: no mask
+struct AttnMask {
+  const uint8_t* key;
+  long stride;
+};
+
+template <int DH, bool STREAM, bool MASK>
 static int attn_launch(int which, const float* qkv, const float* out, const float* dout, float* lse, float* dst,
-                       float* dws, int L, int N, int H, float p, uint64_t seed, hipStream_t st) {
+                       float* dws, int L, int N, int H, float p, uint64_t seed, AttnMask mk, hipStream_t st) {
   const float scale = 1.0f / sqrtf((float)DH);
   const dim3 grid(cdiv(L, 16 * ATTN_WAVES), N * H), block(64 * ATTN_WAVES);
   static bool attr[3] = {false, false, false};
   const size_t lds = attn_lds_bytes(L, DH, which, STREAM);
-  const auto fwd = STREAM ? attn_stream_fwd_kernel<DH> : attn_fwd_kernel<DH>;
-  const auto bwd = which == 1 ? attn_bwd_dq_kernel<DH, STREAM> : attn_bwd_dkv_kernel<DH, STREAM>;
+  const auto fwd = STREAM ? attn_stream_fwd_kernel<DH, MASK> : attn_fwd_kernel<DH, MASK>;
+  const auto bwd = which == 1 ? attn_bwd_dq_kernel<DH, STREAM, MASK> : attn_bwd_dkv_kernel<DH, STREAM, MASK>;
   if (!attr[which]) {
     if (hipFuncSetAttribute(which == 0 ? (const void*)fwd : (const void*)bwd, hipFuncAttributeMaxDynamicSharedMemorySize,
                             160 * 1024) != hipSuccess) {
@@ -474,39 +526,49 @@ static int attn_launch(int which, const float* qkv, const float* out, const floa
     attr[which] = true;
   }
   if (which == 0)
-    hipLaunchKernelGGL(fwd, grid, block, lds, st, qkv, dst, lse, L, N, H, scale, p, seed);
+    hipLaunchKernelGGL(fwd, grid, block, lds, st, qkv, dst, lse, L, N, H, scale, p, seed, mk.key, mk.stride);
   else
-    hipLaunchKernelGGL(bwd, grid, block, lds, st, qkv, out, dout, (const float*)lse, dst, dws, L, N, H, scale, p, seed);
+    hipLaunchKernelGGL(bwd, grid, block, lds, st, qkv, out, dout, (const float*)lse, dst, dws, L, N, H, scale, p, seed, mk.key,
+                       mk.stride);
   return MUVO_OK;
 }
 
-template <bool STREAM>
+template <bool STREAM, bool MASK>
 static int attn_dispatch(int which, const float* qkv, const float* out, const float* dout, float* lse, float* dst,
-                         float* dws, int L, int N, int H, int DH, float p, uint64_t seed, hipStream_t st) {
+                         float* dws, int L, int N, int H, int DH, float p, uint64_t seed, AttnMask mk, hipStream_t st) {
   switch (DH) {
-    case 16: return attn_launch<16, STREAM>(which, qkv, out, dout, lse, dst, dws, L, N, H, p, seed, st);
-    case 32: return attn_launch<32, STREAM>(which, qkv, out, dout, lse, dst, dws, L, N, H, p, seed, st);
-    case 48: return attn_launch<48, STREAM>(which, qkv, out, dout, lse, dst, dws, L, N, H, p, seed, st);
-    case 64: return attn_launch<64, STREAM>(which, qkv, out, dout, lse, dst, dws, L, N, H, p, seed, st);
+    case 16: return attn_launch<16, STREAM, MASK>(which, qkv, out, dout, lse, dst, dws, L, N, H, p, seed, mk, st);
+    case 32: return attn_launch<32, STREAM, MASK>(which, qkv, out, dout, lse, dst, dws, L, N, H, p, seed, mk, st);
+    case 48: return attn_launch<48, STREAM, MASK>(which, qkv, out, dout, lse, dst, dws, L, N, H, p, seed, mk, st);
+    case 64: return attn_launch<64, STREAM, MASK>(which, qkv, out, dout, lse, dst, dws, L, N, H, p, seed, mk, st);
   }
   muvo_set_error("%s: head dimension %d not supported", STREAM ? "attention_stream" : "attention", DH);
   return MUVO_ERR_INVALID_ARG;
 }
 
 // One entry point: the argument check, then kernels first .. last (0 forward, 1 dQ, 2 dK/dV) of the path, queued on st.
-// ptrs: the entry point's own pointers are all there
+// ptrs: the entry point's own pointers are all there.  mk.key == nullptr runs the unmasked instantiations, the kernels as they
+// were; a mask must let a lane read its four keys as one aligned dword: base and stride multiples of 4, stride >= roundup(L, 4)
 static int attn_run(const char* name, bool stream, int first, int last, bool ptrs, const float* qkv, const float* out,
                     const float* dout, float* lse, float* dst, float* dws, int L, int N, int H, int DH, float p, uint64_t seed,
-                    hipStream_t st) {
+                    hipStream_t st, AttnMask mk = {nullptr, 0}) {
   MUVO_CHECK_ARG(ptrs && N > 0 && H > 0 && (long)N * H <= 65535, "%s: bad args", name);
   if (stream)
     MUVO_CHECK_ARG(muvo_attention_stream_supported(L, DH), "%s: L = %d, head dim = %d not supported", name, L, DH);
   else
     MUVO_CHECK_ARG(muvo_attention_supported(L, DH), "%s: L = %d, head dim = %d outside the fused kernel's range", name, L, DH);
   MUVO_CHECK_ARG(p >= 0.f && p < 1.f, "%s: dropout probability", name);
+  if (mk.key)
+    MUVO_CHECK_ARG(((uintptr_t)mk.key & 3) == 0 && (mk.stride & 3) == 0 && mk.stride >= (((long)L + 3) & ~3L),
+                   "%s: key mask base and row stride (%ld) must be multiples of 4 bytes, stride >= roundup(L, 4)", name, mk.stride);
   for (int which = first; which <= last; ++which) {
-    const int rc = stream ? attn_dispatch<true>(which, qkv, out, dout, lse, dst, dws, L, N, H, DH, p, seed, st)
-                          : attn_dispatch<false>(which, qkv, out, dout, lse, dst, dws, L, N, H, DH, p, seed, st);
+    int rc;
+    if (mk.key)
+      rc = stream ? attn_dispatch<true, true>(which, qkv, out, dout, lse, dst, dws, L, N, H, DH, p, seed, mk, st)
+                  : attn_dispatch<false, true>(which, qkv, out, dout, lse, dst, dws, L, N, H, DH, p, seed, mk, st);
+    else
+      rc = stream ? attn_dispatch<true, false>(which, qkv, out, dout, lse, dst, dws, L, N, H, DH, p, seed, mk, st)
+                  : attn_dispatch<false, false>(which, qkv, out, dout, lse, dst, dws, L, N, H, DH, p, seed, mk, st);
     if (rc) return rc;
   }
   MUVO_CHECK_LAUNCH(name);
@@ -544,5 +606,26 @@ int muvo_attention_stream_bwd(const float* qkv, const float* out, const float* d
                               int L, int N, int H, int DH, float p, uint64_t seed, void* stream) {
   return attn_run("attention_stream_bwd", true, 1, 2, qkv && out && dout && lse && dqkv && dws, qkv, out, dout, (float*)lse, dqkv,
                   dws, L, N, H, DH, p, seed, ST);
+}
+int muvo_attention_mask_fwd(const float* qkv, float* out, float* lse, int L, int N, int H, int DH, float p, uint64_t seed,
+                            void* stream, const uint8_t* key_mask, int64_t mask_stride) {
+  return attn_run("attention_mask_fwd", false, 0, 0, qkv && out && lse, qkv, nullptr, nullptr, lse, out, nullptr, L, N, H, DH, p,
+                  seed, ST, {key_mask, (long)mask_stride});
+}
+int muvo_attention_mask_bwd(const float* qkv, const float* out, const float* dout, const float* lse, float* dqkv, int L, int N,
+                            int H, int DH, float p, uint64_t seed, void* stream, const uint8_t* key_mask, int64_t mask_stride) {
+  return attn_run("attention_mask_bwd", false, 1, 2, qkv && out && dout && lse && dqkv, qkv, out, dout, (float*)lse, dqkv, nullptr,
+                  L, N, H, DH, p, seed, ST, {key_mask, (long)mask_stride});
+}
+int muvo_attention_stream_mask_fwd(const float* qkv, float* out, float* lse, int L, int N, int H, int DH, float p, uint64_t seed,
+                                   void* stream, const uint8_t* key_mask, int64_t mask_stride) {
+  return attn_run("attention_stream_mask_fwd", true, 0, 0, qkv && out && lse, qkv, nullptr, nullptr, lse, out, nullptr, L, N, H, DH,
+                  p, seed, ST, {key_mask, (long)mask_stride});
+}
+int muvo_attention_stream_mask_bwd(const float* qkv, const float* out, const float* dout, const float* lse, float* dqkv,
+                                   float* dws, int L, int N, int H, int DH, float p, uint64_t seed, void* stream,
+                                   const uint8_t* key_mask, int64_t mask_stride) {
+  return attn_run("attention_stream_mask_bwd", true, 1, 2, qkv && out && dout && lse && dqkv && dws, qkv, out, dout, (float*)lse,
+                  dqkv, dws, L, N, H, DH, p, seed, ST, {key_mask, (long)mask_stride});
 }
 }

@@ -15,6 +15,40 @@ from muvo_amd.models.transition import RSSM
 from muvo_amd.utils.network_utils import pack_sequence_dim, remove_past, unpack_sequence_dim
 
 
+SENSOR_NONE, SENSOR_CAMERA, SENSOR_LIDAR = 0, 1, 2          # values of batch['sensor_drop'] and of draw_sensor_drop
+
+
+def sensor_key_mask(drop, n_image, n_lidar):
+    """drop (N,) int8, 0 = none, 1 = camera, 2 = lidar -> the (N, n_image + n_lidar) uint8 attention key mask of the fusion tokens
+    (image tokens first, as ops.make_tokens lays them out): 1 where the token belongs to the frame's dropped sensor"""
+    sensor = torch.cat([torch.full((n_image,), SENSOR_CAMERA, dtype=torch.int8, device=drop.device),
+                        torch.full((n_lidar,), SENSOR_LIDAR, dtype=torch.int8, device=drop.device)])
+    return (drop.to(torch.int8)[:, None] == sensor[None, :]).to(torch.uint8)
+
+
+def drop_sensor_features(drop, image_features, lidar_features):
+    """drop (N,) int8 on the features' device -> (image features, lidar features, key mask): the dropped sensor's feature map of a
+    frame is SELECTED to zero - torch.where, not a product, so nothing non-finite of a dead sensor gets through and its encoder
+    gets a zero gradient - which leaves position encoding + type embedding in its tokens; the mask hides those tokens as keys"""
+    image_features = torch.where((drop == SENSOR_CAMERA).view(-1, 1, 1, 1), torch.zeros_like(image_features), image_features)
+    lidar_features = torch.where((drop == SENSOR_LIDAR).view(-1, 1, 1, 1), torch.zeros_like(lidar_features), lidar_features)
+    hi, wi = image_features.shape[-2:]
+    hl, wl = lidar_features.shape[-2:]
+    return image_features, lidar_features, sensor_key_mask(drop, hi * wi, hl * wl)
+
+
+def draw_sensor_drop(seed, b, p_camera, p_lidar):
+    """The training-mode draw, on the host: (b,) int8 per sequence, 1 with probability p_camera, 2 with probability p_lidar, else
+    0 - one uniform number per sequence decides, so both sensors are never dropped.  A function of the seed alone."""
+    g = torch.Generator(device='cpu')
+    g.manual_seed(int(seed) & 0x7FFFFFFFFFFFFFFF)
+    u = torch.rand(b, generator=g, dtype=torch.float64)
+    drop = torch.zeros(b, dtype=torch.int8)
+    drop[u < p_camera] = SENSOR_CAMERA
+    drop[(u >= p_camera) & (u < p_camera + p_lidar)] = SENSOR_LIDAR
+    return drop
+
+
 class _FeatureConv(nn.Sequential):
     """BasicBlock(s2, downsample) -> BasicBlock -> global avg pool -> flatten (mile.py:104-115)."""
 
@@ -45,7 +79,8 @@ class Mile(nn.Module):
             raise NotImplementedError('muvo_amd implements the base_1d hot path (SURVEY.md §8); not in scope: '
                                       + ', '.join(unsupported))
         emb, tc = m.EMBEDDING_DIM, m.TRANSFORMER.CHANNELS
-        from muvo_amd.config import constant_sizes
+        from muvo_amd.config import constant_sizes, sensor_dropout
+        self.sensor_dropout = sensor_dropout(cfg)            # extension (config.py: MODEL.TRANSFORMER.SENSOR_DROPOUT), absent = (0, 0)
         cs_rgb, cs_lidar, cs_voxel = constant_sizes(cfg)     # the reference's (5, 13), (1, 16), (3, 3, 1) unless MODEL.CONSTANT_SIZE says otherwise
         self.encoder = ResNet18Features(3, (2, 3, 4))
         feature_info = self.encoder.feature_info.get_dicts(keys=['num_chs', 'reduction'])
@@ -138,6 +173,21 @@ class Mile(nn.Module):
         self._step_seed += 1
         return (self.dropout_seed + 0x9E3779B97F4A7C15 * (self.dropout_rank + 1) + 0xBF58476D1CE4E5B9 * self.seed_epoch
                 + 0x2545F4914F6CDD1D * self._step_seed) & 0x3FFFFFFFFFFFFFFF
+
+    def _sensor_drop(self, batch, b, s, device):
+        """(b * s,) int8 on the device, the per-sequence decision broadcast over the frames, or None (nothing dropped, no new code
+        runs): batch['sensor_drop'] when given, else drawn in training mode when MODEL.TRANSFORMER.SENSOR_DROPOUT is non-zero"""
+        drop = batch.get('sensor_drop', None)
+        if drop is None:
+            if not (self.training and max(self.sensor_dropout) > 0):
+                return None
+            drop = draw_sensor_drop(self.step_seed(), b, *self.sensor_dropout)
+        drop = torch.as_tensor(drop, dtype=torch.int8).reshape(-1)
+        if drop.numel() != b or int(drop.min()) < SENSOR_NONE or int(drop.max()) > SENSOR_LIDAR:
+            raise ValueError(f"batch['sensor_drop'] must be ({b},) with values 0 (none), 1 (camera), 2 (lidar), got {drop.tolist()}")
+        if int(drop.max()) == SENSOR_NONE:
+            return None
+        return drop.to(device).repeat_interleave(s)
 
     def forward(self, batch, deployment=False, noise=None, use_prior=None):
         if deployment:
@@ -379,11 +429,20 @@ class Mile(nn.Module):
         br_lidar.join()
         hi, wi = x.shape[-2:]
         hl, wl = lidar_features.shape[-2:]
+        drop = self._sensor_drop(batch, b, s, x.device)
+        key_mask = None
+        if drop is not None:
+            # The dropped sensor's encoder has run (its train-mode BatchNorm statistics saw the input).  Its tokens are no keys
+            # in any layer but stay queries: the sensor's output tokens are what the other sensor says about its positions.
+            x, lidar_features, key_mask = drop_sensor_features(drop, x, lidar_features)
         # x + pos -> flatten/permute -> + type embedding -> concat (mile.py:542-557), one transpose kernel per sensor
         tokens = ops.make_tokens(x, lidar_features, self._pos(hi, wi, x.device), self._pos(hl, wl, x.device),
                                  self.type_embedding)
         self._hook(tokens, 'fusion')
-        tokens_out = self.transformer_encoder(tokens, self.step_seed())
+        if key_mask is None:
+            tokens_out = self.transformer_encoder(tokens, self.step_seed())
+        else:
+            tokens_out = self.transformer_encoder(tokens, self.step_seed(), key_mask)
         image_tokens_out = ops.untoken(tokens_out, 0, hi, wi)
         lidar_tokens_out = ops.untoken(tokens_out, hi * wi, hl, wl)
         # route-map encoder (ResNet-18 on 64 x 64 pixels) and speed encoder: ~300 launches of 5-50 us that occupy a few compute

@@ -129,13 +129,15 @@ class TransformerEncoderLayer(nn.Module):
         self.norm1 = LayerNorm(e)
         self.norm2 = LayerNorm(e)
 
-    def forward(self, x, seed):
+    def forward(self, x, seed, key_mask=None):
+        """key_mask: (N, L) bool / uint8 on the device, non-zero = that token is no key for its frame (src_key_padding_mask);
+        it stays a query and keeps its row.  None: the layer as it was."""
         p = self.p if self.training else 0.0
         # validation (trainer.py:404-409) switches only the nn.Dropout MODULES off; MHA's functional dropout stays on
         pm = 0.0 if getattr(self, 'module_dropout_off', False) else p
         sa = self.self_attn
         qkv = ops.linear(x, sa.in_proj_weight, sa.in_proj_bias)
-        o = ops.attention(qkv, self.nhead, p, seed)
+        o = ops.attention(qkv, self.nhead, p, seed) if key_mask is None else ops.attention(qkv, self.nhead, p, seed, key_mask)
         a = sa.out_proj(o)
         x = ops.add_dropout_layernorm(x, a, self.norm1, pm, seed + 1)
         f = self.linear1(x, act=ops.ACT_RELU)
@@ -149,9 +151,14 @@ class TransformerEncoder(nn.Module):
         super().__init__()
         self.layers = nn.ModuleList(TransformerEncoderLayer(e, nhead, dropout=dropout) for _ in range(num_layers))
 
-    def forward(self, x, seed):
+    def forward(self, x, seed, key_mask=None):
+        if key_mask is None:
+            for i, layer in enumerate(self.layers):
+                x = layer(x, seed + 16 * i)
+            return x
+        rows = ops.key_mask_rows(key_mask, x.shape[1], x.shape[0])     # padded once for all the layers
         for i, layer in enumerate(self.layers):
-            x = layer(x, seed + 16 * i)
+            x = layer(x, seed + 16 * i, rows)
         return x
 
 

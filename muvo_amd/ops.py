@@ -119,6 +119,7 @@ EXPORTS = [
     'muvo_visibility_mark', 'muvo_visibility_apply',
     'muvo_voxel_calibration',
     'muvo_voxel_pose_chain', 'muvo_voxel_aggregate',
+    'muvo_attention_mask_fwd', 'muvo_attention_mask_bwd', 'muvo_attention_stream_mask_fwd', 'muvo_attention_stream_mask_bwd',
 ]
 
 
@@ -2262,6 +2263,44 @@ class StreamAttentionFn(_FusedAttentionFn):
     FWD, BWD, DWS = 'muvo_attention_stream_fwd', 'muvo_attention_stream_bwd', True
 
 
+class _MaskedAttentionFn(torch.autograd.Function):
+    """_FusedAttentionFn with a key mask (N, L') uint8, rows padded to a multiple of 16 bytes (key_mask_rows), non-zero = the key
+    is ignored; the semantics are in include/muvo_hip.h.  Backward saves the mask and returns None for it."""
+    FWD = BWD = None
+    DWS = False
+
+    @classmethod
+    def forward(cls, ctx, qkv, nheads, p, seed, mask):
+        qkv = qkv.contiguous()
+        l, n, e3 = qkv.shape
+        e = e3 // 3
+        o = torch.empty(l, n, e, device=qkv.device, dtype=torch.float32)
+        lse = torch.empty(n * nheads, l, device=qkv.device, dtype=torch.float32)
+        _ck(getattr(lib(), cls.FWD)(_f(qkv), _f(o), _f(lse), l, n, nheads, e // nheads, _fl(p), C.c_uint64(seed), _st(), _p(mask),
+                                    _i64(mask.shape[1])))
+        ctx.dims = (l, n, nheads, e // nheads, p, seed)
+        ctx.save_for_backward(qkv, o, lse, mask)
+        return o
+
+    @classmethod
+    def backward(cls, ctx, do):
+        qkv, o, lse, mask = ctx.saved_tensors
+        l, n, nheads, dh, p, seed = ctx.dims
+        dqkv = torch.empty_like(qkv)
+        dws = torch.empty_like(lse) if cls.DWS else None
+        _ck(getattr(lib(), cls.BWD)(_f(qkv), _f(o), _f(do.contiguous()), _f(lse), _f(dqkv), *((_f(dws),) if cls.DWS else ()), l, n,
+                                    nheads, dh, _fl(p), C.c_uint64(seed), _st(), _p(mask), _i64(mask.shape[1])))
+        return dqkv, None, None, None, None
+
+
+class MaskedFlashAttentionFn(_MaskedAttentionFn):
+    FWD, BWD = 'muvo_attention_mask_fwd', 'muvo_attention_mask_bwd'
+
+
+class MaskedStreamAttentionFn(_MaskedAttentionFn):
+    FWD, BWD, DWS = 'muvo_attention_stream_mask_fwd', 'muvo_attention_stream_mask_bwd', True
+
+
 FLASH_ATTENTION = os.environ.get('MUVO_FLASH_ATTN', '1') != '0'
 # Shortest sequence the streamed kernels take from the unfused path.  Everything the fused kernels support (L <= 384) goes to
 # them first, so this only matters above 384.  Set from the measurement in DESIGN.md section 7 (tools/attention_bench.py).
@@ -2281,9 +2320,49 @@ def attention_path(l, dh):
 _ATTENTION_FNS = {'fused': FlashAttentionFn, 'stream': StreamAttentionFn, 'unfused': AttentionFn}
 
 
-def attention(qkv, nheads, p, seed):
-    l, _, e3 = qkv.shape
-    return _ATTENTION_FNS[attention_path(l, e3 // 3 // nheads)].apply(qkv, nheads, p, seed)
+_MASKED_ATTENTION_FNS = {'fused': MaskedFlashAttentionFn, 'stream': MaskedStreamAttentionFn}
+
+
+def masked_attention_path(l, dh):
+    """'fused' | 'stream': which kernels attention() uses under a key mask.  Resident when it fits, otherwise streamed for any
+    l >= 1 (STREAM_MIN_L does not apply: the unfused path has no mask).  ValueError where no fused kernel can run: the mask is
+    never dropped silently."""
+    if not FLASH_ATTENTION:
+        raise ValueError('attention: a key mask needs the fused kernels, which MUVO_FLASH_ATTN=0 turns off')
+    if lib().muvo_attention_supported(l, dh):
+        return 'fused'
+    if lib().muvo_attention_stream_supported(l, dh):
+        return 'stream'
+    raise ValueError(f'attention: no masked kernel for sequence length {l}, head dimension {dh}')
+
+
+def key_mask_rows(key_mask, n, l):
+    """The (n, l) bool / uint8 device mask as the (n, roundup(l, 16)) contiguous uint8 tensor the kernels read (zero padding);
+    a tensor that already is one (what this function returned) comes back as it is"""
+    lp = (l + 15) // 16 * 16
+    if key_mask.dtype == torch.uint8 and key_mask.is_cuda and tuple(key_mask.shape) == (n, lp) and key_mask.is_contiguous() \
+            and key_mask.data_ptr() % 16 == 0:
+        return key_mask
+    if key_mask.dim() != 2 or tuple(key_mask.shape) != (n, l):
+        raise ValueError(f'attention: key_mask must be (N, L) = ({n}, {l}), got {tuple(key_mask.shape)}')
+    if key_mask.dtype not in (torch.bool, torch.uint8):
+        raise ValueError(f'attention: key_mask must be bool or uint8, got {key_mask.dtype}')
+    if not key_mask.is_cuda:
+        raise ValueError('attention: key_mask must be on the device')
+    rows = torch.zeros(n, lp, dtype=torch.uint8, device=key_mask.device)
+    rows[:, :l] = key_mask.to(torch.uint8) if key_mask.dtype == torch.bool else key_mask
+    return rows
+
+
+def attention(qkv, nheads, p, seed, key_mask=None):
+    """key_mask: (N, L) bool or uint8 on the device, non-zero = the key is ignored by every query of its frame (torch's
+    src_key_padding_mask; not differentiable).  A caller with several attention calls under one mask passes key_mask_rows()'s
+    result, which is taken as it is."""
+    l, n, e3 = qkv.shape
+    if key_mask is None:
+        return _ATTENTION_FNS[attention_path(l, e3 // 3 // nheads)].apply(qkv, nheads, p, seed)
+    path = masked_attention_path(l, e3 // 3 // nheads)
+    return _MASKED_ATTENTION_FNS[path].apply(qkv, nheads, p, seed, key_mask_rows(key_mask, n, l))
 
 
 # ================================================================================================ RSSM

@@ -60,6 +60,25 @@ VOXEL_ENTRIES = ('voxel_label', 'voxel_re', 'voxel_im')
 IMAGINE_STEPS = (0, 3, 9)                              # sim_run.py:81,92-93
 
 
+SENSORS = ('camera', 'lidar')              # --drop-sensor; batch['sensor_drop'] codes 1, 2 (muvo_amd/models/mile.py)
+
+
+def check_drop_sensor(cfg, drop_sensor):
+    if drop_sensor is not None and drop_sensor not in SENSORS:
+        raise ValueError(f'drop_sensor {drop_sensor!r}: camera or lidar')
+    if drop_sensor is not None and not cfg.MODEL.TRANSFORMER.ENABLED:
+        raise ValueError('--drop-sensor hides tokens in the fusion transformer: it needs MODEL.TRANSFORMER.ENABLED')
+
+
+def set_sensor_drop(cfg, batch, drop_sensor):
+    """batch['sensor_drop'] = the code of `drop_sensor` ('camera' | 'lidar') for every sequence of the batch; None: nothing"""
+    check_drop_sensor(cfg, drop_sensor)
+    if drop_sensor is None:
+        return batch
+    batch['sensor_drop'] = torch.full((batch['image'].shape[0],), SENSORS.index(drop_sensor) + 1, dtype=torch.int8)
+    return batch
+
+
 def refuse_multi_process(environ=None):
     environ = os.environ if environ is None else environ
     world = int(environ.get('WORLD_SIZE', '1') or 1)
@@ -80,6 +99,9 @@ def build_parser():
     parser.add_argument('--limit-batches', type=int, default=None, metavar='N', help='at most N batches per loader')
     parser.add_argument('--shard-size', type=int, default=500, metavar='N', help='batches per data_{i}.npz (sim)')
     parser.add_argument('--seed', type=int, default=1234)
+    parser.add_argument('--drop-sensor', choices=SENSORS, default=None,
+                        help="every sample runs without that sensor: its tokens are blanked and hidden from the fusion transformer's "
+                             "attention (batch['sensor_drop']); metrics.json gains a \"drop_sensor\" entry")
     parser.add_argument('--panels', type=int, default=0, metavar='N',
                         help='test: write the picture grids of the first N batches per loader below OUT/panels (default: none)')
     parser.add_argument('--traj', action='store_true', help='with --panels: also the ego-trajectory panel `_traj` (ICP between lidar frames)')
@@ -259,7 +281,8 @@ def seed_batch(module, seed, loader_idx, i):
 
 def run(cfg, device, out_dir, mode, loaders=None, limit_batches=None, shard_size=500, seed=1234, hook=None, dataset_root=None,
         data=None, module=None, log=print, panels=0, traj=False, ego_motion=None, icp_options=None, flow=False, optical_flow=False,
-        voxel=False, voxel_size=256, ray_iou=None, voxel_cd=None, bev_pq=None, inst=False, voxel_calibration=None, uncert=False):
+        voxel=False, voxel_size=256, ray_iou=None, voxel_cd=None, bev_pq=None, inst=False, voxel_calibration=None, uncert=False,
+        drop_sensor=None):
     """Runs one mode and returns what it wrote: {'files': [...], 'batches': {loader: n}, 'metrics': {...}, 'confusion': {...} (test)}.
     hook(i, batch, output, output_imagine): called per batch with the device tensors (test mode: output_imagine is the list
     of imagined samples).  data: a set-up DataModule to take the test loaders from (default: one over dataset_root /
@@ -277,8 +300,11 @@ def run(cfg, device, out_dir, mode, loaders=None, limit_batches=None, shard_size
     out_dir/bev_pq.json; metrics.json does not change.  inst (test, with panels): also the `_inst` panel - True: decoded with the
     options of bev_pq (the defaults without it); a dict: with decode options of its own.  voxel_calibration (test): a dict of options
     (bins; empty: 15) - muvo_amd.calibration.VoxelCalibrationMetric runs on every batch and writes out_dir/voxel_calibration.json;
-    metrics.json does not change.  uncert (test, with panels): also the `_uncert` panel."""
+    metrics.json does not change.  uncert (test, with panels): also the `_uncert` panel.  drop_sensor (test and sim): 'camera' or
+    'lidar' - every batch gets `batch['sensor_drop']` for all its sequences (muvo_amd/models/mile.py: the sensor's tokens are
+    blanked and are no attention keys); the file names stay, metrics.json gains the entry "drop_sensor"."""
     refuse_multi_process()
+    check_drop_sensor(cfg, drop_sensor)                                          # refused here, before anything is built
     if mode not in ('test', 'sim'):
         raise ValueError(f'mode {mode!r}: test or sim')
     _check_heads(cfg, mode)
@@ -306,9 +332,9 @@ def run(cfg, device, out_dir, mode, loaders=None, limit_batches=None, shard_size
             raise ValueError('the BEV panoptic quality and the `_inst` panel belong to mode test')
         if voxel_calibration is not None or uncert:
             raise ValueError('the voxel calibration and the `_uncert` panel belong to mode test')
-        return _run_sim(cfg, module, chosen, out_dir, limit_batches, shard_size, seed, hook, log)
+        return _run_sim(cfg, module, chosen, out_dir, limit_batches, shard_size, seed, hook, log, drop_sensor)
     return _run_test(cfg, module, chosen, out_dir, limit_batches, shard_size, seed, hook, log, panels, traj, ego_motion, icp_options, flow, optical_flow,
-                     voxel, voxel_size, ray_iou, voxel_cd, bev_pq, inst, voxel_calibration, uncert)
+                     voxel, voxel_size, ray_iou, voxel_cd, bev_pq, inst, voxel_calibration, uncert, drop_sensor)
 
 
 def _batches(loader, limit):
@@ -319,7 +345,8 @@ def _batches(loader, limit):
 
 
 def _run_test(cfg, module, loaders, out_dir, limit_batches, shard_size, seed, hook, log, panels=0, traj=False, ego_motion=None, icp_options=None,
-              flow=False, optical_flow=False, voxel=False, voxel_size=256, ray_iou=None, voxel_cd=None, bev_pq=None, inst=False, voxel_calibration=None, uncert=False):
+              flow=False, optical_flow=False, voxel=False, voxel_size=256, ray_iou=None, voxel_cd=None, bev_pq=None, inst=False, voxel_calibration=None, uncert=False,
+              drop_sensor=None):
     counts = {}
     writer, was_writer, was_traj, was_opt = None, module.panel_writer, module.traj_panels, module.traj_options
     ego, flow_metric, was_flow = None, None, module.flow_panels
@@ -392,7 +419,7 @@ def _run_test(cfg, module, loaders, out_dir, limit_batches, shard_size, seed, ho
                     module.inst_panels = True
                 if uncert:
                     module.uncert_panels = True
-                output, output_imagines = module.test_step(batch, i, idx)
+                output, output_imagines = module.test_step(set_sensor_drop(cfg, batch, drop_sensor), i, idx)
                 if hook is not None:
                     hook(i, batch, output, output_imagines)
                 if ego is not None:
@@ -424,8 +451,10 @@ def _run_test(cfg, module, loaders, out_dir, limit_batches, shard_size, seed, ho
         module.log_fn, module.on_confusion = was_fn, was_cm
     result = {**logged, **confusion}
     result['batches'] = {str(idx): n for idx, n in counts.items()}
+    if drop_sensor is not None:
+        result['drop_sensor'] = drop_sensor
     for name, value in result.items():
-        if name != 'batches':
+        if name not in ('batches', 'drop_sensor'):
             log(json.dumps({name: value}))
     log(json.dumps({'batches': result['batches']}))
     path = os.path.join(out_dir, 'metrics.json')
@@ -461,7 +490,7 @@ def _run_test(cfg, module, loaders, out_dir, limit_batches, shard_size, seed, ho
     return out
 
 
-def _run_sim(cfg, module, loaders, out_dir, limit_batches, shard_size, seed, hook, log):
+def _run_sim(cfg, module, loaders, out_dir, limit_batches, shard_size, seed, hook, log, drop_sensor=None):
     (idx, loader), = loaders.items()
     module.train()
     m = module.model
@@ -483,7 +512,7 @@ def _run_sim(cfg, module, loaders, out_dir, limit_batches, shard_size, seed, hoo
         with torch.no_grad():
             for i, batch in _batches(loader, limit_batches):
                 seed_batch(module, seed, idx, i)
-                batch = module.preprocess(batch)
+                batch = set_sensor_drop(cfg, module.preprocess(batch), drop_sensor)
                 output, output_imagine = module.model.sim_forward(batch, is_dreaming=False)
                 if hook is not None:
                     hook(i, batch, output, output_imagine)
@@ -500,7 +529,7 @@ def _run_sim(cfg, module, loaders, out_dir, limit_batches, shard_size, seed, hoo
     finally:
         for layer, v in zip(layers, saved):
             layer.module_dropout_off = v
-    return {'files': files, 'batches': {idx: n}}
+    return {'files': files, 'batches': {idx: n}, **({'drop_sensor': drop_sensor} if drop_sensor is not None else {})}
 
 
 def main(argv=None):
@@ -521,7 +550,8 @@ def main(argv=None):
         ray_iou=dict(stride=args.ray_stride) if args.ray_iou else None, voxel_cd={} if args.voxel_cd else None,
         bev_pq=dict(threshold=args.inst_threshold, max_centres=args.inst_max_centres) if args.bev_pq else None,
         inst=dict(threshold=args.inst_threshold, max_centres=args.inst_max_centres) if args.inst else False,
-        voxel_calibration=dict(bins=args.calibration_bins) if args.voxel_calibration else None, uncert=args.uncert)
+        voxel_calibration=dict(bins=args.calibration_bins) if args.voxel_calibration else None, uncert=args.uncert,
+        drop_sensor=args.drop_sensor)
 
 
 if __name__ == '__main__':

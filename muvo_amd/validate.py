@@ -127,7 +127,7 @@ def _n_points(cfg, batch):
     return int(rv.shape[-2]) * int(rv.shape[-1])
 
 
-def run_validation(module, loaders, limit_batches=3, seed=1234, log=None, panels=True):
+def run_validation(module, loaders, limit_batches=3, seed=1234, log=None, panels=True, drop_sensor=None):
     """One validation pass: for every loader idx of `loaders` (a list of iterables of device batches; an empty one is skipped and
     contributes no names) `module.validation_step` over its first `limit_batches` batches, then `on_validation_epoch_end`.
 
@@ -138,6 +138,9 @@ def run_validation(module, loaders, limit_batches=3, seed=1234, log=None, panels
     `batches`: {idx: number of batches}.  Nothing lands in `module.logged`.  panels=False: nothing is drawn even when the module
     has a `panel_writer` (the sanity pass).
 
+    drop_sensor: 'camera' or 'lidar' - every batch runs without that sensor (muvo_amd.predict.set_sensor_drop); the result gains
+    the entry `drop_sensor`.
+
     `model.rssm.active_inference` is read as it stands (the module docstring), like the weights.
 
     The module is left as it was found, also when a step raises: the `training` flags, `model.seed_epoch` and
@@ -145,7 +148,7 @@ def run_validation(module, loaders, limit_batches=3, seed=1234, log=None, panels
     `vis_step`; the validation metric sets are reset.  NOT restored: the BatchNorm running statistics.  The reference validates
     with `self.train()` (trainer.py:405), so its running buffers move during validation, and `_eval_step` reproduces that."""
     from muvo_amd import ops
-    from muvo_amd.predict import seed_batch
+    from muvo_amd.predict import seed_batch, set_sensor_drop
     model = module.model
     device = next(model.parameters()).device
     was_training = [(m, m.training) for m in module.modules()]
@@ -169,7 +172,7 @@ def run_validation(module, loaders, limit_batches=3, seed=1234, log=None, panels
                         batch = next(it)
                     except StopIteration:
                         break
-                    batch = dict(batch)           # preprocess adds the label pyramids to the dict it is given
+                    batch = set_sensor_drop(module.cfg, dict(batch), drop_sensor)   # a copy: preprocess adds the label pyramids to the dict it is given
                     seed_batch(module, seed, idx, n)
                     cd_index =np.random.randint(0, _n_points(module.cfg, batch), CD_POINTS) if module.cfg.LIDAR_RE.ENABLED else None
                     out, loss, _, loss_imagines, _ = module.validation_step(batch, n, idx, cd_index=cd_index)
@@ -202,6 +205,8 @@ def run_validation(module, loaders, limit_batches=3, seed=1234, log=None, panels
     for idx in counts:
         result.update(means[idx].result())
     result['batches'] = counts
+    if drop_sensor is not None:
+        result['drop_sensor'] = drop_sensor
     if log is not None:
         log(json.dumps(jsonable(result)))
     return result
@@ -233,6 +238,9 @@ def build_parser():
     parser.add_argument('--limit-batches', type=int, default=3, metavar='N', help='at most N batches per loader (default 3)')
     parser.add_argument('--out', default='.', metavar='DIR', help='directory for val_metrics.json (default: the current one)')
     parser.add_argument('--seed', type=int, default=1234)
+    parser.add_argument('--drop-sensor', choices=('camera', 'lidar'), default=None,
+                        help='every sample runs without that sensor (as python -m muvo_amd.predict --drop-sensor); val_metrics.json '
+                             'gains a "drop_sensor" entry')
     parser.add_argument('--active-inference', action='store_true',
                         help='set model.rssm.active_inference: the checkpoint comes from a run that had passed micro-batch STEPS')
     return parser
@@ -244,6 +252,11 @@ def main(argv=None):
     if args.limit_batches < 1:
         raise SystemExit('--limit-batches must be positive')
     cfg = get_cfg(args)
+    from muvo_amd.predict import check_drop_sensor
+    try:
+        check_drop_sensor(cfg, args.drop_sensor)
+    except ValueError as e:
+        raise SystemExit(str(e))
     if args.checkpoint:
         cfg.defrost()
         cfg.PRETRAINED.PATH = args.checkpoint
@@ -257,7 +270,8 @@ def main(argv=None):
     module.model.rssm.active_inference = bool(args.active_inference)
     data = DataModule(cfg, args.dataset_root or cfg.DATASET.DATAROOT, device=device, seed=args.seed)
     data.setup()
-    result = jsonable(run_validation(module, data.val_dataloader(), limit_batches=args.limit_batches, seed=args.seed))
+    result = jsonable(run_validation(module, data.val_dataloader(), limit_batches=args.limit_batches, seed=args.seed,
+                                     drop_sensor=args.drop_sensor))
     os.makedirs(args.out, exist_ok=True)
     path = os.path.join(args.out, 'val_metrics.json')
     with open(path, 'w') as fh:
